@@ -54,6 +54,42 @@ def sweep_plan(info):
             "program_fallbacks": int(info.get("program_fallbacks", 0))}
 
 
+DUMP_SAMPLE = 3 << 20         # --dump-outputs: sampled entries of a large iterate (24 MiB of f64)
+DUMP_SEED = 20241015
+
+
+def dump_outputs(out_dir, rank, world, u, its, rn):
+    """--dump-outputs: what the timed solve handed back after its last step, as float64 .npy
+    files (with several ranks, each rank's shard under a ``.rank<r>`` suffix):
+
+    u              the iterate (this rank's rows), or, when it has more than 2 k entries
+                   (k = DUMP_SAMPLE / world), u_sample: its k entries at a fixed, seeded, sorted
+                   set of indices (np.random.default_rng(DUMP_SEED).choice(len(u), k,
+                   replace=False)), stored beside it as u_sample_index: 48 MiB at most in all
+    u_block_norms  2-norms of u over 4096 contiguous slices of equal length (every entry counts)
+    residual_norm, iterations   the solver's scalars, one entry each
+    Inputs are seeded, so two builds run with the same arguments can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f".rank{rank}" if world > 1 else ""
+    u = np.asarray(u, dtype=np.float64)
+    arrays = {"u_block_norms": np.array([np.linalg.norm(s) for s in
+                                         np.array_split(u, min(4096, u.size))]),
+              "residual_norm": np.array([rn], dtype=np.float64),
+              "iterations": np.array([its], dtype=np.float64)}
+    k = DUMP_SAMPLE // world
+    if u.size <= 2 * k:
+        arrays["u"] = u
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(u.size, k, replace=False))
+        arrays["u_sample"] = u[idx]
+        arrays["u_sample_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+    print(f"[bench] outputs of the last timed step written to {out_dir}: "
+          + ", ".join(f"{n}{sfx} {a.shape}" for n, a in arrays.items()), file=sys.stderr,
+          flush=True)
+
+
 def roofline_check(roof):
     """A fraction outside (0, 1] is a bookkeeping error: flag it in the line, keep the line."""
     f = roof.get("frac")
@@ -369,12 +405,18 @@ def bench_stokes(args, rank, world, local_rank):
         outer._ck(lib.kkt_comm_barrier(h))
         dt = C.c_double(time.perf_counter() - t0)
         outer._ck(lib.kkt_comm_max(h, C.byref(dt)))
-        return its.value, dt.value
+        return its.value, dt.value, rn.value
     print(f"[bench] spmv {spmv_ms:.3f} ms, pc {pc_ms:.3f} ms; Krylov leg", file=sys.stderr,
           flush=True)
     if args.warmup > 0:
         run(args.warmup)
-    its, dt = run(args.steps)
+    its, dt, rn = run(args.steps)
+    if its != args.steps:
+        raise RuntimeError(f"the solver ran {its} iterations, {args.steps} were asked for")
+    if args.dump_outputs:       # before the legs below reuse d_u
+        u = np.empty(n_local)
+        outer._ck(lib.kkt_vec_download(h, d_u, _lib.f64(u)[1]))
+        dump_outputs(args.dump_outputs, rank, world, u, its, rn)
     stages = stage_breakdown(outer, lib, h, d_x, d_u, d_x, d_y, n_local, min(args.steps, 10), 1,
                              with_pc_stages=False)
     inner_info = gpc.inner.info() if hasattr(gpc, "inner") else {}
@@ -606,10 +648,16 @@ def main():
                          "apply_xcd=1); printed in config")
     ap.add_argument("--only-spmv", action="store_true",
                     help="time the KKT SpMV only (counter-collection passes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed solve computed in its last "
+                         "step (iterate, residual norm, iterations) as DIR/<name>.npy, float64, "
+                         "at most ~64 MB (a seeded sample of a larger iterate)")
     ap.add_argument("--launch-timeout", type=float, default=1700.0,
                     help="self-launched ranks (--gpus N without a launcher) are stopped after this "
                          "many seconds")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.coarse_cycles is None:
         args.coarse_cycles = 0 if args.workload == "heat3d" else 2
     if args.kp_its is None:
@@ -665,6 +713,7 @@ def main():
         a4.schur_its, a4.schur_emin, a4.schur_emax = 34, 7.44e-3, 2.1
         a4.coarse_cycles = 0      # (3-D: the plain sweeps are at their optimum, profiles/r03)
         a4.steps, a4.warmup, a4.spmv_reps = 10, 2, 10
+        a4.dump_outputs = None     # (the outputs are the headline's)
         o4 = None
         try:
             o4 = measure_heat(a4, rank, world, local_rank, tts=True)
@@ -791,15 +840,19 @@ def measure_heat(args, rank, world, local_rank, tts):
         gsys._ck(lib.kkt_comm_barrier(h))
         dt = C.c_double(time.perf_counter() - t0)
         gsys._ck(lib.kkt_comm_max(h, C.byref(dt)))
-        return its.value, dt.value
+        return its.value, dt.value, rn.value
 
     print(f"[bench] spmv {spmv_ms:.3f} ms, pc {pc_ms:.3f} ms; Krylov leg", file=sys.stderr,
           flush=True)
     if args.warmup > 0:
         run(args.warmup)
-    its, dt = run(args.steps)
+    its, dt, rn = run(args.steps)
     if its != args.steps:
         raise RuntimeError(f"the solver ran {its} iterations, {args.steps} were asked for")
+    if args.dump_outputs:       # before the legs below reuse d_u
+        u = np.empty(n_local)
+        gsys._ck(lib.kkt_vec_download(h, d_u, _lib.f64(u)[1]))
+        dump_outputs(args.dump_outputs, rank, world, u, its, rn)
 
     # ---- SURVEY 8e itemisation (outside the timed region)
     stages = stage_breakdown(gsys, lib, h, d_b, d_u, d_x, d_y, n_local, min(args.steps, 20), 0)
