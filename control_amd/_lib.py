@@ -82,6 +82,13 @@ class PcStageTimes(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CoarseStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("matrices", "launches", "n_coarse")] + [("ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class StepLock(C.Structure):
     _fields_ = [("n_steps", C.c_int), ("restart", C.c_int), ("V", c_f64p), ("h", c_f64p),
                 ("v_next", c_f64p)]
@@ -143,6 +150,9 @@ SIGNATURES = {
     "kkt_get_stage_times": (C.c_int, [C.c_void_p, C.POINTER(StageTimes)]),
     "kkt_time_pc_stages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(PcStageTimes)]),
+    "kkt_coarse_setup_stats": (C.c_int, [C.c_void_p, C.POINTER(CoarseStats)]),
+    "kkt_debug_coarse_matrices": (C.c_int, [C.c_void_p, c_f64p, C.c_int64]),
+    "kkt_debug_dense_inverse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p]),
     "kkt_debug_set_steplock": (C.c_int, [C.c_void_p, C.POINTER(StepLock)]),
     "kkt_get_info": (C.c_int, [C.c_void_p, C.POINTER(Info)]),
     "kkt_comm_unique_id": (C.c_int, [C.c_void_p]),

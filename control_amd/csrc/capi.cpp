@@ -1,4 +1,5 @@
 // extern "C" boundary of libkkt (include/kkt.h).  No C++ exception leaves this file.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -71,7 +72,7 @@ int kkt_set_option(kkt_handle h, const char *key, const char *value) {
                                       "lanes", "lane_chunks", "kernarg_ops", "shared_rows",
                                       "verbose", "stamps", "tile_poll_delay", "tile_unfused",
                                       "debug_drop_handoff", "stage_timers", "sell_sigma", "ragged_switch", "ragged_xcd", "apply_xcd", "pc_xcd",
-                                      "interleave"};
+                                      "interleave", "coarse_setup", "coarse_keep"};
         if (!key || !value) fail(KKT_ERR_ARG, "null option");
         bool ok = false;
         for (const char *k : known) ok = ok || std::strcmp(k, key) == 0;
@@ -327,6 +328,28 @@ int kkt_time_pc_stages(kkt_handle h, const double *d_x, double *d_y, kkt_pc_stag
     KKT_TRY(h, {
         if (!d_x || !d_y || !out) fail(KKT_ERR_ARG, "null argument");
         S.pc_apply_timed_stages(d_x, d_y, out);
+    });
+}
+
+int kkt_coarse_setup_stats(kkt_handle h, kkt_coarse_stats *out) {
+    KKT_TRY(h, {
+        if (!out) fail(KKT_ERR_ARG, "null argument");
+        *out = S.coarse_stats;
+    });
+}
+
+int kkt_debug_coarse_matrices(kkt_handle h, double *out, int64_t cap) {
+    KKT_TRY(h, {
+        if (!out && cap > 0) fail(KKT_ERR_ARG, "null argument");
+        if ((size_t)cap < S.coarse_E.size()) fail(KKT_ERR_ARG, "buffer too small for the coarse matrices");
+        std::copy(S.coarse_E.begin(), S.coarse_E.end(), out);
+    });
+}
+
+int kkt_debug_dense_inverse(kkt_handle h, int n, int nmat, const double *a, double *inv, int *bad) {
+    KKT_TRY(h, {
+        if (n < 1 || nmat < 1 || !a || !inv || !bad) fail(KKT_ERR_ARG, "bad dense inverse arguments");
+        kkt::dense_inverse_host(S, n, nmat, a, inv, bad);
     });
 }
 

@@ -2722,6 +2722,270 @@ void launch_dense_inverse(hipStream_t s, double *a, double *inv, int n, int *d_p
     }
 }
 
+// ---- batched coarse set-up: E_b = P^T A_b P for a batch of level matrices in one launch, and
+// their inverses by blocked Gauss-Jordan (launches per batch: 2 per panel of GJ_NB columns).
+
+// Workgroup (i, b) forms row i of E_b over the structure of E (e_ip / e_ix: the k whose support
+// meets that of coarse function i).  Every entry is summed exactly as the column path forms it
+// (launch_coarse_column + the sub-solves' SpMV + coarse_restrict_kernel): y_k[r] = one fma chain
+// over the SELL slots of row r in slot order (0 on masked rows), then E[i, k] = per-thread fma
+// chains over P^T's row i at stride 256 and the same LDS tree -- so the two paths agree bit for
+// bit.  Entries outside the structure stay the caller's zeros.
+__device__ __forceinline__ double p_entry(const int32_t *__restrict__ p_ip,
+                                          const int32_t *__restrict__ p_ix,
+                                          const double *__restrict__ p_v, int c, int k) {
+    for (int32_t q = p_ip[c]; q < p_ip[c + 1]; ++q)
+        if (p_ix[q] == k) return p_v[q];
+    return 0.0;
+}
+__global__ __launch_bounds__(256) void galerkin_kernel(CoarseDev c, GalerkinDev g,
+                                                       const double *const *__restrict__ vals,
+                                                       double *__restrict__ E) {
+    __shared__ double sh[256];
+    const int i = blockIdx.x, nc = c.nc;
+    const double *__restrict__ a = vals[blockIdx.y];
+    double *__restrict__ Erow = E + (size_t)blockIdx.y * nc * nc + (size_t)i * nc;
+    const int C = 64 * g.R;
+    for (int32_t e = g.e_ip[i]; e < g.e_ip[i + 1]; ++e) {
+        const int k = g.e_ix[e];
+        double s = 0.0;
+        for (int32_t q = c.pt_ip[i] + threadIdx.x; q < c.pt_ip[i + 1]; q += 256) {
+            const int r = c.pt_ix[q];
+            double y = 0.0;
+            if (!(g.mask && g.mask[r])) {
+                const int pos = g.pos ? g.pos[r] : r;
+                const int sl = pos / C, rin = pos - sl * C;
+                int off0, w;
+                if (g.uniform_w >= 0) {
+                    w = g.uniform_w;
+                    off0 = sl * w;
+                } else {
+                    off0 = g.slice_off[sl];
+                    w = g.slice_off[sl + 1] - off0;
+                }
+                const size_t base = (size_t)off0 * C + (size_t)(rin % 64) * g.R + rin / 64;
+                for (int kk = 0; kk < w; ++kk) {
+                    const size_t at = base + (size_t)kk * C;
+                    y = __builtin_fma(a[at], p_entry(c.p_ip, c.p_ix, c.p_v, g.col[at], k), y);
+                }
+            }
+            s = __builtin_fma(c.pt_v[q], y, s);
+        }
+        sh[threadIdx.x] = s;
+        __syncthreads();
+        for (int st = 128; st > 0; st >>= 1) {
+            if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) Erow[k] = sh[0];
+        __syncthreads();
+    }
+}
+void launch_galerkin_batched(hipStream_t s, const CoarseDev &c, const GalerkinDev &g,
+                             const double *const *d_vals, double *E, int nmat) {
+    if (c.nc <= 0 || nmat <= 0) return;
+    hipLaunchKernelGGL(galerkin_kernel, dim3(c.nc, nmat), dim3(256), 0, s, c, g, d_vals, E);
+}
+
+// Blocked Gauss-Jordan with partial pivoting, one matrix per blockIdx.y.  Panel c0 .. c0+nb-1:
+//  panel kernel (one workgroup per matrix): the nb Gauss-Jordan steps on the panel columns Y
+//    (n x nb, column-major scratch) with their row swaps; the same eliminations act on Z = the
+//    panel's identity columns.  The panel's effect on the whole matrix is M <- T' Pi M, Pi its
+//    row swaps and T' the product of its elimination matrices with the later swaps moved past
+//    them (T' differs from I in the columns c0 .. c0+nb-1 only); afterwards Z holds those columns
+//    of T', stored row-major in W.  Pivot rows go to piv.  The matrix itself is not written.
+//  update kernel (workgroup per 64 columns of [A | inv] still live): applies the swaps to its
+//    columns, copies the pivot rows U = M[c0 .. c0+nb-1, j], and forms
+//    M[r, j] = (r outside the panel ? M[r, j] : 0) + sum_l W[r, l] U[l, j], a rank-nb update.
+// Columns of A left of the panel's end are never read again and are not updated.  Singularity:
+// |pivot| < 1e-13 max|diag A| (or not finite) records the smallest such column in bad[b].
+constexpr int GJ_NB = 32;
+constexpr int GJ_PANEL_THREADS = 1024;
+struct GjArgs {
+    double *a;            // nmat matrices n x n, row-major, contiguous (destroyed)
+    double *const *inv;   // inverse of matrix b at inv[b]
+    double *Y, *Z, *W;    // scratch: nmat x n x GJ_NB each
+    int *piv;             // nmat x GJ_NB
+    double *dmax;         // nmat
+    int *bad;             // nmat: first singular column, n if none
+    int n;
+};
+__global__ __launch_bounds__(1024) void gj_init_kernel(GjArgs g) {
+    const int b = blockIdx.y, n = g.n;
+    double *inv = g.inv[b];
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < (size_t)n * n;
+         t += (size_t)gridDim.x * blockDim.x)
+        inv[t] = (t / n == t % n) ? 1.0 : 0.0;
+    if (blockIdx.x == 0) {
+        __shared__ double sh[1024];
+        const double *a = g.a + (size_t)b * n * n;
+        double m = 0.0;
+        for (int r = threadIdx.x; r < n; r += blockDim.x) m = fmax(m, fabs(a[(size_t)r * n + r]));
+        sh[threadIdx.x] = m;
+        __syncthreads();
+        for (int st = blockDim.x / 2; st > 0; st >>= 1) {
+            if ((int)threadIdx.x < st) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + st]);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            g.dmax[b] = sh[0];
+            g.bad[b] = n;
+        }
+    }
+}
+__global__ __launch_bounds__(GJ_PANEL_THREADS) void gj_panel_kernel(GjArgs g, int c0) {
+    constexpr int NT = GJ_PANEL_THREADS;
+    __shared__ double bv[NT];
+    __shared__ int bi[NT];
+    __shared__ double rowc[2 * GJ_NB];
+    const int b = blockIdx.x, n = g.n, nb = min(GJ_NB, n - c0), t = threadIdx.x;
+    const double *a = g.a + (size_t)b * n * n;
+    double *Y = g.Y + (size_t)b * n * GJ_NB, *Z = g.Z + (size_t)b * n * GJ_NB;
+    for (int r = t; r < n; r += NT)
+        for (int l = 0; l < nb; ++l) {
+            Y[(size_t)l * n + r] = a[(size_t)r * n + c0 + l];
+            Z[(size_t)l * n + r] = r == c0 + l ? 1.0 : 0.0;
+        }
+    const double tol = 1e-13 * g.dmax[b];
+    __syncthreads();
+    for (int cc = 0; cc < nb; ++cc) {
+        const int c = c0 + cc;
+        double best = -1.0;
+        int at = c;
+        for (int r = c + t; r < n; r += NT) {
+            const double v = fabs(Y[(size_t)cc * n + r]);
+            if (v > best) {
+                best = v;
+                at = r;
+            }
+        }
+        bv[t] = best;
+        bi[t] = at;
+        __syncthreads();
+        for (int st = NT / 2; st > 0; st >>= 1) {
+            if (t < st) {
+                const double o = bv[t + st];
+                const int oi = bi[t + st];
+                if (o > bv[t] || (o == bv[t] && oi < bi[t])) {
+                    bv[t] = o;
+                    bi[t] = oi;
+                }
+            }
+            __syncthreads();
+        }
+        const int p = bi[0];
+        const double d = Y[(size_t)cc * n + p];
+        const bool sing = !(bv[0] >= tol && bv[0] > 0.0) || !isfinite(bv[0]);
+        __syncthreads();      // every thread has read the pivot before the swap moves it
+        // swap rows c and p of Y and of the processed columns l < cc of Z, scale the new row c,
+        // keep it in LDS.  Z accumulates T' with M_new = T' Pi M (Pi: the panel's swaps, applied
+        // by the update kernel): deferring swap p of Pi past the earlier elimination steps swaps
+        // rows c and p of their columns only -- the columns still to come stay identity columns.
+        if (t < 2 * nb) {
+            double *m = t < nb ? Y : Z;
+            const int l = t < nb ? t : t - nb;
+            const bool sw = t < nb || l < cc;
+            const double vp = m[(size_t)l * n + p], vc = m[(size_t)l * n + c];
+            if (sw) m[(size_t)l * n + p] = vc;
+            const double sv = sing ? 0.0 : (sw ? vp : vc) / d;
+            m[(size_t)l * n + c] = sv;
+            rowc[t] = sv;
+        }
+        if (t == 0) {
+            g.piv[b * GJ_NB + cc] = p;
+            if (sing && g.bad[b] > c) g.bad[b] = c;
+        }
+        __syncthreads();
+        for (int r = t; r < n; r += NT) {
+            if (r == c) continue;
+            const double f = Y[(size_t)cc * n + r];
+            if (f == 0.0) continue;
+            for (int l = cc; l < nb; ++l) Y[(size_t)l * n + r] -= f * rowc[l];
+            for (int l = 0; l <= cc; ++l) Z[(size_t)l * n + r] -= f * rowc[nb + l];
+        }
+        __syncthreads();
+    }
+    double *W = g.W + (size_t)b * n * GJ_NB;
+    for (int r = t; r < n; r += NT)
+        for (int l = 0; l < GJ_NB; ++l) W[(size_t)r * GJ_NB + l] = l < nb ? Z[(size_t)l * n + r] : 0.0;
+}
+__global__ __launch_bounds__(256) void gj_update_kernel(GjArgs g, int c0) {
+    __shared__ double U[GJ_NB][64];
+    const int b = blockIdx.y, n = g.n, nb = min(GJ_NB, n - c0);
+    const int nA = n - (c0 + nb);                      // live columns of A
+    const int tx = threadIdx.x & 63;
+    const int ty = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int jj = blockIdx.x * 64 + tx;
+    const bool live = jj < nA + n;
+    double *m = nullptr;
+    int j = 0;
+    if (live) {
+        if (jj < nA) {
+            m = g.a + (size_t)b * n * n;
+            j = c0 + nb + jj;
+        } else {
+            m = g.inv[b];
+            j = jj - nA;
+        }
+    }
+    const int *piv = g.piv + b * GJ_NB;
+    if (ty == 0 && live) {
+        for (int l = 0; l < nb; ++l) {
+            const int c = c0 + l, p = piv[l];
+            if (p != c) {
+                const double vp = m[(size_t)p * n + j];
+                m[(size_t)p * n + j] = m[(size_t)c * n + j];
+                m[(size_t)c * n + j] = vp;
+            }
+            U[l][tx] = m[(size_t)c * n + j];
+        }
+        for (int l = nb; l < GJ_NB; ++l) U[l][tx] = 0.0;
+    }
+    __syncthreads();
+    if (!live) return;
+    double u[GJ_NB];
+#pragma unroll
+    for (int l = 0; l < GJ_NB; ++l) u[l] = U[l][tx];
+    const double *W = g.W + (size_t)b * n * GJ_NB;
+    for (int r = ty; r < n; r += 4) {
+        const double *w = W + (size_t)r * GJ_NB;
+        double acc = (r >= c0 && r < c0 + nb) ? 0.0 : m[(size_t)r * n + j];
+#pragma unroll
+        for (int l = 0; l < GJ_NB; ++l) acc = __builtin_fma(w[l], u[l], acc);
+        m[(size_t)r * n + j] = acc;
+    }
+}
+size_t dense_inverse_batched_scratch(int n, int nmat) {
+    return (size_t)nmat * ((size_t)3 * n * GJ_NB * sizeof(double) + GJ_NB * sizeof(int) +
+                           sizeof(double) + sizeof(int)) + 256;
+}
+int launch_dense_inverse_batched(hipStream_t s, double *a, double *const *d_inv, int n, int nmat,
+                                 void *scratch, int *d_bad) {
+    if (n <= 0 || nmat <= 0) return 0;
+    GjArgs g;
+    g.a = a;
+    g.inv = d_inv;
+    g.n = n;
+    char *p = (char *)scratch;
+    const size_t blk = (size_t)nmat * n * GJ_NB * sizeof(double);
+    g.Y = (double *)p;
+    g.Z = (double *)(p + blk);
+    g.W = (double *)(p + 2 * blk);
+    g.dmax = (double *)(p + 3 * blk);
+    g.piv = (int *)(p + 3 * blk + nmat * sizeof(double));
+    g.bad = d_bad;
+    int launches = 1;
+    hipLaunchKernelGGL(gj_init_kernel, dim3(grid_for((int64_t)n * n, 1024, 256), nmat), dim3(1024), 0,
+                       s, g);
+    for (int c0 = 0; c0 < n; c0 += GJ_NB) {
+        const int nb = std::min(GJ_NB, n - c0), live = 2 * n - c0 - nb;
+        hipLaunchKernelGGL(gj_panel_kernel, dim3(nmat), dim3(GJ_PANEL_THREADS), 0, s, g, c0);
+        hipLaunchKernelGGL(gj_update_kernel, dim3((live + 63) / 64, nmat), dim3(256), 0, s, g, c0);
+        launches += 2;
+    }
+    return launches;
+}
+
 // the time-out word of the sweep programs as a summand of the Krylov all-reduce (time shards)
 __global__ void flag_to_double_kernel(const unsigned *flag, double *out) {
     out[0] = (flag != nullptr && flag[0] != 0u) ? 1.0 : 0.0;

@@ -322,6 +322,26 @@ void launch_coarse_restrict(hipStream_t s, const CoarseDev &c, const double *r, 
 // inv = a^-1 (n x n row-major, a destroyed) by Gauss-Jordan with partial pivoting on the device
 void launch_dense_inverse(hipStream_t s, double *a, double *inv, int n, int *d_piv,
                           double *d_colbuf, unsigned *d_flag);
+// Batched coarse set-up.  E_b = P^T A_b P (rows of A_b masked) for nmat level matrices on one
+// SELL structure, one launch; the structure of E comes from the host (e_ip / e_ix).  Sums in the
+// order of the column path (launch_coarse_column + SpMV + launch_coarse_restrict): bit-identical
+// to it.  E: nmat row-major nc x nc matrices, zeroed by the caller.
+struct GalerkinDev {
+    const int32_t *e_ip = nullptr, *e_ix = nullptr;   // structure of E: nc rows
+    const int32_t *col = nullptr, *slice_off = nullptr;   // SELL structure of A
+    const int32_t *pos = nullptr;                     // position of each row (null: position == row)
+    const uint8_t *mask = nullptr;                    // masked rows of A P are zero
+    int R = 2, uniform_w = -1;
+};
+void launch_galerkin_batched(hipStream_t s, const CoarseDev &c, const GalerkinDev &g,
+                             const double *const *d_vals, double *E, int nmat);
+// inv[b] = a_b^-1 for nmat n x n row-major matrices stored contiguously at a (destroyed): blocked
+// Gauss-Jordan with partial pivoting, 1 + 2 ceil(n / 32) launches for the whole batch (returned).
+// d_bad[b] = first column whose pivot is below 1e-13 max|diag a_b| (n: none).  scratch: at least
+// dense_inverse_batched_scratch(n, nmat) bytes.
+size_t dense_inverse_batched_scratch(int n, int nmat);
+int launch_dense_inverse_batched(hipStream_t s, double *a, double *const *d_inv, int n, int nmat,
+                                 void *scratch, int *d_bad);
 void launch_flag_to_double(hipStream_t s, const unsigned *flag, double *out);
 // w += sign * sum_i coef[i] * V_i   (coef in device memory)
 void launch_maxpy(hipStream_t s, double *w, VecList V, const double *coef, double sign,

@@ -1,6 +1,7 @@
 #include "pc.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -131,12 +132,14 @@ void SchurPC::values_changed() {
     mats_.clear();
     for (double *p : einv_owned_) (void)hipFree(p);
     einv_owned_.clear();
+    pending_coarse_.clear();
     if (d_.kind == KKT_PC_STATIONARY)
         build_stationary();
     else if (d_.kind == KKT_PC_INSTATIONARY_BE)
         build_BE();
     else
         build_CN();
+    flush_coarse();
     if (S_.opt("verbose") && d_.schur_emin <= 0)
         std::fprintf(stderr, "[kkt] Chebyshev sub-solves: degree %d; %lld Lanczos steps spent on "
                      "%zu matrices\n", schur_its_, (long long)spectrum_steps_, mats_.size());
@@ -1103,67 +1106,243 @@ void SchurPC::build_coarse() {
     coarse_.pt_ip = up(pt_indptr_);
     coarse_.pt_ix = up(pt_indices_);
     coarse_.pt_v = up(pt_values_);
+    {
+        const Pattern &P = S_.patterns[m_pat_];
+        std::vector<int32_t> e_ip, e_ix;
+        galerkin_structure(nc, pt_indptr_, pt_indices_, P.h_indptr, P.h_indices, p_indptr_,
+                           p_indices_, e_ip, e_ix);
+        galerkin_.e_ip = up(e_ip);
+        galerkin_.e_ix = up(e_ix);
+        galerkin_.col = P.d_col;
+        galerkin_.slice_off = P.d_slice_off;
+        galerkin_.pos = P.h_pos_of.empty() ? nullptr : up(P.h_pos_of);
+        galerkin_.mask = mask_;
+        galerkin_.R = P.R;
+        galerkin_.uniform_w = P.uniform_w;
+    }
     coarse_.rc = dev_alloc<double>(nc);
     coarse_.ec = dev_alloc<double>(nc);
     owned_.push_back(coarse_.rc);
     owned_.push_back(coarse_.ec);
 }
 
-// E = P^T A P column by column with the kernels the sweeps use (x = column k of P, y = A x with
-// the boundary rows masked, E(:, k) = P^T y: fixed summation orders, so every rank and every run
-// forms the same matrix), inverted on the device by Gauss-Jordan with partial pivoting.
-double *SchurPC::coarse_inverse(const double *vals) {
-    const Pattern &P = S_.patterns[m_pat_];
-    hipStream_t st = S_.stream;
-    const int nc = coarse_.nc;
-    double *x = dev_alloc<double>(nx_ + 32), *y = dev_alloc<double>(nx_ + 32);
-    double *E = dev_alloc<double>((size_t)nc * nc);
-    auto vref = [](const double *q) { return q ? VRef{(int64_t)(uintptr_t)q, 0, 0} : VRef{0, -1, 0}; };
+void galerkin_structure(int nc, const std::vector<int32_t> &pt_ip, const std::vector<int32_t> &pt_ix,
+                        const std::vector<int32_t> &a_ip, const std::vector<int32_t> &a_ix,
+                        const std::vector<int32_t> &p_ip, const std::vector<int32_t> &p_ix,
+                        std::vector<int32_t> &e_ip, std::vector<int32_t> &e_ix) {
+    std::vector<int32_t> seen(nc, -1), row;
+    e_ip.assign(1, 0);
+    e_ix.clear();
+    for (int i = 0; i < nc; ++i) {
+        row.clear();
+        for (int32_t q = pt_ip[i]; q < pt_ip[i + 1]; ++q) {
+            const int32_t r = pt_ix[q];
+            for (int32_t t = a_ip[r]; t < a_ip[r + 1]; ++t) {
+                const int32_t c = a_ix[t];
+                for (int32_t u = p_ip[c]; u < p_ip[c + 1]; ++u) {
+                    const int32_t k = p_ix[u];
+                    if (seen[k] != i) {
+                        seen[k] = i;
+                        row.push_back(k);
+                    }
+                }
+            }
+        }
+        std::sort(row.begin(), row.end());
+        e_ix.insert(e_ix.end(), row.begin(), row.end());
+        e_ip.push_back((int32_t)e_ix.size());
+    }
+}
+
+// The column path (option "coarse_setup" = "columns"): E = P^T A P column by column with the
+// kernels the sweeps use (x = column k of P, y = A x with the masked rows zero, E(:, k) = P^T y),
+// inverted by Gauss-Jordan with partial pivoting, four launches per pivot.  Returns the launches.
+static int64_t coarse_columns(System &S, const Pattern &P, const CoarseDev &c, const uint8_t *mask,
+                              const double *vals, double *E, double *einv, unsigned *d_flag,
+                              bool deflate, double *h_keep) {
+    hipStream_t st = S.stream;
+    const int nc = c.nc;
+    const int64_t n = P.nrows;
+    double *x = dev_alloc<double>(n + 32), *y = dev_alloc<double>(n + 32);
     RowOp op{};
     op.col = P.d_col;
     op.perm = P.d_perm;
     op.slice_off = P.d_slice_off;
     op.uniform_w = P.uniform_w;
-    op.nrows = (int32_t)nx_;
+    op.nrows = (int32_t)n;
     op.nslices = P.nslices;
     op.nterms = 1;
     op.mode = EPI_LIN;
     op.t[0].vals = vals;
-    op.t[0].x = vref(x);
-    op.y = vref(y);
-    op.y2 = op.yin = op.z = op.mx = op.b = op.pk = op.pkm1 = vref(nullptr);
+    op.t[0].x = vabs(x);
+    op.y = vabs(y);
+    op.y2 = op.yin = op.z = op.mx = op.b = op.pk = op.pkm1 = vabs(nullptr);
     op.ca = 1.0;
-    op.rowmask = mask_;
+    op.post1 = op.post2 = 1.0;
+    op.rowmask = mask;
     RowOp *d_op = dev_upload(&op, 1);
     const Bases B{{nullptr, nullptr, nullptr, nullptr}};
     for (int k = 0; k < nc; ++k) {
-        launch_coarse_column(st, coarse_, k, x, nx_);
+        launch_coarse_column(st, c, k, x, n);
         launch_rowops(st, d_op, 1, P.nslices, P.R, B, 1, P.uniform_w);
-        launch_coarse_restrict(st, coarse_, y, E + k, nc);     // column k of the row-major E
+        launch_coarse_restrict(st, c, y, E + k, nc);     // column k of the row-major E
     }
-    double *d_inv = dev_alloc<double>((size_t)nc * nc);
+    int64_t launches = 4 * (int64_t)nc;     // launch_coarse_column: a zero fill and a scatter
+    if (h_keep)
+        HIPCHK(hipMemcpyAsync(h_keep, E, (size_t)nc * nc * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (deflate) {
+        std::vector<double> diag(nc);
+        HIPCHK(hipMemcpy2DAsync(diag.data(), sizeof(double), E, ((size_t)nc + 1) * sizeof(double),
+                                sizeof(double), nc, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        double tr = 0.0;
+        for (double v : diag) tr += v;
+        launch_add_constant(st, E, tr / ((double)nc * (double)nc), (int64_t)nc * nc);
+        launches += 1;
+    }
     int *d_piv = dev_alloc<int>(1);
     double *d_colbuf = dev_alloc<double>(nc + 1);     // multipliers; slot nc: the pivot
-    unsigned *d_flag = dev_alloc<unsigned>(1);
-    HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
-    launch_dense_inverse(st, E, d_inv, nc, d_piv, d_colbuf, d_flag);
-    unsigned singular = 0;
-    HIPCHK(hipMemcpyAsync(&singular, d_flag, sizeof singular, hipMemcpyDeviceToHost, st));
+    launch_dense_inverse(st, E, einv, nc, d_piv, d_colbuf, d_flag);
+    launches += 1 + 4 * (int64_t)nc;
     HIPCHK(hipStreamSynchronize(st));
-    (void)hipFree(x);
-    (void)hipFree(y);
-    (void)hipFree(E);
-    (void)hipFree(d_op);
-    (void)hipFree(d_piv);
-    (void)hipFree(d_colbuf);
-    (void)hipFree(d_flag);
-    if (singular) {
-        (void)hipFree(d_inv);
-        fail(KKT_ERR_STATE, "coarse matrix P^T A P is singular (a coarse function without support on "
-                            "free rows, or dependent coarse functions)");
+    for (void *q : {(void *)x, (void *)y, (void *)d_op, (void *)d_piv, (void *)d_colbuf})
+        (void)hipFree(q);
+    return launches;
+}
+
+void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
+                  const std::vector<const double *> &vals, const std::vector<double *> &einv,
+                  bool deflate, const char *what) {
+    const Pattern &P = S.patterns[pat];
+    hipStream_t st = S.stream;
+    const int nc = c.nc, nmat = (int)vals.size();
+    const size_t n2 = (size_t)nc * nc;
+    S.coarse_stats = kkt_coarse_stats{};
+    const char *k = S.opt("coarse_keep");
+    const bool keep = k && k[0] == '1';
+    S.coarse_E.clear();
+    if (nmat == 0) return;
+    if (keep) S.coarse_E.resize(n2 * nmat);
+    const char *o = S.opt("coarse_setup");
+    const bool columns = o && std::strcmp(o, "columns") == 0;
+    HIPCHK(hipStreamSynchronize(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    int64_t launches = 0;
+    std::vector<int> bad(nmat, nc);
+    if (columns) {
+        double *E = dev_alloc<double>(n2);
+        unsigned *d_flag = dev_alloc<unsigned>(1);
+        for (int b = 0; b < nmat; ++b) {
+            HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
+            launches += coarse_columns(S, P, c, g.mask, vals[b], E, einv[b], d_flag, deflate,
+                                       keep ? S.coarse_E.data() + b * n2 : nullptr);
+            unsigned singular = 0;
+            HIPCHK(hipMemcpyAsync(&singular, d_flag, sizeof singular, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (singular) bad[b] = -1;      // this path does not know the column
+        }
+        (void)hipFree(E);
+        (void)hipFree(d_flag);
+    } else {
+        // chunks of at most ~1 GiB of Galerkin matrices and scratch (Picard: one matrix per level)
+        const size_t per = n2 * sizeof(double) + dense_inverse_batched_scratch(nc, 1);
+        const int chunk = (int)std::max<size_t>(1, std::min<size_t>(nmat, ((size_t)1 << 30) / per));
+        double *E = dev_alloc<double>(n2 * chunk);
+        const double **d_vals = dev_alloc<const double *>(chunk);
+        double **d_inv = dev_alloc<double *>(chunk);
+        void *scratch = dev_alloc<char>(dense_inverse_batched_scratch(nc, chunk));
+        int *d_bad = dev_alloc<int>(chunk);
+        for (int b0 = 0; b0 < nmat; b0 += chunk) {
+            const int nb = std::min(chunk, nmat - b0);
+            HIPCHK(hipMemcpyAsync(d_vals, vals.data() + b0, nb * sizeof(double *),
+                                  hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_inv, einv.data() + b0, nb * sizeof(double *),
+                                  hipMemcpyHostToDevice, st));
+            launch_zero_bytes(st, E, n2 * nb * sizeof(double));
+            launch_galerkin_batched(st, c, g, d_vals, E, nb);
+            launches += 2;
+            if (keep)
+                HIPCHK(hipMemcpyAsync(S.coarse_E.data() + b0 * n2, E, n2 * nb * sizeof(double),
+                                      hipMemcpyDeviceToHost, st));
+            if (deflate) {
+                // every entry + trace(E) / n_c^2, the diagonal summed on the host in index order
+                std::vector<double> diag((size_t)nc * nb);
+                for (int b = 0; b < nb; ++b)
+                    HIPCHK(hipMemcpy2DAsync(diag.data() + (size_t)b * nc, sizeof(double), E + b * n2,
+                                            ((size_t)nc + 1) * sizeof(double), sizeof(double), nc,
+                                            hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                for (int b = 0; b < nb; ++b) {
+                    double tr = 0.0;
+                    for (int i = 0; i < nc; ++i) tr += diag[(size_t)b * nc + i];
+                    launch_add_constant(st, E + b * n2, tr / ((double)nc * (double)nc), (int64_t)n2);
+                    launches += 1;
+                }
+            }
+            launches += launch_dense_inverse_batched(st, E, d_inv, nc, nb, scratch, d_bad);
+            HIPCHK(hipMemcpyAsync(bad.data() + b0, d_bad, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+        for (void *q : {(void *)E, (void *)d_vals, (void *)d_inv, scratch, (void *)d_bad})
+            (void)hipFree(q);
     }
+    S.coarse_stats.matrices = nmat;
+    S.coarse_stats.launches = launches;
+    S.coarse_stats.n_coarse = nc;
+    S.coarse_stats.ms =
+        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (int b = 0; b < nmat; ++b) {
+        if (bad[b] == nc) continue;
+        char msg[320];
+        if (bad[b] < 0)
+            std::snprintf(msg, sizeof msg, "%s: coarse matrix P^T A P of level matrix %d is singular "
+                          "(a coarse function without support on free rows, or dependent coarse "
+                          "functions)", what, b);
+        else
+            std::snprintf(msg, sizeof msg, "%s: coarse matrix P^T A P of level matrix %d is singular "
+                          "at column %d (pivot below 1e-13 max|diag|: a coarse function without "
+                          "support on free rows, or dependent coarse functions)", what, b, bad[b]);
+        fail(KKT_ERR_STATE, msg);
+    }
+}
+
+void dense_inverse_host(System &S, int n, int nmat, const double *a, double *inv, int *bad) {
+    hipStream_t st = S.stream;
+    const size_t n2 = (size_t)n * n;
+    double *E = dev_upload(a, n2 * nmat);
+    double *I = dev_alloc<double>(n2 * nmat);
+    std::vector<double *> ptr(nmat);
+    for (int b = 0; b < nmat; ++b) ptr[b] = I + b * n2;
+    double **d_inv = dev_upload(ptr.data(), ptr.size());
+    void *scratch = dev_alloc<char>(dense_inverse_batched_scratch(n, nmat));
+    int *d_bad = dev_alloc<int>(nmat);
+    launch_dense_inverse_batched(st, E, d_inv, n, nmat, scratch, d_bad);
+    HIPCHK(hipMemcpyAsync(inv, I, n2 * nmat * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(bad, d_bad, nmat * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (void *q : {(void *)E, (void *)I, (void *)d_inv, scratch, (void *)d_bad}) (void)hipFree(q);
+}
+
+double *SchurPC::coarse_inverse(const double *vals) {
+    const int nc = coarse_.nc;
+    double *d_inv = dev_alloc<double>((size_t)nc * nc);
     einv_owned_.push_back(d_inv);
+    pending_coarse_.emplace_back(vals, d_inv);
     return d_inv;
+}
+
+// every coarse inverse of this build in one batch (before the programs are fused: the tile plan
+// reads the inverses)
+void SchurPC::flush_coarse() {
+    if (pending_coarse_.empty()) return;
+    std::vector<const double *> vals;
+    std::vector<double *> inv;
+    for (auto &pr : pending_coarse_) {
+        vals.push_back(pr.first);
+        inv.push_back(pr.second);
+    }
+    pending_coarse_.clear();
+    coarse_setup(S_, m_pat_, coarse_, galerkin_, vals, inv, false, "Schur sub-solves");
 }
 
 void SchurPC::emit_coarse(const double *r, const double *x_in, double *x_out, const double *einv) {

@@ -56,6 +56,25 @@ struct PcStep {
     uint32_t cepoch0 = 0;           // TILE, coarse: first coarse-exchange tag of this launch minus one
 };
 
+// Coarse set-up of the two-grid solves, shared by the Schur sub-solves and the K_p solve.
+// Structure of E = P^T A P (rows of P^T, rows of A, rows of P in CSR): row i holds every k whose
+// coarse function meets the rows that A couples to coarse function i, ascending.
+void galerkin_structure(int nc, const std::vector<int32_t> &pt_ip, const std::vector<int32_t> &pt_ix,
+                        const std::vector<int32_t> &a_ip, const std::vector<int32_t> &a_ix,
+                        const std::vector<int32_t> &p_ip, const std::vector<int32_t> &p_ix,
+                        std::vector<int32_t> &e_ip, std::vector<int32_t> &e_ix);
+// einv[b] = (P^T A_b P + shift_b 1 1^T)^-1 for a batch of level matrices (SELL values vals[b] on
+// the pattern `pat` of S): one Galerkin launch, a blocked Gauss-Jordan over the batch, or -- option
+// "coarse_setup" = "columns" -- the column path per matrix.  deflate: shift_b = trace(E_b) / nc^2
+// (the K_p solve: E inherits the constants as its kernel).  Fills S.coarse_stats; fails with
+// KKT_ERR_STATE naming the matrix and column of a (relatively) zero pivot.
+void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
+                  const std::vector<const double *> &vals, const std::vector<double *> &einv,
+                  bool deflate, const char *what);
+
+// inv[b] = a_b^-1 for nmat host matrices through the batched device inverse (test hook)
+void dense_inverse_host(System &S, int n, int nmat, const double *a, double *inv, int *bad);
+
 // A device-resident pc_fn: reads the nullspace-corrected right-hand side from in(), leaves
 // pc_fn(b) in out() (both n_local doubles, fixed buffers).
 class PcBase {
@@ -148,7 +167,12 @@ class SchurPC : public PcBase {
     std::vector<double *> einv_owned_;
     double *R_ = nullptr;                // residual of a cycle (one block)
     void build_coarse();
-    double *coarse_inverse(const double *vals);       // (P^T A P)^-1 on the device
+    GalerkinDev galerkin_{};                          // structure of P^T A P on the device
+    // (P^T A P)^-1 on the device: allocated here, formed for all matrices of a build at once by
+    // flush_coarse (the pointer is recorded by the steps emitted before that)
+    double *coarse_inverse(const double *vals);
+    std::vector<std::pair<const double *, double *>> pending_coarse_;
+    void flush_coarse();
     void emit_coarse(const double *r, const double *x_in, double *x_out, const double *einv);
     std::map<std::pair<const double *, uint64_t>, Mat> mats_;
     double *h_u0_ = nullptr, *h_u1_ = nullptr, *h_t_ = nullptr;   // one-block halos

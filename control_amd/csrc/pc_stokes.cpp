@@ -126,7 +126,6 @@ void StokesPC::build_kp_coarse(const kkt_pc_stokes_desc &d) {
     const int nc = (int)d.kp_n_coarse;
     if (nc < 1 || !d.kp_p_indptr || !d.kp_p_indices || !d.kp_p_values)
         fail(KKT_ERR_ARG, "kkt_set_pc_stokes: coarse space of the K_p solve missing");
-    hipStream_t st = S_.stream;
     std::vector<int32_t> ip(d.kp_p_indptr, d.kp_p_indptr + np_ + 1);
     if (ip[0] != 0) fail(KKT_ERR_ARG, "kp_p_indptr must start at 0");
     const int64_t nnz = ip[np_];
@@ -165,51 +164,25 @@ void StokesPC::build_kp_coarse(const kkt_pc_stokes_desc &d) {
     c.ec = dev_alloc<double>((size_t)nc * 2 * n_);
     owned_.push_back(c.rc);
     owned_.push_back(c.ec);
-    // E column by column with the kernels the sweeps use (fixed summation orders)
+    // E = P^T K_p P and its inverse (with the constants deflated) on the device, batched path
+    // unless option "coarse_setup" = "columns"
     const Pattern &P = S_.patterns[Kp_.pat];
-    double *x = dev_alloc<double>(np_ + 32), *y = dev_alloc<double>(np_ + 32);
-    double *E = dev_alloc<double>((size_t)nc * nc);
-    RowOp op = base_op(P);
-    op.mode = EPI_LIN;
-    op.nterms = 1;
-    op.t[0].vals = Kp_.vals;
-    op.t[0].x = vabs(x);
-    op.y = vabs(y);
-    op.ca = 1.0;
-    RowOp *d_op = dev_upload(&op, 1);
-    const Bases B{{nullptr, nullptr, nullptr, nullptr}};
-    for (int k = 0; k < nc; ++k) {
-        launch_coarse_column(st, c, k, x, np_);
-        launch_rowops(st, d_op, 1, P.nslices, P.R, B, 1, P.uniform_w);
-        launch_coarse_restrict(st, c, y, E + k, nc);        // column k of the row-major E
-    }
-    // deflation of the constants: every entry + trace(E) / n_c^2 (diagonal summed on the host in
-    // index order)
+    GalerkinDev g;
     {
-        std::vector<double> diag(nc);
-        HIPCHK(hipMemcpy2DAsync(diag.data(), sizeof(double), E, ((size_t)nc + 1) * sizeof(double),
-                                sizeof(double), nc, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        double tr = 0.0;
-        for (double v : diag) tr += v;
-        launch_add_constant(st, E, tr / ((double)nc * (double)nc), (int64_t)nc * nc);
+        std::vector<int32_t> e_ip, e_ix;
+        galerkin_structure(nc, tip, tix, P.h_indptr, P.h_indices, ip, ix, e_ip, e_ix);
+        g.e_ip = up(e_ip);
+        g.e_ix = up(e_ix);
     }
+    g.col = P.d_col;
+    g.slice_off = P.d_slice_off;
+    g.pos = P.h_pos_of.empty() ? nullptr : up(P.h_pos_of);
+    g.mask = nullptr;
+    g.R = P.R;
+    g.uniform_w = P.uniform_w;
     kp_einv_ = dev_alloc<double>((size_t)nc * nc);
     owned_.push_back(kp_einv_);
-    int *d_piv = dev_alloc<int>(1);
-    double *d_colbuf = dev_alloc<double>(nc + 1);
-    unsigned *d_flag = dev_alloc<unsigned>(1);
-    HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
-    launch_dense_inverse(st, E, kp_einv_, nc, d_piv, d_colbuf, d_flag);
-    unsigned singular = 0;
-    HIPCHK(hipMemcpyAsync(&singular, d_flag, sizeof singular, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (void *q : {(void *)x, (void *)y, (void *)E, (void *)d_op, (void *)d_piv, (void *)d_colbuf,
-                    (void *)d_flag})
-        (void)hipFree(q);
-    if (singular)
-        fail(KKT_ERR_STATE, "coarse matrix of the K_p solve is singular beyond the constants "
-                            "(dependent coarse functions?)");
+    coarse_setup(S_, Kp_.pat, c, g, {Kp_.vals}, {kp_einv_}, true, "K_p solve");
 }
 
 void StokesPC::emit_kp_two_grid(int its, double emin, double emax, const double *b, double *out) {

@@ -207,6 +207,8 @@ struct System {
 
     // byte accounting
     kkt_info info{};
+    kkt_coarse_stats coarse_stats{};   // last two-grid coarse set-up (kkt_coarse_setup_stats)
+    std::vector<double> coarse_E;      // its Galerkin matrices (option "coarse_keep" = "1")
 
     // preconditioner
     std::unique_ptr<PcBase> pc;

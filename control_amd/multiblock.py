@@ -347,6 +347,34 @@ class MultiBlockSystem:
         self._ck(self._lib.kkt_get_info(self._h, C.byref(inf)))
         return inf.as_dict()
 
+    def coarse_setup_stats(self):
+        """``kkt_coarse_setup_stats``: the last coarse set-up of the two-grid solves on this
+        handle -- ``matrices`` formed and inverted, kernel ``launches``, wall time ``ms`` and
+        ``n_coarse``."""
+        st = _lib.CoarseStats()
+        self._ck(self._lib.kkt_coarse_setup_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def coarse_matrices(self):
+        """``kkt_debug_coarse_matrices``: the Galerkin matrices P^T A P of the last coarse set-up,
+        shape ``(matrices, n_coarse, n_coarse)`` (needs option ``coarse_keep`` = ``1``)."""
+        st = self.coarse_setup_stats()
+        E = np.empty((st["matrices"], st["n_coarse"], st["n_coarse"]))
+        self._ck(self._lib.kkt_debug_coarse_matrices(self._h, E.ctypes.data_as(_lib.c_f64p), E.size))
+        return E
+
+    def debug_dense_inverse(self, A):
+        """``kkt_debug_dense_inverse``: inverses of a batch ``A`` (nmat, n, n) by the device's
+        blocked Gauss-Jordan, and per matrix the first column with a too small pivot (n: none)."""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        nmat, n, _ = A.shape
+        inv = np.empty_like(A)
+        bad = np.empty(nmat, dtype=np.int32)
+        self._ck(self._lib.kkt_debug_dense_inverse(self._h, n, nmat, A.ctypes.data_as(_lib.c_f64p),
+                                                   inv.ctypes.data_as(_lib.c_f64p),
+                                                   bad.ctypes.data_as(_lib.c_i32p)))
+        return inv, bad
+
     def update_block_values(self, quadrant, i, j, A):
         """New values on a stored block's structure (Picard re-linearisation)."""
         _, indices, data = _as_csr(A)

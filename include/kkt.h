@@ -95,6 +95,8 @@ const char *kkt_last_error(kkt_handle h);
  *   "tile_waves"  "1".."8"       waves per workgroup of the tile form (default 8)
  *   "stage_timers" "1"           HIP events around the stages of every Krylov iteration
  *                                (kkt_get_stage_times)
+ *   "coarse_setup" "columns"     two-grid set-up column by column (the previous path; default:
+ *                                batched Galerkin products and blocked Gauss-Jordan on the device)
  *   "lanes", "lane_chunks", "kernarg_ops", "shared_rows", "verbose"   diagnostics
  * The library never reads the process environment: a key that was never set has its default.
  * (The Python mirror forwards KKT_<KEY> variables of developer scripts as explicit calls.) */
@@ -336,6 +338,25 @@ typedef struct kkt_pc_stage_times {
     int64_t sweep_launches, sweep_phases, batched_launches, comm_steps;
 } kkt_pc_stage_times;
 int kkt_time_pc_stages(kkt_handle h, const double *d_x, double *d_y, kkt_pc_stage_times *out);
+
+/* The last coarse set-up of the two-grid sub-solves built on this handle (kkt_set_pc_schur, every
+ * rebuild after kkt_update_block_values; kkt_set_pc_stokes: the K_p solve -- the velocity
+ * sub-solves report on the inner handle): Galerkin matrices P^T A P formed and inverted, kernel
+ * launches issued, wall time between two synchronisations of the library's stream, and the
+ * coarse dimension.  All zero before any set-up.  Option "coarse_setup" = "columns" selects the
+ * previous column-by-column path (3 launches per coarse function, 4 per pivot) for A/B runs. */
+typedef struct kkt_coarse_stats {
+    int64_t matrices, launches, n_coarse;
+    double ms;
+} kkt_coarse_stats;
+int kkt_coarse_setup_stats(kkt_handle h, kkt_coarse_stats *out);
+/* Test hooks of the coarse set-up.  With option "coarse_keep" = "1" every set-up keeps its Galerkin
+ * matrices P^T A P (before any deflation) on the host: kkt_debug_coarse_matrices copies them,
+ * matrices x n_coarse^2 doubles row-major in set-up order (cap: doubles available at out).
+ * kkt_debug_dense_inverse inverts nmat host matrices (n x n, row-major, contiguous) with the
+ * batched device inverse; bad[b] = first column with a pivot below 1e-13 max|diag| (n: none). */
+int kkt_debug_coarse_matrices(kkt_handle h, double *out, int64_t cap);
+int kkt_debug_dense_inverse(kkt_handle h, int n, int nmat, const double *a, double *inv, int *bad);
 
 /* Step-locked parity hook (tests): while set, kkt_solve / kkt_solve_device with gmres or
  * fgmres replace their Krylov basis v_0 .. v_it by the caller's vectors before inner step `it`
