@@ -83,7 +83,8 @@ class PcStageTimes(C.Structure):
 
 
 class CoarseStats(C.Structure):
-    _fields_ = [(n, C.c_int64) for n in ("matrices", "launches", "n_coarse")] + [("ms", C.c_double)]
+    _fields_ = ([(n, C.c_int64) for n in ("matrices", "launches", "n_coarse")] + [("ms", C.c_double)]
+                + [(n, C.c_int64) for n in ("blocks", "block_n")])
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -152,6 +153,7 @@ SIGNATURES = {
                                      C.POINTER(PcStageTimes)]),
     "kkt_coarse_setup_stats": (C.c_int, [C.c_void_p, C.POINTER(CoarseStats)]),
     "kkt_debug_coarse_matrices": (C.c_int, [C.c_void_p, c_f64p, C.c_int64]),
+    "kkt_debug_coarse_inverses": (C.c_int, [C.c_void_p, c_f64p, C.c_int64]),
     "kkt_debug_dense_inverse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p]),
     "kkt_debug_set_steplock": (C.c_int, [C.c_void_p, C.POINTER(StepLock)]),
     "kkt_get_info": (C.c_int, [C.c_void_p, C.POINTER(Info)]),

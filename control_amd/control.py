@@ -21,7 +21,26 @@ import scipy.sparse as sp
 from .blocks import (conform_to, instationary_blocks, instationary_incompressible_blocks,
                      stationary_blocks, stationary_incompressible_blocks)
 
-__all__ = ["Instationary", "Stationary", "GpuBackend", "suggest_chebyshev"]
+__all__ = ["Instationary", "Stationary", "GpuBackend", "suggest_chebyshev", "coarse_space"]
+
+
+def coarse_space(coords, boundary=(), copies=1, interleaved=False):
+    """Coarse space of the two-grid sub-solves ``Multigrid=True`` builds: the multilinear coarse
+    functions (``control_amd.coarse``) of a tensor grid over the bounding box of ``coords`` with
+    33^2 nodes in 2-D (256^2 P1, 128^2 P2 velocity and P1 pressure: cells of 8, 4 and 4 mesh
+    widths, the coarse spaces ``bench.py`` measures) and 9^3 in 3-D.  ``copies`` > 1: a
+    vector-valued space whose dofs are ``copies`` component-major copies of the nodes at
+    ``coords`` -- each component gets its own coarse functions; ``interleaved``: the dofs of a
+    node are consecutive instead (Firedrake's layout of a vector space).  Small meshes get at
+    most one coarse node per 2^dim nodes (a coarse space as fine as the mesh would make
+    ``P^T A P`` singular).  ``n x n_c`` CSR, rows of the ``boundary`` dofs empty."""
+    from .coarse import cells_for, multilinear_coarse_space
+    X = np.asarray(coords, dtype=np.float64)
+    dim = X.shape[1]
+    cells = cells_for(X, min(33 ** 2 if dim <= 2 else 9 ** 3, len(X) / 2.0 ** dim))
+    if copies > 1:
+        X = np.repeat(X, int(copies), axis=0) if interleaved else np.vstack([X] * int(copies))
+    return multilinear_coarse_space(X, boundary, cells=cells)
 
 
 def suggest_chebyshev(D, M, shift, nodes, safety=2.0):
@@ -58,7 +77,23 @@ class GpuBackend:
     """The classes ``linear_solve`` instantiates (``preconditioner.preconditioner`` names).
 
     ``schur``: ``(its, emin, emax)`` of the Chebyshev sweeps that replace the reference's AMG
-    sub-solves, or ``"auto"`` (default): ``suggest_chebyshev`` on the first time level's matrix."""
+    sub-solves, or ``"auto"`` (default): degree and intervals from spectrum estimates on the
+    device.
+
+    With ``Multigrid=True`` the drivers pass ``coarse=`` (the coarse space: a CSR prolongation
+    with one row per dof) and the sub-solves take the two-grid form ``bench.py`` measures:
+    ``TWO_GRID_CYCLES`` x [Galerkin correction, Chebyshev sweeps on the upper part of the
+    spectrum] -- ``schur`` and ``kp`` are then not used.  The mass solves keep their 20 sweeps
+    (the reference's ``Multigrid`` swaps them for AMG too; the Jacobi-scaled mass matrix is well
+    conditioned already)."""
+
+    TWO_GRID_CYCLES = 2
+    # smoothing sweeps per cycle (its, emin, emax): heat BE / stationary 2 x 8 on [0.07, 2.1],
+    # CN 2 x 16 on [0.03, 2.1] (bench.py heat2d); Stokes velocity 8 on [0.07, 2.25], K_p (constants
+    # deflated) 12 on [0.05, 2.1] (bench.py stokes2d)
+    TWO_GRID_SWEEPS = {"BE": (8, 0.07, 2.1), "stationary": (8, 0.07, 2.1), "CN": (16, 0.03, 2.1)}
+    TWO_GRID_STOKES = (8, 0.07, 2.25)
+    TWO_GRID_KP = (12, 0.05, 2.1)
 
     def __init__(self, schur="auto", device=0, kp=None):
         from . import multiblock as mb
@@ -71,17 +106,25 @@ class GpuBackend:
         return self._mb.MultiBlockSystem(*a, device=self.device, **kw)
 
     def construct_pc(self, kind, M, block_01, block_10, n_t, tau, beta, nodes, lambda_v_bounds,
-                     epsilon):
+                     epsilon, coarse=None, sweeps=None):
+        """``coarse`` (``Multigrid=True``): the coarse space of the two-grid sub-solves, whose
+        smoothing sweeps are ``sweeps`` (default ``TWO_GRID_SWEEPS[kind]``)."""
         mb = self._mb
-        schur = self.schur
-        if isinstance(schur, str):
-            # "auto": degree and one interval per sub-solve matrix from Lanczos estimates on the
-            # device (kkt_pc_desc: schur_its = -1, schur_emin = 0); the first and last time levels
-            # carry smaller shifts (control.py:2241-2327) and get their own, wider, intervals
-            schur = (-1, 0.0, 0.0)
+        if coarse is not None:
+            spec = mb.ChebSpec(*(sweeps or self.TWO_GRID_SWEEPS[kind]),
+                               coarse=mb.CoarseSpace(coarse, self.TWO_GRID_CYCLES))
+        else:
+            schur = self.schur
+            if isinstance(schur, str):
+                # "auto": degree and one interval per sub-solve matrix from Lanczos estimates on
+                # the device (kkt_pc_desc: schur_its = -1, schur_emin = 0); the first and last
+                # time levels carry smaller shifts (control.py:2241-2327) and get their own,
+                # wider, intervals
+                schur = (-1, 0.0, 0.0)
+            spec = mb.ChebSpec(*schur)
         return mb.SchurPC(kind=kind, M=M, beta=beta, bc_nodes=nodes,
                           mass=mb.ChebSpec(20, *lambda_v_bounds),      # control.py:1967-1982
-                          schur=mb.ChebSpec(*schur), n_t=n_t, tau=tau, epsilon=epsilon)
+                          schur=spec, n_t=n_t, tau=tau, epsilon=epsilon)
 
 
     def _kp_spec(self, inner_pc):
@@ -91,9 +134,19 @@ class GpuBackend:
             return (-1, 0.0, 0.0)       # kkt_pc_stokes_desc: follow the inner sub-solves
         return self.kp
 
+    def _kp(self, inner_pc, coarse):
+        mb = self._mb
+        if coarse is None:
+            return mb.ChebSpec(*self._kp_spec(inner_pc))
+        # two-grid K_p solve: the library deflates the constants of the Neumann problem
+        return mb.ChebSpec(*self.TWO_GRID_KP, coarse=mb.CoarseSpace(coarse[1],
+                                                                    self.TWO_GRID_CYCLES))
+
     def construct_stokes_pc(self, th, blocks, n_t, tau, beta, CN, lambda_v_bounds,
-                            lambda_p_bounds, epsilon):
-        """``pc_fn`` of ``control.py:4318-4687`` as a ``StokesPC`` descriptor."""
+                            lambda_p_bounds, epsilon, coarse=None):
+        """``pc_fn`` of ``control.py:4318-4687`` as a ``StokesPC`` descriptor.  ``coarse``
+        (``Multigrid=True``): coarse spaces ``(P_v, P_p)`` of the velocity sub-solves and of the
+        ``K_p`` solve."""
         mb, m = self._mb, blocks["m"]
         nsv = mb.DirichletBCNullspace(th.boundary_v)
         inner = self.MultiBlockSystem(th.n_v, th.n_v, *blocks["inner"], n_blocks_00=m,
@@ -101,28 +154,31 @@ class GpuBackend:
                                       nullspace_1=(nsv,) * m, CN=CN)
         comm = self.MultiBlockSystem(th.n_p, th.n_p, *blocks["commutator"], n_blocks_00=m,
                                      n_blocks_11=m)
+        kw = {} if coarse is None else dict(coarse=coarse[0], sweeps=self.TWO_GRID_STOKES)
         inner_pc = self.construct_pc("CN" if CN else "BE", th.M_v, blocks["inner"][1],
                                      blocks["inner"][2], n_t, tau, beta, th.boundary_v,
-                                     lambda_v_bounds, epsilon)
+                                     lambda_v_bounds, epsilon, **kw)
         return mb.StokesPC(inner=inner, inner_pc=inner_pc, commutator=comm, B=th.B, K_p=th.K_p,
-                           M_p=th.M_p, kp=mb.ChebSpec(*self._kp_spec(inner_pc)),
+                           M_p=th.M_p, kp=self._kp(inner_pc, coarse),
                            mp=mb.ChebSpec(20, *lambda_p_bounds), n_p_blocks=m, b_scale=tau,
                            post_scale=1.0 / tau**2, cn=CN)
 
 
     def construct_stokes_pc_stationary(self, th, D_v, D_p, beta, lambda_v_bounds,
-                                       lambda_p_bounds):
-        """``pc_fn`` of ``control.py:986-1085`` as a ``StokesPC`` descriptor."""
+                                       lambda_p_bounds, coarse=None):
+        """``pc_fn`` of ``control.py:986-1085`` as a ``StokesPC`` descriptor (``coarse``: as in
+        ``construct_stokes_pc``)."""
         mb = self._mb
         nsv = (mb.DirichletBCNullspace(th.boundary_v),)
         i00, i01, i10, i11 = stationary_blocks(th.M_v, D_v, beta)
         inner = self.MultiBlockSystem(th.n_v, th.n_v, i00, i01, i10, i11, nullspace_0=nsv,
                                       nullspace_1=nsv)
         comm = self.MultiBlockSystem(th.n_p, th.n_p, *stationary_blocks(th.M_p, D_p, beta))
+        kw = {} if coarse is None else dict(coarse=coarse[0], sweeps=self.TWO_GRID_STOKES)
         inner_pc = self.construct_pc("stationary", th.M_v, i01, i10, 1, 0.0, beta,
-                                     th.boundary_v, lambda_v_bounds, 0.0)
+                                     th.boundary_v, lambda_v_bounds, 0.0, **kw)
         return mb.StokesPC(inner=inner, inner_pc=inner_pc, commutator=comm, B=th.B, K_p=th.K_p,
-                           M_p=th.M_p, kp=mb.ChebSpec(*self._kp_spec(inner_pc)),
+                           M_p=th.M_p, kp=self._kp(inner_pc, coarse),
                            mp=mb.ChebSpec(20, *lambda_p_bounds))
 
 
@@ -146,6 +202,25 @@ class _VelocitySpace:
         self.M, self.K, self.n_dofs = th.M_v, th.K_v, th.n_v
         self.coords, self.boundary = th.coords_v, th.boundary_v
         self.bc_coords = th.coords_v[th.boundary_v[:nb]]
+
+
+def _multigrid_kw(disc, Multigrid):
+    """``coarse=`` of a scalar driver's ``construct_pc`` call: only with ``Multigrid=True``, so
+    that backends without two-grid support keep working with the default."""
+    if not Multigrid:
+        return {}
+    return dict(coarse=coarse_space(disc.coords, disc.boundary))
+
+
+def _multigrid_stokes_kw(th, Multigrid):
+    """``coarse=(P_v, P_p)`` of a Stokes driver's pc construction (``Multigrid=True`` only): one
+    copy of the coarse functions per velocity component, and the pressure space's without
+    boundary rows (the ``K_p`` solve deflates the constants)."""
+    if not Multigrid:
+        return {}
+    Xv = np.asarray(th.coords_v)
+    return dict(coarse=(coarse_space(Xv, th.boundary_v, copies=th.n_v // len(Xv)),
+                        coarse_space(th.coords_p)))
 
 
 class Instationary:
@@ -300,9 +375,14 @@ class Instationary:
         return b_0, b_1
 
     def linear_solve(self, *, P=None, solver_parameters=None, lambda_v_bounds=None,
-                     v_d=None, f=None, print_error=False, backend=None):
+                     v_d=None, f=None, print_error=False, backend=None, Multigrid=False):
         """``control.py:2800-3330``.  Returns the KSP-like object of the solve; the fields are
-        in ``self._v`` / ``self._zeta`` (all ``n_t`` levels, boundary values included)."""
+        in ``self._v`` / ``self._zeta`` (all ``n_t`` levels, boundary values included).
+
+        ``Multigrid=True`` (the reference's keyword): two-grid sub-solves, a Galerkin coarse
+        correction on 33^2 (2-D) / 9^3 (3-D) multilinear coarse functions per component in
+        front of each group of Chebyshev sweeps (``GpuBackend``); the backend receives the coarse
+        space as ``coarse=``.  In 3-D the plain sweeps are faster."""
         backend = backend or GpuBackend()
         disc, n_t, beta, CN = self._disc, self._n_t, self._beta, self._CN
         M, nodes = disc.M, disc.boundary
@@ -327,7 +407,8 @@ class Instationary:
 
         if P is None:                                                # :3245-3258
             pc_fn = backend.construct_pc("CN" if CN else "BE", M, b01, b10, n_t, tau, beta,
-                                         nodes, lambda_v_bounds or (0.5, 2.0), 1.0e-3)
+                                         nodes, lambda_v_bounds or (0.5, 2.0), 1.0e-3,
+                                         **_multigrid_kw(disc, Multigrid))
         else:
             pc_fn = P
         if solver_parameters is None:                                # :3260-3266
@@ -392,9 +473,9 @@ class Instationary:
     def non_linear_solve(self, *, P=None, solver_parameters=None, lambda_v_bounds=None,
                          max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                          absolute_non_linear_tol=1.0e-8, print_error_non_linear=False,
-                         backend=None):
+                         backend=None, Multigrid=False):
         """``control.py:3377-3560``: Picard loop around ``linear_solve``; returns the residual
-        norms (initial one first)."""
+        norms (initial one first).  ``Multigrid``: as in ``linear_solve``."""
         disc, n_t, CN = self._disc, self._n_t, self._CN
         v_0 = (np.zeros(disc.n_dofs) if self._initial_condition is None
                else np.asarray(self._initial_condition(disc.coords), dtype=np.float64))
@@ -413,7 +494,7 @@ class Instationary:
             self._v = v_old          # linear_solve linearises at self._v (control.py:2886)
             self.linear_solve(P=P, solver_parameters=solver_parameters,
                               lambda_v_bounds=lambda_v_bounds, v_d=rhs_0, f=rhs_1,
-                              backend=backend)
+                              backend=backend, Multigrid=Multigrid)
             v_old = v_old + self._v
             for i in range(n_t):                                     # :3490-3493
                 v_old[i, disc.boundary] = self._bc_values(i)[disc.boundary]
@@ -443,12 +524,19 @@ class Instationary:
     def incompressible_linear_solve(self, nullspace_p=None, *, forward_operator_p=None, P=None,
                                     solver_parameters=None, lambda_v_bounds=None,
                                     lambda_p_bounds=None, v_d=None, f=None, div_v=None,
-                                    div_zeta=None, print_error=False, backend=None):
+                                    div_zeta=None, print_error=False, backend=None,
+                                    Multigrid=False):
         """``control.py:3592-4760``: the Stokes-type control solve.  ``nullspace_p`` is the
         nullspace class instance put on every pressure block (``ConstantNullspace()`` for
         enclosed flow, ``test/test_control.py:3167``); ``forward_operator_p(v_i, t)`` is the
         forward form on the pressure space (default ``K_p``, ``control.py:3783-3785``).
-        Fields afterwards: ``_v``, ``_zeta`` (``n_t`` levels), ``_p``, ``_mu`` (``m`` levels)."""
+        Fields afterwards: ``_v``, ``_zeta`` (``n_t`` levels), ``_p``, ``_mu`` (``m`` levels).
+
+        ``Multigrid=True``: two-grid velocity sub-solves (coarse functions per velocity
+        component) and a two-grid ``K_p`` solve (constants deflated), the forms ``bench.py``
+        measures on the Stokes workload; the backend receives ``coarse=(P_v, P_p)``.  On 128^2
+        P2-P1 x 32 the outer FGMRES(10) needs about 108 iterations -- above the default
+        ``maximum_iterations`` of 100."""
         backend = backend or GpuBackend()
         th = self._th
         if th is None:
@@ -495,7 +583,8 @@ class Instationary:
         if P is None:
             pc_fn = backend.construct_stokes_pc(th, bl, n_t, tau, beta, CN,
                                                 lambda_v_bounds or (0.3924, 2.0598),
-                                                lambda_p_bounds or (0.5, 2.0), 1.0e-3)
+                                                lambda_p_bounds or (0.5, 2.0), 1.0e-3,
+                                                **_multigrid_stokes_kw(th, Multigrid))
         else:
             pc_fn = P
         nsv = tuple(backend.DirichletBCNullspace(nodes) for _ in range(2 * m))
@@ -586,7 +675,8 @@ class Stationary:
         return M @ self._desired_state(X), f
 
     def linear_solve(self, *, P=None, solver_parameters=None, lambda_v_bounds=None, v_d=None,
-                     f=None, print_error=False, backend=None):
+                     f=None, print_error=False, backend=None, Multigrid=False):
+        """``control.py:487-604``.  ``Multigrid``: as in ``Instationary.linear_solve``."""
         backend = backend or GpuBackend()
         disc, beta = self._disc, self._beta
         M, nodes = disc.M, disc.boundary
@@ -604,7 +694,8 @@ class Stationary:
         b00, b01, b10, b11 = stationary_blocks(M, D_v, beta)
         if P is None:
             pc_fn = backend.construct_pc("stationary", M, b01, b10, 1, 0.0, beta, nodes,
-                                         lambda_v_bounds or (0.5, 2.0), 0.0)
+                                         lambda_v_bounds or (0.5, 2.0), 0.0,
+                                         **_multigrid_kw(disc, Multigrid))
         else:
             pc_fn = P
         if solver_parameters is None:        # control.py:556-562
@@ -633,7 +724,7 @@ class Stationary:
     def non_linear_solve(self, *, P=None, solver_parameters=None, lambda_v_bounds=None,
                          max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                          absolute_non_linear_tol=1.0e-8, print_error_non_linear=False,
-                         backend=None):
+                         backend=None, Multigrid=False):
         """``control.py:640-760``; returns the residual norms (initial one first)."""
         v_old, zeta_old = self._v.copy(), self._zeta.copy()
         v_d, f = self._data()
@@ -644,7 +735,7 @@ class Stationary:
         while norm_k > relative_non_linear_tol * norm_0 and norm_k > absolute_non_linear_tol:
             self.linear_solve(P=P, solver_parameters=solver_parameters,
                               lambda_v_bounds=lambda_v_bounds, v_d=rhs_0, f=rhs_1,
-                              backend=backend)
+                              backend=backend, Multigrid=Multigrid)
             v_old = v_old + self._v
             if self._bcs_v is not None:
                 v_old[self._disc.boundary] = self._v_inhom()[self._disc.boundary]
@@ -667,9 +758,11 @@ class Stationary:
     def incompressible_linear_solve(self, nullspace_p=None, *, forward_operator_p=None, P=None,
                                     solver_parameters=None, lambda_v_bounds=None,
                                     lambda_p_bounds=None, v_d=None, f=None, div_v=None,
-                                    div_zeta=None, print_error=False, backend=None):
+                                    div_zeta=None, print_error=False, backend=None,
+                                    Multigrid=False):
         """``control.py:802-1110``: stationary Stokes-type control.  Fields afterwards: ``_v``,
-        ``_zeta`` (velocity space, component-major), ``_p``, ``_mu``."""
+        ``_zeta`` (velocity space, component-major), ``_p``, ``_mu``.  ``Multigrid``: as in
+        ``Instationary.incompressible_linear_solve``."""
         backend = backend or GpuBackend()
         th = self._th
         if th is None:
@@ -700,7 +793,7 @@ class Stationary:
         if P is None:
             pc_fn = backend.construct_stokes_pc_stationary(
                 th, D_v, D_p, beta, lambda_v_bounds or (0.3924, 2.0598),
-                lambda_p_bounds or (0.5, 2.0))
+                lambda_p_bounds or (0.5, 2.0), **_multigrid_stokes_kw(th, Multigrid))
         else:
             pc_fn = P
         if solver_parameters is None:                                # :921-927
@@ -725,7 +818,8 @@ class Stationary:
                                         lambda_p_bounds=None, max_non_linear_iter=10,
                                         relative_non_linear_tol=1.0e-5,
                                         absolute_non_linear_tol=1.0e-8,
-                                        print_error_non_linear=False, backend=None):
+                                        print_error_non_linear=False, backend=None,
+                                        Multigrid=False):
         """``control.py:1112-1480``: Picard loop of stationary Navier-Stokes-type control around
         ``incompressible_linear_solve``; returns the residual norms (initial one first)."""
         th = self._th
@@ -756,7 +850,7 @@ class Stationary:
                 nullspace_p, forward_operator_p=forward_operator_p, P=P,
                 solver_parameters=solver_parameters, lambda_v_bounds=lambda_v_bounds,
                 lambda_p_bounds=lambda_p_bounds, v_d=r00, f=r01, div_v=r10, div_zeta=r11,
-                backend=backend)
+                backend=backend, Multigrid=Multigrid)
             v_old = v_old + self._v
             if self._bcs_v is not None:
                 v_old[nodes] = self._v_inhom()[nodes]

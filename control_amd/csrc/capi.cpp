@@ -72,7 +72,7 @@ int kkt_set_option(kkt_handle h, const char *key, const char *value) {
                                       "lanes", "lane_chunks", "kernarg_ops", "shared_rows",
                                       "verbose", "stamps", "tile_poll_delay", "tile_unfused",
                                       "debug_drop_handoff", "stage_timers", "sell_sigma", "ragged_switch", "ragged_xcd", "apply_xcd", "pc_xcd",
-                                      "interleave", "coarse_setup", "coarse_keep"};
+                                      "interleave", "coarse_setup", "coarse_keep", "coarse_blocks"};
         if (!key || !value) fail(KKT_ERR_ARG, "null option");
         bool ok = false;
         for (const char *k : known) ok = ok || std::strcmp(k, key) == 0;
@@ -343,6 +343,14 @@ int kkt_debug_coarse_matrices(kkt_handle h, double *out, int64_t cap) {
         if (!out && cap > 0) fail(KKT_ERR_ARG, "null argument");
         if ((size_t)cap < S.coarse_E.size()) fail(KKT_ERR_ARG, "buffer too small for the coarse matrices");
         std::copy(S.coarse_E.begin(), S.coarse_E.end(), out);
+    });
+}
+
+int kkt_debug_coarse_inverses(kkt_handle h, double *out, int64_t cap) {
+    KKT_TRY(h, {
+        if (!out && cap > 0) fail(KKT_ERR_ARG, "null argument");
+        if ((size_t)cap < S.coarse_Einv.size()) fail(KKT_ERR_ARG, "buffer too small for the coarse inverses");
+        std::copy(S.coarse_Einv.begin(), S.coarse_Einv.end(), out);
     });
 }
 

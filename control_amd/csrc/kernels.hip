@@ -2744,10 +2744,14 @@ __global__ __launch_bounds__(256) void galerkin_kernel(CoarseDev c, GalerkinDev 
     __shared__ double sh[256];
     const int i = blockIdx.x, nc = c.nc;
     const double *__restrict__ a = vals[blockIdx.y];
-    double *__restrict__ Erow = E + (size_t)blockIdx.y * nc * nc + (size_t)i * nc;
+    // block_n > 0: row i lands in its diagonal block, stored as a matrix of its own
+    const int bn = g.block_n > 0 ? g.block_n : nc, kb = i / bn, k0 = kb * bn;
+    double *__restrict__ Erow =
+        E + ((size_t)blockIdx.y * (nc / bn) + kb) * bn * bn + (size_t)(i - k0) * bn;
     const int C = 64 * g.R;
     for (int32_t e = g.e_ip[i]; e < g.e_ip[i + 1]; ++e) {
         const int k = g.e_ix[e];
+        if ((unsigned)(k - k0) >= (unsigned)bn) continue;     // (outside the block: none)
         double s = 0.0;
         for (int32_t q = c.pt_ip[i] + threadIdx.x; q < c.pt_ip[i + 1]; q += 256) {
             const int r = c.pt_ix[q];
@@ -2777,7 +2781,7 @@ __global__ __launch_bounds__(256) void galerkin_kernel(CoarseDev c, GalerkinDev 
             if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
             __syncthreads();
         }
-        if (threadIdx.x == 0) Erow[k] = sh[0];
+        if (threadIdx.x == 0) Erow[k - k0] = sh[0];
         __syncthreads();
     }
 }
@@ -2984,6 +2988,30 @@ int launch_dense_inverse_batched(hipStream_t s, double *a, double *const *d_inv,
         launches += 2;
     }
     return launches;
+}
+
+// Component blocks of a block-diagonal E (nc = nblk * bn, block k = indices [k bn, (k+1) bn)).
+// Scatter: inv[b] (nc x nc, row-major) = the block inverses Ib[b * nblk + k] on the diagonal,
+// exact zeros elsewhere (every entry written).
+__global__ __launch_bounds__(256) void coarse_block_scatter_kernel(const double *__restrict__ Ib,
+                                                                   double *const *__restrict__ inv,
+                                                                   int nc, int bn, int nblk) {
+    const int b = blockIdx.y;
+    double *out = inv[b];
+    const size_t b2 = (size_t)bn * bn;
+    const double *src = Ib + (size_t)b * nblk * b2;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < (size_t)nc * nc;
+         t += (size_t)gridDim.x * blockDim.x) {
+        const int r = (int)(t / nc), c = (int)(t - (size_t)r * nc);
+        const int kr = r / bn, kc = c / bn;
+        out[t] = kr == kc ? src[(size_t)kr * b2 + (size_t)(r - kr * bn) * bn + (c - kc * bn)] : 0.0;
+    }
+}
+void launch_coarse_block_scatter(hipStream_t s, const double *Ib, double *const *d_inv, int nc,
+                                 int bn, int nmat) {
+    if (nc <= 0 || bn <= 0 || nmat <= 0) return;
+    hipLaunchKernelGGL(coarse_block_scatter_kernel, dim3(grid_for((int64_t)nc * nc, 256, 1024), nmat),
+                       dim3(256), 0, s, Ib, d_inv, nc, bn, nc / bn);
 }
 
 // the time-out word of the sweep programs as a summand of the Krylov all-reduce (time shards)

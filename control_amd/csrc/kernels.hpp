@@ -325,13 +325,17 @@ void launch_dense_inverse(hipStream_t s, double *a, double *inv, int n, int *d_p
 // Batched coarse set-up.  E_b = P^T A_b P (rows of A_b masked) for nmat level matrices on one
 // SELL structure, one launch; the structure of E comes from the host (e_ip / e_ix).  Sums in the
 // order of the column path (launch_coarse_column + SpMV + launch_coarse_restrict): bit-identical
-// to it.  E: nmat row-major nc x nc matrices, zeroed by the caller.
+// to it.  E: nmat row-major nc x nc matrices (block_n > 0: their diagonal blocks), zeroed by the
+// caller.
 struct GalerkinDev {
     const int32_t *e_ip = nullptr, *e_ix = nullptr;   // structure of E: nc rows
     const int32_t *col = nullptr, *slice_off = nullptr;   // SELL structure of A
     const int32_t *pos = nullptr;                     // position of each row (null: position == row)
     const uint8_t *mask = nullptr;                    // masked rows of A P are zero
     int R = 2, uniform_w = -1;
+    // > 0: E is block diagonal in nc / block_n ranges of this size, and the Galerkin launch writes
+    // each diagonal block as a matrix of its own (nmat * nc / block_n contiguous block_n^2 ones)
+    int block_n = 0;
 };
 void launch_galerkin_batched(hipStream_t s, const CoarseDev &c, const GalerkinDev &g,
                              const double *const *d_vals, double *E, int nmat);
@@ -342,6 +346,11 @@ void launch_galerkin_batched(hipStream_t s, const CoarseDev &c, const GalerkinDe
 size_t dense_inverse_batched_scratch(int n, int nmat);
 int launch_dense_inverse_batched(hipStream_t s, double *a, double *const *d_inv, int n, int nmat,
                                  void *scratch, int *d_bad);
+// Block-diagonal E (nc = nblk * bn; block k: indices [k bn, (k+1) bn)), one launch for all nmat
+// matrices: every entry of inv[b] (nc x nc) -- the block inverses Ib[b * nblk + k] (bn x bn,
+// contiguous) on the diagonal, exact zeros elsewhere.
+void launch_coarse_block_scatter(hipStream_t s, const double *Ib, double *const *d_inv, int nc,
+                                 int bn, int nmat);
 void launch_flag_to_double(hipStream_t s, const unsigned *flag, double *out);
 // w += sign * sum_i coef[i] * V_i   (coef in device memory)
 void launch_maxpy(hipStream_t s, double *w, VecList V, const double *coef, double sign,

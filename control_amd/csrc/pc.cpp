@@ -1119,11 +1119,37 @@ void SchurPC::build_coarse() {
         galerkin_.mask = mask_;
         galerkin_.R = P.R;
         galerkin_.uniform_w = P.uniform_w;
+        galerkin_.block_n = coarse_block_size(nc, e_ip, e_ix);
     }
     coarse_.rc = dev_alloc<double>(nc);
     coarse_.ec = dev_alloc<double>(nc);
     owned_.push_back(coarse_.rc);
     owned_.push_back(coarse_.ec);
+}
+
+int coarse_block_size(int nc, const std::vector<int32_t> &e_ip, const std::vector<int32_t> &e_ix) {
+    std::vector<int32_t> uf(nc);
+    for (int j = 0; j < nc; ++j) uf[j] = j;
+    auto find = [&](int32_t a) {
+        while (uf[a] != a) a = uf[a] = uf[uf[a]];
+        return a;
+    };
+    for (int i = 0; i < nc; ++i)
+        for (int32_t e = e_ip[i]; e < e_ip[i + 1]; ++e) {
+            const int32_t a = find(i), b = find(e_ix[e]);
+            if (a != b) uf[std::max(a, b)] = std::min(a, b);
+        }
+    int b = 1;
+    while (b < nc && find(b) == find(0)) ++b;
+    if (b >= nc || nc % b != 0) return 0;
+    // every block one component of its own: [k b, (k+1) b) all joined to k b, the k b distinct
+    std::vector<int32_t> root(nc / b);
+    for (int k = 0; k < nc / b; ++k) root[k] = find(k * b);
+    for (int i = 0; i < nc; ++i)
+        if (find(i) != root[i / b]) return 0;
+    std::sort(root.begin(), root.end());
+    if (std::adjacent_find(root.begin(), root.end()) != root.end()) return 0;
+    return b;
 }
 
 void galerkin_structure(int nc, const std::vector<int32_t> &pt_ip, const std::vector<int32_t> &pt_ix,
@@ -1221,6 +1247,7 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
     const char *k = S.opt("coarse_keep");
     const bool keep = k && k[0] == '1';
     S.coarse_E.clear();
+    S.coarse_Einv.clear();
     if (nmat == 0) return;
     if (keep) S.coarse_E.resize(n2 * nmat);
     const char *o = S.opt("coarse_setup");
@@ -1244,26 +1271,59 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
         (void)hipFree(E);
         (void)hipFree(d_flag);
     } else {
+        // component blocks: the Galerkin launch writes the nblk diagonal blocks of size bn as
+        // matrices of their own (E: nmat * nblk of them), the inverses go to Ib and are scattered
+        // into einv's full rows
+        const char *ob = S.opt("coarse_blocks");
+        const bool blocked = !deflate && g.block_n > 0 && g.block_n < nc && nc % g.block_n == 0 &&
+                             !(ob && ob[0] == '0');
+        const int bn = blocked ? g.block_n : nc, nblk = nc / bn;
+        const size_t b2 = (size_t)bn * bn, ne = nblk * b2;     // doubles of E per level matrix
+        GalerkinDev gb = g;
+        gb.block_n = blocked ? bn : 0;
         // chunks of at most ~1 GiB of Galerkin matrices and scratch (Picard: one matrix per level)
-        const size_t per = n2 * sizeof(double) + dense_inverse_batched_scratch(nc, 1);
+        const size_t per = (blocked ? 2 : 1) * ne * sizeof(double) +
+                           dense_inverse_batched_scratch(bn, nblk);
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>(nmat, ((size_t)1 << 30) / per));
-        double *E = dev_alloc<double>(n2 * chunk);
+        double *E = dev_alloc<double>(ne * chunk);
         const double **d_vals = dev_alloc<const double *>(chunk);
         double **d_inv = dev_alloc<double *>(chunk);
-        void *scratch = dev_alloc<char>(dense_inverse_batched_scratch(nc, chunk));
-        int *d_bad = dev_alloc<int>(chunk);
+        void *scratch = dev_alloc<char>(dense_inverse_batched_scratch(bn, nblk * chunk));
+        int *d_bad = dev_alloc<int>((size_t)nblk * chunk);
+        double *Ib = nullptr, **d_binv = nullptr;
+        std::vector<int> bad_blk;
+        std::vector<double> h_blocks;
+        if (blocked) {
+            Ib = dev_alloc<double>(ne * chunk);
+            std::vector<double *> ptr((size_t)nblk * chunk);
+            for (size_t q = 0; q < ptr.size(); ++q) ptr[q] = Ib + q * b2;
+            d_binv = dev_upload(ptr.data(), ptr.size());
+            bad_blk.resize((size_t)nblk * chunk);
+            if (keep) h_blocks.resize(ne * chunk);
+        }
         for (int b0 = 0; b0 < nmat; b0 += chunk) {
             const int nb = std::min(chunk, nmat - b0);
             HIPCHK(hipMemcpyAsync(d_vals, vals.data() + b0, nb * sizeof(double *),
                                   hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(d_inv, einv.data() + b0, nb * sizeof(double *),
                                   hipMemcpyHostToDevice, st));
-            launch_zero_bytes(st, E, n2 * nb * sizeof(double));
-            launch_galerkin_batched(st, c, g, d_vals, E, nb);
+            launch_zero_bytes(st, E, ne * nb * sizeof(double));
+            launch_galerkin_batched(st, c, gb, d_vals, E, nb);
             launches += 2;
-            if (keep)
+            if (keep && !blocked)
                 HIPCHK(hipMemcpyAsync(S.coarse_E.data() + b0 * n2, E, n2 * nb * sizeof(double),
                                       hipMemcpyDeviceToHost, st));
+            if (keep && blocked) {      // the full matrices, zeros outside the blocks
+                HIPCHK(hipMemcpyAsync(h_blocks.data(), E, ne * nb * sizeof(double),
+                                      hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                for (int b = 0; b < nb; ++b)
+                    for (int k = 0; k < nblk; ++k)
+                        for (int r = 0; r < bn; ++r)
+                            std::copy_n(h_blocks.data() + ((size_t)b * nblk + k) * b2 + (size_t)r * bn,
+                                        bn, S.coarse_E.data() + (b0 + b) * n2 +
+                                                (size_t)(k * bn + r) * nc + (size_t)k * bn);
+            }
             if (deflate) {
                 // every entry + trace(E) / n_c^2, the diagonal summed on the host in index order
                 std::vector<double> diag((size_t)nc * nb);
@@ -1279,12 +1339,40 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
                     launches += 1;
                 }
             }
-            launches += launch_dense_inverse_batched(st, E, d_inv, nc, nb, scratch, d_bad);
-            HIPCHK(hipMemcpyAsync(bad.data() + b0, d_bad, nb * sizeof(int), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
+            if (blocked) {
+                launches += launch_dense_inverse_batched(st, E, d_binv, bn, nblk * nb, scratch, d_bad);
+                launch_coarse_block_scatter(st, Ib, d_inv, nc, bn, nb);
+                launches += 1;
+                HIPCHK(hipMemcpyAsync(bad_blk.data(), d_bad, (size_t)nblk * nb * sizeof(int),
+                                      hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                for (int b = 0; b < nb; ++b)        // first singular column of the whole E_b
+                    for (int k = nblk - 1; k >= 0; --k)
+                        if (bad_blk[(size_t)b * nblk + k] < bn)
+                            bad[b0 + b] = k * bn + bad_blk[(size_t)b * nblk + k];
+            } else {
+                launches += launch_dense_inverse_batched(st, E, d_inv, nc, nb, scratch, d_bad);
+                HIPCHK(hipMemcpyAsync(bad.data() + b0, d_bad, nb * sizeof(int), hipMemcpyDeviceToHost,
+                                      st));
+                HIPCHK(hipStreamSynchronize(st));
+            }
         }
-        for (void *q : {(void *)E, (void *)d_vals, (void *)d_inv, scratch, (void *)d_bad})
-            (void)hipFree(q);
+        for (void *q : {(void *)E, (void *)d_vals, (void *)d_inv, scratch, (void *)d_bad, (void *)Ib,
+                        (void *)d_binv})
+            if (q) (void)hipFree(q);
+        S.coarse_stats.blocks = nblk;
+        S.coarse_stats.block_n = bn;
+    }
+    if (columns) {
+        S.coarse_stats.blocks = 1;
+        S.coarse_stats.block_n = nc;
+    }
+    if (keep) {
+        S.coarse_Einv.resize(n2 * nmat);
+        for (int b = 0; b < nmat; ++b)
+            HIPCHK(hipMemcpyAsync(S.coarse_Einv.data() + b * n2, einv[b], n2 * sizeof(double),
+                                  hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
     S.coarse_stats.matrices = nmat;
     S.coarse_stats.launches = launches;

@@ -63,11 +63,18 @@ void galerkin_structure(int nc, const std::vector<int32_t> &pt_ip, const std::ve
                         const std::vector<int32_t> &a_ip, const std::vector<int32_t> &a_ix,
                         const std::vector<int32_t> &p_ip, const std::vector<int32_t> &p_ix,
                         std::vector<int32_t> &e_ip, std::vector<int32_t> &e_ix);
+// Size b of the diagonal blocks of E = P^T A P on the structure e_ip / e_ix when its coupled coarse
+// functions form nc / b >= 2 contiguous index ranges of equal size (the components of a
+// vector-valued space: one copy of the coarse functions per component), else 0.
+int coarse_block_size(int nc, const std::vector<int32_t> &e_ip, const std::vector<int32_t> &e_ix);
 // einv[b] = (P^T A_b P + shift_b 1 1^T)^-1 for a batch of level matrices (SELL values vals[b] on
 // the pattern `pat` of S): one Galerkin launch, a blocked Gauss-Jordan over the batch, or -- option
 // "coarse_setup" = "columns" -- the column path per matrix.  deflate: shift_b = trace(E_b) / nc^2
 // (the K_p solve: E inherits the constants as its kernel).  Fills S.coarse_stats; fails with
-// KKT_ERR_STATE naming the matrix and column of a (relatively) zero pivot.
+// KKT_ERR_STATE naming the matrix and column of a (relatively) zero pivot.  Without deflation and
+// with g.block_n > 0 (option "coarse_blocks" = "0" turns it off) the batched path inverts the
+// diagonal blocks of every E_b as matrices of size block_n and scatters them into einv's full
+// rows, exact zeros outside the blocks; the singularity test then scales by each block's max|diag|.
 void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
                   const std::vector<const double *> &vals, const std::vector<double *> &einv,
                   bool deflate, const char *what);

@@ -209,6 +209,7 @@ struct System {
     kkt_info info{};
     kkt_coarse_stats coarse_stats{};   // last two-grid coarse set-up (kkt_coarse_setup_stats)
     std::vector<double> coarse_E;      // its Galerkin matrices (option "coarse_keep" = "1")
+    std::vector<double> coarse_Einv;   // ... and their inverses
 
     // preconditioner
     std::unique_ptr<PcBase> pc;

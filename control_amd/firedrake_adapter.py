@@ -16,20 +16,50 @@ objects of the same shape (``tests/test_firedrake_adapter.py``):
 * a vector's ``.sub(i).dat.data`` / ``.dat.data`` arrays and a boundary condition's ``.nodes``
   and ``.function_space().block_size`` (nodes of a vector space own ``block_size`` dofs each,
   interleaved, as in the ``Mat``).
+
+``coarse_space(V, bcs)`` builds the coarse space of the two-grid sub-solves (the reference's
+``Multigrid=True``) from the node coordinates of ``V`` -- ``SpatialCoordinate`` interpolated into
+the vector version of ``V``'s element (hook ``_coordinates``) -- for ``ChebSpec(...,
+coarse=CoarseSpace(P, cycles))``.
 """
 import numpy as np
 
 from . import multiblock as mb
-from .multiblock import (ChebSpec, ConstantNullspace, FullNullspace, NoneNullspace,  # noqa: F401
-                         SchurPC, StokesPC)
+from .multiblock import (ChebSpec, CoarseSpace, ConstantNullspace, FullNullspace,  # noqa: F401
+                         NoneNullspace, SchurPC, StokesPC)
 
 __all__ = ["MultiBlockSystem", "DirichletBCNullspace", "ConstantNullspace", "NoneNullspace",
-           "FullNullspace", "SchurPC", "StokesPC", "ChebSpec"]
+           "FullNullspace", "SchurPC", "StokesPC", "ChebSpec", "CoarseSpace", "coarse_space"]
 
 
 def _assemble(form, form_compiler_parameters):
     from firedrake import assemble                   # absent here: the tests replace this hook
     return assemble(form, form_compiler_parameters=form_compiler_parameters)
+
+
+def _coordinates(space):
+    """Node coordinates of ``space``, shape ``(nodes, dim)``: ``SpatialCoordinate`` interpolated
+    into the vector-valued space of the element of one component."""
+    from firedrake import Function, SpatialCoordinate, VectorFunctionSpace   # replaced in the tests
+    mesh = space.mesh()
+    elem = space.ufl_element()
+    sub = getattr(elem, "sub_elements", None)
+    sub = sub() if callable(sub) else sub
+    if _block_size(space) > 1 and sub:
+        elem = sub[0]
+    X = Function(VectorFunctionSpace(mesh, elem)).interpolate(SpatialCoordinate(mesh))
+    return np.asarray(X.dat.data_ro, dtype=np.float64).reshape(-1, mesh.geometric_dimension())
+
+
+def coarse_space(space, bcs=None):
+    """Coarse space of the two-grid sub-solves on ``space`` (``control.coarse_space``: 33^2
+    multilinear functions in 2-D, 9^3 in 3-D, one copy per component of a vector space): an
+    ``n x n_c`` CSR prolongation in ``space``'s dof numbering, empty rows on the dofs of the
+    Dirichlet conditions ``bcs``."""
+    from .control import coarse_space as build
+    X = _coordinates(space)
+    nodes = _bc_dofs(bcs) if bcs is not None else ()
+    return build(X, nodes, copies=_block_size(space), interleaved=True)
 
 
 def _block_size(space):
@@ -57,17 +87,25 @@ class DirichletBCNullspace(mb.DirichletBCNullspace):
     def __init__(self, bcs, *, alpha=1.0):
         if hasattr(bcs, "nodes"):
             bcs = (bcs,)
-        dofs = []
         for bc in bcs:
             fa = getattr(bc, "function_arg", 0)
             if not (isinstance(fa, (int, float)) and fa == 0 or type(fa).__name__ == "Zero"):
                 raise ValueError("Homogeneous boundary conditions required")   # :166-169
-            space = bc.function_space() if callable(getattr(bc, "function_space", None)) else None
-            bs = _block_size(space) if space is not None else 1
-            nodes = np.asarray(bc.nodes, dtype=np.int64).ravel()
-            dofs.append((nodes[:, None] * bs + np.arange(bs)[None, :]).ravel())
-        super().__init__(np.concatenate(dofs) if dofs else np.zeros(0, dtype=np.int64),
-                         alpha=alpha)
+        super().__init__(_bc_dofs(bcs), alpha=alpha)
+
+
+def _bc_dofs(bcs):
+    """Dofs of the nodes of boundary conditions (a node of a vector space owns ``block_size``
+    consecutive dofs)."""
+    if hasattr(bcs, "nodes"):
+        bcs = (bcs,)
+    dofs = []
+    for bc in bcs:
+        space = bc.function_space() if callable(getattr(bc, "function_space", None)) else None
+        bs = _block_size(space) if space is not None else 1
+        nodes = np.asarray(bc.nodes, dtype=np.int64).ravel()
+        dofs.append((nodes[:, None] * bs + np.arange(bs)[None, :]).ravel())
+    return np.concatenate(dofs) if dofs else np.zeros(0, dtype=np.int64)
 
 
 def _vector_arrays(f, n):

@@ -349,8 +349,9 @@ class MultiBlockSystem:
 
     def coarse_setup_stats(self):
         """``kkt_coarse_setup_stats``: the last coarse set-up of the two-grid solves on this
-        handle -- ``matrices`` formed and inverted, kernel ``launches``, wall time ``ms`` and
-        ``n_coarse``."""
+        handle -- ``matrices`` formed and inverted, kernel ``launches``, wall time ``ms``,
+        ``n_coarse``, and the diagonal ``blocks`` of ``block_n`` rows inverted separately (1 and
+        ``n_coarse``: the whole matrix)."""
         st = _lib.CoarseStats()
         self._ck(self._lib.kkt_coarse_setup_stats(self._h, C.byref(st)))
         return st.as_dict()
@@ -361,6 +362,14 @@ class MultiBlockSystem:
         st = self.coarse_setup_stats()
         E = np.empty((st["matrices"], st["n_coarse"], st["n_coarse"]))
         self._ck(self._lib.kkt_debug_coarse_matrices(self._h, E.ctypes.data_as(_lib.c_f64p), E.size))
+        return E
+
+    def coarse_inverses(self):
+        """``kkt_debug_coarse_inverses``: the inverses of the last coarse set-up, same shape and
+        option as ``coarse_matrices``."""
+        st = self.coarse_setup_stats()
+        E = np.empty((st["matrices"], st["n_coarse"], st["n_coarse"]))
+        self._ck(self._lib.kkt_debug_coarse_inverses(self._h, E.ctypes.data_as(_lib.c_f64p), E.size))
         return E
 
     def debug_dense_inverse(self, A):

@@ -140,13 +140,32 @@ def non_linear_res_eval(pb: NavierStokesControl, D, v, zeta, p, mu):
     return r00, r01, r10, r11
 
 
+_DEFAULT_SOLVER_PARAMETERS = {"linear_solver": "fgmres", "fgmres_restart": 10,
+                              "maximum_iterations": 100, "relative_tolerance": 1.0e-6,
+                              "absolute_tolerance": 0.0, "monitor_convergence": False}
+
+
 class GpuLinearSolver:
     """The linearised solve of one Picard iteration on the GPU: builds the outer, inner
     (velocity KKT) and commutator (pressure) systems once, afterwards only re-uploads the
-    values of the blocks that carry the re-linearised operator."""
+    values of the blocks that carry the re-linearised operator.
 
-    def __init__(self, pb: NavierStokesControl, *, mass, schur, kp, mp, solver_parameters,
-                 device=0, comm=None, host_allreduce=None, options=None):
+    ``Multigrid=True`` (the reference's keyword): the velocity sub-solves and the ``K_p`` solve
+    take their two-grid form -- ``GpuBackend.TWO_GRID_CYCLES`` x [Galerkin correction on the
+    coarse space of ``control.coarse_space`` (33^2 functions per velocity component; the
+    pressure space's with the constants deflated), Chebyshev sweeps].  ``schur`` and ``kp`` are
+    then the sweeps of a cycle.  Their default for the velocity blocks, which carry the
+    convection term, is ``(-1, 0, 0)``: per level matrix the library estimates ``emax`` and the
+    ellipse's imaginary semi-axis and sweeps 8 times on ``[emax / 30, emax]`` -- the upper part of
+    the spectrum, which the two-grid form needs (pc.cpp, ``SchurPC`` matrix set-up).  Explicit
+    ``(its, emin, emax, eimag)`` bounds replace the estimates.  ``kp`` defaults to 12 sweeps on
+    ``[0.05, 2.1]``.  Without ``Multigrid`` both default to ``(-1, 0, 0)``: plain polynomials
+    from the spectrum estimates.  Every re-linearisation rebuilds the ``2 n_t`` coarse
+    inverses on the device (``coarse_setup_stats`` of ``self.inner``)."""
+
+    def __init__(self, pb: NavierStokesControl, *, mass=(20, 0.3924, 2.0598), schur=None,
+                 kp=None, mp=(20, 0.5, 2.0), solver_parameters=None, device=0, comm=None,
+                 host_allreduce=None, options=None, Multigrid=False):
         """``comm`` (``control_amd.dist``): the three systems are time-sharded (BASELINE
         configs[4] names 8 GPUs) -- every rank runs the same Picard loop on the whole iterate
         (residual and re-linearisation are host work on replicated data, as cheap as in the
@@ -154,9 +173,15 @@ class GpuLinearSolver:
         and the shards are summed into the whole update with ``host_allreduce(array, op)``
         (in place over ranks, op 0 = sum: e.g. ``GlooTransport.allreduce``)."""
         self.pb, self.device = pb, device
+        from .control import GpuBackend
         self.options = options          # execution options of the three systems (kkt_set_option)
-        self.specs = dict(mass=mass, schur=schur, kp=kp, mp=mp)
-        self.solver_parameters = solver_parameters
+        self.multigrid = bool(Multigrid)
+        if kp is None:
+            kp = GpuBackend.TWO_GRID_KP if self.multigrid else (-1, 0.0, 0.0)
+        self.specs = dict(mass=mass, schur=(-1, 0.0, 0.0) if schur is None else schur, kp=kp,
+                          mp=mp)
+        self.solver_parameters = (dict(_DEFAULT_SOLVER_PARAMETERS) if solver_parameters is None
+                                  else solver_parameters)
         self.outer = None
         self.uploads = 0
         self.dist = comm if comm is not None and comm.world > 1 else None
@@ -190,11 +215,19 @@ class GpuLinearSolver:
                                      n_blocks_11=m, device=self.device, comm=self.dist,
                                      options=self.options)
         s = self.specs
+        schur, kp = ChebSpec(*s["schur"]), ChebSpec(*s["kp"])
+        if self.multigrid:
+            from .control import GpuBackend, coarse_space
+            from .multiblock import CoarseSpace
+            Xv = np.asarray(th.coords_v)
+            cycles = GpuBackend.TWO_GRID_CYCLES
+            schur.coarse = CoarseSpace(coarse_space(Xv, th.boundary_v, copies=th.n_v // len(Xv)),
+                                       cycles)
+            kp.coarse = CoarseSpace(coarse_space(th.coords_p), cycles)
         inner_pc = SchurPC(kind="CN" if pb.CN else "BE", M=th.M_v, beta=pb.beta, bc_nodes=th.boundary_v,
-                           mass=ChebSpec(*s["mass"]), schur=ChebSpec(*s["schur"]), n_t=pb.n_t,
-                           tau=pb.tau)
+                           mass=ChebSpec(*s["mass"]), schur=schur, n_t=pb.n_t, tau=pb.tau)
         self.pc = StokesPC(inner=self.inner, inner_pc=inner_pc, commutator=self.comm, B=th.B,
-                           K_p=th.K_p, M_p=th.M_p, kp=ChebSpec(*s["kp"]), mp=ChebSpec(*s["mp"]),
+                           K_p=th.K_p, M_p=th.M_p, kp=kp, mp=ChebSpec(*s["mp"]),
                            n_p_blocks=m, b_scale=pb.tau, post_scale=1.0 / pb.tau**2, cn=pb.CN)
 
     def _update(self, bl):
@@ -252,16 +285,22 @@ class GpuLinearSolver:
         return u_0, u_1, ksp.getIterationNumber()
 
 
-def incompressible_non_linear_solve(pb: NavierStokesControl, linear_solver, *,
+def incompressible_non_linear_solve(pb: NavierStokesControl, linear_solver=None, *,
                                     max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                                     absolute_non_linear_tol=1.0e-8, v=None, zeta=None, p=None,
-                                    mu=None, print_error_non_linear=True):
+                                    mu=None, print_error_non_linear=True, Multigrid=False):
     """``control.py:4886-5232`` (BE).  ``linear_solver.linear_solve(D, Dp, b_0, b_1)`` returns
     the update ``(u_0, u_1, iterations)`` of the linearised system whose forward operator at
-    time level ``i`` is ``D[i]`` (velocity space) / ``Dp[i]`` (pressure space).
+    time level ``i`` is ``D[i]`` (velocity space) / ``Dp[i]`` (pressure space).  ``None``: a
+    ``GpuLinearSolver(pb, Multigrid=Multigrid)`` with its defaults.  ``Multigrid=True`` with a
+    given solver requires one built with ``Multigrid=True``.
 
     Returns a dict with the converged fields, the non-linear residual norms (``norm_0``
     first) and the linear iteration counts."""
+    if linear_solver is None:
+        linear_solver = GpuLinearSolver(pb, Multigrid=Multigrid)
+    elif Multigrid and not getattr(linear_solver, "multigrid", False):
+        raise ValueError("Multigrid=True: the linear solver was not built with Multigrid=True")
     th, n_t, tau = pb.disc, pb.n_t, pb.tau
     m = n_t - 1 if pb.CN else n_t
     v = np.zeros((n_t, th.n_v)) if v is None else np.array(v, dtype=np.float64)

@@ -97,6 +97,10 @@ const char *kkt_last_error(kkt_handle h);
  *                                (kkt_get_stage_times)
  *   "coarse_setup" "columns"     two-grid set-up column by column (the previous path; default:
  *                                batched Galerkin products and blocked Gauss-Jordan on the device)
+ *   "coarse_blocks" "0"          batched set-up: invert P^T A P as one matrix even where it is
+ *                                block diagonal over the components of a vector-valued space
+ *                                (default: one inverse per component block; the rows keep their
+ *                                full layout, exact zeros outside the block)
  *   "lanes", "lane_chunks", "kernarg_ops", "shared_rows", "verbose"   diagnostics
  * The library never reads the process environment: a key that was never set has its default.
  * (The Python mirror forwards KKT_<KEY> variables of developer scripts as explicit calls.) */
@@ -348,6 +352,10 @@ int kkt_time_pc_stages(kkt_handle h, const double *d_x, double *d_y, kkt_pc_stag
 typedef struct kkt_coarse_stats {
     int64_t matrices, launches, n_coarse;
     double ms;
+    /* diagonal blocks of P^T A P inverted as matrices of their own (the components of a
+     * vector-valued space, equal contiguous index ranges) and their size; 1 and n_coarse: the
+     * whole matrix (a scalar space, the deflated K_p solve, or option "coarse_blocks" = "0") */
+    int64_t blocks, block_n;
 } kkt_coarse_stats;
 int kkt_coarse_setup_stats(kkt_handle h, kkt_coarse_stats *out);
 /* Test hooks of the coarse set-up.  With option "coarse_keep" = "1" every set-up keeps its Galerkin
@@ -356,6 +364,9 @@ int kkt_coarse_setup_stats(kkt_handle h, kkt_coarse_stats *out);
  * kkt_debug_dense_inverse inverts nmat host matrices (n x n, row-major, contiguous) with the
  * batched device inverse; bad[b] = first column with a pivot below 1e-13 max|diag| (n: none). */
 int kkt_debug_coarse_matrices(kkt_handle h, double *out, int64_t cap);
+/* ... and the inverses of the same set-up, in the same layout (the rows as the solves read them:
+ * full n_coarse columns, zeros outside the diagonal blocks on the block path) */
+int kkt_debug_coarse_inverses(kkt_handle h, double *out, int64_t cap);
 int kkt_debug_dense_inverse(kkt_handle h, int n, int nmat, const double *a, double *inv, int *bad);
 
 /* Step-locked parity hook (tests): while set, kkt_solve / kkt_solve_device with gmres or
