@@ -156,6 +156,8 @@ SIGNATURES = {
     "kkt_debug_coarse_inverses": (C.c_int, [C.c_void_p, c_f64p, C.c_int64]),
     "kkt_debug_dense_inverse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p]),
     "kkt_debug_set_steplock": (C.c_int, [C.c_void_p, C.POINTER(StepLock)]),
+    "kkt_debug_apply_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
+    "kkt_debug_pc_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "kkt_get_info": (C.c_int, [C.c_void_p, C.POINTER(Info)]),
     "kkt_comm_unique_id": (C.c_int, [C.c_void_p]),
     "kkt_comm_init_rccl": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -373,6 +373,40 @@ int kkt_debug_set_steplock(kkt_handle h, const kkt_steplock *lock) {
     });
 }
 
+// records -> out (NULL: count only); returns the record count
+static int put_forms(const std::vector<int32_t> &rec, int per, int32_t *out, int cap) {
+    const int n = (int)rec.size() / per;
+    if (out) {
+        if (cap < (int)rec.size()) fail(KKT_ERR_ARG, "buffer too small for the form records");
+        std::copy(rec.begin(), rec.end(), out);
+    }
+    return n;
+}
+
+int kkt_debug_apply_forms(kkt_handle h, int32_t *out, int cap) {
+    KKT_TRY(h, {
+        if (!S.finalized) fail(KKT_ERR_STATE, "system not finalized");
+        std::vector<int32_t> rec;
+        for (size_t w = 0; w < S.apply_launches.size(); ++w) {
+            const RowLaunch &L = S.apply_launches[w];
+            int sorted = 0;
+            for (const RowOp &op : S.h_apply_ops[w]) sorted |= op.perm != nullptr;
+            // the test launch_rowops_grouped makes (System::apply)
+            const bool grouped = L.ngroups > 0 && rowops_grouped_kernel(L.R, L.uniform_w);
+            rec.insert(rec.end(), {L.R, L.uniform_w, grouped ? L.ngroups : 0, sorted});
+        }
+        return put_forms(rec, KKT_APPLY_FORM_INTS, out, cap);
+    });
+}
+
+int kkt_debug_pc_forms(kkt_handle h, int32_t *out, int cap) {
+    KKT_TRY(h, {
+        std::vector<int32_t> rec;
+        if (S.pc) S.pc->plain_forms(rec);
+        return put_forms(rec, KKT_PC_FORM_INTS, out, cap);
+    });
+}
+
 int kkt_get_info(kkt_handle h, kkt_info *info) {
     KKT_TRY(h, {
         if (!info) fail(KKT_ERR_ARG, "null info");

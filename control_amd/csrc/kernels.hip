@@ -1874,7 +1874,7 @@ __global__ __launch_bounds__(256) void kkt_spmv_rows_shared(const RowOp *__restr
 bool launch_rowops_grouped(hipStream_t s, const RowOp *d_ops, const int32_t *d_groups, int ngroups,
                            int max_slices, int R, int uniform_w, const Bases &bases) {
     constexpr int NB = 4;
-    if (R != 2 || ngroups <= 0) return false;
+    if (!rowops_grouped_kernel(R, uniform_w) || ngroups <= 0) return false;
     const dim3 grid((max_slices + 3) / 4, ngroups), block(256);
     const int2 *g = reinterpret_cast<const int2 *>(d_groups);
     switch (uniform_w) {

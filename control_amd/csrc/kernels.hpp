@@ -110,6 +110,8 @@ bool launch_rowops_shared(hipStream_t s, const RowOp *d_ops, int nops, int max_s
 // Operator apply for shared values: d_groups[g] = {first op, count <= 4} of runs of EPI_LIN RowOps
 // with identical structure (same pattern, same term matrices); fixed slice widths 1..8, R = 2.
 constexpr int ROW_GROUP_MAX = 4;
+// the launches kkt_spmv_rows_shared serves (launch_rowops_grouped; else the plain kernel runs)
+inline bool rowops_grouped_kernel(int R, int uniform_w) { return R == 2 && uniform_w >= 1 && uniform_w <= 8; }
 bool launch_rowops_grouped(hipStream_t s, const RowOp *d_ops, const int32_t *d_groups, int ngroups,
                            int max_slices, int R, int uniform_w, const Bases &bases);
 

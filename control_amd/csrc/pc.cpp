@@ -865,6 +865,27 @@ void SchurPC::fuse_programs() {
     S_.info.sweep_row_slots = form == 3 ? tile_plan_.rpt : 0;
 }
 
+// The form replay() gives each row step, sweep program and tile launch (kkt_debug_pc_forms)
+void SchurPC::plain_forms(std::vector<int32_t> &out) const {
+    const Pattern &P = S_.patterns[m_pat_];
+    for (const PcStep &s : steps_) {
+        if (s.kind == PcStep::ROWS) {
+            const int form = s.rows.shared_matrix && s.rows.R == 2 ? KKT_PC_ROWS_SHARED
+                             : s.rows.single                       ? KKT_PC_ROWS_KERNARG
+                                                                   : KKT_PC_ROWS_PLAIN;
+            out.insert(out.end(), {form, s.rows.uniform_w, s.rows.R, s.lane, s.rows.nops, 0});
+        } else if (s.kind == PcStep::ROWS_IL) {
+            out.insert(out.end(), {KKT_PC_ROWS_INTERLEAVED, s.il_w, 2, s.lane, s.il_groups, 0});
+        } else if (s.kind == PcStep::PROG) {
+            out.insert(out.end(), {KKT_PC_PROGRAM, P.uniform_w, P.R, s.lane, s.nphases,
+                                   s.gmode == 2 ? 2 : s.granule ? 1 : 0});
+        } else if (s.kind == PcStep::TILE) {
+            out.insert(out.end(), {KKT_PC_TILE, tile_plan_.W, tile_plan_.rpt, s.lane,
+                                   tile_plan_.threads, (s.fused ? 1 : 0) | (s.coarse ? 2 : 0)});
+        }
+    }
+}
+
 void SchurPC::debug_read(unsigned long long *out, int n) {
     if (!d_err_) return;
     HIPCHK(hipStreamSynchronize(S_.stream));
@@ -1829,6 +1850,9 @@ bool SchurPC::emit_solves_interleaved(const std::vector<Solve> &sv, int its, dou
     for (const Solve &q : sv)
         if (q.vals != sv[0].vals || q.dinv != sv[0].dinv) return false;
     const Pattern &P = S_.patterns[m_pat_];
+    // pc_rows_il reads the SELL-128 layout (R = 2): with sell_r = 1 its slice count and offsets
+    // would address 64-row slices as 128-row ones, past the end of the index and value arrays
+    if (P.R != 2) return false;
     const int ng = (int)((m + 3) / 4);
     const size_t need = (size_t)ng * 4 * (size_t)nx_;
     if (need > il_cap_) {

@@ -102,6 +102,8 @@ class PcBase {
     // one application replayed step by step with events (kkt_time_pc_stages)
     virtual void time_stages(kkt_pc_stage_times *out);
     virtual void debug_read(unsigned long long *, int) {}
+    // kkt_debug_pc_forms: KKT_PC_FORM_INTS values per row step or sweep program, replay order
+    virtual void plain_forms(std::vector<int32_t> &) const {}
     // measurement: time the persistent programs of the next run() with events
     virtual void time_programs(float *ms, int *launches, int64_t *phases) {
         *ms = 0.f;
@@ -125,6 +127,7 @@ class SchurPC : public PcBase {
     const unsigned *err_word() const override { return d_err_; }
     void time_stages(kkt_pc_stage_times *out) override;
     void debug_read(unsigned long long *out, int n) override;   // diagnostic builds (KKT_STAMPS)
+    void plain_forms(std::vector<int32_t> &out) const override;
     void time_programs(float *ms, int *launches, int64_t *phases) override;
     int bc_set() const { return bc_set_; }
     // degree and interval the sub-solves of a typical time level run with (given or derived)

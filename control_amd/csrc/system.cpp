@@ -680,8 +680,7 @@ void System::finalize() {
             std::vector<char> used(ops.size(), 0);
             std::vector<int32_t> groups;
             const char *sg = opt("shared_rows");
-            const bool allow = !(sg && sg[0] == '0') && L.R == 2 && L.uniform_w >= 1 &&
-                               L.uniform_w <= 8;
+            const bool allow = !(sg && sg[0] == '0') && rowops_grouped_kernel(L.R, L.uniform_w);
             bool uniform_all = allow;
             for (const RowOp &op : ops) uniform_all = uniform_all && op.nterms > 0 && op.perm == nullptr;
             if (uniform_all) {

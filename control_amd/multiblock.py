@@ -356,6 +356,33 @@ class MultiBlockSystem:
         self._ck(self._lib.kkt_coarse_setup_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def _forms(self, fn, fields):
+        n = fn(self._h, None, 0)
+        if n < 0:
+            self._ck(n)
+        rec = np.zeros(n * len(fields), dtype=np.int32)
+        got = fn(self._h, rec.ctypes.data_as(_lib.c_i32p), rec.size)
+        if got < 0:
+            self._ck(got)
+        return [dict(zip(fields, map(int, r))) for r in rec.reshape(n, len(fields))]
+
+    def apply_forms(self):
+        """``kkt_debug_apply_forms``: one dict per launch of ``mult`` -- ``R``, ``uniform_w``
+        (1..16 fixed width, 0 rows without blocks, -1 slot loop, -2 / -3 / -4 width-switched:
+        four waves / one wave / narrow), shared-values ``groups`` (0: none) and ``sorted``
+        (row-sorted storage)."""
+        return self._forms(self._lib.kkt_debug_apply_forms, ("R", "uniform_w", "groups", "sorted"))
+
+    def pc_forms(self):
+        """``kkt_debug_pc_forms``: one dict per row step, sweep program and tile launch of the
+        built-in preconditioner (built by the first ``pc_apply``), in replay order -- ``form`` (0
+        plain rows, 1 shared matrix, 2 kernel-argument single op, 3 interleaved levels, 4 row
+        program, 5 tile program), ``width``, ``slots`` (R; tile: row slots per thread), ``lane``
+        (1: side stream), ``count`` (row ops; program: phases; tile: threads) and ``variant``
+        (program: 0 counters, 1 data-flow, 2 data-flow any width; tile: 1 fused | 2 coarse)."""
+        return self._forms(self._lib.kkt_debug_pc_forms,
+                           ("form", "width", "slots", "lane", "count", "variant"))
+
     def coarse_matrices(self):
         """``kkt_debug_coarse_matrices``: the Galerkin matrices P^T A P of the last coarse set-up,
         shape ``(matrices, n_coarse, n_coarse)`` (needs option ``coarse_keep`` = ``1``)."""

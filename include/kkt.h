@@ -388,6 +388,32 @@ typedef struct kkt_steplock {
 } kkt_steplock;
 int kkt_debug_set_steplock(kkt_handle h, const kkt_steplock *lock);
 
+/* Test hooks: which kernel form each planned launch runs (read-only; they change no launch).
+ * Both return the number of records (>= 0) or a negative KKT_ERR_*; out == NULL asks for the count,
+ * otherwise `cap` (int32 values available at out) must hold every record.
+ * kkt_debug_apply_forms: one record of KKT_APPLY_FORM_INTS per kkt_apply launch, in launch order:
+ *   R (rows per lane of the SELL-64R storage); uniform_w: 1..16 the fixed-width kernel of that
+ *   width, 0 rows without blocks, -1 or a uniform width above 16 the slot loop, -2 / -3 / -4 the
+ *   width-switched kernel (four
+ *   waves / one wave per workgroup / narrow slices); groups of equal structure served by the
+ *   shared-values kernel (0: none); 1 when the storage is row-sorted (SELL-C-sigma), else 0.
+ * kkt_debug_pc_forms: one record of KKT_PC_FORM_INTS per row step, sweep program and tile launch
+ *   of the built-in preconditioner, in replay order: form (KKT_PC_*); width; slots; stream (0 the
+ *   handle's, 1 the side lane); count; variant.
+ *     row steps (PLAIN, SHARED matrix, KERNARG single op, INTERLEAVED levels): width = uniform_w
+ *       of the level pattern (as above), slots = R, count = row ops (interleaved: groups of four
+ *       time levels), variant 0;
+ *     PROGRAM (a persistent row program): width = uniform_w, slots = R, count = phases, variant
+ *       0 counters ("flags"), 1 data-flow fixed width, 2 data-flow any width ("w");
+ *     TILE: width = W of the tile kernel, slots = row slots per thread, count = threads per
+ *       workgroup, variant = 1 (level update fused) | 2 (coarse corrections).
+ *   0 records before kkt_set_pc_schur. */
+enum { KKT_APPLY_FORM_INTS = 4, KKT_PC_FORM_INTS = 6 };
+enum { KKT_PC_ROWS_PLAIN = 0, KKT_PC_ROWS_SHARED = 1, KKT_PC_ROWS_KERNARG = 2,
+       KKT_PC_ROWS_INTERLEAVED = 3, KKT_PC_PROGRAM = 4, KKT_PC_TILE = 5 };
+int kkt_debug_apply_forms(kkt_handle h, int32_t *out, int cap);
+int kkt_debug_pc_forms(kkt_handle h, int32_t *out, int cap);
+
 /* Byte accounting of the stored operator ("algorithmic bytes"). */
 typedef struct kkt_info {
     int64_t n_local;            /* local KKT vector length */
