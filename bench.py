@@ -18,10 +18,16 @@ line.  Time-block rows are sharded over the ranks, RCCL over xGMI carries the ha
 the Krylov all-reduces.  If RCCL does not start on N distinct GPUs the run FAILS (non-zero exit):
 the host-staged gloo transport is only for rehearsals with all ranks on one GPU (KKT_DEVICE=0).
 
-One JSON line on stdout (rank 0): metric/value = whole-job Krylov iterations per second;
-`roofline` = the KKT block-row SpMV kernel (kkt_spmv_rows) against the 8 TB/s HBM peak,
-timed with HIP events on the library's stream; `cpu_baseline` = the CPU oracle timed on
-this box's host cores on a bounded sample of the same workload (C/OpenMP restatement).
+One JSON line on stdout (rank 0): metric/value = whole-job Krylov iterations per second,
+ms_per_step = milliseconds per timed iteration, and `config` (what ran).  A plain run does only
+that: set-up, warm-up, the timed steps, --dump-outputs, the line.
+
+--full adds the side measurements, each in runs of its own around the timed steps:
+`roofline` = the KKT block-row SpMV kernel (kkt_spmv_rows) against the 8 TB/s HBM peak, timed
+with HIP events on the library's stream; `roofline_sweeps`, `stages` and `pc_apply_ms` /
+`kkt_apply_ms` = the preconditioner and its stages timed the same way; `time_to_solution`;
+`cpu_baseline` = the CPU oracle timed on this box's host cores on a bounded sample of the same
+workload (C/OpenMP restatement); `config4` = the same on BASELINE configs[3].
 No PyTorch: the GPU process binds libkkt.so through ctypes only.
 """
 import argparse
@@ -315,7 +321,7 @@ def bench_stokes(args, rank, world, local_rank):
     StokesPC (5 nested GMRES iterations on the velocity KKT system per application).  Sub-solves:
     the setting with which the outer iteration converges at this size (see --kp-its in main()).
     N > 1: the outer, velocity and commutator systems are time-sharded over the ranks
-    (csrc/pc_stokes.cpp); the time-to-solution leg runs at N = 1 only."""
+    (csrc/pc_stokes.cpp); the time-to-solution leg (--full) runs at N = 1 only."""
     from control_amd import _lib
     from control_amd import problems as common
     from control_amd.dist import make_comm
@@ -372,9 +378,15 @@ def bench_stokes(args, rank, world, local_rank):
     x = common.rng_vector(n_local, common.SEED + rank)
     d_x, d_y, d_u = dvec(x), dvec(), dvec()
     ms = C.c_float()
-    outer._ck(lib.kkt_time_apply(h, d_x, d_y, 5, C.byref(ms)))
-    outer._ck(lib.kkt_time_apply(h, d_x, d_y, args.spmv_reps, C.byref(ms)))
-    spmv_ms = ms.value / args.spmv_reps
+    full = args.full or args.only_spmv
+    if not full:
+        # a plain run: first-use costs outside the timed steps (see measure_heat)
+        outer._ck(lib.kkt_apply_device(h, d_x, d_y))
+        outer._ck(lib.kkt_pc_apply_device(h, d_x, d_y))
+    else:
+        outer._ck(lib.kkt_time_apply(h, d_x, d_y, 5, C.byref(ms)))
+        outer._ck(lib.kkt_time_apply(h, d_x, d_y, args.spmv_reps, C.byref(ms)))
+        spmv_ms = ms.value / args.spmv_reps
     if args.only_spmv:
         if rank == 0:
             alg_ = info["bytes_streamed"]
@@ -388,9 +400,10 @@ def bench_stokes(args, rank, world, local_rank):
                              "algorithmic_bytes_per_launch": alg_, "launch_ms": spmv_ms,
                              "kernel_launches_per_apply": int(info.get("apply_launches", 0))}}))
         return 0
-    outer._ck(lib.kkt_time_pc_apply(h, d_x, d_y, 1, C.byref(ms)))
-    outer._ck(lib.kkt_time_pc_apply(h, d_x, d_y, 3, C.byref(ms)))
-    pc_ms = ms.value / 3
+    if full:
+        outer._ck(lib.kkt_time_pc_apply(h, d_x, d_y, 1, C.byref(ms)))
+        outer._ck(lib.kkt_time_pc_apply(h, d_x, d_y, 3, C.byref(ms)))
+        pc_ms = ms.value / 3
 
     def run(max_it):
         outer._ck(lib.kkt_vec_upload(h, d_u, _lib.f64(np.zeros(n_local))[1]))
@@ -406,8 +419,8 @@ def bench_stokes(args, rank, world, local_rank):
         dt = C.c_double(time.perf_counter() - t0)
         outer._ck(lib.kkt_comm_max(h, C.byref(dt)))
         return its.value, dt.value, rn.value
-    print(f"[bench] spmv {spmv_ms:.3f} ms, pc {pc_ms:.3f} ms; Krylov leg", file=sys.stderr,
-          flush=True)
+    print((f"[bench] spmv {spmv_ms:.3f} ms, pc {pc_ms:.3f} ms; " if full else "[bench] ")
+          + "Krylov leg", file=sys.stderr, flush=True)
     if args.warmup > 0:
         run(args.warmup)
     its, dt, rn = run(args.steps)
@@ -417,107 +430,112 @@ def bench_stokes(args, rank, world, local_rank):
         u = np.empty(n_local)
         outer._ck(lib.kkt_vec_download(h, d_u, _lib.f64(u)[1]))
         dump_outputs(args.dump_outputs, rank, world, u, its, rn)
-    stages = stage_breakdown(outer, lib, h, d_x, d_u, d_x, d_y, n_local, min(args.steps, 10), 1,
-                             with_pc_stages=False)
     inner_info = gpc.inner.info() if hasattr(gpc, "inner") else {}
-    # ---- time to solution (one GPU): b = A x* for a smooth x* (velocity zero on the boundary,
-    # pressure blocks of zero mean), zero initial guess, outer FGMRES(10) to rtol 1e-6; says
-    # whether a cheaper preconditioner application was bought with more outer iterations
-    t_sol = None
-    if world == 1:
-        th_ = p["th"]
-        m2 = 2 * p["m"]
-        Xv, Xp = th_.coords_v, th_.coords_p
-        sv = np.sin(0.5 * np.pi * Xv[:, 0]) * np.sin(0.5 * np.pi * Xv[:, 1])
-        sv = np.concatenate([sv, -0.5 * sv])
-        sv[th_.boundary_v] = 0.0
-        sq = np.cos(0.5 * np.pi * Xp[:, 0]) * np.cos(np.pi * Xp[:, 1])
-        sq -= sq.mean()
-        xs = np.concatenate([np.concatenate([(1.0 + 0.1 * k) * sv for k in range(m2)]),
-                             np.concatenate([(1.0 - 0.05 * k) * sq for k in range(m2)])])
-        d_s, d_b = dvec(xs), dvec()
-        outer._ck(lib.kkt_apply_device(h, d_s, d_b))
-        outer._ck(lib.kkt_vec_upload(h, d_u, _lib.f64(np.zeros(n_local))[1]))
-        outer._ck(lib.kkt_set_krylov(h, 1, -1, 10, 1e-6, 0.0, 1e300, args.tts_max_it))
-        its_s, reason, nh, rn = C.c_int(), C.c_int(), C.c_int(), C.c_double()
-        outer._ck(lib.kkt_sync(h))
-        t0 = time.perf_counter()
-        outer._ck(lib.kkt_solve_device(h, d_b, d_u, C.byref(its_s), C.byref(reason),
-                                       C.byref(rn), None, 0, C.byref(nh)))
-        outer._ck(lib.kkt_sync(h))
-        dt_s = time.perf_counter() - t0
-        got = np.empty(n_local)
-        outer._ck(lib.kkt_vec_download(h, d_u, _lib.f64(got)[1]))
-        nv_all = m2 * th_.n_v
-        gp = got[nv_all:].reshape(m2, th_.n_p)
-        gp = gp - gp.mean(axis=1, keepdims=True)     # pressures are fixed up to a constant
-        t_sol = {"rhs": "A x* for a smooth x* (velocity sin sin, pressure cos cos of zero mean)",
-                 "stopping_test": f"outer fgmres restart 10, rtol 1e-6, max {args.tts_max_it}",
-                 "converged": bool(reason.value > 0), "iterations": int(its_s.value),
-                 "seconds": dt_s,
-                 "velocity_error": float(np.linalg.norm(got[:nv_all] - xs[:nv_all])
-                                         / np.linalg.norm(xs[:nv_all])),
-                 "pressure_error": float(np.linalg.norm(gp.ravel() - xs[nv_all:])
-                                         / np.linalg.norm(xs[nv_all:]))}
-    # the nested velocity solve's block-Schur preconditioner, itemised (5 applications of it and
-    # 5 velocity-operator applies make up most of one StokesPC application)
-    try:
-        inner = gpc.inner
-        ih, n_in = inner.handle, inner.info()["n_local"]
-        dvi = []
-        for seed in (1, 2):
-            d = C.c_void_p()
-            inner._ck(lib.kkt_vec_alloc(ih, C.byref(d)))
-            inner._ck(lib.kkt_vec_upload(ih, d, _lib.f64(common.rng_vector(n_in, seed + rank))[1]))
-            dvi.append(d)
-        inner._ck(lib.kkt_time_apply(ih, dvi[0], dvi[1], 5, C.byref(ms)))
-        inner._ck(lib.kkt_time_apply(ih, dvi[0], dvi[1], 20, C.byref(ms)))
-        stages["velocity_preconditioner_application_ms"] = pc_stages(inner, lib, ih, dvi[0], dvi[1])
-        stages["velocity_operator_apply_ms"] = ms.value / 20
-    except Exception as e:      # noqa: BLE001 -- a side measurement must not lose the line
-        stages["velocity_preconditioner_application_ms"] = {"error": f"{type(e).__name__}: {e}"}
+    stages, t_sol = None, None
+    if full:
+        stages = stage_breakdown(outer, lib, h, d_x, d_u, d_x, d_y, n_local, min(args.steps, 10), 1,
+                                 with_pc_stages=False)
+        # ---- time to solution (one GPU): b = A x* for a smooth x* (velocity zero on the boundary,
+        # pressure blocks of zero mean), zero initial guess, outer FGMRES(10) to rtol 1e-6; says
+        # whether a cheaper preconditioner application was bought with more outer iterations
+        if world == 1:
+            th_ = p["th"]
+            m2 = 2 * p["m"]
+            Xv, Xp = th_.coords_v, th_.coords_p
+            sv = np.sin(0.5 * np.pi * Xv[:, 0]) * np.sin(0.5 * np.pi * Xv[:, 1])
+            sv = np.concatenate([sv, -0.5 * sv])
+            sv[th_.boundary_v] = 0.0
+            sq = np.cos(0.5 * np.pi * Xp[:, 0]) * np.cos(np.pi * Xp[:, 1])
+            sq -= sq.mean()
+            xs = np.concatenate([np.concatenate([(1.0 + 0.1 * k) * sv for k in range(m2)]),
+                                 np.concatenate([(1.0 - 0.05 * k) * sq for k in range(m2)])])
+            d_s, d_b = dvec(xs), dvec()
+            outer._ck(lib.kkt_apply_device(h, d_s, d_b))
+            outer._ck(lib.kkt_vec_upload(h, d_u, _lib.f64(np.zeros(n_local))[1]))
+            outer._ck(lib.kkt_set_krylov(h, 1, -1, 10, 1e-6, 0.0, 1e300, args.tts_max_it))
+            its_s, reason, nh, rn = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+            outer._ck(lib.kkt_sync(h))
+            t0 = time.perf_counter()
+            outer._ck(lib.kkt_solve_device(h, d_b, d_u, C.byref(its_s), C.byref(reason),
+                                           C.byref(rn), None, 0, C.byref(nh)))
+            outer._ck(lib.kkt_sync(h))
+            dt_s = time.perf_counter() - t0
+            got = np.empty(n_local)
+            outer._ck(lib.kkt_vec_download(h, d_u, _lib.f64(got)[1]))
+            nv_all = m2 * th_.n_v
+            gp = got[nv_all:].reshape(m2, th_.n_p)
+            gp = gp - gp.mean(axis=1, keepdims=True)     # pressures are fixed up to a constant
+            t_sol = {"rhs": "A x* for a smooth x* (velocity sin sin, pressure cos cos of zero mean)",
+                     "stopping_test": f"outer fgmres restart 10, rtol 1e-6, max {args.tts_max_it}",
+                     "converged": bool(reason.value > 0), "iterations": int(its_s.value),
+                     "seconds": dt_s,
+                     "velocity_error": float(np.linalg.norm(got[:nv_all] - xs[:nv_all])
+                                             / np.linalg.norm(xs[:nv_all])),
+                     "pressure_error": float(np.linalg.norm(gp.ravel() - xs[nv_all:])
+                                             / np.linalg.norm(xs[nv_all:]))}
+        # the nested velocity solve's block-Schur preconditioner, itemised (5 applications of it and
+        # 5 velocity-operator applies make up most of one StokesPC application)
+        try:
+            inner = gpc.inner
+            ih, n_in = inner.handle, inner.info()["n_local"]
+            dvi = []
+            for seed in (1, 2):
+                d = C.c_void_p()
+                inner._ck(lib.kkt_vec_alloc(ih, C.byref(d)))
+                inner._ck(lib.kkt_vec_upload(ih, d,
+                                             _lib.f64(common.rng_vector(n_in, seed + rank))[1]))
+                dvi.append(d)
+            inner._ck(lib.kkt_time_apply(ih, dvi[0], dvi[1], 5, C.byref(ms)))
+            inner._ck(lib.kkt_time_apply(ih, dvi[0], dvi[1], 20, C.byref(ms)))
+            stages["velocity_preconditioner_application_ms"] = pc_stages(inner, lib, ih, dvi[0],
+                                                                         dvi[1])
+            stages["velocity_operator_apply_ms"] = ms.value / 20
+        except Exception as e:      # noqa: BLE001 -- a side measurement must not lose the line
+            stages["velocity_preconditioner_application_ms"] = {"error": f"{type(e).__name__}: {e}"}
     if rank != 0:
         return None
-    alg = info["bytes_streamed"]          # what the launch must move (index arrays once)
-    achieved = alg / (spmv_ms * 1e-3) / 1e9
     th = p["th"]
-    sw = int(info.get("apply_switched", 0))
-    roof = {"kernel": ("kkt_spmv_rows_ragged (width-switched: a wave runs the body unrolled for its "
-                       "slice's width)" if sw else "kkt_spmv_rows<2,0> (slot loop)") +
-                      f" (outer Stokes-control operator, this rank's shard; {sw} of "
-                      f"{int(info.get('apply_launches', 0))} launches switched)",
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic_named(
-                "traffic_stokes_outer_operator.json", f"stokes2d {n} {n_t} {args.scheme} {args.mode}")
-            if world == 1 else None,
-            "algorithmic_bytes_per_launch": alg, "launch_ms": spmv_ms,
-            "kernel_launches_per_apply": int(info.get("apply_launches", 0)),
-            "note": "one operator apply = kernel_launches_per_apply launches of the kernel (block rows "
-                    "whose terms have two sparsity structures run in two) + the ConstantNullspace "
-                    "corrections of the pressure blocks; bytes, time and traffic are per apply"}
-    ok = roofline_check(roof)
-    print(json.dumps({
-        "metric": "Krylov iterations/s (preconditioned FGMRES(10), all-at-once Stokes-control KKT)",
-        "value": its / dt, "unit": "Krylov iterations/s", "n_gpus": world, "steps": its,
-        "warmup": args.warmup, "ms_per_step": 1e3 * dt / its, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": (f"2-D Stokes control, Taylor-Hood P2-P1 {n}x{n}, n_t={n_t}, "
-                                f"beta={beta:g}, T={args.T:g}, {args.scheme}, mode {args.mode}"),
-                   "unknowns": int(2 * p["m"] * (th.n_v + th.n_p)), "n_v": int(th.n_v),
-                   "n_p": int(th.n_p),
-                   "krylov": "outer fgmres restart 10; inner gmres, 5 iterations per application",
-                   "preconditioner": f"StokesPC, Chebyshev (its, emin, emax): {specs}" + (
-                       f"; velocity sub-solves {coarse[1]} x [Galerkin correction on "
-                       f"{coarse[0].shape[1]} coarse functions + the schur sweeps]" if coarse else "") + (
-                       f"; K_p solve {kp_coarse[1]} x [deflated Galerkin correction on "
-                       f"{kp_coarse[0].shape[1]} coarse functions + the kp sweeps]" if kp_coarse else ""),
-                   "parallelism": f"time-block rows over {world} GPU(s)",
-                   "transport": (getattr(comm, "name", "rccl") if world > 1 else "none"),
-                   "sweeps": sweep_plan(inner_info),
-                   "pc_apply_ms": pc_ms, "kkt_apply_ms": spmv_ms,
-                   "time_to_solution": t_sol},
-        "stages": stages,
-        "roofline": roof}))
+    config = {"workload": (f"2-D Stokes control, Taylor-Hood P2-P1 {n}x{n}, n_t={n_t}, "
+                           f"beta={beta:g}, T={args.T:g}, {args.scheme}, mode {args.mode}"),
+              "unknowns": int(2 * p["m"] * (th.n_v + th.n_p)), "n_v": int(th.n_v),
+              "n_p": int(th.n_p),
+              "krylov": "outer fgmres restart 10; inner gmres, 5 iterations per application",
+              "preconditioner": f"StokesPC, Chebyshev (its, emin, emax): {specs}" + (
+                  f"; velocity sub-solves {coarse[1]} x [Galerkin correction on "
+                  f"{coarse[0].shape[1]} coarse functions + the schur sweeps]" if coarse else "") + (
+                  f"; K_p solve {kp_coarse[1]} x [deflated Galerkin correction on "
+                  f"{kp_coarse[0].shape[1]} coarse functions + the kp sweeps]" if kp_coarse else ""),
+              "parallelism": f"time-block rows over {world} GPU(s)",
+              "transport": (getattr(comm, "name", "rccl") if world > 1 else "none"),
+              "sweeps": sweep_plan(inner_info)}
+    line = {"metric": "Krylov iterations/s (preconditioned FGMRES(10), all-at-once Stokes-control KKT)",
+            "value": its / dt, "unit": "Krylov iterations/s", "n_gpus": world, "steps": its,
+            "warmup": args.warmup, "ms_per_step": 1e3 * dt / its, "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": config}
+    ok = True
+    if full:
+        alg = info["bytes_streamed"]          # what the launch must move (index arrays once)
+        achieved = alg / (spmv_ms * 1e-3) / 1e9
+        sw = int(info.get("apply_switched", 0))
+        roof = {"kernel": ("kkt_spmv_rows_ragged (width-switched: a wave runs the body unrolled for "
+                           "its slice's width)" if sw else "kkt_spmv_rows<2,0> (slot loop)") +
+                          f" (outer Stokes-control operator, this rank's shard; {sw} of "
+                          f"{int(info.get('apply_launches', 0))} launches switched)",
+                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic_named(
+                    "traffic_stokes_outer_operator.json", f"stokes2d {n} {n_t} {args.scheme} {args.mode}")
+                if world == 1 else None,
+                "algorithmic_bytes_per_launch": alg, "launch_ms": spmv_ms,
+                "kernel_launches_per_apply": int(info.get("apply_launches", 0)),
+                "note": "one operator apply = kernel_launches_per_apply launches of the kernel (block "
+                        "rows whose terms have two sparsity structures run in two) + the "
+                        "ConstantNullspace corrections of the pressure blocks; bytes, time and "
+                        "traffic are per apply"}
+        ok = roofline_check(roof)
+        config.update({"pc_apply_ms": pc_ms, "kkt_apply_ms": spmv_ms, "time_to_solution": t_sol})
+        line.update({"stages": stages, "roofline": roof})
+    print(json.dumps(line))
     return 0 if ok else 4
 
 
@@ -636,11 +654,16 @@ def main():
                     help="stokes2d: iteration cap of the time-to-solution solve")
     ap.add_argument("--coarse-cell", type=int, default=8,
                     help="coarse cells of this many mesh widths per axis")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements around the timed steps: SpMV roofline, "
+                         "preconditioner and per-stage timings, time to solution, CPU baseline, "
+                         "the BASELINE configs[3] leg (a plain run only times the steps)")
     ap.add_argument("--spmv-reps", type=int, default=50)
     ap.add_argument("--cpu-its", type=int, default=24)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-config4", action="store_true",
-                    help="skip the side leg on BASELINE configs[3] (3-D heat 64^3, n_t = 128)")
+                    help="--full without the side leg on BASELINE configs[3] (3-D heat 64^3, "
+                         "n_t = 128)")
     ap.add_argument("--no-tile-coordinates", action="store_true",
                     help="do not pass the dof coordinates as the tiling hint of the sweep programs")
     ap.add_argument("--lib-option", action="append", default=[], metavar="KEY=VALUE",
@@ -697,14 +720,15 @@ def main():
         print(json.dumps(out))
         return 0
     if rank == 0 and out is not None:
-        ok = roofline_check(out["roofline"])
         p = out.pop("_problem")
-        if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only (contract)
-            out["cpu_baseline"] = cpu_baseline(p, args.cpu_its, max(1, args.cpu_its // 8))
+        if args.full:
+            ok = roofline_check(out["roofline"])
+            if not args.no_cpu_baseline and world == 1:      # rank 0 at N = 1 only (contract)
+                out["cpu_baseline"] = cpu_baseline(p, args.cpu_its, max(1, args.cpu_its // 8))
     # BASELINE configs[3] (3-D heat 64^3 P1, n_t = 128: the 8-GPU configuration, which also fits
     # one GPU) beside the headline line, as its own object, time-sharded like the headline at
     # N > 1 (every rank takes part); failures are reported, not fatal
-    if (not args.no_config4 and not args.only_spmv and args.workload == "heat2d"
+    if (args.full and not args.no_config4 and not args.only_spmv and args.workload == "heat2d"
             and args.n == 256 and args.n_t == 64):
         a4 = argparse.Namespace(**vars(args))
         a4.workload, a4.n, a4.n_t, a4.mode = "heat3d", 64, 128, args.mode
@@ -737,7 +761,8 @@ def main():
 
 
 def measure_heat(args, rank, world, local_rank, tts):
-    """One heat-control workload: roofline leg (KKT SpMV), preconditioner timings, Krylov leg."""
+    """One heat-control workload: the Krylov leg; with --full also the roofline leg (KKT SpMV),
+    preconditioner timings, per-stage itemisation and (tts) time to solution."""
     from control_amd import _lib
     from control_amd import problems as common
     from control_amd.dist import make_comm
@@ -774,55 +799,63 @@ def measure_heat(args, rank, world, local_rank, tts):
     x = common.rng_vector(n_local, common.SEED + rank)
     d_x, d_y = dvec(x), dvec()
 
-    # ---- roofline leg: the KKT block-row SpMV, HIP events on the library's stream.
-    # achieved = bytes the launch must move (every value array once, every index structure
-    # once -- they are shared on the device --, x in, y out) / launch time.  The SURVEY 8d CSR
-    # formula (12 B per non-zero of every block) is kept as a named side figure: it prices index
-    # bytes the device never streams and can exceed the HBM peak.
-    ms = C.c_float()
-    gsys._ck(lib.kkt_time_apply(h, d_x, d_y, 5, C.byref(ms)))          # warm-up
-    gsys._ck(lib.kkt_time_apply(h, d_x, d_y, args.spmv_reps, C.byref(ms)))
-    spmv_ms = ms.value / args.spmv_reps
-    alg_bytes = info["bytes_streamed"]
-    csr_bytes = info["bytes_algorithmic"]
-    achieved = alg_bytes / (spmv_ms * 1e-3) / 1e9
-    if args.only_spmv:
-        workload_ = (f"{'2-D' if args.workload == 'heat2d' else '3-D'} heat control, "
-                     f"{args.n}^{2 if args.workload == 'heat2d' else 3} P1, n_t={args.n_t}, "
-                     f"beta={args.beta:g}, T={args.T:g}, {args.scheme}, mode {args.mode}")
-        return {"config": {"workload": workload_, "unknowns": int(2 * p["m"] * p["sd"].n_dofs)},
-                "roofline": {"achieved": achieved, "frac": achieved / HBM_PEAK_GBS,
-                             "algorithmic_bytes_per_launch": alg_bytes, "launch_ms": spmv_ms,
-                             "csr_formula_bytes_per_launch": csr_bytes}}
-    gsys._ck(lib.kkt_time_pc_apply(h, d_x, d_y, 2, C.byref(ms)))
-    gsys._ck(lib.kkt_time_pc_apply(h, d_x, d_y, 5, C.byref(ms)))
-    pc_ms = ms.value / 5
-    # the persistent sweep programs of one application, HIP events around each launch
+    full = args.full or args.only_spmv
     sweeps = None
-    if world == 1:
-        sw_ms, sw_n, sw_ph = C.c_float(), C.c_int(), C.c_int64()
-        gsys._ck(lib.kkt_time_pc_sweeps(h, d_x, d_y, C.byref(sw_ms), C.byref(sw_n),
-                                        C.byref(sw_ph)))
-        if sw_n.value > 0:
-            nx = p["sd"].n_dofs
-            nnz_block = info["nnz_blocks"] // max(1, info["n_blocks_stored"])
-            S_bytes = nnz_block * 12 + (nx + 1) * 4 + 16 * nx      # one spatial SpMV
-            alg_sw = sw_ph.value * S_bytes
-            sweeps = {
-                "kernel": "sweep programs (the time sweeps of one preconditioner application)",
-                "bound": "latency (hand-offs between dependent SpMV steps; operands on chip)",
-                "launches": sw_n.value, "phases": int(sw_ph.value), "total_ms": sw_ms.value,
-                "us_per_phase": 1e3 * sw_ms.value / sw_ph.value,
-                "traffic": None, "hbm_GBs": None, "hbm_frac": None,
-                "bytes_if_streamed": int(alg_sw),
-                "GBs_if_streamed": alg_sw / (sw_ms.value * 1e-3) / 1e9,
-                "note": "traffic = HBM bytes of all sweep launches of one application from the "
-                        "committed PMC passes, hbm_GBs = traffic / total_ms, hbm_frac = hbm_GBs / "
-                        f"{HBM_PEAK_GBS:.0f}: matrix, diagonal and iterates stay on chip (registers "
-                        "/ LDS), the launches are bound by the hand-off latency between dependent "
-                        "steps, not by HBM.  *_if_streamed = what plain launches would stream: "
-                        "SpMV steps x S, S = 12 nnz + 4 (N_x + 1) + 16 N_x of one spatial block "
-                        "(SURVEY 8d, B_pc); a side figure, not a fraction of anything"}
+    if not full:
+        # a plain run: one untimed application of the operator and of the preconditioner, so that
+        # first-use costs (code-object loads, the capture of the preconditioner's graphs) stay
+        # outside the timed steps even at --warmup 0, as when the --full legs precede them
+        gsys._ck(lib.kkt_apply_device(h, d_x, d_y))
+        gsys._ck(lib.kkt_pc_apply_device(h, d_x, d_y))
+    else:
+        # ---- roofline leg: the KKT block-row SpMV, HIP events on the library's stream.
+        # achieved = bytes the launch must move (every value array once, every index structure
+        # once -- they are shared on the device --, x in, y out) / launch time.  The SURVEY 8d
+        # CSR formula (12 B per non-zero of every block) is kept as a named side figure: it prices
+        # index bytes the device never streams and can exceed the HBM peak.
+        ms = C.c_float()
+        gsys._ck(lib.kkt_time_apply(h, d_x, d_y, 5, C.byref(ms)))          # warm-up
+        gsys._ck(lib.kkt_time_apply(h, d_x, d_y, args.spmv_reps, C.byref(ms)))
+        spmv_ms = ms.value / args.spmv_reps
+        alg_bytes = info["bytes_streamed"]
+        csr_bytes = info["bytes_algorithmic"]
+        achieved = alg_bytes / (spmv_ms * 1e-3) / 1e9
+        if args.only_spmv:
+            workload_ = (f"{'2-D' if args.workload == 'heat2d' else '3-D'} heat control, "
+                         f"{args.n}^{2 if args.workload == 'heat2d' else 3} P1, n_t={args.n_t}, "
+                         f"beta={args.beta:g}, T={args.T:g}, {args.scheme}, mode {args.mode}")
+            return {"config": {"workload": workload_, "unknowns": int(2 * p["m"] * p["sd"].n_dofs)},
+                    "roofline": {"achieved": achieved, "frac": achieved / HBM_PEAK_GBS,
+                                 "algorithmic_bytes_per_launch": alg_bytes, "launch_ms": spmv_ms,
+                                 "csr_formula_bytes_per_launch": csr_bytes}}
+        gsys._ck(lib.kkt_time_pc_apply(h, d_x, d_y, 2, C.byref(ms)))
+        gsys._ck(lib.kkt_time_pc_apply(h, d_x, d_y, 5, C.byref(ms)))
+        pc_ms = ms.value / 5
+        # the persistent sweep programs of one application, HIP events around each launch
+        if world == 1:
+            sw_ms, sw_n, sw_ph = C.c_float(), C.c_int(), C.c_int64()
+            gsys._ck(lib.kkt_time_pc_sweeps(h, d_x, d_y, C.byref(sw_ms), C.byref(sw_n),
+                                            C.byref(sw_ph)))
+            if sw_n.value > 0:
+                nx = p["sd"].n_dofs
+                nnz_block = info["nnz_blocks"] // max(1, info["n_blocks_stored"])
+                S_bytes = nnz_block * 12 + (nx + 1) * 4 + 16 * nx      # one spatial SpMV
+                alg_sw = sw_ph.value * S_bytes
+                sweeps = {
+                    "kernel": "sweep programs (the time sweeps of one preconditioner application)",
+                    "bound": "latency (hand-offs between dependent SpMV steps; operands on chip)",
+                    "launches": sw_n.value, "phases": int(sw_ph.value), "total_ms": sw_ms.value,
+                    "us_per_phase": 1e3 * sw_ms.value / sw_ph.value,
+                    "traffic": None, "hbm_GBs": None, "hbm_frac": None,
+                    "bytes_if_streamed": int(alg_sw),
+                    "GBs_if_streamed": alg_sw / (sw_ms.value * 1e-3) / 1e9,
+                    "note": "traffic = HBM bytes of all sweep launches of one application from the "
+                            "committed PMC passes, hbm_GBs = traffic / total_ms, hbm_frac = hbm_GBs / "
+                            f"{HBM_PEAK_GBS:.0f}: matrix, diagonal and iterates stay on chip (registers "
+                            "/ LDS), the launches are bound by the hand-off latency between dependent "
+                            "steps, not by HBM.  *_if_streamed = what plain launches would stream: "
+                            "SpMV steps x S, S = 12 nnz + 4 (N_x + 1) + 16 N_x of one spatial block "
+                            "(SURVEY 8d, B_pc); a side figure, not a fraction of anything"}
 
     # ---- Krylov leg: W warm-up iterations, then exactly K timed ones
     d_b, d_u = dvec(x), dvec()
@@ -842,8 +875,8 @@ def measure_heat(args, rank, world, local_rank, tts):
         gsys._ck(lib.kkt_comm_max(h, C.byref(dt)))
         return its.value, dt.value, rn.value
 
-    print(f"[bench] spmv {spmv_ms:.3f} ms, pc {pc_ms:.3f} ms; Krylov leg", file=sys.stderr,
-          flush=True)
+    print((f"[bench] spmv {spmv_ms:.3f} ms, pc {pc_ms:.3f} ms; " if full else "[bench] ")
+          + "Krylov leg", file=sys.stderr, flush=True)
     if args.warmup > 0:
         run(args.warmup)
     its, dt, rn = run(args.steps)
@@ -855,12 +888,13 @@ def measure_heat(args, rank, world, local_rank, tts):
         dump_outputs(args.dump_outputs, rank, world, u, its, rn)
 
     # ---- SURVEY 8e itemisation (outside the timed region)
-    stages = stage_breakdown(gsys, lib, h, d_b, d_u, d_x, d_y, n_local, min(args.steps, 20), 0)
+    stages = (stage_breakdown(gsys, lib, h, d_b, d_u, d_x, d_y, n_local, min(args.steps, 20), 0)
+              if full else None)
 
     # ---- time to solution: the README right-hand side, library-default stopping test (gmres,
     # restart 10, rtol 1e-6, control.py:3261-3266), at most 300 iterations
     t_sol = None
-    if tts:
+    if tts and full:
         sd = p["sd"]
         g0, g1 = readme_rhs(p)
         lo = getattr(gsys, "_lo", 0)
@@ -891,54 +925,57 @@ def measure_heat(args, rank, world, local_rank, tts):
     workload = (f"{'2-D' if args.workload == 'heat2d' else '3-D'} heat control, "
                 f"{args.n}^{2 if args.workload == 'heat2d' else 3} P1, n_t={args.n_t}, "
                 f"beta={args.beta:g}, T={args.T:g}, {args.scheme}, mode {args.mode}")
-    frac = achieved / HBM_PEAK_GBS
     plan = sweep_plan(info_end)
+    config = {
+        "workload": workload,
+        "unknowns": int(2 * p["m"] * p["sd"].n_dofs),
+        "krylov": "gmres, left preconditioning, restart 10, classical Gram-Schmidt",
+        "preconditioner": (f"block Schur: mass Chebyshev {p['mass']}, "
+                           + (f"Schur sub-solves {p['coarse'][1]} x [Galerkin correction on "
+                              f"{p['coarse'][0].shape[1]} multilinear coarse functions + "
+                              f"Chebyshev sweeps {p['schur']}]" if p.get("coarse") else
+                              f"Schur Chebyshev {p['schur']}") + " (its, emin, emax)"),
+        "parallelism": f"time-block rows over {world} GPU(s)",
+        "transport": (getattr(comm, "name", "rccl") if world > 1 else "none"),
+        "sweep_tiles": ("boxes from the dof coordinates (kkt_set_tile_coordinates)"
+                        if not args.no_tile_coordinates else "bisection of the sparsity graph"),
+        "sweeps": plan, "setup_s": t_setup}
+    if full:
+        config.update({"pc_apply_ms": pc_ms, "kkt_apply_ms": spmv_ms, "time_to_solution": t_sol})
     out = {
         "metric": "Krylov iterations/s (preconditioned GMRES(10), all-at-once heat-control KKT)",
         "value": its / dt, "unit": "Krylov iterations/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / its,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "f64", "data": "synthetic",
-        "config": {
-            "workload": workload,
-            "unknowns": int(2 * p["m"] * p["sd"].n_dofs),
-            "krylov": "gmres, left preconditioning, restart 10, classical Gram-Schmidt",
-            "preconditioner": (f"block Schur: mass Chebyshev {p['mass']}, "
-                               + (f"Schur sub-solves {p['coarse'][1]} x [Galerkin correction on "
-                                  f"{p['coarse'][0].shape[1]} multilinear coarse functions + "
-                                  f"Chebyshev sweeps {p['schur']}]" if p.get("coarse") else
-                                  f"Schur Chebyshev {p['schur']}") + " (its, emin, emax)"),
-            "parallelism": f"time-block rows over {world} GPU(s)",
-            "transport": (getattr(comm, "name", "rccl") if world > 1 else "none"),
-            "sweep_tiles": ("boxes from the dof coordinates (kkt_set_tile_coordinates)"
-                            if not args.no_tile_coordinates else "bisection of the sparsity graph"),
-            "sweeps": plan,
-            "pc_apply_ms": pc_ms, "kkt_apply_ms": spmv_ms, "setup_s": t_setup,
-            "time_to_solution": t_sol},
-        "stages": stages,
-        "roofline": {
-            "kernel": "kkt_spmv_rows (fused block-row SpMV of the KKT operator)",
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": frac,
-            "traffic": measured_traffic(workload) if world == 1 else None,
-            "algorithmic_bytes_per_launch": alg_bytes, "launch_ms": spmv_ms,
-            "frac_of_measured_copy_rate": achieved / MEASURED_COPY_GBS,
-            "csr_formula_bytes_per_launch": csr_bytes,
-            "csr_formula_GBs": csr_bytes / (spmv_ms * 1e-3) / 1e9,
-            "note": "algorithmic bytes = 8 B per stored non-zero of every value array + 4 B per "
-                    "non-zero and 4 B per row of every distinct sparsity structure (blocks of "
-                    "equal structure share one index array on the device) + 16 B per unknown; "
-                    "csr_formula_* = SURVEY 8d mode-" + args.mode + " formula (12 B per non-zero "
-                    "of every block), a side figure that may exceed the peak"},
+        "config": config,
         "_problem": p,
     }
     if plan["program_fallbacks"]:
-        out["config"]["warning"] = ("a persistent sweep program timed out during this run and the "
-                                    "preconditioner fell back to plain launches: value and "
-                                    "pc_apply_ms measure that form (see config.sweeps): " + last_error)
+        config["warning"] = ("a persistent sweep program timed out during this run and the "
+                             "preconditioner fell back to plain launches: value"
+                             + (" and pc_apply_ms measure" if full else " measures")
+                             + " that form (see config.sweeps): " + last_error)
+    if not full:
+        return out
+    out["stages"] = stages
+    out["roofline"] = {
+        "kernel": "kkt_spmv_rows (fused block-row SpMV of the KKT operator)",
+        "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS,
+        "traffic": measured_traffic(workload) if world == 1 else None,
+        "algorithmic_bytes_per_launch": alg_bytes, "launch_ms": spmv_ms,
+        "frac_of_measured_copy_rate": achieved / MEASURED_COPY_GBS,
+        "csr_formula_bytes_per_launch": csr_bytes,
+        "csr_formula_GBs": csr_bytes / (spmv_ms * 1e-3) / 1e9,
+        "note": "algorithmic bytes = 8 B per stored non-zero of every value array + 4 B per "
+                "non-zero and 4 B per row of every distinct sparsity structure (blocks of "
+                "equal structure share one index array on the device) + 16 B per unknown; "
+                "csr_formula_* = SURVEY 8d mode-" + args.mode + " formula (12 B per non-zero "
+                "of every block), a side figure that may exceed the peak"}
     if sweeps is not None:
         # HBM-side bytes of one application (all sweep launches) from the committed PMC passes
-        per_launch = measured_sweep_traffic(workload, out["config"]["preconditioner"],
+        per_launch = measured_sweep_traffic(workload, config["preconditioner"],
                                             sweeps["phases"] // sweeps["launches"])
         if per_launch is not None:
             sweeps["traffic"] = per_launch * sweeps["launches"]

@@ -7,7 +7,7 @@ export TMPDIR=/tmp KKT_NO_GRAPH=1
 o=gpurun_out/pmc_sweeps
 mkdir -p $o
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 400 rocprofv3 --pmc $c --kernel-trace -d $o/$c -o p --output-format csv -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 > $o/$c.json 2> $o/$c.err
+  timeout -k 10 400 rocprofv3 --pmc $c --kernel-trace -d $o/$c -o p --output-format csv -- python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > $o/$c.json 2> $o/$c.err
   echo "$c pass done"
 done
 python3 scripts/pmc_sweeps_summary.py $o

@@ -9,20 +9,20 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 o=gpurun_out/r02_prof
 mkdir -p $o
-timeout -k 10 600 python bench.py > $o/bench_r02.json 2> $o/bench_r02.err
+timeout -k 10 600 python bench.py --full > $o/bench_r02.json 2> $o/bench_r02.err
 echo "bench rc=$?"
-KKT_NO_GRAPH=1 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $o/heat -o h --output-format csv -- python3 bench.py --no-cpu-baseline --no-config4 > $o/bench_under_rocprof.json 2> $o/heat.err
+KKT_NO_GRAPH=1 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $o/heat -o h --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-config4 > $o/bench_under_rocprof.json 2> $o/heat.err
 echo "kernel stats rc=$?"
 for c in FETCH_SIZE WRITE_SIZE; do
-  KKT_NO_GRAPH=1 timeout -k 10 400 rocprofv3 --pmc $c --kernel-trace -d $o/$c -o p --output-format csv -- python3 bench.py --no-cpu-baseline --no-config4 --steps 3 --warmup 1 > $o/$c.json 2> $o/$c.err
+  KKT_NO_GRAPH=1 timeout -k 10 400 rocprofv3 --pmc $c --kernel-trace -d $o/$c -o p --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-config4 --steps 3 --warmup 1 > $o/$c.json 2> $o/$c.err
   echo "$c rc=$?"
 done
 : > $o/other_configs.jsonl
 for extra in "--scheme CN" "--mode S" "--schur-auto" "--schur-auto --scheme CN" "--n 512 --schur-auto --steps 10 --warmup 2" "--workload heat3d --n 32 --n_t 32 --schur-auto"; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-config4 $extra >> $o/other_configs.jsonl 2>> $o/other.err
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-config4 $extra >> $o/other_configs.jsonl 2>> $o/other.err
   echo "variant [$extra] rc=$?"
 done
-timeout -k 10 300 python bench.py --workload stokes2d --steps 10 --warmup 2 > $o/bench_stokes2d.json 2> $o/stokes.err
+timeout -k 10 300 python bench.py --full --workload stokes2d --steps 10 --warmup 2 > $o/bench_stokes2d.json 2> $o/stokes.err
 echo "stokes rc=$?"
 python3 - <<'PY'
 import csv, glob, json, os

@@ -9,7 +9,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_parity.py -x -q > $o/parity.lo
 echo "parity rc=$?"; tail -5 $o/parity.log
 run() {  # name, env...
   name=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --no-cpu-baseline --no-config4 --steps 20 --warmup 3 > $o/$name.json 2> $o/$name.err
+  env "$@" timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-config4 --steps 20 --warmup 3 > $o/$name.json 2> $o/$name.err
   echo "$name rc=$? $(python3 - <<PY
 import json
 try:

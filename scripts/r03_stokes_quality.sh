@@ -9,7 +9,7 @@ run() {
   echo "== $*" >> $o/err.log
   # (base flags: what bench.py's defaults were when the first three groups ran -- plain K_p
   # polynomial, estimated unless --kp-its is given, lower bound 2e-3 unless --kp-emin is given)
-  timeout -k 10 330 python bench.py --workload stokes2d --steps 10 --warmup 2 --kp-coarse-cycles 0 --kp-its -1 --kp-emin 0.002 "$@" >> $o/lines.jsonl 2>> $o/err.log
+  timeout -k 10 330 python bench.py --full --workload stokes2d --steps 10 --warmup 2 --kp-coarse-cycles 0 --kp-its -1 --kp-emin 0.002 "$@" >> $o/lines.jsonl 2>> $o/err.log
   echo "[$*] rc=$?"
 }
 if [ "$1" = "fourth" ]; then      # two-grid form of the K_p solve

@@ -146,8 +146,9 @@ def _bench_two_ranks(cmd_prefix, extra=()):
     env = dict(os.environ, KKT_DEVICE="0", PYTHONUNBUFFERED="1")
     for k in ("KKT_TRANSPORT", "RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
+    # --full: the assertions below read the side legs (time to solution, stages, config4)
     cmd = cmd_prefix + [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup",
-                        "1", "--no-cpu-baseline"] + list(extra)
+                        "1", "--full", "--no-cpu-baseline"] + list(extra)
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     return json.loads(out.stdout.strip().splitlines()[-1]), out.stderr
