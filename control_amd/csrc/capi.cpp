@@ -1,5 +1,7 @@
 // extern "C" boundary of libkkt (include/kkt.h).  No C++ exception leaves this file.
 #include <algorithm>
+#include <charconv>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -7,6 +9,7 @@
 #include "comm.hpp"
 #include "pc.hpp"
 #include "system.hpp"
+#include "tiles.hpp"
 
 using namespace kkt;
 
@@ -31,6 +34,71 @@ static std::string g_create_error;
         S.err = e.what();                                 \
         return KKT_ERR_STATE;                             \
     }
+
+// ---- execution options: one row per key (include/kkt.h documents them)
+template <bool Options::*F>
+static bool set_switch(Options &o, const char *v) {
+    if (std::strcmp(v, "0") != 0 && std::strcmp(v, "1") != 0) return false;
+    o.*F = v[0] == '1';
+    return true;
+}
+// a decimal integer, the whole string, in [LO, HI]
+template <int Options::*F, int LO = INT_MIN, int HI = INT_MAX>
+static bool set_int(Options &o, const char *v) {
+    int x = 0;
+    const auto r = std::from_chars(v, v + std::strlen(v), x);
+    if (r.ec != std::errc() || *r.ptr || x < LO || x > HI) return false;
+    o.*F = x;
+    return true;
+}
+static bool set_prog_mode(Options &o, const char *v) {
+    static const char *names[] = {"auto", "tile", "dataflow", "flags", "w"};   // ProgMode order
+    for (int k = 0; k < 5; ++k)
+        if (std::strcmp(v, names[k]) == 0) {
+            o.prog_mode = (ProgMode)k;
+            return true;
+        }
+    return false;
+}
+static bool set_coarse_setup(Options &o, const char *v) {
+    o.coarse_columns = std::strcmp(v, "columns") == 0;
+    return o.coarse_columns || std::strcmp(v, "batched") == 0;
+}
+
+struct OptionKey {
+    const char *key, *accepted;
+    bool (*set)(Options &, const char *);
+};
+static const OptionKey option_keys[] = {
+    {"sell_r", "1 | 2", set_int<&Options::sell_r, 1, 2>},
+    {"sell_sort", "0 | 1", set_switch<&Options::sell_sort>},
+    {"sell_sigma", "1..64", set_int<&Options::sell_sigma, 1, 64>},
+    {"shared_rows", "0 | 1", set_switch<&Options::shared_rows>},
+    {"ragged_switch", "0 | 1", set_switch<&Options::ragged_switch>},
+    {"ragged_xcd", "0 | 1", set_switch<&Options::ragged_xcd>},
+    {"apply_xcd", "0 | 1", set_switch<&Options::apply_xcd>},
+    {"pc_xcd", "0 | 1", set_switch<&Options::pc_xcd>},
+    {"interleave", "0 | 1", set_switch<&Options::interleave>},
+    {"kernarg_ops", "0 | 1", set_switch<&Options::kernarg_ops>},
+    {"no_graph", "0 | 1", set_switch<&Options::no_graph>},
+    {"persistent", "0 | 1", set_switch<&Options::persistent>},
+    {"prog_mode", "auto | tile | dataflow | flags | w", set_prog_mode},
+    {"prog_waves", "1..8", set_int<&Options::prog_waves, 1, 8>},
+    {"prog_steps", "0 | 1", set_switch<&Options::prog_steps>},
+    {"tile_depth", "1..16", set_int<&Options::tile_depth, 1, TILE_MAX_DEPTH>},
+    {"tile_waves", "1..16", set_int<&Options::tile_waves, 1, 16>},
+    {"tile_unfused", "0 | 1", set_switch<&Options::tile_unfused>},
+    {"tile_poll_delay", "an integer", set_int<&Options::tile_poll_delay>},
+    {"lanes", "0 | 1", set_switch<&Options::lanes>},
+    {"lane_chunks", "an integer", set_int<&Options::lane_chunks>},
+    {"coarse_setup", "batched | columns", set_coarse_setup},
+    {"coarse_keep", "0 | 1", set_switch<&Options::coarse_keep>},
+    {"coarse_blocks", "0 | 1", set_switch<&Options::coarse_blocks>},
+    {"stage_timers", "0 | 1", set_switch<&Options::stage_timers>},
+    {"verbose", "0 | 1", set_switch<&Options::verbose>},
+    {"stamps", "0 | 1", set_switch<&Options::stamps>},
+    {"debug_drop_handoff", "an integer", set_int<&Options::debug_drop_handoff>},
+};
 
 extern "C" {
 
@@ -67,17 +135,17 @@ const char *kkt_last_error(kkt_handle h) { return h ? h->S.err.c_str() : g_creat
 
 int kkt_set_option(kkt_handle h, const char *key, const char *value) {
     KKT_TRY(h, {
-        static const char *known[] = {"sell_r", "sell_sort", "no_graph", "persistent", "prog_mode",
-                                      "prog_waves", "prog_steps", "tile_depth", "tile_waves",
-                                      "lanes", "lane_chunks", "kernarg_ops", "shared_rows",
-                                      "verbose", "stamps", "tile_poll_delay", "tile_unfused",
-                                      "debug_drop_handoff", "stage_timers", "sell_sigma", "ragged_switch", "ragged_xcd", "apply_xcd", "pc_xcd",
-                                      "interleave", "coarse_setup", "coarse_keep", "coarse_blocks"};
         if (!key || !value) fail(KKT_ERR_ARG, "null option");
-        bool ok = false;
-        for (const char *k : known) ok = ok || std::strcmp(k, key) == 0;
-        if (!ok) fail(KKT_ERR_ARG, std::string("unknown option: ") + key);
-        S.options[key] = value;
+        for (const OptionKey &k : option_keys) {
+            if (std::strcmp(k.key, key) != 0) continue;
+            Options o = S.opts;      // a rejected value leaves the options as they were
+            if (!k.set(o, value))
+                fail(KKT_ERR_ARG, std::string("option ") + key + ": \"" + value +
+                                      "\" is not accepted (" + k.accepted + ")");
+            S.opts = o;
+            return KKT_OK;
+        }
+        fail(KKT_ERR_ARG, std::string("unknown option: ") + key);
     });
 }
 

@@ -605,8 +605,6 @@ __device__ __forceinline__ int xcd_workgroup(int nwg, int xcd) {
 // the batched preconditioner steps (pc_rows_shared*, pc_rows_il) in the same order (default on,
 // option "pc_xcd" = "0": dispatch order): each XCD gathers from an eighth of every iterate instead
 // of all of it -- cfg 2: batched steps 1.045 -> 0.869 ms per application; 64^3: no change
-static bool g_pc_xcd = true;
-void set_pc_xcd(bool on) { g_pc_xcd = on; }
 template <int R, int WFIX>
 __global__ __launch_bounds__(256) void kkt_spmv_rows(const RowOp *__restrict__ ops,
                                                      const Bases bases, const int xcd) {
@@ -1780,9 +1778,10 @@ __global__ __launch_bounds__(256) void pc_rows_il(const IlOp *__restrict__ ops, 
     }
 }
 
-void launch_rowops_il(hipStream_t s, const IlOp *d_ops, int ngroups, int max_slices, int uniform_w) {
+void launch_rowops_il(hipStream_t s, const IlOp *d_ops, int ngroups, int max_slices, int uniform_w,
+                      bool pc_xcd) {
     if (ngroups <= 0 || max_slices <= 0) return;
-    const int gx = (max_slices + 3) / 4, xcd = g_pc_xcd ? 1 : 0;
+    const int gx = (max_slices + 3) / 4, xcd = pc_xcd ? 1 : 0;
     const dim3 grid(xcd ? (gx + 7) / 8 * 8 : gx, ngroups), block(256);
     if (uniform_w > 0 && uniform_w <= 8)
         hipLaunchKernelGGL((pc_rows_il<8>), grid, block, 0, s, d_ops, xcd);
@@ -1886,10 +1885,10 @@ bool launch_rowops_grouped(hipStream_t s, const RowOp *d_ops, const int32_t *d_g
 }
 
 bool launch_rowops_shared(hipStream_t s, const RowOp *d_ops, int nops, int max_slices, int R,
-                          int uniform_w) {
+                          int uniform_w, bool pc_xcd) {
     constexpr int NB = 4;
     if (R != 2 || nops < NB) return false;
-    const int gx = (max_slices + 3) / 4, xcd = g_pc_xcd ? 1 : 0;
+    const int gx = (max_slices + 3) / 4, xcd = pc_xcd ? 1 : 0;
     const dim3 grid(xcd ? (gx + 7) / 8 * 8 : gx, (nops + NB - 1) / NB), block(256);
     switch (uniform_w) {
 #define KKT_W(n) case n: hipLaunchKernelGGL((pc_rows_shared<n, NB>), grid, block, 0, s, d_ops, nops, xcd); return true;
@@ -1901,67 +1900,61 @@ bool launch_rowops_shared(hipStream_t s, const RowOp *d_ops, int nops, int max_s
     }
 }
 
-static bool g_apply_xcd = false;
-void set_apply_xcd(bool on) { g_apply_xcd = on; }
 template <int R, int WFIX>
 static void launch_one(hipStream_t s, dim3 grid, const RowOp *d_ops, const Bases &bases, int tag,
-                       const RowOp *h_single) {
+                       const RowOp *h_single, bool xcd) {
     if (h_single && tag != 0)
         hipLaunchKernelGGL((pc_row_step<R, WFIX>), grid, dim3(256), 0, s, *h_single, bases);
     else if (tag == 0)
-        hipLaunchKernelGGL((kkt_spmv_rows<R, WFIX>),
-                           dim3(g_apply_xcd ? (grid.x + 7) / 8 * 8 : grid.x, grid.y), dim3(256), 0, s,
-                           d_ops, bases, g_apply_xcd ? 1 : 0);
+        hipLaunchKernelGGL((kkt_spmv_rows<R, WFIX>), dim3(xcd ? (grid.x + 7) / 8 * 8 : grid.x, grid.y),
+                           dim3(256), 0, s, d_ops, bases, xcd ? 1 : 0);
     else
         hipLaunchKernelGGL((pc_rows<R, WFIX>), grid, dim3(256), 0, s, d_ops, bases);
 }
 
-static bool g_ragged_xcd = true;
-void set_ragged_xcd(bool on) { g_ragged_xcd = on; }
-
 void launch_rowops(hipStream_t s, const RowOp *d_ops, int nops, int max_slices, int R,
-                   const Bases &bases, int tag, int uniform_w, const RowOp *h_single) {
+                   const Bases &bases, int tag, int uniform_w, const RowOp *h_single, XcdOrder xcd) {
     if (nops <= 0 || max_slices <= 0) return;
     dim3 grid((max_slices + 3) / 4, nops);
     if (nops != 1) h_single = nullptr;
     if (R != 2) {
-        launch_one<1, 0>(s, grid, d_ops, bases, tag, h_single);
+        launch_one<1, 0>(s, grid, d_ops, bases, tag, h_single, xcd.fixed);
         return;
     }
     switch (uniform_w) {
-#define KKT_W(n) case n: launch_one<2, n>(s, grid, d_ops, bases, tag, h_single); break;
+#define KKT_W(n) case n: launch_one<2, n>(s, grid, d_ops, bases, tag, h_single, xcd.fixed); break;
         KKT_W(1) KKT_W(2) KKT_W(3) KKT_W(4) KKT_W(5) KKT_W(6) KKT_W(7) KKT_W(8)
         KKT_W(9) KKT_W(10) KKT_W(11) KKT_W(12) KKT_W(13) KKT_W(14) KKT_W(15) KKT_W(16)
 #undef KKT_W
         case UNIFORM_W_SWITCH_NARROW:
             if (tag == 0) {
-                const int per = g_ragged_xcd ? ((max_slices + 3) / 4 + 7) / 8 : 0;
+                const int per = xcd.ragged ? ((max_slices + 3) / 4 + 7) / 8 : 0;
                 hipLaunchKernelGGL(kkt_spmv_rows_ragged_narrow, dim3(per ? 8 * per : grid.x, nops),
                                    dim3(256), 0, s, d_ops, bases, per);
                 break;
             }
-            launch_one<2, 0>(s, grid, d_ops, bases, tag, h_single);
+            launch_one<2, 0>(s, grid, d_ops, bases, tag, h_single, xcd.fixed);
             break;
         case UNIFORM_W_SWITCH:   // ragged, most slots in slices of a width the switch kernel unrolls
             if (tag == 0) {
-                const int per = g_ragged_xcd ? ((max_slices + 3) / 4 + 7) / 8 : 0;
+                const int per = xcd.ragged ? ((max_slices + 3) / 4 + 7) / 8 : 0;
                 hipLaunchKernelGGL(kkt_spmv_rows_ragged, dim3(per ? 8 * per : grid.x, nops),
                                    dim3(256), 0, s, d_ops, bases, per);
                 break;
             }
-            launch_one<2, 0>(s, grid, d_ops, bases, tag, h_single);
+            launch_one<2, 0>(s, grid, d_ops, bases, tag, h_single, xcd.fixed);
             break;
         case UNIFORM_W_SWITCH_1WAVE:
             if (tag == 0) {
                 // one wave per workgroup: the slices of a window differ in width (19, 19, 12, 9, ...),
                 // and a four-wave workgroup holds its registers until its widest slice is done
-                const int per = g_ragged_xcd ? (max_slices + 7) / 8 : 0;
+                const int per = xcd.ragged ? (max_slices + 7) / 8 : 0;
                 hipLaunchKernelGGL(kkt_spmv_rows_ragged, dim3(per ? 8 * per : max_slices, nops),
                                    dim3(64), 0, s, d_ops, bases, per);
                 break;
             }
             [[fallthrough]];
-        default: launch_one<2, 0>(s, grid, d_ops, bases, tag, h_single); break;
+        default: launch_one<2, 0>(s, grid, d_ops, bases, tag, h_single, xcd.fixed); break;
     }
 }
 

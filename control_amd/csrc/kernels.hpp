@@ -60,9 +60,15 @@ struct RowOp {
     double c1, c2, c3, post1, post2;
 };
 
+// XCD-aware workgroup order of the operator launches (tag 0; tag 1 ignores it), per handle:
+// ragged kernels (option "ragged_xcd", default on) and fixed-width ones (option "apply_xcd",
+// default off).  Ragged: P2 0.507 -> 0.46-0.48 ms, Stokes outer operator 0.778 -> 0.729 ms.
+// (On the fixed-width P1 launches the same relabelling was slower, profiles/DIARY_r01_r02.md
+// 8.1b: their traffic is 1.1 x the bytes already; the ragged launches fetched 1.4 x.)
+struct XcdOrder { bool ragged = false, fixed = false; };
 void launch_rowops(hipStream_t s, const RowOp *d_ops, int nops, int max_slices, int R,
                    const Bases &bases, int tag, int uniform_w,
-                   const RowOp *h_single = nullptr);
+                   const RowOp *h_single = nullptr, XcdOrder xcd = {});
 // uniform_w of a launch of ragged structures whose slots lie (>= 75 %) in slices of a width
 // ragged_switch_width() accepts: the operator apply then runs kkt_spmv_rows_ragged, where a wave
 // picks the body unrolled for its slice's width (other widths: the slot loop, in the same kernel)
@@ -76,13 +82,6 @@ constexpr int UNIFORM_W_SWITCH_1WAVE = -3;
 // that more waves are resident)
 constexpr int UNIFORM_W_SWITCH_NARROW = -4;
 bool ragged_switch_width(int w);
-// XCD-aware workgroup order in the ragged kernel (default on; option "ragged_xcd" = "0": dispatch
-// order).  P2 0.507 -> 0.46-0.48 ms, Stokes outer operator 0.778 -> 0.729 ms.  (On the fixed-width
-// P1 launches the same relabelling was slower, profiles/DIARY_r01_r02.md 8.1b: their traffic is
-// 1.1 x the bytes already; the ragged launches fetched 1.4 x.)
-void set_ragged_xcd(bool on);
-void set_apply_xcd(bool on);
-void set_pc_xcd(bool on);       // ... and for the batched preconditioner steps (option "pc_xcd")    // the same order for the fixed-width operator launches (option "apply_xcd")
 
 // Batched Chebyshev steps on ONE matrix with the iterates of four time levels interleaved
 // (element (row r, level l) of a group at 4 r + l): a gather serves four levels with one 32-byte
@@ -100,12 +99,15 @@ struct IlOp {
     double c1, c2, c3;
     double post1[4], post2[4]; // per level (the last step's output scalings)
 };
-void launch_rowops_il(hipStream_t s, const IlOp *d_ops, int ngroups, int max_slices, int uniform_w);
+// (xcd: the XCD-aware workgroup order of the batched preconditioner steps, option "pc_xcd")
+void launch_rowops_il(hipStream_t s, const IlOp *d_ops, int ngroups, int max_slices, int uniform_w,
+                      bool xcd);
 
 // Batched launch for RowOps that all have ONE term with the same matrix and pattern
 // (uniform width 1..8, R = 2): four time levels per thread.  Returns false if not applicable.
+// (xcd: as for launch_rowops_il)
 bool launch_rowops_shared(hipStream_t s, const RowOp *d_ops, int nops, int max_slices, int R,
-                          int uniform_w);
+                          int uniform_w, bool xcd);
 
 // Operator apply for shared values: d_groups[g] = {first op, count <= 4} of runs of EPI_LIN RowOps
 // with identical structure (same pattern, same term matrices); fixed slice widths 1..8, R = 2.

@@ -381,10 +381,7 @@ void System::solve_once(const double *d_b, double *d_u, int *its_out, int *reaso
     pc_cb_failed = false;
     info.last_pc_applies = 0;
     info.last_op_applies = 0;
-    {
-        const char *st = opt("stage_timers");
-        clock.on = st && st[0] == '1';
-    }
+    clock.on = opts.stage_timers;
     // operator / preconditioner applications bracketed by stage marks
     auto apply = [&](const double *x, double *y) {
         clock.mark(stream, StageClock::OTHER);

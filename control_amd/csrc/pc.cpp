@@ -61,14 +61,11 @@ SchurPC::SchurPC(System &S, const kkt_pc_desc &d) : S_(S), d_(d) {
     d_.m_indptr = d_.m_indices = nullptr;
     d_.m_values = nullptr;
     d_.bc_idx = nullptr;
-    const char *e = S_.opt("no_graph");
-    use_graph_ = !(e && e[0] == '1');
-    e = S_.opt("persistent");
-    use_programs_ = !(e && e[0] == '0');
+    use_graph_ = !S_.opts.no_graph;
+    use_programs_ = S_.opts.persistent;
     // opt-in: measured 0-3 % on cfg 2 (both lanes slow down when they share the chip, and the
     // smaller batches of a chunk are less efficient), DESIGN.md section 6
-    e = S_.opt("lanes");
-    use_lanes_ = e && e[0] == '1';
+    use_lanes_ = S_.opts.lanes;
     build();
 }
 
@@ -140,7 +137,7 @@ void SchurPC::values_changed() {
     else
         build_CN();
     flush_coarse();
-    if (S_.opt("verbose") && d_.schur_emin <= 0)
+    if (S_.opts.verbose && d_.schur_emin <= 0)
         std::fprintf(stderr, "[kkt] Chebyshev sub-solves: degree %d; %lld Lanczos steps spent on "
                      "%zu matrices\n", schur_its_, (long long)spectrum_steps_, mats_.size());
     S_.info.sweep_form = 0;
@@ -154,18 +151,18 @@ bool SchurPC::setup_row_programs() {
     const Pattern &P = S_.patterns[m_pat_];
     {
         int wpw = 0, nwg = 0;
-        const char *pm0 = S_.opt("prog_mode");
-        const bool try_g0 = !(pm0 && pm0[0] == 'f') && row_program_g_available(P.R, P.uniform_w);
+        const ProgMode pm = S_.opts.prog_mode;
+        const bool try_g0 = pm != ProgMode::Flags && row_program_g_available(P.R, P.uniform_w);
         // the data-flow form for any width (matrix re-read from L2 every phase) is opt-in
-        // (KKT_PROG_MODE=w): re-polling whole chunks of granules costs more fabric traffic
+        // (prog_mode "w"): re-polling whole chunks of granules costs more fabric traffic
         // than the counter form's single gather round once rows are wide or row-sorted
         // (measured: Stokes P2 47 -> 121 ms, 3-D P1 3.3 -> 4.8 ms per application)
-        const bool try_gw = pm0 && pm0[0] == 'w' && P.R == 2;
+        const bool try_gw = pm == ProgMode::W && P.R == 2;
         const bool try_g = !try_gw && try_g0;
         // data-flow form: one wave per workgroup (no workgroup barrier on the critical path)
         // while all of them are co-resident; else 4 / 8 waves per workgroup
-        const char *pw = S_.opt("prog_waves");
-        const int first = pw ? std::atoi(pw) : (try_g ? 1 : 4);
+        const int pw = S_.opts.prog_waves;      // 0: not chosen
+        const int first = pw ? pw : (try_g ? 1 : 4);
         int n_cus = 0, dev_id = 0;
         if (hipGetDevice(&dev_id) != hipSuccess ||
             hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess)
@@ -177,7 +174,7 @@ bool SchurPC::setup_row_programs() {
         for (int pass = 0; pass < 2 && !wpw; ++pass)
         for (int cand : {first, 4, 8}) {
             if (cand < 1 || cand > 8) continue;
-            if (pass == 0 && cand > 1 && !(pw && cand == first) &&
+            if (pass == 0 && cand > 1 && cand != pw &&
                 (P.nslices + cand - 1) / cand > n_cus)
                 continue;
             // (Round 1 fenced the data-flow form with two 4-wave workgroups on a CU off: programs
@@ -250,12 +247,10 @@ bool SchurPC::setup_row_programs() {
         }
         // data-flow form: needs the exact gather relation between workgroups to be symmetric
         {
-            const char *pm = S_.opt("prog_mode");
-            const bool gw_ok = pm && pm[0] == 'w' && P.R == 2 &&
-                               nwg <= row_program_gw_max_wgs(wpw);
+            const bool gw_ok = pm == ProgMode::W && P.R == 2 && nwg <= row_program_gw_max_wgs(wpw);
             const bool g_ok = !gw_ok && row_program_g_available(P.R, P.uniform_w) &&
                               nwg <= row_program_g_max_wgs(P.uniform_w, wpw);
-            bool want = !(pm && pm[0] == 'f') && (g_ok || gw_ok) && !prog_lowreg_;
+            bool want = pm != ProgMode::Flags && (g_ok || gw_ok) && !prog_lowreg_;
             if (want) {
                 // between waves (the unit that publishes and polls), in storage positions
                 const int64_t rw = 64 * P.R;
@@ -289,7 +284,7 @@ bool SchurPC::setup_row_programs() {
         }
         prog_wpw_ = wpw;
         prog_nwg_ = nwg;
-        if (S_.opt("verbose"))
+        if (S_.opts.verbose)
             std::fprintf(stderr, "[kkt] sweep program: mode %d (0 counters, 1 data-flow, 2 data-flow "
                          "any width), %d workgroups x %d waves, %d slices\n",
                          prog_mode_, nwg, wpw, P.nslices);
@@ -312,9 +307,7 @@ bool SchurPC::prepare_tiles() {
         hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess ||
         n_cus < 1)
         return false;
-    const char *tw = S_.opt("tile_waves");
-    const char *td = S_.opt("tile_depth");
-    const int depth = td ? std::atoi(td) : 0;
+    const int depth = S_.opts.tile_depth;      // 0: modelled
     // one workgroup per CU; tiny meshes get fewer tiles (at least 32 own rows each)
     const int ntiles = (int)std::max<int64_t>(1, std::min<int64_t>(n_cus, P.nrows / 32));
     // workgroup size: 1 024 threads (one row slot per thread, 128 registers) or 512 (up to three
@@ -331,8 +324,8 @@ bool SchurPC::prepare_tiles() {
     const double *tc = (S_.tile_dim > 0 && (int64_t)S_.tile_coords.size() == P.nrows * S_.tile_dim)
                            ? S_.tile_coords.data() : nullptr;
     const int xh = coarse_cycles_ > 0 ? 2 : 0;     // extra hand-offs per cycle of a two-grid level
-    if (tw) {
-        threads = 64 * std::max(1, std::min(16, std::atoi(tw)));
+    if (S_.opts.tile_waves) {
+        threads = 64 * S_.opts.tile_waves;
         // (the depth model must only consider what a kernel variant exists for: wide rows have
         // one or two row slots, and a deeper plan that needs more would lose the tile form)
         if (!build_tile_plan(P, ntiles, depth, threads,
@@ -406,7 +399,7 @@ bool SchurPC::prepare_tiles() {
         d_tg_[i] = dev_alloc<unsigned long long>(words);
         owned_.push_back(d_tg_[i]);
     }
-    if (S_.opt("verbose"))
+    if (S_.opts.verbose)
         std::fprintf(stderr, "[kkt] tile sweep program: %d tiles x %d threads, depth %d, W %d, "
                      "%d row slots per thread; largest tile: %lld own rows, %lld computed rows, "
                      "%lld ring rows; mean redundancy %.2f; modelled %.2f us per step\n", tp.ntiles,
@@ -574,7 +567,7 @@ bool SchurPC::build_tile_coarse() {
                 D.ew = nc;
             }
         }
-        if (S_.opt("verbose"))
+        if (S_.opts.verbose)
             std::fprintf(stderr, "[kkt] coarse inverse: rows of at most %d of %d columns (diagonal "
                          "blocks of P^T A P)\n", ew, nc);
     }
@@ -588,7 +581,7 @@ bool SchurPC::build_tile_coarse() {
     }
     d_tile_coarse_ = dev_upload(&D, 1);
     owned_.push_back(d_tile_coarse_);
-    if (S_.opt("verbose"))
+    if (S_.opts.verbose)
         std::fprintf(stderr, "[kkt] tile sweep program, coarse corrections: %d coarse functions, at most "
                      "%d per tile, %d partial-sum slots\n", nc, jmax, nslots);
     return true;
@@ -693,7 +686,7 @@ bool SchurPC::fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out) {
     for (const TileLevel &L : levels) max_terms = std::max(max_terms, (int)L.n_upd);
     if (coarse && !tile_sweep_fuses_update(tile_plan_.W, max_terms)) return false;
     if (tile_sweep_fuses_update(tile_plan_.W, max_terms) &&
-        !(tile_plan_.W > 9 && S_.opt("tile_unfused") && !coarse)) {
+        !(tile_plan_.W > 9 && S_.opts.tile_unfused && !coarse)) {
         for (size_t q = k; q < e; ++q) (void)hipFree(steps_[q].rows.d_ops);
         tile_step(levels.data(), (int)levels.size(), (int)(e - k), true);
         return true;
@@ -730,9 +723,7 @@ void SchurPC::fuse_programs() {
         HIPCHK(hipMemset(d_err_, 0, (64 + 16 * 1024) * sizeof(unsigned)));
         owned_.push_back(d_err_);
     }
-    const char *pm_all = S_.opt("prog_mode");
-    const bool tile_forced = pm_all && pm_all[0] == 't';
-    const bool tile_wanted = tile_forced || !pm_all || pm_all[0] == 'a';
+    const bool tile_wanted = S_.opts.prog_mode == ProgMode::Auto || S_.opts.prog_mode == ProgMode::Tile;
     const bool use_tiles = tile_wanted && prepare_tiles();
     tile_epoch_cursor_ = 0;
     tile_cepoch_cursor_ = 0;
@@ -765,8 +756,7 @@ void SchurPC::fuse_programs() {
             // compact records: Chebyshev steps that only continue the previous phase's
             // solve are marked STEP (kernels.hpp, PhaseLite)
             std::vector<PhaseLite> lite(ops.size());
-            const char *ps = S_.opt("prog_steps");
-            const bool use_steps = !(ps && ps[0] == '0');
+            const bool use_steps = S_.opts.prog_steps;
             auto same = [](const VRef &a, const VRef &b) {
                 return a.base == b.base && (a.base < 0 || a.off == b.off);
             };
@@ -1265,14 +1255,12 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
     const int nc = c.nc, nmat = (int)vals.size();
     const size_t n2 = (size_t)nc * nc;
     S.coarse_stats = kkt_coarse_stats{};
-    const char *k = S.opt("coarse_keep");
-    const bool keep = k && k[0] == '1';
+    const bool keep = S.opts.coarse_keep;
     S.coarse_E.clear();
     S.coarse_Einv.clear();
     if (nmat == 0) return;
     if (keep) S.coarse_E.resize(n2 * nmat);
-    const char *o = S.opt("coarse_setup");
-    const bool columns = o && std::strcmp(o, "columns") == 0;
+    const bool columns = S.opts.coarse_columns;
     HIPCHK(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();
     int64_t launches = 0;
@@ -1295,9 +1283,8 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
         // component blocks: the Galerkin launch writes the nblk diagonal blocks of size bn as
         // matrices of their own (E: nmat * nblk of them), the inverses go to Ib and are scattered
         // into einv's full rows
-        const char *ob = S.opt("coarse_blocks");
         const bool blocked = !deflate && g.block_n > 0 && g.block_n < nc && nc % g.block_n == 0 &&
-                             !(ob && ob[0] == '0');
+                             S.opts.coarse_blocks;
         const int bn = blocked ? g.block_n : nc, nblk = nc / bn;
         const size_t b2 = (size_t)bn * bn, ne = nblk * b2;     // doubles of E per level matrix
         GalerkinDev gb = g;
@@ -1682,15 +1669,11 @@ void SchurPC::push_rows(std::vector<RowOp> &r) {
     s.rows.R = P.R;
     s.rows.uniform_w = P.uniform_w;
     s.rows.d_ops = dev_upload(r.data(), r.size());
-    const char *ko = S_.opt("kernarg_ops");
-    const bool kernarg_ops = ko && ko[0] == '1';
     if (r.size() == 1) {
-        s.rows.single = kernarg_ops;
+        s.rows.single = S_.opts.kernarg_ops;
         s.rows.h_op = r[0];
     }
-    const char *sr = S_.opt("shared_rows");
-    const bool use_shared = !(sr && sr[0] == '0');
-    s.rows.shared_matrix = use_shared && r.size() >= 4;
+    s.rows.shared_matrix = S_.opts.shared_rows && r.size() >= 4;
     for (const RowOp &op : r)
         s.rows.shared_matrix = s.rows.shared_matrix && op.nterms == 1 &&
                                op.t[0].vals == r[0].t[0].vals && op.col == r[0].col &&
@@ -1842,11 +1825,9 @@ void SchurPC::emit_update_and_solve(Lin upd, const Solve &sv, int its, double em
 // coefficients and the same fma chain per row and level as emit_solves below.
 bool SchurPC::emit_solves_interleaved(const std::vector<Solve> &sv, int its, double emin,
                                       double emax) {
-    const char *o = S_.opt("interleave");
-    if (o && o[0] == '0') return false;
+    // (lanes: chunks on two streams would share the buffers)
+    if (!S_.opts.interleave || S_.opts.lanes) return false;
     const size_t m = sv.size();
-    const char *ln = S_.opt("lanes");
-    if (ln && ln[0] != '0') return false;       // (chunks on two streams would share the buffers)
     for (const Solve &q : sv)
         if (q.vals != sv[0].vals || q.dinv != sv[0].dinv) return false;
     const Pattern &P = S_.patterns[m_pat_];
@@ -2059,10 +2040,7 @@ void SchurPC::build_BE() {
     // through chunk c - 1 on the main lane.
     const bool lanes = use_lanes_ && !S_.sharded && (hi - lo) >= 16;
     int n_chunks = 1;
-    if (lanes) {
-        const char *e = S_.opt("lane_chunks");
-        n_chunks = std::max(2, std::min((hi - lo) / 4, e ? std::atoi(e) : 4));
-    }
+    if (lanes) n_chunks = std::max(2, std::min((hi - lo) / 4, S_.opts.lane_chunks));
     std::vector<int> cfirst(n_chunks + 1);
     for (int c = 0; c <= n_chunks; ++c) cfirst[c] = lo + (int)((int64_t)(hi - lo) * c / n_chunks);
     std::vector<int> chunk_done(n_chunks, -1);
@@ -2267,10 +2245,7 @@ void SchurPC::emit_comm(const double *send, int dst, double *recv, int src) {
 }
 
 void SchurPC::replay(size_t first, size_t last) {
-    {
-        const char *px = S_.opt("pc_xcd");
-        set_pc_xcd(!(px && px[0] == '0'));
-    }
+    const bool xcd = S_.opts.pc_xcd;
     Bases B{{nullptr, nullptr, nullptr, nullptr}};
     if (n_events_ > 0 && !side_) {
         HIPCHK(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
@@ -2293,13 +2268,13 @@ void SchurPC::replay(size_t first, size_t last) {
             case PcStep::ROWS:
                 if (s.rows.shared_matrix &&
                     launch_rowops_shared(st, s.rows.d_ops, s.rows.nops, s.rows.max_slices,
-                                         s.rows.R, s.rows.uniform_w))
+                                         s.rows.R, s.rows.uniform_w, xcd))
                     break;
                 launch_rowops(st, s.rows.d_ops, s.rows.nops, s.rows.max_slices, s.rows.R, B, 1,
                               s.rows.uniform_w, s.rows.single ? &s.rows.h_op : nullptr);
                 break;
             case PcStep::ROWS_IL:
-                launch_rowops_il(st, s.d_il, s.il_groups, s.il_slices, s.il_w);
+                launch_rowops_il(st, s.d_il, s.il_groups, s.il_slices, s.il_w, xcd);
                 break;
             case PcStep::TIME:
                 launch_time_transform(st, s.y, s.x, s.tkind, s.n, s.nx, s.lo_halo, s.hi_halo);
@@ -2347,17 +2322,11 @@ void SchurPC::replay(size_t first, size_t last) {
                 a.clear = s.clear ? 1 : 0;
                 a.fused_update = s.fused ? 1 : 0;
                 a.hslots = tp.hslots;
-                a.stamps = S_.opt("stamps") != nullptr;
-                {
-                    const char *dd = S_.opt("debug_drop_handoff");
-                    a.debug_drop = dd ? std::atoi(dd) : 0;
-                }
-                {
-                    const char *pd = S_.opt("tile_poll_delay");
-                    // s_sleep units before the first poll: ~0.7 us; ~1.4 us for the big rings of
-                    // 3-D tiles (measured optima: 256^2 P1 24, 64^3 P1 48)
-                    a.poll_delay = pd ? std::atoi(pd) : 24;
-                }
+                a.stamps = S_.opts.stamps;
+                a.debug_drop = S_.opts.debug_drop_handoff;
+                // s_sleep units before the first poll (default 24: ~0.7 us; ~1.4 us for the big
+                // rings of 3-D tiles -- measured optima: 256^2 P1 24, 64^3 P1 48)
+                a.poll_delay = S_.opts.tile_poll_delay;
                 try {
                     launch_tile_sweep(st, a, s.d_levels, tp.d_n, tp.d_grow, tp.d_lcol, tp.d_gpos,
                                       mask_, tp.ntiles, tp.threads, words,

@@ -468,12 +468,12 @@ void StokesPC::run_chain(Chain &c, const std::vector<ChainStep> &steps) {
             }
             const RowLaunch &L = cs.L;
             if (!L.shared_matrix ||
-                !launch_rowops_shared(st, L.d_ops, L.nops, L.max_slices, L.R, L.uniform_w))
+                !launch_rowops_shared(st, L.d_ops, L.nops, L.max_slices, L.R, L.uniform_w,
+                                      S_.opts.pc_xcd))
                 launch_rowops(st, L.d_ops, L.nops, L.max_slices, L.R, B, 1, L.uniform_w);
         }
     };
-    const char *ng = S_.opt("no_graph");
-    if ((ng && ng[0] == '1') || c.failed || steps.size() < 8) {
+    if (S_.opts.no_graph || c.failed || steps.size() < 8) {
         launches();
         return;
     }

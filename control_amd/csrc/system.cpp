@@ -23,11 +23,6 @@ void hip_check(hipError_t e, const char *what, const char *file, int line) {
     }
 }
 
-const char *System::opt(const char *key) const {
-    auto it = options.find(key);
-    return it != options.end() ? it->second.c_str() : nullptr;
-}
-
 // ---- stage clock: one event per mark; the interval since the previous mark belongs to `stage`
 void StageClock::begin(hipStream_t s) {
     used = 0;
@@ -143,8 +138,7 @@ void System::set_layout(int n_blocks_00, int n_blocks_11, int64_t nx0_, int64_t 
     n1_loc = n1;
     nullspaces.assign(n0 + n1, NullspaceSpec{});
     layout_set = true;
-    const char *e = opt("sell_r");
-    if (e && (e[0] == '1' || e[0] == '2')) sell_R = e[0] - '0';
+    sell_R = opts.sell_r;
 }
 
 void System::set_shard(int rank_, int world_, int families_) {
@@ -255,13 +249,9 @@ int System::find_or_add_pattern(int64_t nrows, int64_t ncols, const int32_t *ind
     // slots: sort the rows of every window of 8 slices by length (SELL-C-sigma) when that
     // saves at least 10 % of the storage.  Vectors keep their order; kernels reach the row
     // of a position through `perm`.
-    const char *sort_env = opt("sell_sort");   // read per pattern: tests toggle it
-    const bool allow_sort = !(sort_env && sort_env[0] == '0');
-    if (allow_sort && nnz > 0) {
+    if (opts.sell_sort && nnz > 0) {         // read per pattern: tests toggle it
         // (window: 8 slices = the rows of two workgroups, unless "sell_sigma" says otherwise)
-        const char *sg = opt("sell_sigma");
-        const int sig_slices = sg ? std::max(1, std::min(64, std::atoi(sg))) : 8;
-        const int64_t npos = (int64_t)P.nslices * C, sigma = sig_slices * (int64_t)C;
+        const int64_t npos = (int64_t)P.nslices * C, sigma = opts.sell_sigma * (int64_t)C;
         std::vector<int32_t> cand(npos, -1);
         for (int64_t w0 = 0; w0 < nrows; w0 += sigma) {
             const int64_t w1 = std::min<int64_t>(nrows, w0 + sigma);
@@ -679,8 +669,7 @@ void System::finalize() {
             std::vector<int> order;
             std::vector<char> used(ops.size(), 0);
             std::vector<int32_t> groups;
-            const char *sg = opt("shared_rows");
-            const bool allow = !(sg && sg[0] == '0') && rowops_grouped_kernel(L.R, L.uniform_w);
+            const bool allow = opts.shared_rows && rowops_grouped_kernel(L.R, L.uniform_w);
             bool uniform_all = allow;
             for (const RowOp &op : ops) uniform_all = uniform_all && op.nterms > 0 && op.perm == nullptr;
             if (uniform_all) {
@@ -713,7 +702,7 @@ void System::finalize() {
                     ops.swap(sorted);
                     L.d_groups = dev_upload(groups.data(), groups.size());
                     L.ngroups = (int)groups.size() / 2;
-                    if (opt("verbose"))
+                    if (opts.verbose)
                         std::fprintf(stderr, "[kkt] operator apply, launch %zu: %zu block rows in %d "
                                      "groups of equal structure (shared values)\n", w, ops.size(),
                                      L.ngroups);
@@ -722,8 +711,7 @@ void System::finalize() {
         }
         // ragged launch: which kernel (kernels.hpp, UNIFORM_W_SWITCH)
         {
-            const char *rs = opt("ragged_switch");
-            if (L.uniform_w == -1 && L.R == 2 && !(rs && rs[0] == '0')) {
+            if (L.uniform_w == -1 && L.R == 2 && opts.ragged_switch) {
                 int64_t slots = 0, covered = 0, nsl = 0;
                 int widest = 0;
                 for (const RowOp &op : waves[w]) {
@@ -747,7 +735,7 @@ void System::finalize() {
                     L.uniform_w = slots >= 10 * nsl ? UNIFORM_W_SWITCH_1WAVE : UNIFORM_W_SWITCH;
                     info.apply_switched++;
                 }
-                if (opt("verbose"))
+                if (opts.verbose)
                     std::fprintf(stderr, "[kkt] operator apply, launch %zu: ragged, %.1f %% of the "
                                  "slots in slices of an unrolled width -> %s\n", w,
                                  slots ? 100.0 * covered / slots : 0.0,
@@ -932,18 +920,13 @@ void System::apply(const double *d_x, double *d_y) {
         rows_out = d_tmp_y;
     }
     Bases B{{xin, rows_out, d_halo_x0_lo, d_halo_x1_hi}};
-    {
-        const char *rx = opt("ragged_xcd");
-        set_ragged_xcd(!(rx && rx[0] == '0'));
-        const char *ax = opt("apply_xcd");
-        set_apply_xcd(ax && ax[0] == '1');
-    }
+    const XcdOrder xcd{opts.ragged_xcd, opts.apply_xcd};
     auto launch = [&](const RowLaunch &L) {
         if (L.ngroups > 0 &&
             launch_rowops_grouped(stream, L.d_ops, L.d_groups, L.ngroups, L.max_slices, L.R,
                                   L.uniform_w, B))
             return;
-        launch_rowops(stream, L.d_ops, L.nops, L.max_slices, L.R, B, 0, L.uniform_w);
+        launch_rowops(stream, L.d_ops, L.nops, L.max_slices, L.R, B, 0, L.uniform_w, nullptr, xcd);
     };
     // ... while the block rows that need no neighbour's level are already queued
     for (int w = 0; w < first_halo_launch; ++w) launch(apply_launches[w]);

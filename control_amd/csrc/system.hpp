@@ -36,6 +36,28 @@ T *dev_upload(const T *h, size_t n) {
     return p;
 }
 
+// Execution options (kkt_set_option; include/kkt.h documents the keys): which kernel form runs,
+// never what is computed.  One field per key, with its built-in default; kkt_set_option checks
+// every value against the key's domain before it lands here.
+enum class ProgMode { Auto, Tile, Dataflow, Flags, W };
+struct Options {
+    // storage and operator apply
+    int sell_r = 2, sell_sigma = 8;
+    bool sell_sort = true, shared_rows = true, ragged_switch = true;
+    bool ragged_xcd = true, apply_xcd = false, pc_xcd = true;     // XCD-aware workgroup orders
+    // preconditioner
+    bool interleave = true, kernarg_ops = false, no_graph = false, lanes = false;
+    int lane_chunks = 4;
+    bool persistent = true, prog_steps = true, tile_unfused = false;
+    ProgMode prog_mode = ProgMode::Auto;
+    int prog_waves = 0, tile_depth = 0, tile_waves = 0;          // 0: chosen by shape / modelled
+    bool coarse_columns = false;                                  // "coarse_setup" = "columns"
+    bool coarse_keep = false, coarse_blocks = true;
+    // diagnostics and test hooks
+    bool stage_timers = false, verbose = false, stamps = false;
+    int tile_poll_delay = 24, debug_drop_handoff = 0;
+};
+
 // One sparsity structure in SELL-64R layout, shared by every block that has it.
 struct Pattern {
     int64_t nrows = 0, ncols = 0, nnz = 0;
@@ -224,12 +246,11 @@ struct System {
     kkt_steplock steplock{};   // test hook (kkt_debug_set_steplock); n_steps == 0: off
     // execution options (kkt_set_option); a key that was never set has its built-in default
     // (the library does not read the environment)
-    std::map<std::string, std::string> options;
+    Options opts;
     StageClock clock;
     kkt_stage_times stage_times{};
     std::vector<double> tile_coords;   // kkt_set_tile_coordinates: N_x x tile_dim, or empty
     int tile_dim = 0;
-    const char *opt(const char *key) const;
     // Krylov workspace (lazily sized)
     int ws_restart = 0;
     bool ws_flexible = false;

@@ -72,36 +72,55 @@ const char *kkt_last_error(kkt_handle h);
 /* Execution options: which kernel form runs, not what is computed (every form of a step
  * performs the same arithmetic in the same order; tests toggle them to assert that).  Set a
  * key before the call that reads it: storage keys before kkt_set_layout / kkt_add_block,
- * preconditioner keys before kkt_set_pc_schur.  Unknown keys are rejected.
- *   "sell_r"      "1" | "2"      rows per lane of the SELL-64R storage (default 2)
- *   "sell_sort"   "0" | "1"      row-sorted storage for ragged structures (default 1)
- *   "ragged_switch" "0"          operator apply on ragged structures (P2 / Stokes blocks) with the
- *                                slot loop instead of the width-switched kernel
- *   "ragged_xcd"  "0"            ... in dispatch order instead of the XCD-aware workgroup order
- *   "apply_xcd"   "1"            XCD-aware order for the fixed-width operator launches too
- *                                (measured slower; off)
- *   "pc_xcd"      "0"            batched preconditioner steps in dispatch order instead of the
- *                                XCD-aware workgroup order
- *   "interleave"  "0"            batched mass solves with one vector per time level instead of
- *                                the iterates of four levels interleaved
- *   "no_graph"    "1"            replay the preconditioner as plain launches, no hipGraph
- *   "persistent"  "0"            time sweeps as one launch per step (no sweep programs)
- *   "prog_mode"   "auto" | "tile" | "dataflow" | "flags" | "w"   sweep-program form (auto, the
- *                                default: tile where it fits, else dataflow, else flags;
- *                                "dataflow": the row programs only, data-flow form preferred)
- *   "prog_waves"  "1".."8"       waves per workgroup of the dataflow / flags forms
- *   "prog_steps"  "0"            dataflow form without compact STEP records
- *   "tile_depth"  "1".."16"      SpMV steps per hand-off of the tile form (default: modelled)
- *   "tile_waves"  "1".."8"       waves per workgroup of the tile form (default 8)
- *   "stage_timers" "1"           HIP events around the stages of every Krylov iteration
- *                                (kkt_get_stage_times)
- *   "coarse_setup" "columns"     two-grid set-up column by column (the previous path; default:
- *                                batched Galerkin products and blocked Gauss-Jordan on the device)
- *   "coarse_blocks" "0"          batched set-up: invert P^T A P as one matrix even where it is
- *                                block diagonal over the components of a vector-valued space
- *                                (default: one inverse per component block; the rows keep their
- *                                full layout, exact zeros outside the block)
- *   "lanes", "lane_chunks", "kernarg_ops", "shared_rows", "verbose"   diagnostics
+ * preconditioner keys before kkt_set_pc_schur.  Unknown keys, and values outside a key's list,
+ * are rejected with KKT_ERR_ARG and leave the handle's options as they were.  Switches take
+ * "0" | "1"; the default is given first.  Options are per handle: each handle's launches follow
+ * its own.
+ *   "sell_r"        "2" | "1"      rows per lane of the SELL-64R storage
+ *   "sell_sort"     "1" | "0"      row-sorted storage for ragged structures (read per pattern)
+ *   "sell_sigma"    "1".."64"      slices per sorting window (default 8)
+ *   "shared_rows"   "1" | "0"      one load of a shared matrix serves several block rows
+ *   "ragged_switch" "1" | "0"      operator apply on ragged structures (P2 / Stokes blocks) with the
+ *                                  width-switched kernel; "0": the slot loop
+ *   "ragged_xcd"    "1" | "0"      ... in the XCD-aware workgroup order; "0": dispatch order
+ *   "apply_xcd"     "0" | "1"      XCD-aware order for the fixed-width operator launches too
+ *                                  (measured slower; off)
+ *   "pc_xcd"        "1" | "0"      batched preconditioner steps in the XCD-aware workgroup order;
+ *                                  "0": dispatch order
+ *   "interleave"    "1" | "0"      batched mass solves with the iterates of four time levels
+ *                                  interleaved; "0": one vector per time level
+ *   "kernarg_ops"   "0" | "1"      single-block preconditioner steps take their RowOp as a kernel
+ *                                  argument
+ *   "no_graph"      "0" | "1"      "1": replay the preconditioner as plain launches, no hipGraph
+ *   "persistent"    "1" | "0"      time sweeps as sweep programs; "0": one launch per step
+ *   "prog_mode"     "auto" | "tile" | "dataflow" | "flags" | "w"   sweep-program form (auto:
+ *                                  tile where it fits, else dataflow, else flags; "tile": the
+ *                                  same; "dataflow": the row programs only, data-flow form
+ *                                  preferred; "flags": the counter form; "w": the data-flow form
+ *                                  for any width)
+ *   "prog_waves"    "1".."8"       waves per workgroup of the dataflow / flags forms (default:
+ *                                  chosen by shape)
+ *   "prog_steps"    "1" | "0"      dataflow form with compact STEP records
+ *   "tile_depth"    "1".."16"      SpMV steps per hand-off of the tile form (default: modelled)
+ *   "tile_waves"    "1".."16"      waves per workgroup of the tile form (default: modelled)
+ *   "tile_unfused"  "0" | "1"      tile form: wide rows keep the level update as a plain launch
+ *   "lanes"         "0" | "1"      BE preconditioner in chunks on two streams
+ *   "lane_chunks"   integer        ... that many chunks (default 4; at least 2, at most one per
+ *                                  four time levels)
+ *   "coarse_setup"  "batched" | "columns"   two-grid set-up with batched Galerkin products and
+ *                                  blocked Gauss-Jordan on the device; "columns": column by
+ *                                  column (the previous path)
+ *   "coarse_keep"   "0" | "1"      keep the Galerkin matrices and inverses of the last set-up
+ *   "coarse_blocks" "1" | "0"      batched set-up: one inverse per component block of a
+ *                                  vector-valued space (the rows keep their full layout, exact
+ *                                  zeros outside the block); "0": invert P^T A P as one matrix
+ *   "stage_timers"  "0" | "1"      HIP events around the stages of every Krylov iteration
+ *                                  (kkt_get_stage_times)
+ *   "verbose"       "0" | "1"      set-up decisions on stderr
+ *   Diagnostics and test hooks of the tile form: "stamps" "0" | "1" (hand-off time stamps in
+ *   its diagnostics buffer), "tile_poll_delay" integer (sleep units before the first poll,
+ *   default 24), "debug_drop_handoff" integer (default 0; n > 0: tile 0 skips hand-off n;
+ *   n < 0: tile 0 never checks in).
  * The library never reads the process environment: a key that was never set has its default.
  * (The Python mirror forwards KKT_<KEY> variables of developer scripts as explicit calls.) */
 int kkt_set_option(kkt_handle h, const char *key, const char *value);
