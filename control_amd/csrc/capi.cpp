@@ -475,6 +475,31 @@ int kkt_debug_pc_forms(kkt_handle h, int32_t *out, int cap) {
     });
 }
 
+static int put_records(const std::vector<double> &rec, int per, double *out, int cap) {
+    const int n = (int)rec.size() / per;
+    if (out) {
+        if (cap < (int)rec.size()) fail(KKT_ERR_ARG, "buffer too small for the records");
+        std::copy(rec.begin(), rec.end(), out);
+    }
+    return n;
+}
+
+int kkt_debug_pc_solves(kkt_handle h, double *out, int cap) {
+    KKT_TRY(h, {
+        std::vector<double> rec;
+        if (S.pc) S.pc->solve_records(rec);
+        return put_records(rec, KKT_PC_SOLVE_VALS, out, cap);
+    });
+}
+
+int kkt_debug_pc_matrices(kkt_handle h, double *out, int cap) {
+    KKT_TRY(h, {
+        std::vector<double> rec;
+        if (S.pc) S.pc->matrix_records(rec);
+        return put_records(rec, KKT_PC_MATRIX_VALS, out, cap);
+    });
+}
+
 int kkt_get_info(kkt_handle h, kkt_info *info) {
     KKT_TRY(h, {
         if (!info) fail(KKT_ERR_ARG, "null info");

@@ -127,6 +127,8 @@ void SchurPC::values_changed() {
         (void)hipFree(kv.second.dinv);
     }
     mats_.clear();
+    mat_recs_.clear();
+    solve_recs_.clear();
     for (double *p : einv_owned_) (void)hipFree(p);
     einv_owned_.clear();
     pending_coarse_.clear();
@@ -1557,23 +1559,37 @@ void SchurPC::emit_coarse_solve(const Lin *upd, const Solve &sv, const Mat &F) {
 }
 
 // base + c * M with bc rows/cols of `assemble(form, bcs=...)`, and its Jacobi diagonal
-SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c) {
+SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solved) {
     uint64_t bits;
     std::memcpy(&bits, &c, sizeof bits);
     auto key = std::make_pair(base_vals, bits);
     auto it = mats_.find(key);
-    if (it != mats_.end()) return it->second;
+    if (it != mats_.end() && (!solved || it->second.est != KKT_PC_EST_NONE)) return it->second;
     const Pattern &P = S_.patterns[m_pat_];
     hipStream_t st = S_.stream;
     Mat m;
-    m.vals = dev_alloc<double>(P.npadded);
-    m.dinv = dev_alloc<double>(nx_);
-    launch_vals_axpy(st, m.vals, base_vals, c, m_vals_, P.npadded);
-    if (mask_) launch_mask_columns(st, m.vals, P.d_col, mask_, P.npadded);
-    launch_extract_dinv(st, P.d_col, P.d_slice_off, m.vals, mask_, m.dinv, (int)nx_, P.nslices,
-                        P.R, P.d_perm);
+    if (it != mats_.end()) {
+        m = it->second;      // formed for products only, now solved with: interval and inverse below
+    } else {
+        m.vals = dev_alloc<double>(P.npadded);
+        m.dinv = dev_alloc<double>(nx_);
+        launch_vals_axpy(st, m.vals, base_vals, c, m_vals_, P.npadded);
+        if (mask_) launch_mask_columns(st, m.vals, P.d_col, mask_, P.npadded);
+        launch_extract_dinv(st, P.d_col, P.d_slice_off, m.vals, mask_, m.dinv, (int)nx_, P.nslices,
+                            P.R, P.d_perm);
+        m.index = (int)mat_recs_.size();
+        MatRec r;
+        r.c = c;
+        mat_recs_.push_back(r);
+    }
+    if (!solved) {
+        mats_[key] = m;
+        return m;
+    }
+    MatRec &rec = mat_recs_[m.index];
     // an earlier matrix with the same shift and the same values (mode G stores one copy per time
     // level of a time-invariant operator) shares its spectrum estimate and its coarse inverse
+    // (matrices only multiplied with carry neither: emax == 0)
     const Mat *twin = nullptr;
     if (d_.schur_emin <= 0 || coarse_cycles_ > 0) {
         for (auto &kv : mats_) {
@@ -1595,12 +1611,14 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c) {
         m.emin = d_.schur_emin;
         m.emax = d_.schur_emax;
         m.eimag = d_.schur_eimag > 0 ? d_.schur_eimag : 0.0;
+        m.est = KKT_PC_EST_GIVEN;
     } else if (twin) {
         // Interval from the matrix itself; the first and last levels carry other shifts
         // (control.py:2241-2327) and get their own, wider, intervals.
         m.emin = twin->emin;
         m.emax = twin->emax;
         m.eimag = twin->eimag;
+        m.est = KKT_PC_EST_SHARED;
     } else {
         // Blocks with a convection term are not symmetric: the interval comes from the
         // symmetric part H = (A + A^T) / 2 (Bendixson: Re lambda lies in the spectrum of
@@ -1621,6 +1639,7 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c) {
         }
         const Spectrum sp = jacobi_spectrum(S_, m_pat_, nonsym ? hv : m.vals, m.dinv, mask_, 400);
         spectrum_steps_ += sp.steps;
+        rec.lanczos = sp.steps;
         if (!(sp.emin > 0.0) || !(sp.emax > sp.emin))
             fail(KKT_ERR_STATE, "sub-solve matrix is not positive definite: no Chebyshev interval");
         m.emin = 0.85 * sp.emin;      // Ritz values lie inside the spectrum
@@ -1629,6 +1648,7 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c) {
             int steps = 0;
             m.eimag = 1.1 * jacobi_skew_radius(S_, m_pat_, sv2, m.dinv, mask_, 40, &steps);
             spectrum_steps_ += 2 * steps;
+            rec.power = steps;
         }
         if (hv) (void)hipFree(hv);
         if (sv2) (void)hipFree(sv2);
@@ -1636,10 +1656,29 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c) {
         // coarse space the rest (emax / 30: measured optimum for 8 sweeps at coarse cells of 8
         // to 16 mesh widths, scripts/proto_subsolve.py)
         if (coarse_cycles_ > 0) m.emin = std::max(m.emin, m.emax / 30.0);
+        m.est = KKT_PC_EST_LANCZOS;
     }
     if (coarse_cycles_ > 0) m.einv = twin && twin->einv ? twin->einv : coarse_inverse(m.vals);
+    rec.est = m.est;
+    rec.coarse = m.einv != nullptr;
     mats_[key] = m;
     return m;
+}
+
+void SchurPC::note_solve(int sweep, int level, const Mat &m) {
+    mat_recs_[m.index].solves++;
+    solve_recs_.insert(solve_recs_.end(),
+                       {(double)sweep, (double)level, (double)m.index, mat_recs_[m.index].c, m.emin,
+                        m.emax, m.eimag, (double)schur_its_, (double)m.est});
+}
+
+void SchurPC::solve_records(std::vector<double> &out) const { out = solve_recs_; }
+
+void SchurPC::matrix_records(std::vector<double> &out) const {
+    out.clear();
+    for (const MatRec &r : mat_recs_)
+        out.insert(out.end(), {r.c, (double)r.est, (double)r.lanczos, (double)r.power,
+                               r.coarse ? 1.0 : 0.0, (double)r.solves});
 }
 
 // Degree of the sub-solves: as given, or 1.6 sqrt(kappa) of a typical (interior-level) matrix --
@@ -2015,8 +2054,10 @@ void SchurPC::build_stationary() {
     emit_lin({Lin{{Term{Dv, u0}}, B_, 1.0, 0.0, -1.0, nullptr, b1}});
     Mat S1 = schur_matrix(Dv, c), S2 = schur_matrix(Dz, c);
     schur_its_ = resolve_its(S1);
+    note_solve(KKT_PC_SWEEP_FIRST, 0, S1);
     emit_solves({Solve{S1.vals, S1.dinv, B_, u1}}, schur_its_, S1.emin, S1.emax, P_, nx_, false, nullptr, S1.eimag, &S1);
     emit_lin({Lin{{Term{m_vals_, u1}}, B_, 1.0}});
+    note_solve(KKT_PC_SWEEP_SECOND, 0, S2);
     emit_solves({Solve{S2.vals, S2.dinv, B_, u1}}, schur_its_, S2.emin, S2.emax, P_, nx_, false, nullptr, S2.eimag, &S2);
 }
 
@@ -2086,6 +2127,7 @@ void SchurPC::build_BE() {
         if (lanes) emit_wait(0, chunk_done[c]);
         for (int i = cfirst[c]; i < cfirst[c + 1]; ++i) {
             Mat F = schur_matrix(block_vals(KKT_Q10, i, i), coef(i));
+            note_solve(KKT_PC_SWEEP_FORWARD, i, F);
             const Solve sv{F.vals, F.dinv, blk(B_, i), blk(u1, i)};
             if (i >= 1)
                 emit_update_and_solve(Lin{{Term{block_vals(KKT_Q10, i, i - 1),
@@ -2124,6 +2166,7 @@ void SchurPC::build_BE() {
     if (up >= 0) emit_comm(nullptr, -1, h_u1_, up);
     for (int i = hi - 1; i >= lo; --i) {
         Mat G = schur_matrix(block_vals(KKT_Q01, i, i), coef(i));
+        note_solve(KKT_PC_SWEEP_BACKWARD, i, G);
         const Solve sv{G.vals, G.dinv, blk(B_, i), blk(u1, i)};
         if (i <= n - 2)
             emit_update_and_solve(Lin{{Term{block_vals(KKT_Q01, i, i + 1),
@@ -2147,7 +2190,7 @@ void SchurPC::build_CN() {
     double *u0 = out_, *u1 = out_ + nl * nx_;
     auto blk = [&](double *base, int i) { return base + (int64_t)(i - lo) * nx_; };
     const int up = hi < n ? S_.rank + 1 : -1, dn = lo > 0 ? S_.rank - 1 : -1;
-    Mat cM = schur_matrix(nullptr, c);   // c * M~ (base absent): products with my_const * M
+    Mat cM = schur_matrix(nullptr, c, false);   // c * M~ (base absent): products with my_const * M
     {
         const int imid = (lo + hi) / 2;
         schur_its_ = resolve_its(schur_matrix(block_vals(KKT_Q10, imid, imid), c));
@@ -2195,6 +2238,7 @@ void SchurPC::build_CN() {
     if (dn >= 0) emit_comm(nullptr, -1, h_u1_, dn);
     for (int i = lo; i < hi; ++i) {
         Mat F = schur_matrix(block_vals(KKT_Q10, i, i), c);
+        note_solve(KKT_PC_SWEEP_FORWARD, i, F);
         const Solve sv{F.vals, F.dinv, blk(B_, i), blk(u1, i)};
         if (i >= 1) {
             const double *prev = i - 1 >= lo ? blk(u1, i - 1) : h_u1_;
@@ -2219,9 +2263,11 @@ void SchurPC::build_CN() {
     if (up >= 0) emit_comm(nullptr, -1, h_u1_, up);
     for (int i = hi - 1; i >= lo; --i) {
         Mat G = schur_matrix(block_vals(KKT_Q01, i, i), c);
+        note_solve(KKT_PC_SWEEP_BACKWARD, i, G);
         const Solve sv{G.vals, G.dinv, blk(B_, i), blk(u1, i)};
         if (i <= n - 2) {
-            Mat H = schur_matrix(block_vals(KKT_Q01, i, i + 1), c);
+            // h K^T + (c - 1) M: only multiplied with (indefinite for c < 1)
+            Mat H = schur_matrix(block_vals(KKT_Q01, i, i + 1), c, false);
             emit_update_and_solve(Lin{{Term{H.vals, i + 1 < hi ? blk(u1, i + 1) : h_u1_}},
                                       blk(B_, i), -1.0, 1.0, 0.0, blk(B_, i), nullptr},
                                   sv, schur_its_, G.emin, G.emax, G.eimag, &G);

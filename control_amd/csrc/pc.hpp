@@ -104,6 +104,10 @@ class PcBase {
     virtual void debug_read(unsigned long long *, int) {}
     // kkt_debug_pc_forms: KKT_PC_FORM_INTS values per row step or sweep program, replay order
     virtual void plain_forms(std::vector<int32_t> &) const {}
+    // kkt_debug_pc_solves / kkt_debug_pc_matrices: KKT_PC_SOLVE_VALS values per sub-solve,
+    // KKT_PC_MATRIX_VALS per distinct sub-solve matrix (include/kkt.h)
+    virtual void solve_records(std::vector<double> &) const {}
+    virtual void matrix_records(std::vector<double> &) const {}
     // measurement: time the persistent programs of the next run() with events
     virtual void time_programs(float *ms, int *launches, int64_t *phases) {
         *ms = 0.f;
@@ -128,6 +132,8 @@ class SchurPC : public PcBase {
     void time_stages(kkt_pc_stage_times *out) override;
     void debug_read(unsigned long long *out, int n) override;   // diagnostic builds (KKT_STAMPS)
     void plain_forms(std::vector<int32_t> &out) const override;
+    void solve_records(std::vector<double> &out) const override;
+    void matrix_records(std::vector<double> &out) const override;
     void time_programs(float *ms, int *launches, int64_t *phases) override;
     int bc_set() const { return bc_set_; }
     // degree and interval the sub-solves of a typical time level run with (given or derived)
@@ -162,7 +168,18 @@ class SchurPC : public PcBase {
         double eimag = 0.0;              // > 0: imaginary semi-axis of the spectrum's ellipse
         double *einv = nullptr;          // two-grid form: (P^T A P)^-1, nc x nc row-major (shared
                                          // by matrices with equal values: freed through einv_owned_)
+        int index = -1;                  // position in mat_recs_ (creation order)
+        int est = KKT_PC_EST_NONE;       // KKT_PC_EST_*: where emin / emax come from
     };
+    // what kkt_debug_pc_matrices reports per matrix, and one record per sub-solve emitted
+    struct MatRec {
+        double c = 0.0;
+        int est = KKT_PC_EST_NONE, lanczos = 0, power = 0, solves = 0;
+        bool coarse = false;
+    };
+    std::vector<MatRec> mat_recs_;
+    std::vector<double> solve_recs_;
+    void note_solve(int sweep, int level, const Mat &m);
     int schur_its_ = 0;                  // degree of the sub-solves (given or derived)
     double typical_emin_ = 0.0, typical_emax_ = 0.0;
     int resolve_its(const Mat &typical);
@@ -269,7 +286,9 @@ class SchurPC : public PcBase {
     void build();
     void clear_program();
     const double *block_vals(int q, int i, int j) const;
-    Mat schur_matrix(const double *base_vals, double c);
+    // `solved`: false for matrices only multiplied with (CN: c M~ and the upper blocks): no
+    // interval, no coarse inverse (formed later if the same matrix is solved with after all)
+    Mat schur_matrix(const double *base_vals, double c, bool solved = true);
     void emit_lin(const std::vector<Lin> &ops);
     void emit_cheb(const std::vector<Cheb> &ops);
     double *il_P_[3] = {nullptr, nullptr, nullptr};
@@ -323,6 +342,7 @@ class StokesPC : public PcBase {
     double *out() override { return out_; }
     void check() override;
     bool timed_out(std::string *why) override { return inner_.pc && inner_.pc->timed_out(why); }
+    void solve_records(std::vector<double> &out) const override;
     bool fallback_plain() override { return inner_.pc && inner_.pc->fallback_plain(); }
     const unsigned *err_word() const override { return inner_.pc ? inner_.pc->err_word() : nullptr; }
 
@@ -334,6 +354,7 @@ class StokesPC : public PcBase {
     double sB_ = 1.0, s2_ = 1.0;
     int kp_its_ = 0, mp_its_ = 0;
     double kp_emin_ = 0, kp_emax_ = 0, mp_emin_ = 0, mp_emax_ = 0;
+    int kp_est_ = KKT_PC_EST_GIVEN;    // where kp_emin_ / kp_emax_ come from (KKT_PC_EST_*)
     struct DevMat {
         int pat = -1;
         double *vals = nullptr, *dinv = nullptr;

@@ -362,6 +362,7 @@ StokesPC::StokesPC(System &outer, System &inner, System &commutator, const kkt_p
             if (kp_emin <= 0) {
                 kp_emin = 0.85 * ks.emin;      // Ritz values approach the ends from inside
                 kp_emax = 1.05 * ks.emax;
+                kp_est_ = KKT_PC_EST_ZERO_MEAN;
             }
             if (kp_its < 0)
                 kp_its = std::max(4, std::min(600, (int)std::ceil(5.0 * std::sqrt(kp_emax / kp_emin))));
@@ -372,9 +373,12 @@ StokesPC::StokesPC(System &outer, System &inner, System &commutator, const kkt_p
             // K_p is singular (constants): only the upper end of its spectrum is estimated
             kp_emax = 1.05 * jacobi_spectrum(S_, Kp_.pat, Kp_.vals, Kp_.dinv, nullptr, 60).emax;
             if (!(kp_emax > kp_emin)) fail(KKT_ERR_STATE, "no Chebyshev interval for K_p");
+            kp_est_ = KKT_PC_EST_UPPER;
         }
     }
     kp_its_ = kp_its;
+    kp_emin_ = kp_emin;
+    kp_emax_ = kp_emax;
     kp_cycles_ = d.kp_coarse_cycles;
     if (kp_cycles_ < 0) fail(KKT_ERR_ARG, "negative number of coarse cycles for K_p");
     if (kp_cycles_ > 0) {
@@ -389,6 +393,11 @@ StokesPC::StokesPC(System &outer, System &inner, System &commutator, const kkt_p
     }
     emit_cheb(mp_steps_, Mp_, d.mp_its, d.mp_emin, d.mp_emax, g_, out_ + n0);
     HIPCHK(hipStreamSynchronize(S_.stream));
+}
+
+void StokesPC::solve_records(std::vector<double> &out) const {
+    out = {(double)KKT_PC_SWEEP_KP, -1.0, -1.0, 0.0, kp_emin_, kp_emax_, 0.0, (double)kp_its_,
+           (double)kp_est_};
 }
 
 StokesPC::~StokesPC() {

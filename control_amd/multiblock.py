@@ -383,6 +383,51 @@ class MultiBlockSystem:
         return self._forms(self._lib.kkt_debug_pc_forms,
                            ("form", "width", "slots", "lane", "count", "variant"))
 
+    def _records(self, fn, width):
+        n = fn(self._h, None, 0)
+        if n < 0:
+            self._ck(n)
+        rec = np.zeros(n * width)
+        got = fn(self._h, rec.ctypes.data_as(_lib.c_f64p), rec.size)
+        if got < 0:
+            self._ck(got)
+        return rec.reshape(n, width)
+
+    _SWEEPS = ("first", "second", "forward", "backward", "kp")
+    _ESTIMATES = ("given", "lanczos", "shared", "none", "zero_mean", "upper")
+
+    def pc_solves(self):
+        """``kkt_debug_pc_solves``: one dict per Schur sub-solve of the built-in preconditioner
+        (built by the first ``pc_apply``), in emission order -- ``sweep`` ("first" / "second":
+        stationary; "forward" / "backward": time sweeps), time ``level``, ``matrix`` (index into
+        ``pc_matrices()``), shift ``c``, ``emin``, ``emax``, ``eimag``, degree ``its`` (two-grid:
+        sweeps per cycle) and ``estimate`` ("given", "lanczos" or "shared" with an equal matrix).
+        With a ``StokesPC``: one dict ``{"sweep": "kp", "kp_emin", "kp_emax", "kp_its",
+        "estimate"}`` for the K_p solve, ``estimate`` "zero_mean" (both ends by Lanczos on the
+        range), "upper" (upper end only, ``kp_emin`` from the velocity sub-solves) or "given";
+        the velocity sub-solves are on the inner system's ``pc_solves()``."""
+        out = []
+        for r in self._records(self._lib.kkt_debug_pc_solves, 9):
+            sweep, est = self._SWEEPS[int(r[0])], self._ESTIMATES[int(r[8])]
+            if sweep == "kp":
+                out.append(dict(sweep=sweep, kp_emin=float(r[4]), kp_emax=float(r[5]),
+                                kp_its=int(r[7]), estimate=est))
+            else:
+                out.append(dict(sweep=sweep, level=int(r[1]), matrix=int(r[2]), c=float(r[3]),
+                                emin=float(r[4]), emax=float(r[5]), eimag=float(r[6]),
+                                its=int(r[7]), estimate=est))
+        return out
+
+    def pc_matrices(self):
+        """``kkt_debug_pc_matrices``: one dict per distinct matrix ``blk + c M~`` the built-in
+        Schur preconditioner formed, in creation order -- ``c``, ``estimate`` ("given",
+        "lanczos", "shared" with an earlier matrix of equal values, "none": only multiplied
+        with), ``lanczos`` and ``power`` steps spent on it, ``coarse`` (has a coarse inverse) and
+        the number of ``solves`` that use it."""
+        return [dict(c=float(r[0]), estimate=self._ESTIMATES[int(r[1])], lanczos=int(r[2]),
+                     power=int(r[3]), coarse=bool(r[4]), solves=int(r[5]))
+                for r in self._records(self._lib.kkt_debug_pc_matrices, 6)]
+
     def coarse_matrices(self):
         """``kkt_debug_coarse_matrices``: the Galerkin matrices P^T A P of the last coarse set-up,
         shape ``(matrices, n_coarse, n_coarse)`` (needs option ``coarse_keep`` = ``1``)."""

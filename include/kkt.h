@@ -433,6 +433,31 @@ enum { KKT_PC_ROWS_PLAIN = 0, KKT_PC_ROWS_SHARED = 1, KKT_PC_ROWS_KERNARG = 2,
 int kkt_debug_apply_forms(kkt_handle h, int32_t *out, int cap);
 int kkt_debug_pc_forms(kkt_handle h, int32_t *out, int cap);
 
+/* Test hooks: the Chebyshev intervals the built-in preconditioner runs with (read-only; they
+ * change no launch).  Same calling convention as kkt_debug_pc_forms, in doubles: the return value
+ * is the number of records, `cap` counts doubles.  0 records before the preconditioner is built.
+ * kkt_debug_pc_solves: one record of KKT_PC_SOLVE_VALS per Schur sub-solve of the block Schur
+ *   preconditioner, in emission order: sweep (KKT_PC_SWEEP_*); time level; index of the matrix
+ *   (a kkt_debug_pc_matrices record); shift c of the matrix blk + c M~; emin; emax; eimag; degree
+ *   its (two-grid: sweeps per cycle); estimate (KKT_PC_EST_* of the matrix).
+ *   On a handle with the Stokes preconditioner: one record, sweep KKT_PC_SWEEP_KP, for the K_p
+ *   solve -- level and matrix -1, c 0, emin / emax / its of K_p, eimag 0, estimate
+ *   KKT_PC_EST_ZERO_MEAN (both ends by Lanczos on the range), KKT_PC_EST_UPPER (upper end only,
+ *   emin from the velocity sub-solves) or KKT_PC_EST_GIVEN; the velocity sub-solves are reported
+ *   by the inner handle.
+ * kkt_debug_pc_matrices: one record of KKT_PC_MATRIX_VALS per distinct matrix blk + c M~ the
+ *   Schur preconditioner formed, in creation order: c; estimate (KKT_PC_EST_GIVEN, _LANCZOS,
+ *   _SHARED with an earlier matrix of equal values, _NONE: only multiplied with); Lanczos steps;
+ *   power-iteration steps (skew part); 1 if it has a coarse inverse, else 0; number of sub-solves
+ *   that use it. */
+enum { KKT_PC_SOLVE_VALS = 9, KKT_PC_MATRIX_VALS = 6 };
+enum { KKT_PC_SWEEP_FIRST = 0, KKT_PC_SWEEP_SECOND = 1, KKT_PC_SWEEP_FORWARD = 2,
+       KKT_PC_SWEEP_BACKWARD = 3, KKT_PC_SWEEP_KP = 4 };
+enum { KKT_PC_EST_GIVEN = 0, KKT_PC_EST_LANCZOS = 1, KKT_PC_EST_SHARED = 2, KKT_PC_EST_NONE = 3,
+       KKT_PC_EST_ZERO_MEAN = 4, KKT_PC_EST_UPPER = 5 };
+int kkt_debug_pc_solves(kkt_handle h, double *out, int cap);
+int kkt_debug_pc_matrices(kkt_handle h, double *out, int cap);
+
 /* Byte accounting of the stored operator ("algorithmic bytes"). */
 typedef struct kkt_info {
     int64_t n_local;            /* local KKT vector length */

@@ -8,6 +8,7 @@ import pytest
 import scipy.sparse as sp
 
 import common
+import spectrum_ref
 from control_amd._lib import KktError
 from control_amd.coarse import multilinear_coarse_space
 
@@ -23,20 +24,36 @@ def _apply(p, P, cycles, columns, x):
     return y, g.coarse_setup_stats()
 
 
-@pytest.mark.parametrize("CN", [False, True])
-@pytest.mark.parametrize("time_dependent", [False, True])
-def test_batched_setup_matches_the_column_path(CN, time_dependent):
-    """P1, shared interior levels (three distinct matrices for BE) and a forward operator that
-    differs per level (one matrix per level)."""
-    p = common.heat_problem(n=48, n_t=6, CN=CN, beta=1e-4, time_dependent=time_dependent)
+def _batched_against_columns(p):
     P = multilinear_coarse_space(p["sd"].coords, p["nodes"], cells=8)
     x = common.rng_vector(2 * p["m"] * p["sd"].n_dofs)
     ref, st_ref = _apply(p, P, 2, True, x)
     got, st = _apply(p, P, 2, False, x)
-    assert st["matrices"] == st_ref["matrices"] >= 2
+    # one inverse per distinct value set among the matrices that are solved with
+    assert st["matrices"] == st_ref["matrices"] == spectrum_ref.distinct_solved_matrices(p)
     assert st["n_coarse"] == P.shape[1]
     assert st["launches"] < st_ref["launches"]
     assert common.rel_err(got, ref) < 1e-11
+    return st
+
+
+# (time-invariant CN: test_batched_setup_of_cn_inverts_only_the_solved_matrix)
+@pytest.mark.parametrize("time_dependent,CN", [(False, False), (True, False), (True, True)])
+def test_batched_setup_matches_the_column_path(CN, time_dependent):
+    """P1, shared interior levels (three distinct matrices for BE) and a forward operator that
+    differs per level (one matrix per level)."""
+    p = common.heat_problem(n=48, n_t=6, CN=CN, beta=1e-4, time_dependent=time_dependent)
+    st = _batched_against_columns(p)
+    assert st["matrices"] >= 3
+
+
+def test_batched_setup_of_cn_inverts_only_the_solved_matrix():
+    """Time-invariant CN solves with one value set (every level's forward and backward matrices
+    are equal): exactly one inverse.  c M~ and the upper blocks h K^T + (c - 1) M are only
+    multiplied with and get none."""
+    p = common.heat_problem(n=48, n_t=6, CN=True, beta=1e-4)
+    st = _batched_against_columns(p)
+    assert st["matrices"] == 1
 
 
 def test_stokes_setup_matches_the_column_path():
