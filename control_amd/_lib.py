@@ -95,6 +95,25 @@ class StepLock(C.Structure):
                 ("v_next", c_f64p)]
 
 
+class RelinDesc(C.Structure):
+    _fields_ = ([("n_t", C.c_int), ("cn", C.c_int), ("nq", C.c_int),
+                 ("ne", C.c_int64), ("n2", C.c_int64), ("n1", C.c_int64),
+                 ("nu", C.c_double), ("tau", C.c_double), ("beta", C.c_double),
+                 ("V", c_i32p)] + [(n, c_f64p) for n in ("W", "phi", "gphi", "lam", "glam")]
+                + [("nnz2", C.c_int64)]
+                + [(n, c_i32p) for n in ("v_indptr", "v_indices", "v_tperm", "v_cptr", "v_clist")]
+                + [("K2", c_f64p), ("M2", c_f64p), ("nnz1", C.c_int64)]
+                + [(n, c_i32p) for n in ("p_indptr", "p_indices", "p_tperm", "p_cptr", "p_clist")]
+                + [("Kp", c_f64p), ("Mp", c_f64p), ("nnz_b", C.c_int64),
+                   ("b_indptr", c_i32p), ("b_indices", c_i32p), ("b_values", c_f64p),
+                   ("n_bc", C.c_int64), ("bc_idx", c_i32p), ("data", c_f64p)])
+
+
+class RelinRecipe(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("quadrant", "i", "j", "space", "level", "transpose")] + \
+               [("alpha", C.c_double), ("gamma", C.c_double)]
+
+
 PC_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, c_f64p, c_f64p, c_f64p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int, C.c_int)
 SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int64, C.c_int,
@@ -142,6 +161,13 @@ SIGNATURES = {
                                    C.POINTER(C.c_int), c_f64p, c_f64p, C.c_int,
                                    C.POINTER(C.c_int)]),
     "kkt_sync": (C.c_int, [C.c_void_p]),
+    "kkt_set_relinearisation": (C.c_int, [C.c_void_p, C.POINTER(RelinDesc)]),
+    "kkt_relinearise_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.POINTER(RelinRecipe)]),
+    "kkt_picard_state": (C.c_int, [C.c_void_p, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p]),
+    "kkt_picard_iterate": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4),
+    "kkt_picard_residual_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_f64p]),
+    "kkt_picard_update_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kkt_time_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.POINTER(C.c_float)]),
     "kkt_time_pc_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

@@ -18,7 +18,7 @@ from typing import Sequence
 import scipy.sparse as sp
 
 __all__ = ["instationary_blocks", "stationary_blocks", "instationary_incompressible_blocks",
-           "stationary_incompressible_blocks", "conform_to"]
+           "stationary_incompressible_blocks", "conform_to", "instationary_relinearisation_recipes"]
 
 
 def _csr(A):
@@ -248,3 +248,34 @@ def instationary_incompressible_blocks(M_v, K_v, B, M_p, K_p, tau: float, beta: 
         b10[(i, i)] = _own(tB, share)
     return {"outer": (b00, b01, b10, b11), "inner": (i00, i01, i10, i11),
             "commutator": (c00, c01, c10, c11), "m": m}
+
+
+def instationary_relinearisation_recipes(tau: float, beta: float, n_t: int, CN: bool):
+    """The blocks of ``instationary_incompressible_blocks`` that carry the forward operator, as
+    recipes ``(quadrant, i, j, level, alpha, transpose, gamma)``: block
+    ``= alpha D_level(^T) + gamma M`` -- the ``comb`` calls of ``instationary_blocks``
+    (``control/control.py:2907-2978`` BE, ``2938-2958`` CN).  Every other block is a multiple of
+    a mass matrix or ``B`` and does not change with the linearisation point.
+
+    Returns ``{"inner": [...], "commutator": [...], "outer": [...], "m": m}``: the inner
+    (velocity KKT) and commutator (pressure) systems use ``block_01`` (quadrant 1) and
+    ``block_10`` (quadrant 2); the outer system holds the same velocity blocks inside its
+    ``block_00`` at ``(i, m + j)`` and ``(m + i, j)``."""
+    inner = []
+    if not CN:
+        m = n_t
+        for i in range(n_t):
+            inner.append((1, i, i, i, tau, True, 1.0))
+            inner.append((2, i, i, i, tau, False, 1.0))
+    else:
+        m = n_t - 1
+        h = 0.5 * tau
+        for i in range(m):
+            if i >= 1:
+                inner.append((2, i, i - 1, i, h, False, -1.0))
+            inner.append((1, i, i, i, h, True, 1.0))
+            inner.append((2, i, i, i + 1, h, False, 1.0))
+            if i + 1 < m:
+                inner.append((1, i, i + 1, i + 1, h, True, -1.0))
+    outer = [(0, i, m + j, *r) if q == 1 else (0, m + i, j, *r) for (q, i, j, *r) in inner]
+    return {"inner": inner, "commutator": list(inner), "outer": outer, "m": m}

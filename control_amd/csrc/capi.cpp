@@ -8,6 +8,7 @@
 
 #include "comm.hpp"
 #include "pc.hpp"
+#include "relin.hpp"
 #include "system.hpp"
 #include "tiles.hpp"
 
@@ -351,6 +352,31 @@ int kkt_solve_device(kkt_handle h, const double *d_b, double *d_u, int *its, int
     KKT_TRY(h, S.solve(d_b, d_u, its, reason, rnorm, hist, hist_cap, hist_len));
 }
 int kkt_sync(kkt_handle h) { KKT_TRY(h, S.sync()); }
+
+int kkt_set_relinearisation(kkt_handle h, const kkt_relin_desc *desc) {
+    KKT_TRY(h, relin_set(S, desc));
+}
+int kkt_relinearise_device(kkt_handle h, kkt_handle plan, const double *d_v, int n,
+                           const kkt_relin_recipe *recipes) {
+    KKT_TRY(h, {
+        if (!plan) fail(KKT_ERR_ARG, "kkt_relinearise_device: null plan handle");
+        relin_apply(S, plan->S, d_v, n, recipes);
+    });
+}
+int kkt_picard_state(kkt_handle plan, int download, double *v, double *zeta, double *p,
+                     double *mu) {
+    KKT_TRY(plan, relin_state(S, download, v, zeta, p, mu));
+}
+int kkt_picard_iterate(kkt_handle plan, double **d_v, double **d_zeta, double **d_p,
+                       double **d_mu) {
+    KKT_TRY(plan, relin_iterate(S, d_v, d_zeta, d_p, d_mu));
+}
+int kkt_picard_residual_device(kkt_handle plan, double *d_out, int rhs, double *norm) {
+    KKT_TRY(plan, relin_residual(S, d_out, rhs, norm));
+}
+int kkt_picard_update_device(kkt_handle plan, double *d_u) {
+    KKT_TRY(plan, relin_update(S, d_u));
+}
 
 static void time_loop(System &S, bool pc, const double *d_x, double *d_y, int reps, float *ms) {
     if (reps < 1 || !ms) fail(KKT_ERR_ARG, "bad timing arguments");

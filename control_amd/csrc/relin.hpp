@@ -1,0 +1,88 @@
+// Device re-linearisation of the Picard loop (include/kkt.h, kkt_set_relinearisation):
+// convection assembly of the Taylor-Hood discretisation into block values, the non-linear
+// residual and the update of the iterate.  DESIGN.md section 6.6.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+#include <set>
+#include <tuple>
+#include <vector>
+
+#include "../../include/kkt.h"
+
+namespace kkt {
+
+struct System;
+
+constexpr int RELIN_NQ = 7;        // Radon's 7-point rule
+constexpr int RELIN_EV = 36;       // P2 element matrix entries
+constexpr int RELIN_EP = 9;        // P1 element matrix entries
+
+// One target block of a composition: dst = alpha D(^T) + gamma M on a SELL value array.
+struct ComposeJob {
+    double *dst;
+    const int32_t *sell2csr;   // CSR position of every SELL slot (-1: padding)
+    const int32_t *col;        // SELL column of every slot
+    const uint8_t *colmask;    // Dirichlet columns zeroed (null: none)
+    int64_t npadded;
+    const double *D;           // the level's scalar values (CSR of the scalar pattern)
+    const double *M;           // scalar mass values
+    const int32_t *tperm;      // transpose permutation of the scalar pattern, null: D itself
+    int64_t nnz_s;             // scalar nnz: positions of the second component fold onto it
+    double alpha, gamma;
+};
+
+struct RelinPlan {
+    int n_t = 0, m = 0;
+    bool CN = false;
+    int64_t ne = 0, n2 = 0, n1 = 0, nv = 0, nnz2 = 0, nnz1 = 0;
+    double nu = 0.0, tau = 0.0, beta = 0.0;
+    int32_t *d_V = nullptr;
+    double *d_W = nullptr, *d_phi = nullptr, *d_gphi = nullptr, *d_lam = nullptr,
+           *d_glam = nullptr;
+    // scalar P2 pattern (one velocity component) and P1 pattern
+    std::vector<int32_t> h_ip2, h_ix2, h_ipp, h_ixp;
+    int32_t *d_ip2 = nullptr, *d_ix2 = nullptr, *d_t2 = nullptr, *d_tp = nullptr;
+    double *d_K2 = nullptr, *d_M2 = nullptr, *d_Kp = nullptr, *d_Mp = nullptr;
+    // contribution lists: CSR over stored positions of flat element-entry indices, ascending
+    int32_t *d_cptr2 = nullptr, *d_clist2 = nullptr, *d_cptrp = nullptr, *d_clistp = nullptr;
+    // B (n1 x nv) and B^T (nv x n1)
+    int32_t *d_Bip = nullptr, *d_Bix = nullptr, *d_BTip = nullptr, *d_BTix = nullptr;
+    double *d_Bv = nullptr, *d_BTv = nullptr;
+    uint8_t *d_bc = nullptr;   // nv bytes: Dirichlet velocity dofs
+    double *d_data = nullptr;  // 2m x nv data rows of the velocity residual
+    // work: element matrices and the assembled D per level
+    double *d_Ev = nullptr, *d_Ep = nullptr, *d_D2 = nullptr, *d_Dp = nullptr;
+    bool assembled = false;
+    // the iterate: v, zeta (n_t x nv), p, mu (m x n1)
+    double *d_v = nullptr, *d_zeta = nullptr, *d_p = nullptr, *d_mu = nullptr;
+    double *d_red = nullptr;   // reduction scratch + result
+    ComposeJob *d_jobs = nullptr;
+    int jobs_cap = 0;
+    // target patterns already proven equal to the plan's: (system, pattern id, space)
+    std::set<std::tuple<const void *, int, int>> checked;
+    ~RelinPlan();
+};
+
+// element matrices of every (element, level): Ev[(l ne + e) 36 + 6a + b], Ep[... 9 + 3c + d]
+void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v);
+// D[l nnz + k] = nu K[k] + sum of the contributions of position k in list order
+void launch_relin_gather(hipStream_t s, const RelinPlan &P);
+void launch_relin_compose(hipStream_t s, const ComposeJob *d_jobs, int njobs, int64_t max_padded);
+// velocity and pressure rows of the residual in the outer system's vector layout
+void launch_relin_residual(hipStream_t s, const RelinPlan &P, double *d_r);
+// the solve's right-hand side from the residual: pressure rows times tau, CN time transforms
+void launch_relin_rhs(hipStream_t s, const RelinPlan &P, const double *d_r, double *d_b);
+// v, zeta, mu, p += the update's blocks, the update zeroed; zeta zero on the Dirichlet dofs
+void launch_relin_update(hipStream_t s, const RelinPlan &P, double *d_u);
+
+// host side (relin.cpp), behind the C-ABI of the same names
+void relin_set(System &S, const kkt_relin_desc *d);
+void relin_apply(System &T, System &plan, const double *d_v, int n, const kkt_relin_recipe *rec);
+void relin_state(System &S, int download, double *v, double *zeta, double *p, double *mu);
+void relin_iterate(System &S, double **v, double **zeta, double **p, double **mu);
+void relin_residual(System &S, double *d_out, int rhs, double *norm);
+void relin_update(System &S, double *d_u);
+
+}  // namespace kkt

@@ -1,0 +1,325 @@
+// Device re-linearisation kernels (relin.hpp): P2-P1 convection element matrices, their
+// deterministic gather into stored positions, composition into SELL block values, the Picard
+// residual and the update.  gfx950, wave64; every store is a plain vector store, and no
+// floating-point atomics: every sum runs in a fixed order.
+#include <hip/hip_runtime.h>
+
+#include "relin.hpp"
+
+namespace kkt {
+
+static inline int relin_grid(int64_t n, int cap = 256 * 8) {
+    int64_t g = (n + 255) / 256;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
+// One thread per (element, level): the velocity element matrix
+//   N[a][b] = sum_q W_eq phi_qa (w_q . grad phi_eqb)
+// and the pressure one  sum_q W_eq lam_qc (w_q . grad lam_ed)  (fem.py convection_v_data /
+// convection_p), w_q the P2 wind (component-major) at the quadrature point.
+__global__ __launch_bounds__(256) void relin_elements_kernel(
+    const double *__restrict__ vlev, int64_t ne, int64_t n2, int n_t,
+    const int32_t *__restrict__ V, const double *__restrict__ W, const double *__restrict__ phi,
+    const double *__restrict__ gphi, const double *__restrict__ lam,
+    const double *__restrict__ glam, double *__restrict__ Ev, double *__restrict__ Ep) {
+    const int64_t total = ne * n_t;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t l = t / ne, e = t - l * ne;
+        const double *w = vlev + l * 2 * n2;
+        double wx[6], wy[6];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            const int32_t node = V[e * 6 + a];
+            wx[a] = w[node];
+            wy[a] = w[n2 + node];
+        }
+        double gl[3][2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            gl[c][0] = glam[e * 6 + c * 2];
+            gl[c][1] = glam[e * 6 + c * 2 + 1];
+        }
+        double Nv[6][6], Np[3][3];
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = 0; b < 6; ++b) Nv[a][b] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) Np[c][d] = 0.0;
+        for (int q = 0; q < RELIN_NQ; ++q) {
+            double qx = 0.0, qy = 0.0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                qx += wx[a] * phi[q * 6 + a];
+                qy += wy[a] * phi[q * 6 + a];
+            }
+            const double wq = W[e * RELIN_NQ + q];
+            const double *g = gphi + (e * RELIN_NQ + q) * 12;
+            double adv[6];
+#pragma unroll
+            for (int b = 0; b < 6; ++b) adv[b] = g[2 * b] * qx + g[2 * b + 1] * qy;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const double s = wq * phi[q * 6 + a];
+#pragma unroll
+                for (int b = 0; b < 6; ++b) Nv[a][b] += s * adv[b];
+            }
+            double advp[3];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) advp[d] = gl[d][0] * qx + gl[d][1] * qy;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const double s = wq * lam[q * 3 + c];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) Np[c][d] += s * advp[d];
+            }
+        }
+        double *ov = Ev + t * RELIN_EV;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = 0; b < 6; b += 2)
+                *reinterpret_cast<double2 *>(ov + a * 6 + b) = make_double2(Nv[a][b], Nv[a][b + 1]);
+        double *op = Ep + t * RELIN_EP;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int d = 0; d < 3; ++d) op[c * 3 + d] = Np[c][d];
+    }
+}
+
+void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v) {
+    hipLaunchKernelGGL(relin_elements_kernel, dim3(relin_grid(P.ne * P.n_t, 256 * 64)), dim3(256),
+                       0, s, d_v, P.ne, P.n2, P.n_t, P.d_V, P.d_W, P.d_phi, P.d_gphi, P.d_lam,
+                       P.d_glam, P.d_Ev, P.d_Ep);
+}
+
+// One thread per (stored position, level): the contributions in ascending element-entry order
+// (np.bincount's order), then nu K + C with separate roundings (fem / picard D_v on the host).
+__global__ __launch_bounds__(256) void relin_gather_kernel(
+    const int32_t *__restrict__ cptr, const int32_t *__restrict__ clist,
+    const double *__restrict__ E, int64_t per_level, const double *__restrict__ K, double nu,
+    int64_t nnz, int n_t, double *__restrict__ D) {
+    const int64_t total = nnz * n_t;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t l = t / nnz, k = t - l * nnz;
+        const double *El = E + l * per_level;
+        double acc = 0.0;
+        for (int32_t j = cptr[k]; j < cptr[k + 1]; ++j) acc = __dadd_rn(acc, El[clist[j]]);
+        D[t] = __dadd_rn(__dmul_rn(nu, K[k]), acc);
+    }
+}
+
+void launch_relin_gather(hipStream_t s, const RelinPlan &P) {
+    hipLaunchKernelGGL(relin_gather_kernel, dim3(relin_grid(P.nnz2 * P.n_t, 256 * 64)), dim3(256),
+                       0, s, P.d_cptr2, P.d_clist2, P.d_Ev, P.ne * RELIN_EV, P.d_K2, P.nu, P.nnz2,
+                       P.n_t, P.d_D2);
+    hipLaunchKernelGGL(relin_gather_kernel, dim3(relin_grid(P.nnz1 * P.n_t, 256 * 64)), dim3(256),
+                       0, s, P.d_cptrp, P.d_clistp, P.d_Ep, P.ne * RELIN_EP, P.d_Kp, P.nu, P.nnz1,
+                       P.n_t, P.d_Dp);
+}
+
+// blockIdx.y selects the target block; each SELL slot gets alpha D(^T) + gamma M (blocks.py
+// _axpby: two products, one sum), Dirichlet columns zeroed as kkt_update_block_values does.
+__global__ __launch_bounds__(256) void relin_compose_kernel(const ComposeJob *__restrict__ jobs) {
+    const ComposeJob J = jobs[blockIdx.y];
+    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < J.npadded;
+         p += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t k = J.sell2csr[p];
+        double v = 0.0;
+        if (k >= 0) {
+            const int64_t ks = k >= J.nnz_s ? k - J.nnz_s : k;
+            const int64_t kd = J.tperm ? J.tperm[ks] : ks;
+            v = __dadd_rn(__dmul_rn(J.alpha, J.D[kd]), __dmul_rn(J.gamma, J.M[ks]));
+            if (J.colmask && J.colmask[J.col[p]]) v = 0.0;
+        }
+        J.dst[p] = v;
+    }
+}
+
+void launch_relin_compose(hipStream_t s, const ComposeJob *d_jobs, int njobs, int64_t max_padded) {
+    if (njobs <= 0) return;
+    hipLaunchKernelGGL(relin_compose_kernel, dim3(relin_grid(max_padded, 256), njobs), dim3(256), 0,
+                       s, d_jobs);
+}
+
+// sum_k A[k] x[off + col[k]] over CSR row r (tperm: the transposed matrix on a symmetric pattern)
+__device__ inline double relin_row(const int32_t *__restrict__ ip, const int32_t *__restrict__ ix,
+                                   const double *__restrict__ A, const int32_t *__restrict__ tperm,
+                                   int64_t r, const double *__restrict__ x) {
+    double acc = 0.0;
+    for (int32_t k = ip[r]; k < ip[r + 1]; ++k) acc += (tperm ? A[tperm[k]] : A[k]) * x[ix[k]];
+    return acc;
+}
+
+struct RelinArgs {
+    const int32_t *ip2, *ix2, *t2, *Bip, *Bix, *BTip, *BTix;
+    const double *M2, *D2, *Bv, *BTv, *data, *v, *zeta, *p, *mu;
+    const uint8_t *bc;
+    int64_t n2, nv, n1, nnz2;
+    int n_t, m, cn;
+    double tau, beta;
+};
+
+// Velocity rows (picard.non_linear_res_eval): one thread per (row block, dof).  Row blocks
+// 0..m-1 are the adjoint rows (r00), m..2m-1 the state rows (r01); Dirichlet rows are zero.
+__global__ __launch_bounds__(256) void relin_residual_v_kernel(RelinArgs A, double *__restrict__ r) {
+    const int rb = blockIdx.y, fam = rb >= A.m, i = fam ? rb - A.m : rb;
+    for (int64_t R = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; R < A.nv;
+         R += (int64_t)gridDim.x * blockDim.x) {
+        double out = 0.0;
+        if (!A.bc[R]) {
+            const int64_t c = R >= A.n2, row = R - c * A.n2, off = c * A.n2;
+            auto Mx = [&](const double *lev) {
+                return relin_row(A.ip2, A.ix2, A.M2, nullptr, row, lev + off);
+            };
+            auto Dx = [&](int l, const double *lev) {
+                return relin_row(A.ip2, A.ix2, A.D2 + l * A.nnz2, nullptr, row, lev + off);
+            };
+            auto DTx = [&](int l, const double *lev) {
+                return relin_row(A.ip2, A.ix2, A.D2 + l * A.nnz2, A.t2, row, lev + off);
+            };
+            auto BTx = [&](const double *lev) {
+                return relin_row(A.BTip, A.BTix, A.BTv, nullptr, R, lev);
+            };
+            const double *v = A.v, *z = A.zeta;
+            const int64_t nv = A.nv;
+            const double tau = A.tau, d = A.data[rb * nv + R];
+            if (!A.cn) {
+                if (!fam) {
+                    const double Dz = tau * DTx(i, z + i * nv) + Mx(z + i * nv);
+                    out = d - Dz;
+                    if (i < A.n_t - 1) out += -tau * Mx(v + i * nv) + Mx(z + (i + 1) * nv);
+                    out -= tau * BTx(A.mu + i * A.n1);
+                } else {
+                    const double Dv = tau * Dx(i, v + i * nv) + Mx(v + i * nv);
+                    out = d - Dv;
+                    if (i >= 1) out += Mx(v + (i - 1) * nv) + (tau / A.beta) * Mx(z + i * nv);
+                    out -= tau * BTx(A.p + i * A.n1);
+                }
+            } else {
+                const double h = 0.5 * tau;
+                const double *v0 = v + i * nv, *v1 = v + (i + 1) * nv;
+                const double *z0 = z + i * nv, *z1 = z + (i + 1) * nv;
+                if (!fam) {
+                    out = d - h * (Mx(v0) + Mx(v1)) - (h * DTx(i, z0) + Mx(z0)) -
+                          (h * DTx(i + 1, z1) - Mx(z1)) - tau * BTx(A.mu + i * A.n1);
+                } else {
+                    out = d - (h * Dx(i, v0) - Mx(v0)) - (h * Dx(i + 1, v1) + Mx(v1)) +
+                          (h / A.beta) * (Mx(z0) + Mx(z1)) - tau * BTx(A.p + i * A.n1);
+                }
+            }
+        }
+        r[rb * A.nv + R] = out;
+    }
+}
+
+// Pressure rows: -B v (row blocks 0..m-1; CN: the level i + 1) and -B zeta.
+__global__ __launch_bounds__(256) void relin_residual_p_kernel(RelinArgs A, double *__restrict__ r) {
+    const int rb = blockIdx.y, fam = rb >= A.m, i = fam ? rb - A.m : rb;
+    const double *x = fam ? A.zeta + i * A.nv : A.v + (A.cn ? i + 1 : i) * A.nv;
+    for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < A.n1;
+         q += (int64_t)gridDim.x * blockDim.x)
+        r[rb * A.n1 + q] = -relin_row(A.Bip, A.Bix, A.Bv, nullptr, q, x);
+}
+
+static RelinArgs relin_args(const RelinPlan &P) {
+    RelinArgs A;
+    A.ip2 = P.d_ip2; A.ix2 = P.d_ix2; A.t2 = P.d_t2;
+    A.Bip = P.d_Bip; A.Bix = P.d_Bix; A.BTip = P.d_BTip; A.BTix = P.d_BTix;
+    A.M2 = P.d_M2; A.D2 = P.d_D2; A.Bv = P.d_Bv; A.BTv = P.d_BTv; A.data = P.d_data;
+    A.v = P.d_v; A.zeta = P.d_zeta; A.p = P.d_p; A.mu = P.d_mu; A.bc = P.d_bc;
+    A.n2 = P.n2; A.nv = P.nv; A.n1 = P.n1; A.nnz2 = P.nnz2;
+    A.n_t = P.n_t; A.m = P.m; A.cn = P.CN;
+    A.tau = P.tau; A.beta = P.beta;
+    return A;
+}
+
+void launch_relin_residual(hipStream_t s, const RelinPlan &P, double *d_r) {
+    const RelinArgs A = relin_args(P);
+    hipLaunchKernelGGL(relin_residual_v_kernel, dim3(relin_grid(P.nv, 512), 2 * P.m), dim3(256), 0,
+                       s, A, d_r);
+    hipLaunchKernelGGL(relin_residual_p_kernel, dim3(relin_grid(P.n1, 512), 2 * P.m), dim3(256), 0,
+                       s, A, d_r + 2 * P.m * P.nv);
+}
+
+// b from r: velocity rows as they are, pressure rows times tau; CN: T_1 on the adjoint rows and
+// on the zeta pressure rows, T_2 on the state rows and the v pressure rows (picard.py)
+__global__ __launch_bounds__(256) void relin_rhs_kernel(const double *__restrict__ r,
+                                                        double *__restrict__ b, int m,
+                                                        int64_t nv, int64_t n1, int cn,
+                                                        double tau) {
+    const int64_t n0 = 2 * (int64_t)m * nv, n = n0 + 2 * (int64_t)m * n1;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const bool pres = t >= n0;
+        const int64_t nx = pres ? n1 : nv, u = pres ? t - n0 : t;
+        const int64_t rb = u / nx;
+        const int fam = rb >= m, i = (int)(fam ? rb - m : rb);
+        const double c = pres ? tau : 1.0;
+        double out = pres ? c * r[t] : r[t];
+        if (cn) {
+            // T_1 (i + 1 into i): adjoint rows, zeta pressure rows; T_2 (i - 1 into i): the others
+            const bool t1 = fam == (int)pres;
+            if (t1 && i + 1 < m) out += pres ? c * r[t + nx] : r[t + nx];
+            if (!t1 && i >= 1) out += pres ? c * r[t - nx] : r[t - nx];
+        }
+        b[t] = out;
+    }
+}
+
+void launch_relin_rhs(hipStream_t s, const RelinPlan &P, const double *d_r, double *d_b) {
+    const int64_t n = 2 * P.m * (P.nv + P.n1);
+    hipLaunchKernelGGL(relin_rhs_kernel, dim3(relin_grid(n)), dim3(256), 0, s, d_r, d_b, P.m, P.nv,
+                       P.n1, (int)P.CN, P.tau);
+}
+
+__global__ __launch_bounds__(256) void relin_update_kernel(double *__restrict__ u,
+                                                           double *__restrict__ v,
+                                                           double *__restrict__ zeta,
+                                                           double *__restrict__ mu,
+                                                           double *__restrict__ p, int m,
+                                                           int64_t nv, int64_t n1, int cn) {
+    const int64_t n0 = 2 * (int64_t)m * nv, n = n0 + 2 * (int64_t)m * n1;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        if (t < n0) {
+            const int64_t rb = t / nv, R = t - rb * nv;
+            if (rb < m)        // unknown block i: v at level i (CN: i + 1), zeta at level i
+                v[(rb + cn) * nv + R] += u[t];
+            else
+                zeta[(rb - m) * nv + R] += u[t];
+        } else {
+            const int64_t k = t - n0, rb = k / n1, q = k - rb * n1;
+            if (rb < m)        // pressure blocks: mu with the v rows, p with the zeta rows
+                mu[rb * n1 + q] += u[t];
+            else
+                p[(rb - m) * n1 + q] += u[t];
+        }
+        u[t] = 0.0;   // consumed: the next solve starts from zero
+    }
+}
+
+__global__ __launch_bounds__(256) void relin_zero_bc_kernel(double *__restrict__ zeta,
+                                                            const uint8_t *__restrict__ bc,
+                                                            int64_t n, int64_t nv) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n;
+         t += (int64_t)gridDim.x * blockDim.x)
+        if (bc[t % nv]) zeta[t] = 0.0;
+}
+
+void launch_relin_update(hipStream_t s, const RelinPlan &P, double *d_u) {
+    const int64_t n = 2 * P.m * (P.nv + P.n1);
+    hipLaunchKernelGGL(relin_update_kernel, dim3(relin_grid(n)), dim3(256), 0, s, d_u, P.d_v,
+                       P.d_zeta, P.d_mu, P.d_p, P.m, P.nv, P.n1, (int)P.CN);
+    hipLaunchKernelGGL(relin_zero_bc_kernel, dim3(relin_grid(P.n_t * P.nv)), dim3(256), 0, s,
+                       P.d_zeta, P.d_bc, P.n_t * P.nv, P.nv);
+}
+
+}  // namespace kkt

@@ -11,6 +11,7 @@
 
 #include "comm.hpp"
 #include "pc.hpp"
+#include "relin.hpp"
 
 namespace kkt {
 
@@ -863,6 +864,15 @@ void System::update_block_values(int q, int i, int j, const double *vals) {
         HIPCHK(hipFree(d_new));
         return;
     }
+    give_private_values(q, i, j, d_new);
+    pc_stale = true;
+}
+
+// Block (q, i, j) leaves the value array it shares and takes d_new (device, npadded doubles)
+// as a private one; its RowOp term of the apply plan is re-pointed.
+void System::give_private_values(int q, int i, int j, double *d_new) {
+    Block &blk = blocks.at(std::make_tuple(q, i, j));
+    const Pattern &P = patterns[values[blk.va].pattern];
     ValueArray c = values[blk.va];
     const double *d_old = c.d_vals;
     c.d_vals = d_new;
@@ -881,7 +891,6 @@ void System::update_block_values(int q, int i, int j, const double *vals) {
     op.t[t].vals = d_new;
     HIPCHK(hipMemcpy(apply_launches[L].d_ops + o, &op, sizeof(RowOp), hipMemcpyHostToDevice));
     apply_launches[L].ngroups = 0;   // the op left its group of equal structure: plain kernel
-    pc_stale = true;
 }
 
 // y = A x  (preconditioner.py:375-543)

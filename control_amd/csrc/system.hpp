@@ -137,6 +137,7 @@ struct TimeGroup {   // CN transform applied to a contiguous range of local bloc
 
 class PcBase;
 class Comm;
+struct RelinPlan;
 
 struct KrylovCfg {
     int type = KKT_KSP_FGMRES;
@@ -241,6 +242,7 @@ struct System {
     bool pc_cb_failed = false;
 
     std::unique_ptr<Comm> comm;
+    std::unique_ptr<RelinPlan> relin;   // kkt_set_relinearisation (relin.hpp)
 
     KrylovCfg ksp;
     kkt_steplock steplock{};   // test hook (kkt_debug_set_steplock); n_steps == 0: off
@@ -268,6 +270,7 @@ struct System {
     void add_block(int q, int i, int j, int64_t nrows, int64_t ncols, const int32_t *indptr,
                    const int32_t *indices, const double *vals, int64_t share_id);
     void update_block_values(int q, int i, int j, const double *vals);
+    void give_private_values(int q, int i, int j, double *d_new);
     void set_bc(int k, int64_t n, const int32_t *idx, double alpha);
     void set_const_ns(int k, double alpha);
     void finalize();

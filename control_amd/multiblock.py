@@ -588,6 +588,35 @@ class MultiBlockSystem:
         U1 = _array_of(u_1, self._n1_loc, self._nx1)
         B0 = _array_of(b_0, self._n0_loc, self._nx0)
         B1 = _array_of(b_1, self._n1_loc, self._nx1)
+        cap = self._prepare_solve(sp, pc_fn)
+        b, pb = _lib.f64(self._join(B0, B1))
+        u, pu = _lib.f64(self._join(U0, U1))
+        hist = np.zeros(cap)
+        its, reason, nh, rnorm = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        rc = self._lib.kkt_solve(self._h, pb, pu, C.byref(its), C.byref(reason),
+                                 C.byref(rnorm), hist.ctypes.data_as(_lib.c_f64p), cap,
+                                 C.byref(nh))
+        result = self._finish_solve(sp, rc, its, reason, rnorm, hist, nh)
+        k = self._n0_loc * self._nx0
+        U0[:] = u[:k].reshape(U0.shape)
+        U1[:] = u[k:].reshape(U1.shape)
+        return result
+
+    def solve_device(self, d_b, d_u, *, solver_parameters=None, pc_fn=None):
+        """``solve`` on device vectors (``kkt_solve_device``): ``d_b`` and ``d_u`` are local
+        vectors of this handle (``kkt_vec_alloc``); ``d_u`` holds the initial guess on entry and
+        the solution on return."""
+        sp = {} if solver_parameters is None else solver_parameters
+        cap = self._prepare_solve(sp, pc_fn)
+        hist = np.zeros(cap)
+        its, reason, nh, rnorm = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        rc = self._lib.kkt_solve_device(self._h, d_b, d_u, C.byref(its), C.byref(reason),
+                                        C.byref(rnorm), hist.ctypes.data_as(_lib.c_f64p), cap,
+                                        C.byref(nh))
+        return self._finish_solve(sp, rc, its, reason, rnorm, hist, nh)
+
+    def _prepare_solve(self, sp, pc_fn):
+        """Preconditioner and KSP options of a solve; returns the history capacity."""
         self._set_pc(pc_fn)
         ksp_type = sp.get("linear_solver", "fgmres")
         if ksp_type not in _KSP_TYPES:
@@ -600,14 +629,10 @@ class MultiBlockSystem:
             self._h, _KSP_TYPES[ksp_type], side, int(sp.get("gmres_restart", 30)),
             float(sp["relative_tolerance"]), float(sp["absolute_tolerance"]),
             -1.0 if divtol is None else float(divtol), max_it))
-        b, pb = _lib.f64(self._join(B0, B1))
-        u, pu = _lib.f64(self._join(U0, U1))
-        cap = max_it + 4 + max_it // max(1, int(sp.get("gmres_restart", 30)))
-        hist = np.zeros(cap)
-        its, reason, nh, rnorm = C.c_int(), C.c_int(), C.c_int(), C.c_double()
-        rc = self._lib.kkt_solve(self._h, pb, pu, C.byref(its), C.byref(reason),
-                                 C.byref(rnorm), hist.ctypes.data_as(_lib.c_f64p), cap,
-                                 C.byref(nh))
+        return max_it + 4 + max_it // max(1, int(sp.get("gmres_restart", 30)))
+
+    def _finish_solve(self, sp, rc, its, reason, rnorm, hist, nh):
+        cap = len(hist)
         if rc == -4:
             raise RuntimeError("Error encountered in PETSc solve")
         self._ck(rc)
@@ -618,7 +643,4 @@ class MultiBlockSystem:
                 print(f"KSP: iteration {it:d}, residual norm {r_norm:.16e}")
         if not sp.get("preconditioner", False) and reason.value <= 0:
             raise RuntimeError("Solver failed to converge")
-        k = self._n0_loc * self._nx0
-        U0[:] = u[:k].reshape(U0.shape)
-        U1[:] = u[k:].reshape(U1.shape)
         return KSPResult(reason.value, its.value, rnorm.value, history, self.info())

@@ -20,6 +20,7 @@ as in the lid-driven cavity of ``test/test_control.py:4171-4268``.
 """
 from __future__ import annotations
 
+import time
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -165,13 +166,30 @@ class GpuLinearSolver:
 
     def __init__(self, pb: NavierStokesControl, *, mass=(20, 0.3924, 2.0598), schur=None,
                  kp=None, mp=(20, 0.5, 2.0), solver_parameters=None, device=0, comm=None,
-                 host_allreduce=None, options=None, Multigrid=False):
+                 host_allreduce=None, options=None, Multigrid=False, relinearise="host"):
         """``comm`` (``control_amd.dist``): the three systems are time-sharded (BASELINE
         configs[4] names 8 GPUs) -- every rank runs the same Picard loop on the whole iterate
         (residual and re-linearisation are host work on replicated data, as cheap as in the
         reference), uploads the blocks of its own levels, solves for its shard of the update,
         and the shards are summed into the whole update with ``host_allreduce(array, op)``
-        (in place over ranks, op 0 = sum: e.g. ``GlooTransport.allreduce``)."""
+        (in place over ranks, op 0 = sum: e.g. ``GlooTransport.allreduce``).
+
+        ``relinearise="device"``: ``incompressible_non_linear_solve(..., device=True)`` keeps the
+        Picard iterate in HBM -- the first linear solve builds the three systems from host
+        blocks as before, every later re-linearisation re-assembles the convection blocks, the
+        residual and the update on the GPU (``control_amd.relinearise``).  Needs the element
+        data of ``fem.rectangle_p2p1`` and a single GPU."""
+        if relinearise not in ("host", "device"):
+            raise ValueError("relinearise must be 'host' or 'device'")
+        if relinearise == "device":
+            if comm is not None:
+                raise ValueError("relinearise='device' does not support time-sharded solvers")
+            if getattr(pb.disc, "elem", None) is None:
+                raise ValueError("relinearise='device' needs a discretisation with element data "
+                                 "(fem.rectangle_p2p1)")
+        self.relinearise = relinearise
+        self._device = None             # control_amd.relinearise.DeviceRelinearisation
+        self.solve_times = []           # (start, end) perf_counter of every linearised solve
         self.pb, self.device = pb, device
         from .control import GpuBackend
         self.options = options          # execution options of the three systems (kkt_set_option)
@@ -268,8 +286,10 @@ class GpuLinearSolver:
         u_0 = np.zeros_like(b_0)
         u_1 = np.zeros_like(b_1)
         if self.dist is None:
+            t0 = time.perf_counter()
             ksp = self.outer.solve(u_0, u_1, b_0, b_1, solver_parameters=self.solver_parameters,
                                    pc_fn=self.pc)
+            self.solve_times.append((t0, time.perf_counter()))
             return u_0, u_1, ksp.getIterationNumber()
         # this rank's levels of both block families of a variable: rows [lo, hi) and m + [lo, hi)
         m, lo, hi = bl["m"], self.inner._lo, self.inner._hi
@@ -285,22 +305,109 @@ class GpuLinearSolver:
         return u_0, u_1, ksp.getIterationNumber()
 
 
+    # -- the device loop (relinearise="device")
+    def device_plan(self):
+        """The re-linearisation plan on the outer system (built after the first solve)."""
+        if self._device is None:
+            from .blocks import instationary_relinearisation_recipes
+            from .relinearise import DeviceRelinearisation
+            pb = self.pb
+            recipes = instationary_relinearisation_recipes(pb.tau, pb.beta, pb.n_t, pb.CN)
+            self._device = DeviceRelinearisation(pb, self.outer, recipes)
+        return self._device
+
+    def device_relinearise(self):
+        """Rewrite the linearised blocks of the outer, inner and commutator systems from the
+        plan's last assembly (``_update`` of the host path)."""
+        dev = self.device_plan()
+        dev.relinearise(self.outer, "outer")
+        dev.relinearise(self.inner, "inner")
+        dev.relinearise(self.comm, "commutator")
+
+    def device_solve(self, d_b, d_u):
+        t0 = time.perf_counter()
+        ksp = self.outer.solve_device(d_b, d_u, solver_parameters=self.solver_parameters,
+                                      pc_fn=self.pc)
+        self.solve_times.append((t0, time.perf_counter()))
+        return ksp.getIterationNumber()
+
+
+def _device_non_linear_solve(pb, ls, v, zeta, p, mu, max_non_linear_iter, rtol, atol,
+                             print_error_non_linear):
+    """``incompressible_non_linear_solve`` with the iterate in HBM: per iteration one assembly
+    of the convection blocks, one residual (the host reads its norm), one linearised solve and
+    one update, all on the device."""
+    import ctypes as C
+    th, n_t = pb.disc, pb.n_t
+    fresh = ls.outer is None
+    if fresh:                # the first call builds the systems from host blocks, as before
+        ls._build(ls._blocks([pb.D_v(v[i]) for i in range(n_t)],
+                             [pb.D_p(v[i]) for i in range(n_t)]))
+    dev = ls.device_plan()
+    dev.set_state(v, zeta, p, mu)
+    lib, outer = ls.outer._lib, ls.outer
+    d_b, d_u = C.c_void_p(), C.c_void_p()
+    outer._ck(lib.kkt_vec_alloc(outer.handle, C.byref(d_b)))
+    try:
+        outer._ck(lib.kkt_vec_alloc(outer.handle, C.byref(d_u)))   # zeroed
+        dev.assemble()
+        norm_0 = dev.residual(d_b, rhs=True)
+        norm_k = norm_0
+        norms, lin_its = [norm_0], []
+        if print_error_non_linear:
+            print(f"Initial non-linear residual: {norm_0:.16e}")
+        k = 0
+        while norm_k > rtol * norm_0 and norm_k > atol:
+            if not fresh:
+                ls.device_relinearise()
+            fresh = False
+            lin_its.append(ls.device_solve(d_b, d_u))
+            dev.update(d_u)
+            dev.assemble()
+            norm_k = dev.residual(d_b, rhs=True)
+            norms.append(norm_k)
+            k += 1
+            if print_error_non_linear:
+                print(f"Non-linear solver: iteration {k:d}, non-linear residual norm "
+                      f"{norm_k:.16e}")
+            if k + 1 > max_non_linear_iter:
+                break
+        v, zeta, p, mu = dev.get_state()
+    finally:
+        lib.kkt_vec_free(outer.handle, d_b)
+        if d_u:
+            lib.kkt_vec_free(outer.handle, d_u)
+    return dict(v=v, zeta=zeta, p=p, mu=mu, norms=norms, linear_iterations=lin_its,
+                converged=bool(norm_k <= rtol * norm_0 or norm_k <= atol))
+
+
 def incompressible_non_linear_solve(pb: NavierStokesControl, linear_solver=None, *,
                                     max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                                     absolute_non_linear_tol=1.0e-8, v=None, zeta=None, p=None,
-                                    mu=None, print_error_non_linear=True, Multigrid=False):
+                                    mu=None, print_error_non_linear=True, Multigrid=False,
+                                    device=False):
     """``control.py:4886-5232`` (BE).  ``linear_solver.linear_solve(D, Dp, b_0, b_1)`` returns
     the update ``(u_0, u_1, iterations)`` of the linearised system whose forward operator at
     time level ``i`` is ``D[i]`` (velocity space) / ``Dp[i]`` (pressure space).  ``None``: a
     ``GpuLinearSolver(pb, Multigrid=Multigrid)`` with its defaults.  ``Multigrid=True`` with a
     given solver requires one built with ``Multigrid=True``.
 
+    ``device=True``: the same loop with the iterate in HBM (residual, re-linearisation and
+    update on the GPU; the host reads one norm per iteration and the fields once at the end).
+    Needs a ``GpuLinearSolver(..., relinearise="device")`` (``None``: one is built).
+
     Returns a dict with the converged fields, the non-linear residual norms (``norm_0``
     first) and the linear iteration counts."""
+    if device and getattr(pb.disc, "elem", None) is None:
+        raise ValueError("device=True needs a discretisation with element data "
+                         "(fem.rectangle_p2p1)")
     if linear_solver is None:
-        linear_solver = GpuLinearSolver(pb, Multigrid=Multigrid)
+        linear_solver = GpuLinearSolver(pb, Multigrid=Multigrid,
+                                        relinearise="device" if device else "host")
     elif Multigrid and not getattr(linear_solver, "multigrid", False):
         raise ValueError("Multigrid=True: the linear solver was not built with Multigrid=True")
+    if device and getattr(linear_solver, "relinearise", None) != "device":
+        raise ValueError("device=True needs a GpuLinearSolver built with relinearise='device'")
     th, n_t, tau = pb.disc, pb.n_t, pb.tau
     m = n_t - 1 if pb.CN else n_t
     v = np.zeros((n_t, th.n_v)) if v is None else np.array(v, dtype=np.float64)
@@ -310,6 +417,10 @@ def incompressible_non_linear_solve(pb: NavierStokesControl, linear_solver=None,
     if pb.CN:
         v[0] = np.zeros(th.n_v) if pb.v_0 is None else pb.v_0   # :4961-4962
     zeta[n_t - 1] = 0.0                                          # :4963
+    if device:
+        return _device_non_linear_solve(pb, linear_solver, v, zeta, p, mu, max_non_linear_iter,
+                                        relative_non_linear_tol, absolute_non_linear_tol,
+                                        print_error_non_linear)
 
     def evaluate():
         D = [pb.D_v(v[i]) for i in range(n_t)]

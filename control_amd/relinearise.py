@@ -1,0 +1,192 @@
+"""Picard re-linearisation on the device (``kkt_set_relinearisation``).
+
+Host side: the plan of a Taylor-Hood P2-P1 discretisation (``fem.rectangle_p2p1``) --
+element tables, the contribution lists that make the device assembly deterministic, transpose
+permutations, the data rows of the residual -- and a thin binding of the device entry points.
+The lists are CSR over stored positions: position ``k`` of the scalar P2 (P1) pattern sums the
+flat element entries ``clist[cptr[k]:cptr[k + 1]]`` in that (ascending) order, which is the order
+in which ``np.bincount`` sums them in ``fem.TaylorHoodDiscretisation.convection_v_data``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import scipy.sparse as sp
+
+from . import _lib
+from .fem import _row_positions
+
+__all__ = ["contribution_lists", "gather", "transpose_permutation", "RelinearisationPlan",
+           "DeviceRelinearisation"]
+
+
+def contribution_lists(conn, pattern):
+    """``(cptr, clist)`` of the element matrices over connectivity ``conn`` (ne x k) on the
+    sorted CSR ``pattern``: flat entry ``e k^2 + a k + b`` (row ``conn[e, a]``, column
+    ``conn[e, b]``) contributes to the position of that pair."""
+    conn = np.asarray(conn)
+    k = conn.shape[1]
+    rows = np.repeat(conn, k, axis=1).ravel()
+    cols = np.tile(conn, (1, k)).ravel()
+    pos = pattern.indptr[rows].astype(np.int64) + _row_positions(pattern, rows, cols)
+    clist = np.argsort(pos, kind="stable").astype(np.int32)     # ascending within a position
+    cptr = np.zeros(pattern.nnz + 1, dtype=np.int32)
+    cptr[1:] = np.cumsum(np.bincount(pos, minlength=pattern.nnz))
+    return cptr, clist
+
+
+def gather(E, cptr, clist):
+    """Reference gather: position ``k`` = the sum of ``E.ravel()[clist[cptr[k]:cptr[k + 1]]]``
+    from 0.0, term by term in list order (what the device kernel does)."""
+    E = np.ravel(E)
+    counts = np.diff(cptr)
+    out = np.zeros(len(counts))
+    for t in range(int(counts.max()) if len(counts) else 0):
+        has = counts > t
+        out[has] += E[clist[cptr[:-1][has] + t]]
+    return out
+
+
+def transpose_permutation(A):
+    """``perm[k]``: the position of the transposed entry of position ``k`` of a structurally
+    symmetric sorted CSR matrix (``A^T.data = A.data[perm]``)."""
+    A = sp.csr_matrix(A)
+    n = A.nnz
+    T = sp.csr_matrix((np.arange(1, n + 1, dtype=np.float64), A.indices, A.indptr),
+                      shape=A.shape).T.tocsr()
+    T.sort_indices()
+    if not (T.nnz == n and np.array_equal(T.indptr, A.indptr)
+            and np.array_equal(T.indices, A.indices)):
+        raise ValueError("the pattern is not structurally symmetric")
+    return (T.data.astype(np.int64) - 1).astype(np.int32)
+
+
+class RelinearisationPlan:
+    """Everything ``kkt_set_relinearisation`` uploads, built once per problem on the host."""
+
+    def __init__(self, pb):
+        from .picard import non_linear_res_eval
+        th = pb.disc
+        if getattr(th, "elem", None) is None:
+            raise ValueError("device re-linearisation needs the element data of "
+                             "fem.rectangle_p2p1")
+        e = th.elem
+        n2 = th.n_v // 2
+        K2 = th.K_v[:n2, :n2].tocsr()
+        K2.sort_indices()
+        M2 = th.M_v[:n2, :n2].tocsr()
+        M2.sort_indices()
+        if not (np.array_equal(M2.indptr, K2.indptr) and np.array_equal(M2.indices, K2.indices)):
+            raise ValueError("M_v and K_v must share one sparsity structure")
+        Kp, Mp = sp.csr_matrix(th.K_p), sp.csr_matrix(th.M_p)
+        if not (np.array_equal(Mp.indptr, Kp.indptr) and np.array_equal(Mp.indices, Kp.indices)):
+            raise ValueError("M_p and K_p must share one sparsity structure")
+        self.pb, self.n2, self.K2, self.M2, self.Kp, self.Mp = pb, n2, K2, M2, Kp, Mp
+        self.V = np.ascontiguousarray(e["V"], dtype=np.int32)
+        self.P = np.ascontiguousarray(e["P"], dtype=np.int32)
+        self.tables = {k: np.ascontiguousarray(e[k], dtype=np.float64)
+                       for k in ("W", "phi", "gphi", "lam", "glam")}
+        self.v_lists = contribution_lists(self.V, K2)
+        self.p_lists = contribution_lists(self.P, Kp)
+        self.v_tperm = transpose_permutation(K2)
+        self.p_tperm = transpose_permutation(Kp)
+        self.B = sp.csr_matrix(th.B)
+        self.B.sort_indices()
+        m = pb.n_t - 1 if pb.CN else pb.n_t
+        self.m = m
+        z = np.zeros((pb.n_t, th.n_v))
+        r00, r01, _, _ = non_linear_res_eval(pb, [th.K_v] * pb.n_t, z, z.copy(),
+                                             np.zeros((m, th.n_p)), np.zeros((m, th.n_p)))
+        self.data = np.ascontiguousarray(np.concatenate([r00, r01]))
+
+    def descriptor(self):
+        """``kkt_relin_desc`` over this plan's arrays (valid while the plan lives)."""
+        pb, th, t = self.pb, self.pb.disc, self.tables
+        keep = []
+
+        def i32(a):
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            keep.append(a)
+            return a.ctypes.data_as(_lib.c_i32p)
+
+        def f64(a):
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            keep.append(a)
+            return a.ctypes.data_as(_lib.c_f64p)
+        d = _lib.RelinDesc(
+            n_t=pb.n_t, cn=int(bool(pb.CN)), nq=t["W"].shape[1], ne=len(self.V), n2=self.n2,
+            n1=th.n_p, nu=float(pb.nu), tau=float(pb.tau), beta=float(pb.beta), V=i32(self.V),
+            W=f64(t["W"]), phi=f64(t["phi"]), gphi=f64(t["gphi"]), lam=f64(t["lam"]),
+            glam=f64(t["glam"]), nnz2=self.K2.nnz, v_indptr=i32(self.K2.indptr),
+            v_indices=i32(self.K2.indices), v_tperm=i32(self.v_tperm),
+            v_cptr=i32(self.v_lists[0]), v_clist=i32(self.v_lists[1]), K2=f64(self.K2.data),
+            M2=f64(self.M2.data), nnz1=self.Kp.nnz, p_indptr=i32(self.Kp.indptr),
+            p_indices=i32(self.Kp.indices), p_tperm=i32(self.p_tperm),
+            p_cptr=i32(self.p_lists[0]), p_clist=i32(self.p_lists[1]), Kp=f64(self.Kp.data),
+            Mp=f64(self.Mp.data), nnz_b=self.B.nnz, b_indptr=i32(self.B.indptr),
+            b_indices=i32(self.B.indices), b_values=f64(self.B.data),
+            n_bc=len(th.boundary_v), bc_idx=i32(th.boundary_v), data=f64(self.data))
+        return d, keep
+
+
+def _recipe_array(recipes, space):
+    arr = (_lib.RelinRecipe * max(1, len(recipes)))()
+    for k, (q, i, j, level, alpha, transpose, gamma) in enumerate(recipes):
+        arr[k] = _lib.RelinRecipe(quadrant=q, i=i, j=j, space=space, level=level,
+                                  transpose=int(bool(transpose)), alpha=alpha, gamma=gamma)
+    return arr
+
+
+class DeviceRelinearisation:
+    """The plan on the outer system of a ``GpuLinearSolver`` and the Picard iterate in HBM."""
+
+    def __init__(self, pb, outer, recipes, plan=None):
+        self.pb, self.outer = pb, outer
+        self.plan = RelinearisationPlan(pb) if plan is None else plan
+        self._lib = outer._lib
+        d, keep = self.plan.descriptor()
+        outer._ck(self._lib.kkt_set_relinearisation(outer.handle, C.byref(d)))
+        del keep
+        self.recipes = {name: (_recipe_array(recipes[name], 1 if name == "commutator" else 0),
+                               len(recipes[name])) for name in ("outer", "inner", "commutator")}
+        ptr = [C.c_void_p() for _ in range(4)]
+        outer._ck(self._lib.kkt_picard_iterate(outer.handle, *[C.byref(p) for p in ptr]))
+        self.d_v = ptr[0]
+
+    def set_state(self, v, zeta, p, mu):
+        th, n_t, m = self.pb.disc, self.pb.n_t, self.plan.m
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (v, zeta, p, mu)]
+        for a, shape in zip(arrs, ((n_t, th.n_v), (n_t, th.n_v), (m, th.n_p), (m, th.n_p))):
+            if a.shape != shape:
+                raise ValueError(f"iterate block of shape {a.shape}, expected {shape}")
+        self.outer._ck(self._lib.kkt_picard_state(self.outer.handle, 0,
+                                                  *[a.ctypes.data_as(_lib.c_f64p) for a in arrs]))
+
+    def get_state(self):
+        th, pb, m = self.pb.disc, self.pb, self.plan.m
+        out = [np.empty((pb.n_t, th.n_v)), np.empty((pb.n_t, th.n_v)), np.empty((m, th.n_p)),
+               np.empty((m, th.n_p))]
+        self.outer._ck(self._lib.kkt_picard_state(self.outer.handle, 1,
+                                                  *[a.ctypes.data_as(_lib.c_f64p) for a in out]))
+        return out
+
+    def assemble(self):
+        """D_v, D_p of every level at the device iterate's v."""
+        self.outer._ck(self._lib.kkt_relinearise_device(self.outer.handle, self.outer.handle,
+                                                        self.d_v, 0, None))
+
+    def relinearise(self, system, name):
+        """Rewrite ``system``'s recipe blocks (``name``: "outer", "inner" or "commutator") from
+        the last assembly."""
+        arr, n = self.recipes[name]
+        system._ck(self._lib.kkt_relinearise_device(system.handle, self.outer.handle, None, n, arr))
+
+    def residual(self, d_out, rhs):
+        norm = C.c_double()
+        self.outer._ck(self._lib.kkt_picard_residual_device(self.outer.handle, d_out, int(rhs),
+                                                            C.byref(norm)))
+        return norm.value
+
+    def update(self, d_u):
+        self.outer._ck(self._lib.kkt_picard_update_device(self.outer.handle, d_u))

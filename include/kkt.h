@@ -329,6 +329,91 @@ int kkt_solve_device(kkt_handle h, const double *d_b, double *d_u,
                      double *hist, int hist_cap, int *hist_len);
 int kkt_sync(kkt_handle h);
 
+/* ------------------------------------------- Picard re-linearisation on the device */
+
+/* The Navier-Stokes Picard loop of Instationary.incompressible_non_linear_solve
+ * (control.py:4886-5232) with its iterate in HBM: the convection blocks are re-assembled from
+ * the device iterate (construct_D_v, control.py:1887-1896 on the velocity space, 3779-3785 on
+ * the pressure space), the non-linear residual is evaluated there (control.py:2442-2620 and
+ * 4976-5082) and the update is added in place.  Taylor-Hood P2-P1 triangles, Radon's 7-point
+ * rule (control_amd/fem.py rectangle_p2p1: the arrays of its `elem` dict).  Not for
+ * time-sharded handles.
+ *
+ * The plan lives on the handle it is set on, which must be the outer incompressible system of
+ * the loop: n_blocks_00 = n_blocks_11 = 2m (m = n_t, CN: n_t - 1), nx0 = 2 n2, nx1 = n1.
+ * Scalar P2 pattern: the structure of one velocity component of K_v / M_v (sorted CSR; the
+ * velocity blocks carry it once per component, component-major); P1 pattern: K_p / M_p.
+ * Both must be structurally symmetric: *_tperm[k] is the position of the transposed entry of
+ * position k.  Contribution lists: for stored position k, the flat element-entry indices
+ * (e * 36 + 6 a + b for the P2 element matrix rows a / columns b, e * 9 + 3 c + d for P1) in
+ * *_clist[*_cptr[k] .. *_cptr[k + 1]), ascending; the assembly sums them in that order, the
+ * order of np.bincount on the host, so it is deterministic (no atomics).  D = nu K + C(w) per
+ * level.  B: the divergence block (n1 x 2 n2, sorted CSR).  data: the 2m x 2 n2 velocity rows
+ * of the residual at the zero iterate (desired state, forces, the initial condition); bc_idx:
+ * Dirichlet velocity dofs.  Arrays are copied; KKT_ERR_ARG on sizes, ranges or patterns that do
+ * not fit. */
+typedef struct kkt_relin_desc {
+    int n_t, cn, nq;              /* time levels, Crank-Nicolson (1) or backward Euler, nq = 7 */
+    int64_t ne, n2, n1;           /* triangles, P2 nodes (one component), P1 nodes */
+    double nu, tau, beta;
+    const int32_t *V;             /* ne x 6 P2 nodes per triangle */
+    const double *W;              /* ne x nq quadrature weights times |det J| */
+    const double *phi;            /* nq x 6 P2 basis at the points */
+    const double *gphi;           /* ne x nq x 6 x 2 their gradients */
+    const double *lam;            /* nq x 3 P1 basis (barycentric coordinates) */
+    const double *glam;           /* ne x 3 x 2 their gradients */
+    int64_t nnz2;                 /* scalar P2 pattern */
+    const int32_t *v_indptr, *v_indices, *v_tperm, *v_cptr, *v_clist;
+    const double *K2, *M2;        /* nnz2 values: grad-grad and mass of one component */
+    int64_t nnz1;                 /* P1 pattern */
+    const int32_t *p_indptr, *p_indices, *p_tperm, *p_cptr, *p_clist;
+    const double *Kp, *Mp;
+    int64_t nnz_b;
+    const int32_t *b_indptr, *b_indices;
+    const double *b_values;
+    int64_t n_bc;
+    const int32_t *bc_idx;
+    const double *data;
+} kkt_relin_desc;
+int kkt_set_relinearisation(kkt_handle h, const kkt_relin_desc *desc);
+
+/* One block a recipe rewrites: block (quadrant; i, j) = alpha D_level(^T) + gamma M, with D, M
+ * on the velocity (space 0, both components) or pressure (space 1) pattern -- the `comb`
+ * coefficients of blocks.instationary_blocks (control.py:2889-2978, 3851-3885). */
+typedef struct kkt_relin_recipe {
+    int quadrant, i, j;
+    int space;
+    int level;
+    int transpose;
+    double alpha, gamma;
+} kkt_relin_recipe;
+/* Rewrites the recipes' blocks of handle h from the plan on handle `plan`.  d_v (device,
+ * n_t x 2 n2, component-major levels) != NULL first re-assembles D at that velocity; NULL
+ * composes from the last assembly (so the outer, inner and commutator handles of one
+ * linearisation share one).  n = 0 only assembles.  The blocks are written on the device as
+ * kkt_update_block_values would write them (Dirichlet columns zeroed, a value array shared with
+ * other blocks is first made private) and a built-in preconditioner is marked stale.  The
+ * target pattern must be the plan's. */
+int kkt_relinearise_device(kkt_handle h, kkt_handle plan, const double *d_v, int n,
+                           const kkt_relin_recipe *recipes);
+/* The plan's iterate (v, zeta: n_t x 2 n2; p, mu: m x n1) in HBM: host copies in (download 0)
+ * or out (download 1), and its device addresses (any out pointer may be NULL). */
+int kkt_picard_state(kkt_handle plan, int download, double *v, double *zeta, double *p,
+                     double *mu);
+int kkt_picard_iterate(kkt_handle plan, double **d_v, double **d_zeta, double **d_p,
+                       double **d_mu);
+/* Non-linear residual at the plan's iterate, with D of the last assembly (assemble at the
+ * iterate's v first).  rhs = 0: d_out (one local vector of the plan's handle) receives the
+ * residual rows [r00, r01, r10, r11] of picard.non_linear_res_eval, Dirichlet rows zero;
+ * rhs = 1: the right-hand side of the linearised solve (pressure rows times tau, CN: T_1 / T_2,
+ * control.py:4266-4269).  *norm (host) = ||[r00, r01, r10, r11]||_2 by the deterministic
+ * reduction. */
+int kkt_picard_residual_device(kkt_handle plan, double *d_out, int rhs, double *norm);
+/* v, zeta, mu, p += the blocks of the update d_u (one local vector; CN: v from level 1);
+ * then zeta = 0 on the Dirichlet dofs of every level (control.py:5127-5147).  d_u is zeroed:
+ * the initial guess of the next linearised solve. */
+int kkt_picard_update_device(kkt_handle plan, double *d_u);
+
 /* `reps` back-to-back kkt_apply_device / kkt_pc_apply_device launches timed with HIP
  * events on the library's own stream; *ms = total elapsed milliseconds. */
 int kkt_time_apply(kkt_handle h, const double *d_x, double *d_y, int reps, float *ms);
