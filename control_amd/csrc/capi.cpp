@@ -253,12 +253,6 @@ int kkt_set_krylov(kkt_handle h, int type, int pc_side, int restart, double rtol
 
 // ---- host-array variants: stage through temporary device vectors
 namespace {
-struct TmpVec {
-    System &S;
-    double *p;
-    explicit TmpVec(System &S_) : S(S_), p(S_.new_vec()) {}
-    ~TmpVec() { (void)hipFree(p); }
-};
 void up(System &S, double *d, const double *h) {
     HIPCHK(hipMemcpyAsync(d, h, S.n_local * 8, hipMemcpyHostToDevice, S.stream));
     HIPCHK(hipStreamSynchronize(S.stream));
@@ -273,10 +267,10 @@ int kkt_apply(kkt_handle h, const double *x, double *y) {
     KKT_TRY(h, {
         if (!x || !y) fail(KKT_ERR_ARG, "null vector");
         if (!S.finalized) fail(KKT_ERR_STATE, "system not finalized");
-        TmpVec dx(S), dy(S);
-        up(S, dx.p, x);
-        S.apply(dx.p, dy.p);
-        down(S, dy.p, y);
+        DevBuf<double> dx = S.new_vec(), dy = S.new_vec();
+        up(S, dx.get(), x);
+        S.apply(dx.get(), dy.get());
+        down(S, dy.get(), y);
     });
 }
 
@@ -284,9 +278,9 @@ int kkt_pc_apply(kkt_handle h, const double *x, double *y) {
     KKT_TRY(h, {
         if (!x || !y) fail(KKT_ERR_ARG, "null vector");
         if (!S.finalized) fail(KKT_ERR_STATE, "system not finalized");
-        TmpVec dx(S), dy(S);
-        up(S, dx.p, x);
-        S.pc_apply(dx.p, dy.p);
+        DevBuf<double> dx = S.new_vec(), dy = S.new_vec();
+        up(S, dx.get(), x);
+        S.pc_apply(dx.get(), dy.get());
         if (S.pc) {
             // a sweep program that timed out (on any rank of a time shard: the decision is
             // collective) is replaced by plain launches and the application redone (same
@@ -294,11 +288,11 @@ int kkt_pc_apply(kkt_handle h, const double *x, double *y) {
             std::string why;
             if (S.pc_timed_out_agreed(&why)) {
                 if (!S.pc_fallback_plain(why)) fail(KKT_ERR_HIP, why);
-                S.pc_apply(dx.p, dy.p);
+                S.pc_apply(dx.get(), dy.get());
                 if (S.pc_timed_out_agreed(&why)) fail(KKT_ERR_HIP, why);
             }
         }
-        down(S, dy.p, y);
+        down(S, dy.get(), y);
         if (S.pc_cb_failed) {
             S.pc_cb_failed = false;
             fail(KKT_ERR_CALLBACK, "Error encountered in preconditioner callback");
@@ -311,11 +305,11 @@ int kkt_solve(kkt_handle h, const double *b, double *u, int *its, int *reason, d
     KKT_TRY(h, {
         if (!b || !u) fail(KKT_ERR_ARG, "null vector");
         if (!S.finalized) fail(KKT_ERR_STATE, "system not finalized");
-        TmpVec db(S), du(S);
-        up(S, db.p, b);
-        up(S, du.p, u);
-        S.solve(db.p, du.p, its, reason, rnorm, hist, hist_cap, hist_len);
-        down(S, du.p, u);
+        DevBuf<double> db = S.new_vec(), du = S.new_vec();
+        up(S, db.get(), b);
+        up(S, du.get(), u);
+        S.solve(db.get(), du.get(), its, reason, rnorm, hist, hist_cap, hist_len);
+        down(S, du.get(), u);
     });
 }
 
@@ -326,7 +320,7 @@ int kkt_vec_alloc(kkt_handle h, double **d_vec) {
     KKT_TRY(h, {
         if (!d_vec) fail(KKT_ERR_ARG, "null out pointer");
         if (!S.finalized) fail(KKT_ERR_STATE, "system not finalized");
-        *d_vec = S.new_vec();
+        *d_vec = S.new_vec().release();   // the caller owns it (kkt_vec_free)
         S.sync();
     });
 }

@@ -131,18 +131,17 @@ void nccl_check(int r, const char *what) {
 
 class RcclComm : public Comm {
     ncclComm_p comm_ = nullptr;
-    double *d_scalar_ = nullptr;
+    DevBuf<double> scalar_;
 
    public:
     RcclComm(int rank, int world, const void *uid) {
         ncclUniqueIdT id;
         memcpy(&id, uid, sizeof id);
         nccl_check(rccl().CommInitRank(&comm_, world, id, rank), "ncclCommInitRank");
-        d_scalar_ = dev_alloc<double>(1);
+        scalar_ = DevBuf<double>::alloc(1);
     }
     ~RcclComm() override {
         if (comm_) rccl().CommDestroy(comm_);
-        if (d_scalar_) (void)hipFree(d_scalar_);
     }
     void allreduce_sum(double *d_buf, int n, hipStream_t s) override {
         nccl_check(rccl().AllReduce(d_buf, d_buf, (size_t)n, NCCL_FLOAT64, NCCL_SUM, comm_, s),
@@ -158,16 +157,16 @@ class RcclComm : public Comm {
         nccl_check(rccl().GroupEnd(), "ncclGroupEnd");
     }
     void barrier(hipStream_t s) override {
-        HIPCHK(hipMemsetAsync(d_scalar_, 0, sizeof(double), s));
-        allreduce_sum(d_scalar_, 1, s);
+        HIPCHK(hipMemsetAsync(scalar_.get(), 0, sizeof(double), s));
+        allreduce_sum(scalar_.get(), 1, s);
         HIPCHK(hipStreamSynchronize(s));
     }
     double max_host(double v, hipStream_t s) override {
-        HIPCHK(hipMemcpyAsync(d_scalar_, &v, sizeof v, hipMemcpyHostToDevice, s));
-        nccl_check(rccl().AllReduce(d_scalar_, d_scalar_, 1, NCCL_FLOAT64, NCCL_MAX, comm_, s),
+        HIPCHK(hipMemcpyAsync(scalar_.get(), &v, sizeof v, hipMemcpyHostToDevice, s));
+        nccl_check(rccl().AllReduce(scalar_.get(), scalar_.get(), 1, NCCL_FLOAT64, NCCL_MAX, comm_, s),
                    "ncclAllReduce(max)");
         double out = 0.0;
-        HIPCHK(hipMemcpyAsync(&out, d_scalar_, sizeof out, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&out, scalar_.get(), sizeof out, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return out;
     }
@@ -212,7 +211,7 @@ void comm_exchange_x_halos2(System &S, const double *d_x) {
                     S.halo2_used[v][f][side] = m > 0.5;
                     if (S.halo2_used[v][f][side] && !S.d_halo2[v][f][side]) {
                         const int64_t nxh = v == 0 ? S.nx0 : S.nx1;
-                        S.d_halo2[v][f][side] = dev_alloc<double>(nxh);
+                        S.d_halo2[v][f][side] = S.mem.alloc<double>(nxh);
                         HIPCHK(hipMemset(S.d_halo2[v][f][side], 0, nxh * 8));
                     }
                 }

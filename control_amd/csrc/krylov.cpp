@@ -41,26 +41,20 @@ void System::norm2(const double *w, double *d_out) {
 
 void System::ensure_workspace(int restart, bool flexible) {
     if (d_V && ws_restart >= restart && (ws_flexible || !flexible)) return;
-    auto F = [](double *&p) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    };
-    F(d_V);
-    F(d_Z);
-    d_V = dev_alloc<double>((size_t)(restart + 1) * vec_stride);
+    ws_mem.release();
+    d_V = d_Z = d_hcol = d_coef = nullptr;
+    d_V = ws_mem.alloc<double>((size_t)(restart + 1) * vec_stride);
     HIPCHK(hipMemsetAsync(d_V, 0, (size_t)(restart + 1) * vec_stride * 8, stream));
     if (flexible) {
-        d_Z = dev_alloc<double>((size_t)restart * vec_stride);
+        d_Z = ws_mem.alloc<double>((size_t)restart * vec_stride);
         HIPCHK(hipMemsetAsync(d_Z, 0, (size_t)restart * vec_stride * 8, stream));
     }
-    if (!d_t1) d_t1 = new_vec();
-    if (!d_t2) d_t2 = new_vec();
-    if (!d_rhs) d_rhs = new_vec();
-    if (!d_red_scratch) d_red_scratch = dev_alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX);
-    F(d_hcol);
-    F(d_coef);
-    d_hcol = dev_alloc<double>(restart + 16);
-    d_coef = dev_alloc<double>(restart + 16);
+    if (!d_t1) d_t1 = mem.adopt(new_vec());
+    if (!d_t2) d_t2 = mem.adopt(new_vec());
+    if (!d_rhs) d_rhs = mem.adopt(new_vec());
+    if (!d_red_scratch) d_red_scratch = mem.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX);
+    d_hcol = ws_mem.alloc<double>(restart + 16);
+    d_coef = ws_mem.alloc<double>(restart + 16);
     if (h_pinned) (void)hipHostFree(h_pinned);
     HIPCHK(hipHostMalloc((void **)&h_pinned, (restart + 16) * sizeof(double), 0));
     ws_restart = restart;
@@ -104,8 +98,8 @@ void System::pc_apply(const double *d_x, double *d_y) {
         in = pc->in();
         out = pc->out();
     } else {
-        if (!d_pc_in) d_pc_in = new_vec();
-        if (!d_pc_out) d_pc_out = new_vec();
+        if (!d_pc_in) d_pc_in = mem.adopt(new_vec());
+        if (!d_pc_out) d_pc_out = mem.adopt(new_vec());
         in = d_pc_in;
         out = d_pc_out;
     }
@@ -343,7 +337,7 @@ void System::solve(const double *d_b, double *d_u, int *its_out, int *reason_out
     if (!finalized) fail(KKT_ERR_STATE, "system not finalized");
     double *u0 = nullptr;
     if (pc) {
-        if (!d_guess) d_guess = new_vec();
+        if (!d_guess) d_guess = mem.adopt(new_vec());
         u0 = d_guess;
         launch_copy(stream, u0, d_u, n_local);
     }

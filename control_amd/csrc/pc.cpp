@@ -70,32 +70,15 @@ SchurPC::SchurPC(System &S, const kkt_pc_desc &d) : S_(S), d_(d) {
 }
 
 SchurPC::~SchurPC() {
-    clear_program();
-    tile_plan_.release();
+    segments_.clear();   // the graphs before the events and the stream they were captured on
     for (hipEvent_t e : events_) (void)hipEventDestroy(e);
     if (side_) (void)hipStreamDestroy(side_);
-    for (void *p : owned_)
-        if (p) (void)hipFree(p);
-    for (double *p : einv_owned_) (void)hipFree(p);
 }
 
 void SchurPC::clear_program() {
-    for (Segment &g : segments_) {
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        if (g.graph) (void)hipGraphDestroy(g.graph);
-    }
-    segments_.clear();
-    for (auto &s : steps_)
-        if ((s.kind == PcStep::ROWS || s.kind == PcStep::PROG) && s.rows.d_ops)
-            (void)hipFree(s.rows.d_ops);
-    for (auto &s : steps_)
-        if (s.d_il) (void)hipFree(s.d_il);
-    for (auto &s : steps_)
-        if (s.d_lite) (void)hipFree(s.d_lite);
-    for (auto &s : steps_)
-        if (s.d_levels) (void)hipFree(s.d_levels);
-    for (void *p : tile_owned_) (void)hipFree(p);
-    tile_owned_.clear();
+    segments_.clear();   // the graphs first: their nodes point into the program's memory
+    program_mem_.release();
+    il_cap_ = 0;
     sweep_levels_.clear();
     steps_.clear();
     n_events_ = 0;
@@ -122,15 +105,11 @@ void SchurPC::emit_wait(int lane, int ev) {
 void SchurPC::values_changed() {
     // Schur matrices are sums with block values: rebuild them and the program
     clear_program();
-    for (auto &kv : mats_) {
-        (void)hipFree(kv.second.vals);
-        (void)hipFree(kv.second.dinv);
-    }
+    values_mem_.release();
     mats_.clear();
     mat_recs_.clear();
     solve_recs_.clear();
-    for (double *p : einv_owned_) (void)hipFree(p);
-    einv_owned_.clear();
+    einvs_.clear();
     pending_coarse_.clear();
     if (d_.kind == KKT_PC_STATIONARY)
         build_stationary();
@@ -278,10 +257,8 @@ bool SchurPC::setup_row_programs() {
             prog_granule_ = want;
             if (want) {
                 granule_words_ = 2 * (size_t)P.nslices * 64 * P.R;
-                d_g0_ = dev_alloc<unsigned long long>(granule_words_);
-                d_g1_ = dev_alloc<unsigned long long>(granule_words_);
-                owned_.push_back(d_g0_);
-                owned_.push_back(d_g1_);
+                d_g0_ = handle_mem_.alloc<unsigned long long>(granule_words_);
+                d_g1_ = handle_mem_.alloc<unsigned long long>(granule_words_);
             }
         }
         prog_wpw_ = wpw;
@@ -290,10 +267,8 @@ bool SchurPC::setup_row_programs() {
             std::fprintf(stderr, "[kkt] sweep program: mode %d (0 counters, 1 data-flow, 2 data-flow "
                          "any width), %d workgroups x %d waves, %d slices\n",
                          prog_mode_, nwg, wpw, P.nslices);
-        d_dep_ = dev_upload(dep.data(), dep.size());
-        d_flags_ = dev_alloc<unsigned>(prog_flag_words(nwg));
-        owned_.push_back(d_dep_);
-        owned_.push_back(d_flags_);
+        d_dep_ = handle_mem_.upload(dep.data(), dep.size());
+        d_flags_ = handle_mem_.alloc<unsigned>(prog_flag_words(nwg));
     }
     return true;
 }
@@ -395,12 +370,10 @@ bool SchurPC::prepare_tiles() {
             }
         }
     }
-    tp.upload();
+    tp.upload(handle_mem_);   // once per handle (tile_tried_)
     const size_t words = 2 * (size_t)P.nrows;
-    for (int i = 0; i < 4; ++i) {
-        d_tg_[i] = dev_alloc<unsigned long long>(words);
-        owned_.push_back(d_tg_[i]);
-    }
+    for (int i = 0; i < 4; ++i)
+        d_tg_[i] = handle_mem_.alloc<unsigned long long>(words);
     if (S_.opts.verbose)
         std::fprintf(stderr, "[kkt] tile sweep program: %d tiles x %d threads, depth %d, W %d, "
                      "%d row slots per thread; largest tile: %lld own rows, %lld computed rows, "
@@ -476,10 +449,9 @@ bool SchurPC::build_tile_coarse() {
         for (int32_t sl : contrib[j]) c_slot.push_back(sl);
         c_ip[j + 1] = (int32_t)c_slot.size();
     }
+    // handle memory: prepare_tiles() runs once per handle, and so does this
     auto up = [&](const auto &v) {
-        auto *p = dev_upload(v.data(), std::max<size_t>(1, v.size()));
-        owned_.push_back((void *)p);
-        return p;
+        return handle_mem_.upload(v.data(), std::max<size_t>(1, v.size()));
     };
     TileCoarseDev &D = h_tile_coarse_;
     D.nc = nc;
@@ -551,14 +523,13 @@ bool SchurPC::build_tile_coarse() {
         if (ew < nc) {
             // belt and braces: every inverse formed so far must be zero outside these ranges
             // (exact zeros: elimination never touches an entry outside a block); else full rows
-            unsigned *d_flag = dev_alloc<unsigned>(1);
-            HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(unsigned), S_.stream));
-            for (const double *inv : einv_owned_)
-                launch_einv_outside(S_.stream, inv, nc, D.e_lo, D.e_hi, d_flag);
+            auto d_flag = DevBuf<unsigned>::alloc(1);
+            HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(unsigned), S_.stream));
+            for (const double *inv : einvs_)
+                launch_einv_outside(S_.stream, inv, nc, D.e_lo, D.e_hi, d_flag.get());
             unsigned bad = 0;
-            HIPCHK(hipMemcpyAsync(&bad, d_flag, sizeof bad, hipMemcpyDeviceToHost, S_.stream));
+            HIPCHK(hipMemcpyAsync(&bad, d_flag.get(), sizeof bad, hipMemcpyDeviceToHost, S_.stream));
             HIPCHK(hipStreamSynchronize(S_.stream));
-            HIPCHK(hipFree(d_flag));
             if (bad) {
                 std::fprintf(stderr, "[kkt] coarse inverse: entries outside the diagonal blocks of its "
                              "structure -- the tile program applies full rows\n");
@@ -574,15 +545,12 @@ bool SchurPC::build_tile_coarse() {
                          "blocks of P^T A P)\n", ew, nc);
     }
     for (int i = 0; i < 2; ++i) {
-        D.cg[i] = dev_alloc<unsigned long long>((size_t)nslots * 2);
+        D.cg[i] = handle_mem_.alloc<unsigned long long>((size_t)nslots * 2);
         HIPCHK(hipMemset(D.cg[i], 0, D.cg_bytes));
-        owned_.push_back(D.cg[i]);
-        D.eg[i] = dev_alloc<unsigned long long>((size_t)nc * 2);
+        D.eg[i] = handle_mem_.alloc<unsigned long long>((size_t)nc * 2);
         HIPCHK(hipMemset(D.eg[i], 0, D.eg_bytes));
-        owned_.push_back(D.eg[i]);
     }
-    d_tile_coarse_ = dev_upload(&D, 1);
-    owned_.push_back(d_tile_coarse_);
+    d_tile_coarse_ = handle_mem_.upload(&D, 1);
     if (S_.opts.verbose)
         std::fprintf(stderr, "[kkt] tile sweep program, coarse corrections: %d coarse functions, at most "
                      "%d per tile, %d partial-sum slots\n", nc, jmax, nslots);
@@ -650,10 +618,7 @@ bool SchurPC::fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out) {
             if (run[j]->coef.size() == lv.coef.size() &&
                 std::memcmp(run[j]->coef.data(), lv.coef.data(), lv.coef.size() * sizeof(TileCoef)) == 0)
                 d_coef = const_cast<TileCoef *>(levels[j].coef);
-        if (!d_coef) {
-            d_coef = dev_upload(lv.coef.data(), lv.coef.size());
-            tile_owned_.push_back(d_coef);
-        }
+        if (!d_coef) d_coef = program_mem_.upload(lv.coef.data(), lv.coef.size());
         L.coef = d_coef;
         levels.push_back(L);
     }
@@ -669,12 +634,11 @@ bool SchurPC::fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out) {
         s.fused = fused;
         s.coarse = coarse;
         if (coarse) {
-            s.d_einv = dev_upload(einvs.data(), einvs.size());
-            tile_owned_.push_back((void *)s.d_einv);
+            s.d_einv = program_mem_.upload(einvs.data(), einvs.size());
             s.cepoch0 = tile_cepoch_cursor_;
             tile_cepoch_cursor_ += (uint32_t)(n * coarse_cycles_);
         }
-        s.d_levels = dev_upload(lv, (size_t)n);
+        s.d_levels = program_mem_.upload(lv, (size_t)n);
         s.nlevels = n;
         s.its = its;
         s.nphases = nphases;
@@ -689,7 +653,8 @@ bool SchurPC::fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out) {
     if (coarse && !tile_sweep_fuses_update(tile_plan_.W, max_terms)) return false;
     if (tile_sweep_fuses_update(tile_plan_.W, max_terms) &&
         !(tile_plan_.W > 9 && S_.opts.tile_unfused && !coarse)) {
-        for (size_t q = k; q < e; ++q) (void)hipFree(steps_[q].rows.d_ops);
+        // the RowOp arrays of the steps this launch replaces (a few hundred bytes per step) stay
+        // in the program's memory until the next clear_program()
         tile_step(levels.data(), (int)levels.size(), (int)(e - k), true);
         return true;
     }
@@ -709,7 +674,6 @@ bool SchurPC::fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out) {
             L.bin = lv.b_after;
             L.bout = nullptr;
         }
-        for (size_t q = first_cheb; q < lv.last; ++q) (void)hipFree(steps_[q].rows.d_ops);
         tile_step(&L, 1, (int)(lv.last - first_cheb), false);
     }
     return true;
@@ -721,9 +685,8 @@ bool SchurPC::fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out) {
 void SchurPC::fuse_programs() {
     if (!use_programs_) return;
     if (!d_err_) {
-        d_err_ = dev_alloc<unsigned>(64 + 16 * 1024);   // word 0: error bits; rest: diagnostics
+        d_err_ = handle_mem_.alloc<unsigned>(64 + 16 * 1024);   // word 0: error bits; rest: diagnostics
         HIPCHK(hipMemset(d_err_, 0, (64 + 16 * 1024) * sizeof(unsigned)));
-        owned_.push_back(d_err_);
     }
     const bool tile_wanted = S_.opts.prog_mode == ProgMode::Auto || S_.opts.prog_mode == ProgMode::Tile;
     const bool use_tiles = tile_wanted && prepare_tiles();
@@ -746,13 +709,11 @@ void SchurPC::fuse_programs() {
     // one row program for the single-block steps [q0, q1)
     auto emit_prog = [&](size_t q0, size_t q1) {
         std::vector<RowOp> ops;
-        for (size_t q = q0; q < q1; ++q) {
-            ops.push_back(steps_[q].rows.h_op);
-            (void)hipFree(steps_[q].rows.d_ops);
-        }
+        // (the replaced steps' own RowOp arrays stay in the program's memory, as above)
+        for (size_t q = q0; q < q1; ++q) ops.push_back(steps_[q].rows.h_op);
         PcStep s;
         s.kind = PcStep::PROG;
-        s.rows.d_ops = dev_upload(ops.data(), ops.size());
+        s.rows.d_ops = program_mem_.upload(ops.data(), ops.size());
         s.nphases = (int)ops.size();
         {
             // compact records: Chebyshev steps that only continue the previous phase's
@@ -791,7 +752,7 @@ void SchurPC::fuse_programs() {
                 }
                 lite[e2] = L;
             }
-            s.d_lite = dev_upload(lite.data(), lite.size());
+            s.d_lite = program_mem_.upload(lite.data(), lite.size());
         }
         s.granule = prog_granule_;
         s.gmode = prog_mode_;
@@ -1028,27 +989,22 @@ void SchurPC::build() {
     m_pat_ = S_.find_or_add_pattern(nx_, nx_, m_indptr_.data(), m_indices_.data());
     const Pattern &P = S_.patterns[m_pat_];
     {
-        double *d_csr = dev_upload(m_values_.data(), m_values_.size());
-        m_vals_ = dev_alloc<double>(P.npadded);
-        owned_.push_back(m_vals_);
-        launch_csr_to_sell(st, d_csr, P.d_sell2csr, m_vals_, P.npadded);
+        auto d_csr = DevBuf<double>::upload(m_values_.data(), m_values_.size());
+        m_vals_ = handle_mem_.alloc<double>(P.npadded);
+        launch_csr_to_sell(st, d_csr.get(), P.d_sell2csr, m_vals_, P.npadded);
         if (mask_) launch_mask_columns(st, m_vals_, P.d_col, mask_, P.npadded);
         HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipFree(d_csr));
     }
-    m_dinv_ = dev_alloc<double>(nx_);
-    owned_.push_back(m_dinv_);
+    m_dinv_ = handle_mem_.alloc<double>(nx_);
     launch_extract_dinv(st, P.d_col, P.d_slice_off, m_vals_, mask_, m_dinv_, (int)nx_, P.nslices,
                         P.R, P.d_perm);
     {
         std::vector<int32_t> z(P.nslices + 1, 0);
-        zero_off_ = dev_upload(z.data(), z.size());
-        owned_.push_back(zero_off_);
+        zero_off_ = handle_mem_.upload(z.data(), z.size());
     }
     auto vec = [&](int64_t blocks) {
-        double *p = dev_alloc<double>(blocks * nx_ + 32);
+        double *p = handle_mem_.alloc<double>(blocks * nx_ + 32);
         HIPCHK(hipMemsetAsync(p, 0, (blocks * nx_ + 32) * sizeof(double), st));
-        owned_.push_back(p);
         return p;
     };
     const int nl = hi_ - lo_;
@@ -1085,8 +1041,7 @@ const int32_t *SchurPC::transpose_positions() {
             t[(size_t)P.sell_index(r, q - P.h_indptr[r])] =
                 (int32_t)P.sell_index(c, (int)(hit - b));
         }
-    d_tpos_ = dev_upload(t.data(), t.size());
-    owned_.push_back(d_tpos_);
+    d_tpos_ = handle_mem_.upload(t.data(), t.size());   // built once per handle (tpos_tried_)
     return d_tpos_;
 }
 
@@ -1107,11 +1062,7 @@ void SchurPC::build_coarse() {
             pt_indices_[at] = (int32_t)r;
             pt_values_[at] = p_values_[q];
         }
-    auto up = [&](const auto &v) {
-        auto *p = dev_upload(v.data(), v.size());
-        owned_.push_back((void *)p);
-        return p;
-    };
+    auto up = [&](const auto &v) { return handle_mem_.upload(v.data(), v.size()); };
     coarse_.nc = nc;
     coarse_.p_ip = up(p_indptr_);
     coarse_.p_ix = up(p_indices_);
@@ -1134,10 +1085,8 @@ void SchurPC::build_coarse() {
         galerkin_.uniform_w = P.uniform_w;
         galerkin_.block_n = coarse_block_size(nc, e_ip, e_ix);
     }
-    coarse_.rc = dev_alloc<double>(nc);
-    coarse_.ec = dev_alloc<double>(nc);
-    owned_.push_back(coarse_.rc);
-    owned_.push_back(coarse_.ec);
+    coarse_.rc = handle_mem_.alloc<double>(nc);
+    coarse_.ec = handle_mem_.alloc<double>(nc);
 }
 
 int coarse_block_size(int nc, const std::vector<int32_t> &e_ip, const std::vector<int32_t> &e_ix) {
@@ -1202,7 +1151,8 @@ static int64_t coarse_columns(System &S, const Pattern &P, const CoarseDev &c, c
     hipStream_t st = S.stream;
     const int nc = c.nc;
     const int64_t n = P.nrows;
-    double *x = dev_alloc<double>(n + 32), *y = dev_alloc<double>(n + 32);
+    DevPool tmp;   // released on every way out
+    double *x = tmp.alloc<double>(n + 32), *y = tmp.alloc<double>(n + 32);
     RowOp op{};
     op.col = P.d_col;
     op.perm = P.d_perm;
@@ -1219,7 +1169,7 @@ static int64_t coarse_columns(System &S, const Pattern &P, const CoarseDev &c, c
     op.ca = 1.0;
     op.post1 = op.post2 = 1.0;
     op.rowmask = mask;
-    RowOp *d_op = dev_upload(&op, 1);
+    RowOp *d_op = tmp.upload(&op, 1);
     const Bases B{{nullptr, nullptr, nullptr, nullptr}};
     for (int k = 0; k < nc; ++k) {
         launch_coarse_column(st, c, k, x, n);
@@ -1239,13 +1189,11 @@ static int64_t coarse_columns(System &S, const Pattern &P, const CoarseDev &c, c
         launch_add_constant(st, E, tr / ((double)nc * (double)nc), (int64_t)nc * nc);
         launches += 1;
     }
-    int *d_piv = dev_alloc<int>(1);
-    double *d_colbuf = dev_alloc<double>(nc + 1);     // multipliers; slot nc: the pivot
+    int *d_piv = tmp.alloc<int>(1);
+    double *d_colbuf = tmp.alloc<double>(nc + 1);     // multipliers; slot nc: the pivot
     launch_dense_inverse(st, E, einv, nc, d_piv, d_colbuf, d_flag);
     launches += 1 + 4 * (int64_t)nc;
     HIPCHK(hipStreamSynchronize(st));
-    for (void *q : {(void *)x, (void *)y, (void *)d_op, (void *)d_piv, (void *)d_colbuf})
-        (void)hipFree(q);
     return launches;
 }
 
@@ -1268,8 +1216,9 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
     int64_t launches = 0;
     std::vector<int> bad(nmat, nc);
     if (columns) {
-        double *E = dev_alloc<double>(n2);
-        unsigned *d_flag = dev_alloc<unsigned>(1);
+        DevPool tmp;
+        double *E = tmp.alloc<double>(n2);
+        unsigned *d_flag = tmp.alloc<unsigned>(1);
         for (int b = 0; b < nmat; ++b) {
             HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
             launches += coarse_columns(S, P, c, g.mask, vals[b], E, einv[b], d_flag, deflate,
@@ -1279,8 +1228,6 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
             HIPCHK(hipStreamSynchronize(st));
             if (singular) bad[b] = -1;      // this path does not know the column
         }
-        (void)hipFree(E);
-        (void)hipFree(d_flag);
     } else {
         // component blocks: the Galerkin launch writes the nblk diagonal blocks of size bn as
         // matrices of their own (E: nmat * nblk of them), the inverses go to Ib and are scattered
@@ -1295,19 +1242,20 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
         const size_t per = (blocked ? 2 : 1) * ne * sizeof(double) +
                            dense_inverse_batched_scratch(bn, nblk);
         const int chunk = (int)std::max<size_t>(1, std::min<size_t>(nmat, ((size_t)1 << 30) / per));
-        double *E = dev_alloc<double>(ne * chunk);
-        const double **d_vals = dev_alloc<const double *>(chunk);
-        double **d_inv = dev_alloc<double *>(chunk);
-        void *scratch = dev_alloc<char>(dense_inverse_batched_scratch(bn, nblk * chunk));
-        int *d_bad = dev_alloc<int>((size_t)nblk * chunk);
+        DevPool tmp;
+        double *E = tmp.alloc<double>(ne * chunk);
+        const double **d_vals = tmp.alloc<const double *>(chunk);
+        double **d_inv = tmp.alloc<double *>(chunk);
+        void *scratch = tmp.alloc<char>(dense_inverse_batched_scratch(bn, nblk * chunk));
+        int *d_bad = tmp.alloc<int>((size_t)nblk * chunk);
         double *Ib = nullptr, **d_binv = nullptr;
         std::vector<int> bad_blk;
         std::vector<double> h_blocks;
         if (blocked) {
-            Ib = dev_alloc<double>(ne * chunk);
+            Ib = tmp.alloc<double>(ne * chunk);
             std::vector<double *> ptr((size_t)nblk * chunk);
             for (size_t q = 0; q < ptr.size(); ++q) ptr[q] = Ib + q * b2;
-            d_binv = dev_upload(ptr.data(), ptr.size());
+            d_binv = tmp.upload(ptr.data(), ptr.size());
             bad_blk.resize((size_t)nblk * chunk);
             if (keep) h_blocks.resize(ne * chunk);
         }
@@ -1367,9 +1315,6 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
                 HIPCHK(hipStreamSynchronize(st));
             }
         }
-        for (void *q : {(void *)E, (void *)d_vals, (void *)d_inv, scratch, (void *)d_bad, (void *)Ib,
-                        (void *)d_binv})
-            if (q) (void)hipFree(q);
         S.coarse_stats.blocks = nblk;
         S.coarse_stats.block_n = bn;
     }
@@ -1407,24 +1352,24 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
 void dense_inverse_host(System &S, int n, int nmat, const double *a, double *inv, int *bad) {
     hipStream_t st = S.stream;
     const size_t n2 = (size_t)n * n;
-    double *E = dev_upload(a, n2 * nmat);
-    double *I = dev_alloc<double>(n2 * nmat);
+    DevPool tmp;
+    double *E = tmp.upload(a, n2 * nmat);
+    double *I = tmp.alloc<double>(n2 * nmat);
     std::vector<double *> ptr(nmat);
     for (int b = 0; b < nmat; ++b) ptr[b] = I + b * n2;
-    double **d_inv = dev_upload(ptr.data(), ptr.size());
-    void *scratch = dev_alloc<char>(dense_inverse_batched_scratch(n, nmat));
-    int *d_bad = dev_alloc<int>(nmat);
+    double **d_inv = tmp.upload(ptr.data(), ptr.size());
+    void *scratch = tmp.alloc<char>(dense_inverse_batched_scratch(n, nmat));
+    int *d_bad = tmp.alloc<int>(nmat);
     launch_dense_inverse_batched(st, E, d_inv, n, nmat, scratch, d_bad);
     HIPCHK(hipMemcpyAsync(inv, I, n2 * nmat * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(bad, d_bad, nmat * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (void *q : {(void *)E, (void *)I, (void *)d_inv, scratch, (void *)d_bad}) (void)hipFree(q);
 }
 
 double *SchurPC::coarse_inverse(const double *vals) {
     const int nc = coarse_.nc;
-    double *d_inv = dev_alloc<double>((size_t)nc * nc);
-    einv_owned_.push_back(d_inv);
+    double *d_inv = values_mem_.alloc<double>((size_t)nc * nc);
+    einvs_.push_back(d_inv);
     pending_coarse_.emplace_back(vals, d_inv);
     return d_inv;
 }
@@ -1571,8 +1516,8 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
     if (it != mats_.end()) {
         m = it->second;      // formed for products only, now solved with: interval and inverse below
     } else {
-        m.vals = dev_alloc<double>(P.npadded);
-        m.dinv = dev_alloc<double>(nx_);
+        m.vals = values_mem_.alloc<double>(P.npadded);
+        m.dinv = values_mem_.alloc<double>(nx_);
         launch_vals_axpy(st, m.vals, base_vals, c, m_vals_, P.npadded);
         if (mask_) launch_mask_columns(st, m.vals, P.d_col, mask_, P.npadded);
         launch_extract_dinv(st, P.d_col, P.d_slice_off, m.vals, mask_, m.dinv, (int)nx_, P.nslices,
@@ -1594,13 +1539,12 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
     if (d_.schur_emin <= 0 || coarse_cycles_ > 0) {
         for (auto &kv : mats_) {
             if (kv.first.second != bits || kv.second.emax <= 0.0) continue;
-            unsigned *d_flag = dev_alloc<unsigned>(1);
-            HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
-            launch_vals_differ(st, m.vals, kv.second.vals, P.npadded, d_flag);
+            auto d_flag = DevBuf<unsigned>::alloc(1);
+            HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(unsigned), st));
+            launch_vals_differ(st, m.vals, kv.second.vals, P.npadded, d_flag.get());
             unsigned differ = 1;
-            HIPCHK(hipMemcpyAsync(&differ, d_flag, sizeof differ, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(&differ, d_flag.get(), sizeof differ, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            HIPCHK(hipFree(d_flag));
             if (!differ) {
                 twin = &kv.second;
                 break;
@@ -1624,20 +1568,19 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
         // symmetric part H = (A + A^T) / 2 (Bendixson: Re lambda lies in the spectrum of
         // D^-1/2 H D^-1/2) and the ellipse's imaginary semi-axis from the spectral radius of
         // the skew part (|Im lambda| <= rho(D^-1/2 (A - A^T) / 2 D^-1/2)).
-        double *hv = nullptr, *sv2 = nullptr;
+        DevBuf<double> hv, sv2;
         unsigned nonsym = 0;
         const int32_t *tpos = transpose_positions();
         if (tpos) {
-            hv = dev_alloc<double>(P.npadded);
-            sv2 = dev_alloc<double>(P.npadded);
-            unsigned *d_flag = dev_alloc<unsigned>(1);
-            HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(unsigned), st));
-            launch_vals_sym_skew(st, m.vals, tpos, hv, sv2, P.npadded, d_flag);
-            HIPCHK(hipMemcpyAsync(&nonsym, d_flag, sizeof nonsym, hipMemcpyDeviceToHost, st));
+            hv = DevBuf<double>::alloc(P.npadded);
+            sv2 = DevBuf<double>::alloc(P.npadded);
+            auto d_flag = DevBuf<unsigned>::alloc(1);
+            HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(unsigned), st));
+            launch_vals_sym_skew(st, m.vals, tpos, hv.get(), sv2.get(), P.npadded, d_flag.get());
+            HIPCHK(hipMemcpyAsync(&nonsym, d_flag.get(), sizeof nonsym, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            HIPCHK(hipFree(d_flag));
         }
-        const Spectrum sp = jacobi_spectrum(S_, m_pat_, nonsym ? hv : m.vals, m.dinv, mask_, 400);
+        const Spectrum sp = jacobi_spectrum(S_, m_pat_, nonsym ? hv.get() : m.vals, m.dinv, mask_, 400);
         spectrum_steps_ += sp.steps;
         rec.lanczos = sp.steps;
         if (!(sp.emin > 0.0) || !(sp.emax > sp.emin))
@@ -1646,12 +1589,11 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
         m.emax = 1.05 * sp.emax;
         if (nonsym) {
             int steps = 0;
-            m.eimag = 1.1 * jacobi_skew_radius(S_, m_pat_, sv2, m.dinv, mask_, 40, &steps);
+            m.eimag = 1.1 * jacobi_skew_radius(S_, m_pat_, sv2.get(), m.dinv, mask_, 40, &steps);
             spectrum_steps_ += 2 * steps;
             rec.power = steps;
         }
-        if (hv) (void)hipFree(hv);
-        if (sv2) (void)hipFree(sv2);
+        hv.reset(), sv2.reset();   // before the coarse inverse below is allocated
         // two-grid form: the sweeps smooth -- they cover the upper part of the spectrum, the
         // coarse space the rest (emax / 30: measured optimum for 8 sweeps at coarse cells of 8
         // to 16 mesh widths, scripts/proto_subsolve.py)
@@ -1707,7 +1649,7 @@ void SchurPC::push_rows(std::vector<RowOp> &r) {
     s.rows.max_slices = P.nslices;
     s.rows.R = P.R;
     s.rows.uniform_w = P.uniform_w;
-    s.rows.d_ops = dev_upload(r.data(), r.size());
+    s.rows.d_ops = program_mem_.upload(r.data(), r.size());
     if (r.size() == 1) {
         s.rows.single = S_.opts.kernarg_ops;
         s.rows.h_op = r[0];
@@ -1877,9 +1819,9 @@ bool SchurPC::emit_solves_interleaved(const std::vector<Solve> &sv, int its, dou
     const size_t need = (size_t)ng * 4 * (size_t)nx_;
     if (need > il_cap_) {
         for (int k = 0; k < 3; ++k) {
-            il_P_[k] = dev_alloc<double>(need + 32);
+            // program memory: steps emitted before a regrow keep the smaller buffers
+            il_P_[k] = program_mem_.alloc<double>(need + 32);
             HIPCHK(hipMemsetAsync(il_P_[k], 0, (need + 32) * sizeof(double), S_.stream));
-            owned_.push_back(il_P_[k]);
         }
         il_cap_ = need;
     }
@@ -1933,7 +1875,7 @@ bool SchurPC::emit_solves_interleaved(const std::vector<Solve> &sv, int its, dou
         }
         PcStep s;
         s.kind = PcStep::ROWS_IL;
-        s.d_il = dev_upload(ops.data(), ops.size());
+        s.d_il = program_mem_.upload(ops.data(), ops.size());
         s.il_groups = ng;
         s.il_slices = P.nslices;
         s.il_w = P.uniform_w;
@@ -2408,7 +2350,7 @@ void SchurPC::run() {
                 g.last = e;
             }
             k = g.last;
-            segments_.push_back(g);
+            segments_.push_back(std::move(g));
         }
     }
     for (Segment &g : segments_) {

@@ -146,6 +146,11 @@ class SchurPC : public PcBase {
    private:
     System &S_;
     kkt_pc_desc d_;
+    // Device memory by lifetime: the handle's; the current values' (mats_ and the coarse
+    // inverses: values_changed() releases it); the current program's (steps_, tile tables, the
+    // interleaved iterates: clear_program() releases it).  Declared before everything that points
+    // into them -- segments_' graphs above all -- so that they are destroyed last.
+    DevPool handle_mem_, values_mem_, program_mem_;
     std::vector<int32_t> m_indptr_, m_indices_, bc_idx_;
     std::vector<double> m_values_;
     int n_ = 1;                // blocks per variable (global)
@@ -160,14 +165,13 @@ class SchurPC : public PcBase {
     double *in_ = nullptr, *out_ = nullptr;
     double *B_ = nullptr, *T_ = nullptr;             // n_ blocks each
     double *P_[3] = {nullptr, nullptr, nullptr};     // Chebyshev rotation, n_ blocks each
-    std::vector<void *> owned_;                      // device allocations to free
     struct Mat {
         double *vals;
         double *dinv;
         double emin = 0.0, emax = 0.0;   // Chebyshev interval of this matrix (given or estimated)
         double eimag = 0.0;              // > 0: imaginary semi-axis of the spectrum's ellipse
         double *einv = nullptr;          // two-grid form: (P^T A P)^-1, nc x nc row-major (shared
-                                         // by matrices with equal values: freed through einv_owned_)
+                                         // by matrices with equal values)
         int index = -1;                  // position in mat_recs_ (creation order)
         int est = KKT_PC_EST_NONE;       // KKT_PC_EST_*: where emin / emax come from
     };
@@ -191,7 +195,7 @@ class SchurPC : public PcBase {
     std::vector<int32_t> pt_indptr_, pt_indices_;      // P^T (host copies: tile plan)
     std::vector<double> pt_values_;
     CoarseDev coarse_;
-    std::vector<double *> einv_owned_;
+    std::vector<const double *> einvs_;   // every coarse inverse of the current values
     double *R_ = nullptr;                // residual of a cycle (one block)
     void build_coarse();
     GalerkinDev galerkin_{};                          // structure of P^T A P on the device
@@ -204,11 +208,9 @@ class SchurPC : public PcBase {
     std::map<std::pair<const double *, uint64_t>, Mat> mats_;
     double *h_u0_ = nullptr, *h_u1_ = nullptr, *h_t_ = nullptr;   // one-block halos
     std::vector<PcStep> steps_;
-    struct Segment {
+    struct Segment : GraphExec {
         size_t first = 0, last = 0;
         bool comm = false;
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
     };
     std::vector<Segment> segments_;
     bool use_graph_ = true;
@@ -257,7 +259,6 @@ class SchurPC : public PcBase {
     uint32_t tile_cepoch_cursor_ = 0;
     bool build_tile_coarse();
     unsigned long long *d_tg_[4] = {nullptr, nullptr, nullptr, nullptr};
-    std::vector<void *> tile_owned_;    // coefficient tables of the current program
     uint32_t tile_epoch_cursor_ = 0;    // hand-off tags handed out to the launches of one application
     bool tile_cleared_ = false;
     bool prepare_tiles();
@@ -336,7 +337,6 @@ class SchurPC : public PcBase {
 class StokesPC : public PcBase {
    public:
     StokesPC(System &outer, System &inner, System &commutator, const kkt_pc_stokes_desc &d);
-    ~StokesPC() override;
     void run() override;
     double *in() override { return in_; }
     double *out() override { return out_; }
@@ -362,7 +362,7 @@ class StokesPC : public PcBase {
     double *in_ = nullptr, *out_ = nullptr, *h_ = nullptr, *m_ = nullptr, *g_ = nullptr;
     double *P_[3] = {nullptr, nullptr, nullptr};
     double *halo_a_ = nullptr, *halo_b_ = nullptr;   // CN on time shards: neighbour blocks of the T scans
-    std::vector<void *> owned_;
+    DevPool mem_;   // declared before the chains: their graphs go first
     // a step of a pressure-space chain: a batched row launch, or -- two-grid K_p solve -- the
     // Galerkin correction x_out = x_in + P E^-1 P^T r of every block
     struct ChainStep {
@@ -374,9 +374,7 @@ class StokesPC : public PcBase {
     std::vector<RowLaunch> lin_;
     std::vector<ChainStep> kp_steps_, mp_steps_;
     // the two Chebyshev chains (hundreds of small launches on fixed buffers) replayed as graphs
-    struct Chain {
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
+    struct Chain : GraphExec {
         bool failed = false;
     } kp_chain_, mp_chain_;
     void run_chain(Chain &c, const std::vector<ChainStep> &steps);

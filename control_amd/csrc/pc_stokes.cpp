@@ -25,7 +25,7 @@ static RowOp base_op(const Pattern &P) {
     return op;
 }
 
-static RowLaunch upload_launch(const Pattern &P, std::vector<RowOp> &ops) {
+static RowLaunch upload_launch(DevPool &mem, const Pattern &P, std::vector<RowOp> &ops) {
     RowLaunch L;
     L.nops = (int)ops.size();
     L.max_slices = P.nslices;
@@ -36,7 +36,7 @@ static RowLaunch upload_launch(const Pattern &P, std::vector<RowOp> &ops) {
     for (const RowOp &op : ops)
         L.shared_matrix = L.shared_matrix && op.nterms == 1 && op.t[0].vals == ops[0].t[0].vals &&
                           op.col == ops[0].col && op.rowmask == ops[0].rowmask;
-    L.d_ops = dev_upload(ops.data(), ops.size());
+    L.d_ops = mem.upload(ops.data(), ops.size());
     return L;
 }
 
@@ -46,18 +46,15 @@ StokesPC::DevMat StokesPC::upload(int64_t nrows, int64_t ncols, const int32_t *i
     DevMat A;
     A.pat = S_.find_or_add_pattern(nrows, ncols, ip, ix);
     const Pattern &P = S_.patterns[A.pat];
-    double *d_csr = dev_upload(v, (size_t)P.nnz);
-    A.vals = dev_alloc<double>(P.npadded);
-    owned_.push_back(A.vals);
-    launch_csr_to_sell(S_.stream, d_csr, P.d_sell2csr, A.vals, P.npadded);
+    auto d_csr = DevBuf<double>::upload(v, (size_t)P.nnz);
+    A.vals = mem_.alloc<double>(P.npadded);
+    launch_csr_to_sell(S_.stream, d_csr.get(), P.d_sell2csr, A.vals, P.npadded);
     if (want_dinv) {
-        A.dinv = dev_alloc<double>(nrows);
-        owned_.push_back(A.dinv);
+        A.dinv = mem_.alloc<double>(nrows);
         launch_extract_dinv(S_.stream, P.d_col, P.d_slice_off, A.vals, nullptr, A.dinv, (int)nrows,
                             P.nslices, P.R, P.d_perm);
     }
     HIPCHK(hipStreamSynchronize(S_.stream));
-    HIPCHK(hipFree(d_csr));
     return A;
 }
 
@@ -84,7 +81,7 @@ void StokesPC::emit_cheb(std::vector<ChainStep> &dst, const DevMat &A, int its, 
         op.c3 = scale;
         ops[k] = op;
     }
-    dst.push_back(ChainStep{upload_launch(P, ops)});
+    dst.push_back(ChainStep{upload_launch(mem_, P, ops)});
     if (its <= 1) return;
     const double alpha = 1.0 - scale * emin, mu = 1.0 / alpha, omegaprod = 2.0 / alpha;
     double c_km1 = 1.0, c_k = mu;
@@ -107,7 +104,7 @@ void StokesPC::emit_cheb(std::vector<ChainStep> &dst, const DevMat &A, int its, 
             op.c3 = scale * omega;
             ops[k] = op;
         }
-        dst.push_back(ChainStep{upload_launch(P, ops)});
+        dst.push_back(ChainStep{upload_launch(mem_, P, ops)});
         c_km1 = c_k;
         c_k = c_kp1;
     }
@@ -147,11 +144,7 @@ void StokesPC::build_kp_coarse(const kkt_pc_stokes_desc &d) {
                 tv[at] = pv[q];
             }
     }
-    auto up = [&](const auto &v) {
-        auto *p = dev_upload(v.data(), std::max<size_t>(1, v.size()));
-        owned_.push_back((void *)p);
-        return p;
-    };
+    auto up = [&](const auto &v) { return mem_.upload(v.data(), std::max<size_t>(1, v.size())); };
     CoarseDev &c = kp_coarse_;
     c.nc = nc;
     c.p_ip = up(ip);
@@ -160,10 +153,8 @@ void StokesPC::build_kp_coarse(const kkt_pc_stokes_desc &d) {
     c.pt_ip = up(tip);
     c.pt_ix = up(tix);
     c.pt_v = up(tv);
-    c.rc = dev_alloc<double>((size_t)nc * 2 * n_);      // one coarse residual per pressure block
-    c.ec = dev_alloc<double>((size_t)nc * 2 * n_);
-    owned_.push_back(c.rc);
-    owned_.push_back(c.ec);
+    c.rc = mem_.alloc<double>((size_t)nc * 2 * n_);      // one coarse residual per pressure block
+    c.ec = mem_.alloc<double>((size_t)nc * 2 * n_);
     // E = P^T K_p P and its inverse (with the constants deflated) on the device, batched path
     // unless option "coarse_setup" = "columns"
     const Pattern &P = S_.patterns[Kp_.pat];
@@ -180,8 +171,7 @@ void StokesPC::build_kp_coarse(const kkt_pc_stokes_desc &d) {
     g.mask = nullptr;
     g.R = P.R;
     g.uniform_w = P.uniform_w;
-    kp_einv_ = dev_alloc<double>((size_t)nc * nc);
-    owned_.push_back(kp_einv_);
+    kp_einv_ = mem_.alloc<double>((size_t)nc * nc);
     coarse_setup(S_, Kp_.pat, c, g, {Kp_.vals}, {kp_einv_}, true, "K_p solve");
 }
 
@@ -223,7 +213,7 @@ void StokesPC::emit_kp_two_grid(int its, double emin, double emax, const double 
                 op.z = vabs(blk(b, k));
                 ops[k] = op;
             }
-            kp_steps_.push_back(ChainStep{upload_launch(P, ops)});
+            kp_steps_.push_back(ChainStep{upload_launch(mem_, P, ops)});
             r = kp_r_;
         }
         ChainStep cs;
@@ -255,7 +245,7 @@ void StokesPC::emit_kp_two_grid(int its, double emin, double emax, const double 
                 op.c3 = step == 1 ? scale : c3[step];
                 ops[k] = op;
             }
-            kp_steps_.push_back(ChainStep{upload_launch(P, ops)});
+            kp_steps_.push_back(ChainStep{upload_launch(mem_, P, ops)});
         }
         xcur = target(its);
     }
@@ -306,9 +296,8 @@ StokesPC::StokesPC(System &outer, System &inner, System &commutator, const kkt_p
     Kp_ = upload(np_, np_, d.kp_indptr, d.kp_indices, d.kp_values, true);
     Mp_ = upload(np_, np_, d.mp_indptr, d.mp_indices, d.mp_values, true);
     auto vec = [&](int64_t n) {
-        double *p = dev_alloc<double>(n + 32);
+        double *p = mem_.alloc<double>(n + 32);
         HIPCHK(hipMemsetAsync(p, 0, (n + 32) * sizeof(double), S_.stream));
-        owned_.push_back(p);
         return p;
     };
     const int64_t n0 = 2 * (int64_t)n_ * nv_, n1 = 2 * (int64_t)n_ * np_;
@@ -343,7 +332,7 @@ StokesPC::StokesPC(System &outer, System &inner, System &commutator, const kkt_p
             }
             ops.push_back(op);
         }
-        lin_.push_back(upload_launch(P, ops));
+        lin_.push_back(upload_launch(mem_, P, ops));
     }
     int kp_its = d.kp_its;
     double kp_emin = d.kp_emin, kp_emax = d.kp_emax;
@@ -398,20 +387,6 @@ StokesPC::StokesPC(System &outer, System &inner, System &commutator, const kkt_p
 void StokesPC::solve_records(std::vector<double> &out) const {
     out = {(double)KKT_PC_SWEEP_KP, -1.0, -1.0, 0.0, kp_emin_, kp_emax_, 0.0, (double)kp_its_,
            (double)kp_est_};
-}
-
-StokesPC::~StokesPC() {
-    for (Chain *c : {&kp_chain_, &mp_chain_}) {
-        if (c->exec) (void)hipGraphExecDestroy(c->exec);
-        if (c->graph) (void)hipGraphDestroy(c->graph);
-    }
-    for (auto &L : lin_)
-        if (L.d_ops) (void)hipFree(L.d_ops);
-    for (auto *v : {&kp_steps_, &mp_steps_})
-        for (auto &c : *v)
-            if (c.L.d_ops) (void)hipFree(c.L.d_ops);
-    for (void *p : owned_)
-        if (p) (void)hipFree(p);
 }
 
 void StokesPC::run() {

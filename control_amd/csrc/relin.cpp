@@ -9,21 +9,6 @@
 
 namespace kkt {
 
-RelinPlan::~RelinPlan() {
-    auto F = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    for (void *p : {(void *)d_V, (void *)d_W, (void *)d_phi, (void *)d_gphi, (void *)d_lam,
-                    (void *)d_glam, (void *)d_ip2, (void *)d_ix2, (void *)d_t2, (void *)d_tp,
-                    (void *)d_K2, (void *)d_M2, (void *)d_Kp, (void *)d_Mp, (void *)d_cptr2,
-                    (void *)d_clist2, (void *)d_cptrp, (void *)d_clistp, (void *)d_Bip,
-                    (void *)d_Bix, (void *)d_BTip, (void *)d_BTix, (void *)d_Bv, (void *)d_BTv,
-                    (void *)d_bc, (void *)d_data, (void *)d_Ev, (void *)d_Ep, (void *)d_D2,
-                    (void *)d_Dp, (void *)d_v, (void *)d_zeta, (void *)d_p, (void *)d_mu,
-                    (void *)d_red, (void *)d_jobs})
-        F(p);
-}
-
 static void need(bool ok, const std::string &msg) {
     if (!ok) fail(KKT_ERR_ARG, "kkt_set_relinearisation: " + msg);
 }
@@ -102,28 +87,28 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     P->tau = d->tau;
     P->beta = d->beta;
     const int64_t ne = d->ne, nq = RELIN_NQ;
-    P->d_V = dev_upload(d->V, ne * 6);
-    P->d_W = dev_upload(d->W, ne * nq);
-    P->d_phi = dev_upload(d->phi, nq * 6);
-    P->d_gphi = dev_upload(d->gphi, ne * nq * 12);
-    P->d_lam = dev_upload(d->lam, nq * 3);
-    P->d_glam = dev_upload(d->glam, ne * 6);
+    P->d_V = P->mem.upload(d->V, ne * 6);
+    P->d_W = P->mem.upload(d->W, ne * nq);
+    P->d_phi = P->mem.upload(d->phi, nq * 6);
+    P->d_gphi = P->mem.upload(d->gphi, ne * nq * 12);
+    P->d_lam = P->mem.upload(d->lam, nq * 3);
+    P->d_glam = P->mem.upload(d->glam, ne * 6);
     P->h_ip2.assign(d->v_indptr, d->v_indptr + d->n2 + 1);
     P->h_ix2.assign(d->v_indices, d->v_indices + d->nnz2);
     P->h_ipp.assign(d->p_indptr, d->p_indptr + d->n1 + 1);
     P->h_ixp.assign(d->p_indices, d->p_indices + d->nnz1);
-    P->d_ip2 = dev_upload(d->v_indptr, d->n2 + 1);
-    P->d_ix2 = dev_upload(d->v_indices, d->nnz2);
-    P->d_t2 = dev_upload(d->v_tperm, d->nnz2);
-    P->d_tp = dev_upload(d->p_tperm, d->nnz1);
-    P->d_K2 = dev_upload(d->K2, d->nnz2);
-    P->d_M2 = dev_upload(d->M2, d->nnz2);
-    P->d_Kp = dev_upload(d->Kp, d->nnz1);
-    P->d_Mp = dev_upload(d->Mp, d->nnz1);
-    P->d_cptr2 = dev_upload(d->v_cptr, d->nnz2 + 1);
-    P->d_clist2 = dev_upload(d->v_clist, ne * RELIN_EV);
-    P->d_cptrp = dev_upload(d->p_cptr, d->nnz1 + 1);
-    P->d_clistp = dev_upload(d->p_clist, ne * RELIN_EP);
+    P->d_ip2 = P->mem.upload(d->v_indptr, d->n2 + 1);
+    P->d_ix2 = P->mem.upload(d->v_indices, d->nnz2);
+    P->d_t2 = P->mem.upload(d->v_tperm, d->nnz2);
+    P->d_tp = P->mem.upload(d->p_tperm, d->nnz1);
+    P->d_K2 = P->mem.upload(d->K2, d->nnz2);
+    P->d_M2 = P->mem.upload(d->M2, d->nnz2);
+    P->d_Kp = P->mem.upload(d->Kp, d->nnz1);
+    P->d_Mp = P->mem.upload(d->Mp, d->nnz1);
+    P->d_cptr2 = P->mem.upload(d->v_cptr, d->nnz2 + 1);
+    P->d_clist2 = P->mem.upload(d->v_clist, ne * RELIN_EV);
+    P->d_cptrp = P->mem.upload(d->p_cptr, d->nnz1 + 1);
+    P->d_clistp = P->mem.upload(d->p_clist, ne * RELIN_EP);
     // B and its transpose (rows of B^T in ascending column order of B: sorted)
     const int64_t nb = d->nnz_b;
     std::vector<int32_t> tip(nv + 1, 0), tix(nb);
@@ -137,29 +122,29 @@ void relin_set(System &S, const kkt_relin_desc *d) {
             tix[at] = (int32_t)r;
             tv[at] = d->b_values[k];
         }
-    P->d_Bip = dev_upload(d->b_indptr, d->n1 + 1);
-    P->d_Bix = dev_upload(d->b_indices, nb);
-    P->d_Bv = dev_upload(d->b_values, nb);
-    P->d_BTip = dev_upload(tip.data(), nv + 1);
-    P->d_BTix = dev_upload(tix.data(), nb);
-    P->d_BTv = dev_upload(tv.data(), nb);
+    P->d_Bip = P->mem.upload(d->b_indptr, d->n1 + 1);
+    P->d_Bix = P->mem.upload(d->b_indices, nb);
+    P->d_Bv = P->mem.upload(d->b_values, nb);
+    P->d_BTip = P->mem.upload(tip.data(), nv + 1);
+    P->d_BTix = P->mem.upload(tix.data(), nb);
+    P->d_BTv = P->mem.upload(tv.data(), nb);
     std::vector<uint8_t> bc(nv, 0);
     for (int64_t k = 0; k < d->n_bc; ++k) bc[d->bc_idx[k]] = 1;
-    P->d_bc = dev_upload(bc.data(), nv);
-    P->d_data = dev_upload(d->data, 2 * (int64_t)m * nv);
-    P->d_Ev = dev_alloc<double>(ne * RELIN_EV * d->n_t);
-    P->d_Ep = dev_alloc<double>(ne * RELIN_EP * d->n_t);
-    P->d_D2 = dev_alloc<double>(d->nnz2 * d->n_t);
-    P->d_Dp = dev_alloc<double>(d->nnz1 * d->n_t);
-    P->d_v = dev_alloc<double>(d->n_t * nv);
-    P->d_zeta = dev_alloc<double>(d->n_t * nv);
-    P->d_p = dev_alloc<double>((int64_t)m * d->n1);
-    P->d_mu = dev_alloc<double>((int64_t)m * d->n1);
+    P->d_bc = P->mem.upload(bc.data(), nv);
+    P->d_data = P->mem.upload(d->data, 2 * (int64_t)m * nv);
+    P->d_Ev = P->mem.alloc<double>(ne * RELIN_EV * d->n_t);
+    P->d_Ep = P->mem.alloc<double>(ne * RELIN_EP * d->n_t);
+    P->d_D2 = P->mem.alloc<double>(d->nnz2 * d->n_t);
+    P->d_Dp = P->mem.alloc<double>(d->nnz1 * d->n_t);
+    P->d_v = P->mem.alloc<double>(d->n_t * nv);
+    P->d_zeta = P->mem.alloc<double>(d->n_t * nv);
+    P->d_p = P->mem.alloc<double>((int64_t)m * d->n1);
+    P->d_mu = P->mem.alloc<double>((int64_t)m * d->n1);
     HIPCHK(hipMemset(P->d_v, 0, d->n_t * nv * 8));
     HIPCHK(hipMemset(P->d_zeta, 0, d->n_t * nv * 8));
     HIPCHK(hipMemset(P->d_p, 0, m * d->n1 * 8));
     HIPCHK(hipMemset(P->d_mu, 0, m * d->n1 * 8));
-    P->d_red = dev_alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX + 2);
+    P->d_red = P->mem.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX + 2);
     S.relin = std::move(P);
 }
 
@@ -244,22 +229,22 @@ void relin_apply(System &T, System &PS, const double *d_v, int n, const kkt_reli
         if (users > 1) {
             const Pattern &Q = T.patterns[T.values[blk.va].pattern];
             T.give_private_values(rec[r].quadrant, rec[r].i, rec[r].j,
-                                  dev_alloc<double>(Q.npadded));
+                                  DevBuf<double>::alloc(Q.npadded));
         }
         const ValueArray &va = T.values[blk.va];
         jobs[r].dst = va.d_vals;
         jobs[r].colmask = va.colmask_set >= 0 ? T.bc_sets[va.colmask_set].d_mask : nullptr;
     }
     if (P.jobs_cap < n) {
-        if (P.d_jobs) HIPCHK(hipFree(P.d_jobs));
-        P.d_jobs = dev_alloc<ComposeJob>(n);
+        P.d_jobs.reset();
+        P.d_jobs = DevBuf<ComposeJob>::alloc(n);
         P.jobs_cap = n;
     }
     // the job table is shared by every target of the plan: the copy and the launch run in order
     // on the target's stream, and the host waits before the table is reused
-    HIPCHK(hipMemcpyAsync(P.d_jobs, jobs.data(), n * sizeof(ComposeJob), hipMemcpyHostToDevice,
+    HIPCHK(hipMemcpyAsync(P.d_jobs.get(), jobs.data(), n * sizeof(ComposeJob), hipMemcpyHostToDevice,
                           T.stream));
-    launch_relin_compose(T.stream, P.d_jobs, n, max_padded);
+    launch_relin_compose(T.stream, P.d_jobs.get(), n, max_padded);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(T.stream));
     T.pc_stale = true;
@@ -295,7 +280,7 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
     if (!P.assembled) fail(KKT_ERR_STATE, "kkt_picard_residual_device: D not assembled yet");
     double *r = d_out;
     if (rhs) {
-        if (!S.d_tmp_y) S.d_tmp_y = S.new_vec();
+        if (!S.d_tmp_y) S.d_tmp_y = S.mem.adopt(S.new_vec());
         r = S.d_tmp_y;
     }
     launch_relin_residual(S.stream, P, r);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/kkt.h"
+#include "devmem.hpp"
 
 namespace kkt {
 
@@ -38,6 +39,7 @@ struct RelinPlan {
     bool CN = false;
     int64_t ne = 0, n2 = 0, n1 = 0, nv = 0, nnz2 = 0, nnz1 = 0;
     double nu = 0.0, tau = 0.0, beta = 0.0;
+    DevPool mem;   // everything below but the job table
     int32_t *d_V = nullptr;
     double *d_W = nullptr, *d_phi = nullptr, *d_gphi = nullptr, *d_lam = nullptr,
            *d_glam = nullptr;
@@ -58,11 +60,10 @@ struct RelinPlan {
     // the iterate: v, zeta (n_t x nv), p, mu (m x n1)
     double *d_v = nullptr, *d_zeta = nullptr, *d_p = nullptr, *d_mu = nullptr;
     double *d_red = nullptr;   // reduction scratch + result
-    ComposeJob *d_jobs = nullptr;
+    DevBuf<ComposeJob> d_jobs;   // regrown with the largest job count seen
     int jobs_cap = 0;
     // target patterns already proven equal to the plan's: (system, pattern id, space)
     std::set<std::tuple<const void *, int, int>> checked;
-    ~RelinPlan();
 };
 
 // element matrices of every (element, level): Ev[(l ne + e) 36 + 6a + b], Ep[... 9 + 3c + d]

@@ -75,14 +75,15 @@ Spectrum jacobi_spectrum(System &S, int pattern, const double *vals, const doubl
     const Pattern &P = S.patterns[pattern];
     const int64_t n = P.nrows;
     hipStream_t st = S.stream;
+    DevPool tmp;   // released on every way out
     auto vec = [&]() {
-        double *p = dev_alloc<double>(n + 32);
+        double *p = tmp.alloc<double>(n + 32);
         HIPCHK(hipMemsetAsync(p, 0, (n + 32) * sizeof(double), st));
         return p;
     };
     double *r = vec(), *z = vec(), *p = vec(), *w = vec();
-    double *scratch = dev_alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX);
-    double *d_out = dev_alloc<double>(4);
+    double *scratch = tmp.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX);
+    double *d_out = tmp.alloc<double>(4);
     // deterministic start vector with all frequencies, zero on the boundary rows
     {
         std::vector<double> h(n);
@@ -126,7 +127,7 @@ Spectrum jacobi_spectrum(System &S, int pattern, const double *vals, const doubl
     opZ.nterms = 0;
     opZ.uniform_w = 0;
     std::vector<int32_t> zoff(P.nslices + 1, 0);
-    int32_t *d_zoff = dev_upload(zoff.data(), zoff.size());
+    int32_t *d_zoff = tmp.upload(zoff.data(), zoff.size());
     opZ.slice_off = d_zoff;
     opZ.mode = EPI_CHEB;
     opZ.y = vabs(z);
@@ -138,7 +139,7 @@ Spectrum jacobi_spectrum(System &S, int pattern, const double *vals, const doubl
     RowOp *d_ops = nullptr;
     {
         RowOp both[2] = {opA, opZ};
-        d_ops = dev_upload(both, 2);
+        d_ops = tmp.upload(both, 2);
     }
     const Bases B{{nullptr, nullptr, nullptr, nullptr}};
     auto run = [&](int which) {
@@ -192,9 +193,6 @@ Spectrum jacobi_spectrum(System &S, int pattern, const double *vals, const doubl
         launch_axpby(st, p, 1.0, z, b, n);    // p = z + b p
         rz = rz_new;
     }
-    for (double *q : {r, z, p, w, scratch, d_out}) (void)hipFree(q);
-    (void)hipFree(d_zoff);
-    (void)hipFree(d_ops);
     Spectrum out{0.0, 0.0, (int)alpha.size()};
     const int m = (int)alpha.size();
     if (m == 0) return out;
@@ -211,14 +209,15 @@ double jacobi_skew_radius(System &S, int pattern, const double *skew_vals, const
     const Pattern &P = S.patterns[pattern];
     const int64_t n = P.nrows;
     hipStream_t st = S.stream;
+    DevPool tmp;   // released on every way out
     auto vec = [&]() {
-        double *p = dev_alloc<double>(n + 32);
+        double *p = tmp.alloc<double>(n + 32);
         HIPCHK(hipMemsetAsync(p, 0, (n + 32) * sizeof(double), st));
         return p;
     };
     double *v = vec(), *z = vec();
-    double *scratch = dev_alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX);
-    double *d_out = dev_alloc<double>(4);
+    double *scratch = tmp.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX);
+    double *d_out = tmp.alloc<double>(4);
     {
         std::vector<double> h(n);
         uint64_t sd = 0x2545f4914f6cdd1dull;
@@ -257,7 +256,7 @@ double jacobi_skew_radius(System &S, int pattern, const double *skew_vals, const
     both[0].y = vabs(z);
     both[1].t[0].x = vabs(z);
     both[1].y = vabs(v);
-    RowOp *d_ops = dev_upload(both, 2);
+    RowOp *d_ops = tmp.upload(both, 2);
     const Bases B{{nullptr, nullptr, nullptr, nullptr}};
     double host[2];
     auto norm = [&](const double *a) {
@@ -283,8 +282,6 @@ double jacobi_skew_radius(System &S, int pattern, const double *skew_vals, const
         last = mu2;
     }
     if (steps_out) *steps_out = k;
-    for (double *q : {v, z, scratch, d_out}) (void)hipFree(q);
-    (void)hipFree(d_ops);
     return (mu2 > 0.0 && std::isfinite(mu2)) ? std::sqrt(mu2) : 0.0;
 }
 

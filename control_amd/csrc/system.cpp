@@ -69,48 +69,8 @@ System::~System() {
     (void)hipSetDevice(device);
     pc.reset();
     comm.reset();
-    auto F = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    for (auto &p : patterns) {
-        F(p.d_col);
-        F(p.d_perm);
-        F(p.d_slice_off);
-        F(p.d_sell2csr);
-    }
-    for (auto &v : values) F(v.d_vals);
-    for (auto &b : bc_sets) {
-        F(b.d_mask);
-        F(b.d_idx);
-    }
-    for (auto &l : apply_launches) {
-        F(l.d_ops);
-        F(l.d_groups);
-    }
-    F(d_mask_jobs);
-    F(d_mask_jobs_one);
-    F(d_pc_in);
-    F(d_pc_out);
-    F(d_rhs);
-    F(d_guess);
-    F(d_xc);
-    F(d_tmp_y);
-    F(d_sums);
-    F(d_const_jobs);
-    F(d_halo_x0_lo);
-    F(d_halo_x1_hi);
-    for (TimeGroup &g : time_groups) F(g.d_halo);
-    for (auto &a : d_halo2)
-        for (auto &b : a)
-            for (double *q : b) F(q);
-    F(d_V);
-    F(d_Z);
-    F(d_w);
-    F(d_t1);
-    F(d_t2);
-    F(d_red_scratch);
-    F(d_hcol);
-    F(d_coef);
+    ws_mem.release();   // after pc and comm, before the streams
+    mem.release();
     if (h_pinned) (void)hipHostFree(h_pinned);
     if (ev_x_ready) (void)hipEventDestroy(ev_x_ready);
     if (ev_halo_ready) (void)hipEventDestroy(ev_halo_ready);
@@ -273,7 +233,7 @@ int System::find_or_add_pattern(int64_t nrows, int64_t ncols, const int32_t *ind
             P.h_pos_of.assign(nrows, -1);
             for (int64_t p = 0; p < npos; ++p)
                 if (cand[p] >= 0) P.h_pos_of[cand[p]] = (int32_t)p;
-            P.d_perm = dev_upload(cand.data(), cand.size());
+            P.d_perm = mem.upload(cand.data(), cand.size());
         } else {
             off = off_before;
             P.uniform_w = uni_before;
@@ -306,10 +266,10 @@ int System::find_or_add_pattern(int64_t nrows, int64_t ncols, const int32_t *ind
             }
         }
     }
-    P.d_col = dev_upload(col.data(), col.size());
-    P.d_slice_off = dev_upload(off.data(), off.size());
+    P.d_col = mem.upload(col.data(), col.size());
+    P.d_slice_off = mem.upload(off.data(), off.size());
     P.h_slice_off = off;
-    P.d_sell2csr = dev_upload(map.data(), map.size());
+    P.d_sell2csr = mem.upload(map.data(), map.size());
     patterns.push_back(std::move(P));
     info.bytes_device_index += patterns.back().npadded * 4 + (patterns.back().nslices + 1) * 4 +
                                (patterns.back().d_perm ? (int64_t)patterns.back().nslices * C * 4 : 0);
@@ -320,11 +280,10 @@ int System::new_value_array(int pattern, const double *csr_vals) {
     const Pattern &P = patterns[pattern];
     ValueArray va;
     va.pattern = pattern;
-    va.d_vals = dev_alloc<double>(P.npadded);
-    double *d_csr = dev_upload(csr_vals, (size_t)P.nnz);
-    launch_csr_to_sell(stream, d_csr, P.d_sell2csr, va.d_vals, P.npadded);
+    va.d_vals = mem.alloc<double>(P.npadded);
+    auto d_csr = DevBuf<double>::upload(csr_vals, (size_t)P.nnz);
+    launch_csr_to_sell(stream, d_csr.get(), P.d_sell2csr, va.d_vals, P.npadded);
     HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipFree(d_csr));
     values.push_back(va);
     info.bytes_device_values += P.npadded * 8;
     return (int)values.size() - 1;
@@ -399,8 +358,8 @@ int System::add_bc_set(int64_t nx, int64_t n, const int32_t *idx) {
     b.idx = v;
     std::vector<uint8_t> m(nx, 0);
     for (int32_t k : v) m[k] = 1;
-    b.d_mask = dev_upload(m.data(), m.size());
-    b.d_idx = dev_upload(v.data(), v.size());
+    b.d_mask = mem.upload(m.data(), m.size());
+    b.d_idx = mem.upload(v.data(), v.size());
     bc_sets.push_back(std::move(b));
     return (int)bc_sets.size() - 1;
 }
@@ -424,9 +383,9 @@ void System::set_const_ns(int k, double alpha) {
     nullspaces[k] = ns;
 }
 
-double *System::new_vec() {
-    double *p = dev_alloc<double>(vec_stride);
-    HIPCHK(hipMemsetAsync(p, 0, vec_stride * sizeof(double), stream));
+DevBuf<double> System::new_vec() {
+    auto p = DevBuf<double>::alloc(vec_stride);
+    HIPCHK(hipMemsetAsync(p.get(), 0, vec_stride * sizeof(double), stream));
     return p;
 }
 
@@ -473,7 +432,7 @@ void System::finalize() {
                 if (it == clones.end()) {
                     const Pattern &P = patterns[va.pattern];
                     ValueArray c = va;
-                    c.d_vals = dev_alloc<double>(P.npadded);
+                    c.d_vals = mem.alloc<double>(P.npadded);
                     HIPCHK(hipMemcpy(c.d_vals, va.d_vals, P.npadded * 8, hipMemcpyDeviceToDevice));
                     c.colmask_set = want;
                     values.push_back(c);
@@ -495,7 +454,7 @@ void System::finalize() {
 
     any_const_ns = false;
     for (auto &ns : nullspaces) any_const_ns |= ns.kind == 2;
-    if (any_const_ns && !d_xc) d_xc = new_vec();
+    if (any_const_ns && !d_xc) d_xc = mem.adopt(new_vec());
     fused_row_masks = !CN;
 
     // ---- row plan: one RowOp per (row, run of same-pattern terms), chained by accumulation
@@ -596,7 +555,7 @@ void System::finalize() {
                             const int v = col0 ? 0 : 1, f = family_of(b->j), side = lj < lo ? 0 : 1;
                             if (!d_halo2[v][f][side]) {
                                 const int64_t nxh = v == 0 ? nx0 : nx1;
-                                d_halo2[v][f][side] = dev_alloc<double>(nxh);
+                                d_halo2[v][f][side] = mem.alloc<double>(nxh);
                                 HIPCHK(hipMemset(d_halo2[v][f][side], 0, nxh * 8));
                             }
                             op.t[nt].x = VRef{(int64_t)(uintptr_t)d_halo2[v][f][side], 0, 0};
@@ -612,7 +571,7 @@ void System::finalize() {
                     op.col = nullptr;
                     // slice_off of zeros: every slice has width 0
                     std::vector<int32_t> z(nslices + 1, 0);
-                    op.slice_off = dev_upload(z.data(), z.size());
+                    op.slice_off = mem.upload(z.data(), z.size());
                     op.uniform_w = 0;
                 }
                 const bool last = t0 >= terms.size();
@@ -701,7 +660,7 @@ void System::finalize() {
                         if (std::get<0>(kv.second) == (int)w)
                             std::get<1>(kv.second) = new_index[std::get<1>(kv.second)];
                     ops.swap(sorted);
-                    L.d_groups = dev_upload(groups.data(), groups.size());
+                    L.d_groups = mem.upload(groups.data(), groups.size());
                     L.ngroups = (int)groups.size() / 2;
                     if (opts.verbose)
                         std::fprintf(stderr, "[kkt] operator apply, launch %zu: %zu block rows in %d "
@@ -747,7 +706,7 @@ void System::finalize() {
                                  "narrow slices" : "slot loop");
             }
         }
-        L.d_ops = dev_upload(waves[w].data(), waves[w].size());
+        L.d_ops = mem.upload(waves[w].data(), waves[w].size());
         info.apply_launches++;
         apply_launches.push_back(L);
     }
@@ -789,9 +748,9 @@ void System::finalize() {
                 jobs.push_back(j);
             }
         }
-        d_mask_jobs = dev_upload(jobs.data(), jobs.size());
+        d_mask_jobs = mem.upload(jobs.data(), jobs.size());
         for (auto &j : jobs) j.alpha = 1.0;
-        d_mask_jobs_one = dev_upload(jobs.data(), jobs.size());
+        d_mask_jobs_one = mem.upload(jobs.data(), jobs.size());
     }
     if (any_const_ns) {
         std::vector<ConstJob> cj;
@@ -807,16 +766,16 @@ void System::finalize() {
             }
         }
         n_const_jobs = (int)cj.size();
-        d_const_jobs = dev_upload(cj.data(), cj.size());
-        d_sums = dev_alloc<double>(2 * cj.size());
+        d_const_jobs = mem.upload(cj.data(), cj.size());
+        d_sums = mem.alloc<double>(2 * cj.size());
     }
     if (sharded) {
-        d_halo_x0_lo = dev_alloc<double>(nx0);
-        d_halo_x1_hi = dev_alloc<double>(nx1);
+        d_halo_x0_lo = mem.alloc<double>(nx0);
+        d_halo_x1_hi = mem.alloc<double>(nx1);
         HIPCHK(hipMemset(d_halo_x0_lo, 0, nx0 * 8));
         HIPCHK(hipMemset(d_halo_x1_hi, 0, nx1 * 8));
         for (TimeGroup &g : time_groups) {
-            g.d_halo = dev_alloc<double>(g.nx);
+            g.d_halo = mem.alloc<double>(g.nx);
             HIPCHK(hipMemset(g.d_halo, 0, g.nx * 8));
         }
     }
@@ -833,16 +792,15 @@ void System::update_block_values(int q, int i, int j, const double *vals) {
     for (auto &kv : blocks) users += kv.second.va == blk.va;
     const int pat = values[blk.va].pattern;
     const Pattern &P = patterns[pat];
-    double *d_csr = dev_upload(vals, (size_t)P.nnz);
+    auto d_csr = DevBuf<double>::upload(vals, (size_t)P.nnz);
     auto fill = [&](double *dst, int colmask_set) {
-        launch_csr_to_sell(stream, d_csr, P.d_sell2csr, dst, P.npadded);
+        launch_csr_to_sell(stream, d_csr.get(), P.d_sell2csr, dst, P.npadded);
         if (colmask_set >= 0)
             launch_mask_columns(stream, dst, P.d_col, bc_sets[colmask_set].d_mask, P.npadded);
     };
     if (users <= 1) {
         fill(values[blk.va].d_vals, values[blk.va].colmask_set);
         HIPCHK(hipStreamSynchronize(stream));
-        HIPCHK(hipFree(d_csr));
         pc_stale = true;
         return;
     }
@@ -850,27 +808,23 @@ void System::update_block_values(int q, int i, int j, const double *vals) {
     // reference re-assembles every block on its own, so an update must not reach the sharers.
     // Identical values (a Picard loop re-sending its mass couplings) change nothing; new
     // values give this block a private array (copy on write) and its RowOp term is re-pointed.
-    double *d_new = dev_alloc<double>(P.npadded);
-    fill(d_new, values[blk.va].colmask_set);
-    unsigned *d_flag = dev_alloc<unsigned>(1);
-    HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(unsigned), stream));
-    launch_vals_differ(stream, d_new, values[blk.va].d_vals, P.npadded, d_flag);
+    auto d_new = DevBuf<double>::alloc(P.npadded);
+    fill(d_new.get(), values[blk.va].colmask_set);
+    auto d_flag = DevBuf<unsigned>::alloc(1);
+    HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(unsigned), stream));
+    launch_vals_differ(stream, d_new.get(), values[blk.va].d_vals, P.npadded, d_flag.get());
     unsigned differ = 0;
-    HIPCHK(hipMemcpyAsync(&differ, d_flag, sizeof differ, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(&differ, d_flag.get(), sizeof differ, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    HIPCHK(hipFree(d_flag));
-    HIPCHK(hipFree(d_csr));
-    if (!differ) {
-        HIPCHK(hipFree(d_new));
-        return;
-    }
-    give_private_values(q, i, j, d_new);
+    if (!differ) return;
+    give_private_values(q, i, j, std::move(d_new));
     pc_stale = true;
 }
 
 // Block (q, i, j) leaves the value array it shares and takes d_new (device, npadded doubles)
 // as a private one; its RowOp term of the apply plan is re-pointed.
-void System::give_private_values(int q, int i, int j, double *d_new) {
+void System::give_private_values(int q, int i, int j, DevBuf<double> fresh) {
+    double *d_new = mem.adopt(std::move(fresh));
     Block &blk = blocks.at(std::make_tuple(q, i, j));
     const Pattern &P = patterns[values[blk.va].pattern];
     ValueArray c = values[blk.va];
@@ -925,7 +879,7 @@ void System::apply(const double *d_x, double *d_y) {
     // post-correction fused (one pass instead of a serial in-place transform and a mask pass)
     double *rows_out = d_y;
     if (CN) {
-        if (!d_tmp_y) d_tmp_y = new_vec();
+        if (!d_tmp_y) d_tmp_y = mem.adopt(new_vec());
         rows_out = d_tmp_y;
     }
     Bases B{{xin, rows_out, d_halo_x0_lo, d_halo_x1_hi}};

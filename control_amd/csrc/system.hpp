@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/kkt.h"
+#include "devmem.hpp"
 #include "kernels.hpp"
 
 namespace kkt {
@@ -19,23 +20,6 @@ struct Error {
     std::string msg;
 };
 [[noreturn]] void fail(int code, const std::string &msg);
-void hip_check(hipError_t e, const char *what, const char *file, int line);
-#define HIPCHK(x) ::kkt::hip_check((x), #x, __FILE__, __LINE__)
-
-template <class T>
-T *dev_alloc(size_t n) {
-    void *p = nullptr;
-    if (n == 0) n = 1;
-    HIPCHK(hipMalloc(&p, n * sizeof(T)));
-    return static_cast<T *>(p);
-}
-template <class T>
-T *dev_upload(const T *h, size_t n) {
-    T *p = dev_alloc<T>(n);
-    if (n) HIPCHK(hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice));
-    return p;
-}
-
 // Execution options (kkt_set_option; include/kkt.h documents the keys): which kernel form runs,
 // never what is computed.  One field per key, with its built-in default; kkt_set_option checks
 // every value against the key's domain before it lands here.
@@ -195,6 +179,10 @@ struct System {
 
     int sell_R = 2;
 
+    // Device memory of the handle (patterns, value arrays, boundary sets, apply plan, halos, work
+    // vectors: the raw pointers below point into it) and of the Krylov workspace, which
+    // ensure_workspace() releases when it regrows.
+    DevPool mem, ws_mem;
     std::vector<Pattern> patterns;
     std::vector<ValueArray> values;
     std::map<std::tuple<int, int, int>, Block> blocks;
@@ -270,7 +258,7 @@ struct System {
     void add_block(int q, int i, int j, int64_t nrows, int64_t ncols, const int32_t *indptr,
                    const int32_t *indices, const double *vals, int64_t share_id);
     void update_block_values(int q, int i, int j, const double *vals);
-    void give_private_values(int q, int i, int j, double *d_new);
+    void give_private_values(int q, int i, int j, DevBuf<double> d_new);
     void set_bc(int k, int64_t n, const int32_t *idx, double alpha);
     void set_const_ns(int k, double alpha);
     void finalize();
@@ -291,7 +279,7 @@ struct System {
         const int nl = hi - lo;
         return (local_i / nl) * mf + lo + local_i % nl;
     }
-    double *new_vec();   // internal vector of vec_stride doubles (zeroed)
+    DevBuf<double> new_vec();   // vector of vec_stride doubles (zeroed)
 
     // -- operations on device vectors of n_local doubles
     void apply(const double *d_x, double *d_y);

@@ -109,24 +109,11 @@ struct Bisector {
 
 }  // namespace
 
-void TilePlan::upload() {
-    release();
-    d_n = dev_upload(n.data(), n.size());
-    d_grow = dev_upload(grow.data(), grow.size());
-    d_gpos = dev_upload(gpos.data(), gpos.size());
-    d_lcol = dev_upload(lcol.data(), lcol.size());
-}
-
-void TilePlan::release() {
-    auto F = [](void *p) {
-        if (p) (void)hipFree(p);
-    };
-    F(d_n);
-    F(d_grow);
-    F(d_gpos);
-    F(d_lcol);
-    d_n = d_grow = d_gpos = nullptr;
-    d_lcol = nullptr;
+void TilePlan::upload(DevPool &mem) {
+    d_n = mem.upload(n.data(), n.size());
+    d_grow = mem.upload(grow.data(), grow.size());
+    d_gpos = mem.upload(gpos.data(), gpos.size());
+    d_lcol = mem.upload(lcol.data(), lcol.size());
 }
 
 bool build_tile_plan(const Pattern &P, int ntiles, int depth, int threads, int max_rpt,

@@ -34,14 +34,13 @@ struct TilePlan {
     std::vector<uint16_t> lcol;   // [ntiles][rpt][W][threads]: local column of entry k of a row
     std::vector<int32_t> gpos;    // same shape: index into a SELL value array (-1: padding)
     std::vector<int32_t> part;    // tile of every global row
-    // device copies
+    // device copies (in the pool given to upload())
     int32_t *d_n = nullptr, *d_grow = nullptr, *d_gpos = nullptr;
     uint16_t *d_lcol = nullptr;
     int64_t max_own = 0, max_rows = 0, max_halo = 0;   // statistics (largest tile)
     double mean_redundancy = 0.0;                      // mean n[depth-1] / n[0]
     double model_us = 0.0;                             // modelled microseconds per dependent step
-    void upload();
-    void release();
+    void upload(DevPool &mem);
 };
 
 // Partition the rows of `P` into `ntiles` compact parts (recursive graph bisection along the
