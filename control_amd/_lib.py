@@ -58,7 +58,7 @@ class Info(C.Structure):
                 ("last_op_applies", C.c_int64), ("program_fallbacks", C.c_int64)] + \
                [(n, C.c_int64) for n in
                 ("sweep_form", "sweep_tiles", "sweep_threads", "sweep_depth", "sweep_row_slots",
-                 "sweep_its", "apply_launches", "apply_switched")]
+                 "sweep_its", "apply_launches", "apply_switched", "blocks_unset")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -134,6 +134,8 @@ SIGNATURES = {
                                   C.POINTER(C.c_int)]),
     "kkt_add_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64,
                                 C.c_int64, c_i32p, c_i32p, c_f64p, C.c_int64]),
+    "kkt_add_block_structure": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                          C.c_int64, c_i32p, c_i32p]),
     "kkt_update_block_values": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_f64p]),
     "kkt_set_bc": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, c_i32p, C.c_double]),
     "kkt_set_const_nullspace": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),

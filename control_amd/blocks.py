@@ -18,7 +18,8 @@ from typing import Sequence
 import scipy.sparse as sp
 
 __all__ = ["instationary_blocks", "stationary_blocks", "instationary_incompressible_blocks",
-           "stationary_incompressible_blocks", "conform_to", "instationary_relinearisation_recipes"]
+           "stationary_incompressible_blocks", "conform_to", "instationary_relinearisation_recipes",
+           "instationary_build_recipes"]
 
 
 def _csr(A):
@@ -278,4 +279,50 @@ def instationary_relinearisation_recipes(tau: float, beta: float, n_t: int, CN: 
             if i + 1 < m:
                 inner.append((1, i, i + 1, i + 1, h, True, -1.0))
     outer = [(0, i, m + j, *r) if q == 1 else (0, m + i, j, *r) for (q, i, j, *r) in inner]
+    return {"inner": inner, "commutator": list(inner), "outer": outer, "m": m}
+
+
+def instationary_build_recipes(tau: float, beta: float, n_t: int, CN: bool):
+    """Every block of the inner, commutator and outer ``block_00`` systems of
+    ``instationary_incompressible_blocks`` as a recipe ``(quadrant, i, j, level, alpha, transpose,
+    gamma)``: block ``= alpha D_level(^T) + gamma M``.  The ``comb`` blocks are those of
+    ``instationary_relinearisation_recipes``; ``alpha = 0`` recipes are the ``mass(c)`` blocks,
+    ``gamma M`` with one rounding (``level`` 0, unused).  ``D = nu K + C(w)`` already carries the
+    stiffness term, so no block needs a stiffness operand of its own.  Per system the recipes
+    come in the row-major ``(i, j)`` order of the block dicts.  What is left to the host are the
+    outer system's ``tau B^T`` / ``tau B`` blocks: one value set each.
+
+    Returns ``{"inner": [...], "commutator": [...], "outer": [...], "m": m}`` with the quadrants of
+    the inner system (0..3) mapped into the outer ``block_00`` as
+    ``instationary_incompressible_blocks`` places them."""
+    rec = []
+    if not CN:
+        m = n_t
+        for i in range(n_t):
+            if i < n_t - 1:
+                rec.append((0, i, i, 0, 0.0, False, tau))
+                rec.append((1, i, i + 1, 0, 0.0, False, -1.0))
+            rec.append((1, i, i, i, tau, True, 1.0))
+            rec.append((2, i, i, i, tau, False, 1.0))
+            if i >= 1:
+                rec.append((2, i, i - 1, 0, 0.0, False, -1.0))
+                rec.append((3, i, i, 0, 0.0, False, -tau / beta))
+    else:
+        m = n_t - 1
+        h = 0.5 * tau
+        for i in range(m):
+            if i >= 1:
+                rec.append((0, i, i - 1, 0, 0.0, False, h))
+                rec.append((2, i, i - 1, i, h, False, -1.0))
+            rec.append((0, i, i, 0, 0.0, False, h))
+            rec.append((1, i, i, i, h, True, 1.0))
+            rec.append((2, i, i, i + 1, h, False, 1.0))
+            rec.append((3, i, i, 0, 0.0, False, -h / beta))
+            if i + 1 < m:
+                rec.append((1, i, i + 1, i + 1, h, True, -1.0))
+                rec.append((3, i, i + 1, 0, 0.0, False, -h / beta))
+    inner = sorted(rec, key=lambda r: r[:3])
+    shift = {0: (0, 0), 1: (0, m), 2: (m, 0), 3: (m, m)}
+    outer = sorted(((0, i + shift[q][0], j + shift[q][1], *r) for (q, i, j, *r) in inner),
+                   key=lambda r: r[:3])
     return {"inner": inner, "commutator": list(inner), "outer": outer, "m": m}

@@ -182,7 +182,15 @@ int kkt_set_shard_families(kkt_handle h, int rank, int world, int families) {
 int kkt_add_block(kkt_handle h, int q, int i, int j, int64_t nrows, int64_t ncols,
                   const int32_t *indptr, const int32_t *indices, const double *values,
                   int64_t share_id) {
-    KKT_TRY(h, S.add_block(q, i, j, nrows, ncols, indptr, indices, values, share_id));
+    KKT_TRY(h, {
+        if (!values) fail(KKT_ERR_ARG, "bad block args");
+        S.add_block(q, i, j, nrows, ncols, indptr, indices, values, share_id);
+    });
+}
+
+int kkt_add_block_structure(kkt_handle h, int q, int i, int j, int64_t nrows, int64_t ncols,
+                            const int32_t *indptr, const int32_t *indices) {
+    KKT_TRY(h, S.add_block(q, i, j, nrows, ncols, indptr, indices, nullptr, -1));
 }
 
 int kkt_update_block_values(kkt_handle h, int q, int i, int j, const double *values) {
@@ -202,6 +210,7 @@ int kkt_finalize(kkt_handle h) { KKT_TRY(h, S.finalize()); }
 int kkt_set_pc_schur(kkt_handle h, const kkt_pc_desc *desc) {
     KKT_TRY(h, {
         if (!desc) fail(KKT_ERR_ARG, "null descriptor");
+        S.require_values("kkt_set_pc_schur");
         S.pc.reset();
         S.pc_cb = nullptr;
         S.pc.reset(new SchurPC(S, *desc));
@@ -213,6 +222,9 @@ int kkt_set_pc_stokes(kkt_handle h, kkt_handle inner, kkt_handle commutator,
                       const kkt_pc_stokes_desc *desc) {
     KKT_TRY(h, {
         if (!desc || !inner || !commutator) fail(KKT_ERR_ARG, "null argument");
+        S.require_values("kkt_set_pc_stokes");
+        inner->S.require_values("kkt_set_pc_stokes (inner handle)");
+        commutator->S.require_values("kkt_set_pc_stokes (commutator handle)");
         S.pc.reset();
         S.pc_cb = nullptr;
         S.pc.reset(new StokesPC(S, inner->S, commutator->S, *desc));
@@ -267,6 +279,7 @@ int kkt_apply(kkt_handle h, const double *x, double *y) {
     KKT_TRY(h, {
         if (!x || !y) fail(KKT_ERR_ARG, "null vector");
         if (!S.finalized) fail(KKT_ERR_STATE, "system not finalized");
+        S.require_values("kkt_apply");   // before anything is staged
         DevBuf<double> dx = S.new_vec(), dy = S.new_vec();
         up(S, dx.get(), x);
         S.apply(dx.get(), dy.get());
@@ -278,6 +291,7 @@ int kkt_pc_apply(kkt_handle h, const double *x, double *y) {
     KKT_TRY(h, {
         if (!x || !y) fail(KKT_ERR_ARG, "null vector");
         if (!S.finalized) fail(KKT_ERR_STATE, "system not finalized");
+        S.require_values("kkt_pc_apply");   // before anything is staged
         DevBuf<double> dx = S.new_vec(), dy = S.new_vec();
         up(S, dx.get(), x);
         S.pc_apply(dx.get(), dy.get());
@@ -305,6 +319,7 @@ int kkt_solve(kkt_handle h, const double *b, double *u, int *its, int *reason, d
     KKT_TRY(h, {
         if (!b || !u) fail(KKT_ERR_ARG, "null vector");
         if (!S.finalized) fail(KKT_ERR_STATE, "system not finalized");
+        S.require_values("kkt_solve");   // before anything is staged
         DevBuf<double> db = S.new_vec(), du = S.new_vec();
         up(S, db.get(), b);
         up(S, du.get(), u);

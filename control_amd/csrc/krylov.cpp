@@ -88,6 +88,7 @@ void System::ns_pc_post(double *y, const double *u, const double *b) {
 // y = P pc_fn(P x) + (I - P) x   (preconditioner.py:562-656)
 void System::pc_apply(const double *d_x, double *d_y) {
     if (!finalized) fail(KKT_ERR_STATE, "system not finalized");
+    require_values("kkt_pc_apply");
     info.last_pc_applies++;
     if (pc && pc_stale) {
         pc->values_changed();
@@ -127,6 +128,7 @@ void System::pc_apply(const double *d_x, double *d_y) {
 void System::pc_apply_timed(const double *d_x, double *d_y, float *ms, int *launches,
                             int64_t *phases) {
     if (!finalized) fail(KKT_ERR_STATE, "system not finalized");
+    require_values("kkt_time_pc_sweeps");
     if (!pc) fail(KKT_ERR_STATE, "no built-in preconditioner");
     if (sharded) fail(KKT_ERR_STATE, "kkt_time_pc_sweeps on a time-sharded handle");
     if (pc_stale) {
@@ -140,6 +142,7 @@ void System::pc_apply_timed(const double *d_x, double *d_y, float *ms, int *laun
 
 void System::pc_apply_timed_stages(const double *d_x, double *d_y, kkt_pc_stage_times *out) {
     if (!finalized) fail(KKT_ERR_STATE, "system not finalized");
+    require_values("kkt_time_pc_stages");
     if (!pc) fail(KKT_ERR_STATE, "no built-in preconditioner");
     if (pc_stale) {
         pc->values_changed();
@@ -335,6 +338,7 @@ struct ProgramTimeout {
 void System::solve(const double *d_b, double *d_u, int *its_out, int *reason_out,
                    double *rnorm_out, double *hist, int hist_cap, int *hist_len) {
     if (!finalized) fail(KKT_ERR_STATE, "system not finalized");
+    require_values("kkt_solve");
     double *u0 = nullptr;
     if (pc) {
         if (!d_guess) d_guess = mem.adopt(new_vec());

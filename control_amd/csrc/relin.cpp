@@ -247,6 +247,7 @@ void relin_apply(System &T, System &PS, const double *d_v, int n, const kkt_reli
     launch_relin_compose(T.stream, P.d_jobs.get(), n, max_padded);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(T.stream));
+    for (int r = 0; r < n; ++r) T.mark_set(rec[r].quadrant, rec[r].i, rec[r].j);
     T.pc_stale = true;
 }
 

@@ -127,16 +127,23 @@ void launch_relin_gather(hipStream_t s, const RelinPlan &P) {
 
 // blockIdx.y selects the target block; each SELL slot gets alpha D(^T) + gamma M (blocks.py
 // _axpby: two products, one sum), Dirichlet columns zeroed as kkt_update_block_values does.
+// alpha == 0 (uniform over the block: the job is read through the scalar path): the constant
+// block gamma M (blocks.py `mass`: one product), D and the transpose permutation are not read.
 __global__ __launch_bounds__(256) void relin_compose_kernel(const ComposeJob *__restrict__ jobs) {
     const ComposeJob J = jobs[blockIdx.y];
+    const bool constant = J.alpha == 0.0;
     for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < J.npadded;
          p += (int64_t)gridDim.x * blockDim.x) {
         const int32_t k = J.sell2csr[p];
         double v = 0.0;
         if (k >= 0) {
             const int64_t ks = k >= J.nnz_s ? k - J.nnz_s : k;
-            const int64_t kd = J.tperm ? J.tperm[ks] : ks;
-            v = __dadd_rn(__dmul_rn(J.alpha, J.D[kd]), __dmul_rn(J.gamma, J.M[ks]));
+            if (constant) {
+                v = __dmul_rn(J.gamma, J.M[ks]);
+            } else {
+                const int64_t kd = J.tperm ? J.tperm[ks] : ks;
+                v = __dadd_rn(__dmul_rn(J.alpha, J.D[kd]), __dmul_rn(J.gamma, J.M[ks]));
+            }
             if (J.colmask && J.colmask[J.col[p]]) v = 0.0;
         }
         J.dst[p] = v;

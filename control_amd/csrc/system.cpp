@@ -281,9 +281,14 @@ int System::new_value_array(int pattern, const double *csr_vals) {
     ValueArray va;
     va.pattern = pattern;
     va.d_vals = mem.alloc<double>(P.npadded);
-    auto d_csr = DevBuf<double>::upload(csr_vals, (size_t)P.nnz);
-    launch_csr_to_sell(stream, d_csr.get(), P.d_sell2csr, va.d_vals, P.npadded);
-    HIPCHK(hipStreamSynchronize(stream));
+    if (csr_vals) {
+        auto d_csr = DevBuf<double>::upload(csr_vals, (size_t)P.nnz);
+        launch_csr_to_sell(stream, d_csr.get(), P.d_sell2csr, va.d_vals, P.npadded);
+        HIPCHK(hipStreamSynchronize(stream));
+    } else {
+        HIPCHK(hipMemsetAsync(va.d_vals, 0, P.npadded * sizeof(double), stream));
+        va.unset = true;
+    }
     values.push_back(va);
     info.bytes_device_values += P.npadded * 8;
     return (int)values.size() - 1;
@@ -293,7 +298,8 @@ void System::add_block(int q, int i, int j, int64_t nrows, int64_t ncols,
                        const int32_t *indptr, const int32_t *indices, const double *vals,
                        int64_t share_id) {
     if (!layout_set || finalized) fail(KKT_ERR_STATE, "kkt_add_block: wrong state");
-    if (q < 0 || q > 3 || !indptr || !indices || !vals) fail(KKT_ERR_ARG, "bad block args");
+    if (q < 0 || q > 3 || !indptr || !indices) fail(KKT_ERR_ARG, "bad block args");
+    if (!vals && share_id >= 0) fail(KKT_ERR_ARG, "a block without values cannot share them");
     const int nr = (q == KKT_Q00 || q == KKT_Q01) ? n0 : n1;
     const int nc = (q == KKT_Q00 || q == KKT_Q10) ? n0 : n1;
     const int64_t er = (q == KKT_Q00 || q == KKT_Q01) ? nx0 : nx1;
@@ -341,6 +347,7 @@ void System::add_block(int q, int i, int j, int64_t nrows, int64_t ncols,
     }
     blocks[key] = Block{q, i, j, va, order_counter[q]++};
     info.n_blocks_stored++;
+    info.blocks_unset += values[va].unset;
     info.nnz_blocks += indptr[nrows];
     info.rows_blocks += nrows;
 }
@@ -783,8 +790,27 @@ void System::finalize() {
     finalized = true;
 }
 
+void System::mark_set(int q, int i, int j) {
+    ValueArray &va = values[blocks.at(std::make_tuple(q, i, j)).va];
+    if (va.unset) {
+        va.unset = false;
+        info.blocks_unset--;
+    }
+}
+
+void System::require_values(const char *what) const {
+    if (!info.blocks_unset) return;
+    for (auto &kv : blocks)
+        if (values[kv.second.va].unset)
+            fail(KKT_ERR_STATE, std::string(what) + ": block (" + std::to_string(kv.second.q) + ", " +
+                                    std::to_string(kv.second.i) + ", " + std::to_string(kv.second.j) +
+                                    ") has a structure but no values yet (kkt_add_block_structure: " +
+                                    "compose or update it first)");
+}
+
 void System::update_block_values(int q, int i, int j, const double *vals) {
     if (!finalized) fail(KKT_ERR_STATE, "kkt_update_block_values needs a finalized system");
+    if (!vals) fail(KKT_ERR_ARG, "kkt_update_block_values: null values");
     auto it = blocks.find(std::make_tuple(q, i, j));
     if (it == blocks.end()) fail(KKT_ERR_ARG, "no such block");
     Block &blk = it->second;
@@ -801,6 +827,7 @@ void System::update_block_values(int q, int i, int j, const double *vals) {
     if (users <= 1) {
         fill(values[blk.va].d_vals, values[blk.va].colmask_set);
         HIPCHK(hipStreamSynchronize(stream));
+        mark_set(q, i, j);   // (an unset block has a value array of its own)
         pc_stale = true;
         return;
     }
@@ -850,6 +877,7 @@ void System::give_private_values(int q, int i, int j, DevBuf<double> fresh) {
 // y = A x  (preconditioner.py:375-543)
 void System::apply(const double *d_x, double *d_y) {
     if (!finalized) fail(KKT_ERR_STATE, "system not finalized");
+    require_values("kkt_apply");
     info.last_op_applies++;
     const double *xin = d_x;
     const int nb = n0_loc + n1_loc;

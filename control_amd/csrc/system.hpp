@@ -75,6 +75,7 @@ struct ValueArray {
     double *d_vals = nullptr;
     int64_t share_id = -1;
     int colmask_set = -2;   // -2: not decided yet; -1: none; >= 0: id of the bc set applied
+    bool unset = false;     // kkt_add_block_structure: zero-filled, nothing has written it yet
 };
 
 struct Block {
@@ -255,8 +256,13 @@ struct System {
     void set_layout(int n_blocks_00, int n_blocks_11, int64_t nx0_, int64_t nx1_, int CN_,
                     int s00, int s11);
     void set_shard(int rank_, int world_, int families_ = 1);
+    // vals == nullptr: structure only (kkt_add_block_structure) -- a zeroed, unset value array
     void add_block(int q, int i, int j, int64_t nrows, int64_t ncols, const int32_t *indptr,
                    const int32_t *indices, const double *vals, int64_t share_id);
+    // block (q, i, j) has been written on the device: no longer unset
+    void mark_set(int q, int i, int j);
+    // KKT_ERR_STATE naming the first unset block, if there is one (before `what` launches anything)
+    void require_values(const char *what) const;
     void update_block_values(int q, int i, int j, const double *vals);
     void give_private_values(int q, int i, int j, DevBuf<double> d_new);
     void set_bc(int k, int64_t n, const int32_t *idx, double alpha);

@@ -20,7 +20,7 @@ from . import _lib
 
 __all__ = ["Nullspace", "NoneNullspace", "ConstantNullspace", "DirichletBCNullspace",
            "FullNullspace", "MultiBlockSystem", "SchurPC", "StokesPC", "KSPResult",
-           "ChebSpec"]
+           "ChebSpec", "PatternOnly"]
 
 Q00, Q01, Q10, Q11 = 0, 1, 2, 3
 _KSP_TYPES = {"gmres": 0, "fgmres": 1, "minres": 2}
@@ -156,6 +156,17 @@ class KSPResult:
         return np.asarray(self.history)
 
 
+@dataclass
+class PatternOnly:
+    """A block given by its sparsity structure alone (sorted CSR ``indptr``, ``indices``):
+    ``kkt_add_block_structure`` registers it with a zeroed value array of its own, and the block
+    stays *unset* -- the system refuses to apply or solve -- until the device composes its values
+    (``kkt_relinearise_device``) or ``update_block_values`` writes them."""
+    indptr: object
+    indices: object
+    shape: tuple
+
+
 # --------------------------------------------------------------------------- helpers
 def _space_dim(space):
     if isinstance(space, (int, np.integer)):
@@ -272,9 +283,19 @@ class MultiBlockSystem:
                     continue
                 if self._sharded and not (self._lo <= i % self._mf < self._hi):
                     continue
+                ncols = nx0 if q in (Q00, Q10) else nx1
+                if isinstance(A, PatternOnly):
+                    indptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
+                    indices = np.ascontiguousarray(A.indices, dtype=np.int32)
+                    if tuple(A.shape) != (len(indptr) - 1, ncols):
+                        raise ValueError(f"block ({q}; {i}, {j}): pattern of the wrong shape")
+                    self._structure[(q, i, j)] = [len(indices), None, indices]
+                    self._ck(self._lib.kkt_add_block_structure(
+                        self._h, q, i, j, len(indptr) - 1, ncols,
+                        indptr.ctypes.data_as(_lib.c_i32p), indices.ctypes.data_as(_lib.c_i32p)))
+                    continue
                 indptr, indices, data = _as_csr(A)
                 nrows = len(indptr) - 1
-                ncols = nx0 if q in (Q00, Q10) else nx1
                 # the same Python object given for several (i, j) shares device storage
                 # (share_values=False: every block gets its own device copy -- "mode G", what
                 # the reference stores -- even when the host objects are shared)

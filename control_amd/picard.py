@@ -127,7 +127,9 @@ def non_linear_res_eval(pb: NavierStokesControl, D, v, zeta, p, mu):
             r00[i] = -Dz
         Dv = tau * (D[i] @ v[i]) + M @ v[i]
         if i == 0:               # :2499-2512: the initial-condition row
-            D0 = pb.D_v(v_0)
+            # v_0 omitted: D0 multiplies zeros, any finite matrix gives the same +0.0 rows --
+            # no assembly (a given initial condition costs this one, for a constant data row)
+            D0 = D[0] if pb.v_0 is None else pb.D_v(v_0)
             r01[0] = tau * (D0 @ v_0) + M @ v_0 - Dv
         else:                    # :2518-2540, :2586-2615
             r01[i] = (tau * (M @ pb.f[i]) + M @ v[i - 1] - Dv
@@ -166,7 +168,8 @@ class GpuLinearSolver:
 
     def __init__(self, pb: NavierStokesControl, *, mass=(20, 0.3924, 2.0598), schur=None,
                  kp=None, mp=(20, 0.5, 2.0), solver_parameters=None, device=0, comm=None,
-                 host_allreduce=None, options=None, Multigrid=False, relinearise="host"):
+                 host_allreduce=None, options=None, Multigrid=False, relinearise="host",
+                 build="host"):
         """``comm`` (``control_amd.dist``): the three systems are time-sharded (BASELINE
         configs[4] names 8 GPUs) -- every rank runs the same Picard loop on the whole iterate
         (residual and re-linearisation are host work on replicated data, as cheap as in the
@@ -175,19 +178,31 @@ class GpuLinearSolver:
         (in place over ranks, op 0 = sum: e.g. ``GlooTransport.allreduce``).
 
         ``relinearise="device"``: ``incompressible_non_linear_solve(..., device=True)`` keeps the
-        Picard iterate in HBM -- the first linear solve builds the three systems from host
-        blocks as before, every later re-linearisation re-assembles the convection blocks, the
+        Picard iterate in HBM -- the first linear solve builds the three systems (``build``),
+        every later re-linearisation re-assembles the convection blocks, the
         residual and the update on the GPU (``control_amd.relinearise``).  Needs the element
-        data of ``fem.rectangle_p2p1`` and a single GPU."""
+        data of ``fem.rectangle_p2p1`` and a single GPU.
+
+        ``build="device"`` (with ``relinearise="device"``): the first build crosses to the GPU
+        as patterns, the constant matrices of the plan and the starting iterate only --
+        ``_build_device`` registers every block of the three systems by its structure
+        (``PatternOnly``; ``tau B`` / ``tau B^T`` excepted: one value set each) and the device
+        composes them all (``blocks.instationary_build_recipes``).  No ``D_v`` / ``D_p`` assembly
+        and no block sums on the host."""
         if relinearise not in ("host", "device"):
             raise ValueError("relinearise must be 'host' or 'device'")
+        if build not in ("host", "device"):
+            raise ValueError("build must be 'host' or 'device'")
+        if build == "device" and relinearise != "device":
+            raise ValueError("build='device' needs relinearise='device'")
         if relinearise == "device":
             if comm is not None:
                 raise ValueError("relinearise='device' does not support time-sharded solvers")
             if getattr(pb.disc, "elem", None) is None:
                 raise ValueError("relinearise='device' needs a discretisation with element data "
                                  "(fem.rectangle_p2p1)")
-        self.relinearise = relinearise
+        self.relinearise, self.build = relinearise, build
+        self.setup_s = None             # wall time of setup(): the builds and the preconditioner
         self._device = None             # control_amd.relinearise.DeviceRelinearisation
         self.solve_times = []           # (start, end) perf_counter of every linearised solve
         self.pb, self.device = pb, device
@@ -213,8 +228,11 @@ class GpuLinearSolver:
                                                   pb.tau, pb.beta, pb.n_t, pb.CN)
 
     def _build(self, bl):
-        from .multiblock import (ChebSpec, ConstantNullspace, DirichletBCNullspace,
-                                 MultiBlockSystem, SchurPC, StokesPC)
+        self._build_systems(bl)
+        self._attach_pc(bl["m"])
+
+    def _build_systems(self, bl):
+        from .multiblock import ConstantNullspace, DirichletBCNullspace, MultiBlockSystem
         th, pb, m = self.pb.disc, self.pb, bl["m"]
         nsv = DirichletBCNullspace(th.boundary_v)
         kw = dict(sub_n_blocks_00_0=m, sub_n_blocks_11_0=m) if pb.CN else {}
@@ -232,6 +250,10 @@ class GpuLinearSolver:
         self.comm = MultiBlockSystem(th.n_p, th.n_p, *bl["commutator"], n_blocks_00=m,
                                      n_blocks_11=m, device=self.device, comm=self.dist,
                                      options=self.options)
+
+    def _attach_pc(self, m):
+        from .multiblock import ChebSpec, SchurPC, StokesPC
+        th, pb = self.pb.disc, self.pb
         s = self.specs
         schur, kp = ChebSpec(*s["schur"]), ChebSpec(*s["kp"])
         if self.multigrid:
@@ -247,6 +269,59 @@ class GpuLinearSolver:
         self.pc = StokesPC(inner=self.inner, inner_pc=inner_pc, commutator=self.comm, B=th.B,
                            K_p=th.K_p, M_p=th.M_p, kp=kp, mp=ChebSpec(*s["mp"]),
                            n_p_blocks=m, b_scale=pb.tau, post_scale=1.0 / pb.tau**2, cn=pb.CN)
+
+    def _build_device(self, v, zeta, p, mu):
+        """The three systems from patterns: every velocity- and pressure-space block is a
+        ``PatternOnly`` of the plan's pattern, in the dict order of
+        ``instationary_incompressible_blocks`` (row-major: the apply order); the plan goes on the
+        finalized outer handle, the iterate is uploaded, ``D`` assembled and all blocks composed.
+        The preconditioner descriptors come last: their set-up reads composed values."""
+        from .blocks import (_csr, instationary_build_recipes,
+                             instationary_relinearisation_recipes)
+        from .multiblock import PatternOnly
+        from .relinearise import DeviceRelinearisation, RelinearisationPlan
+        pb, th = self.pb, self.pb.disc
+        plan = RelinearisationPlan(pb)
+        full = instationary_build_recipes(pb.tau, pb.beta, pb.n_t, pb.CN)
+        m = full["m"]
+        pat_v = PatternOnly(*plan.velocity_pattern(), (th.n_v, th.n_v))
+        pat_p = PatternOnly(*plan.pressure_pattern(), (th.n_p, th.n_p))
+
+        def dicts(n, recipes, pat):
+            quads = [{(i, j): None for i in range(n) for j in range(n)} for _ in range(4)]
+            for (q, i, j, *_) in recipes:
+                quads[q][(i, j)] = pat
+            return quads
+        outer = dicts(2 * m, full["outer"], pat_v)
+        tB = _csr(pb.tau * sp.csr_matrix(th.B))
+        tBT = _csr(tB.T)
+        for i in range(2 * m):
+            outer[1][(i, i)] = tBT
+            outer[2][(i, i)] = tB
+        self._build_systems({"outer": outer, "inner": dicts(m, full["inner"], pat_v),
+                             "commutator": dicts(m, full["commutator"], pat_p), "m": m})
+        recipes = instationary_relinearisation_recipes(pb.tau, pb.beta, pb.n_t, pb.CN)
+        self._device = dev = DeviceRelinearisation(pb, self.outer, recipes, plan=plan)
+        dev.set_state(v, zeta, p, mu)
+        dev.assemble()
+        for system, name in ((self.outer, "outer"), (self.inner, "inner"),
+                             (self.comm, "commutator")):
+            dev.relinearise(system, name, recipes=full[name])
+        self._attach_pc(m)
+
+    def setup(self, v, zeta, p, mu):
+        """Everything before the first linearised solve at the iterate ``(v, zeta, p, mu)``: the
+        three systems (``build="host"``: host assembly, block sums, uploads; ``"device"``:
+        ``_build_device``) and the preconditioner's set-up.  ``setup_s``: its wall time."""
+        t0 = time.perf_counter()
+        if self.build == "device":
+            self._build_device(v, zeta, p, mu)
+        else:
+            n_t = self.pb.n_t
+            self._build(self._blocks([self.pb.D_v(v[i]) for i in range(n_t)],
+                                     [self.pb.D_p(v[i]) for i in range(n_t)]))
+        self.outer._set_pc(self.pc)
+        self.setup_s = time.perf_counter() - t0
 
     def _update(self, bl):
         """Blocks that carry the linearised operator: all of ``block_01_int`` / ``block_10_int``
@@ -278,6 +353,9 @@ class GpuLinearSolver:
         return self.dist is None or self.inner._lo <= level < self.inner._hi
 
     def linear_solve(self, D, Dp, b_0, b_1):
+        if self.outer is None and self.build == "device":
+            raise RuntimeError("a build='device' solver is set up from the iterate: setup(), or "
+                               "incompressible_non_linear_solve(..., device=True)")
         bl = self._blocks(D, Dp)
         if self.outer is None:
             self._build(bl)
@@ -340,9 +418,8 @@ def _device_non_linear_solve(pb, ls, v, zeta, p, mu, max_non_linear_iter, rtol, 
     import ctypes as C
     th, n_t = pb.disc, pb.n_t
     fresh = ls.outer is None
-    if fresh:                # the first call builds the systems from host blocks, as before
-        ls._build(ls._blocks([pb.D_v(v[i]) for i in range(n_t)],
-                             [pb.D_p(v[i]) for i in range(n_t)]))
+    if fresh:                # the first call builds the systems (host blocks or patterns)
+        ls.setup(v, zeta, p, mu)
     dev = ls.device_plan()
     dev.set_state(v, zeta, p, mu)
     lib, outer = ls.outer._lib, ls.outer

@@ -100,6 +100,16 @@ class RelinearisationPlan:
                                              np.zeros((m, th.n_p)), np.zeros((m, th.n_p)))
         self.data = np.ascontiguousarray(np.concatenate([r00, r01]))
 
+    def velocity_pattern(self):
+        """``(indptr, indices)`` of a velocity-space block: the scalar P2 pattern once per
+        component, component-major (the structure of ``M_v`` / ``K_v``)."""
+        ip, ix, nnz = self.K2.indptr, self.K2.indices, self.K2.nnz
+        return (np.concatenate([ip, nnz + ip[1:]]).astype(np.int32),
+                np.concatenate([ix, self.n2 + ix]).astype(np.int32))
+
+    def pressure_pattern(self):
+        return self.Kp.indptr.astype(np.int32), self.Kp.indices.astype(np.int32)
+
     def descriptor(self):
         """``kkt_relin_desc`` over this plan's arrays (valid while the plan lives)."""
         pb, th, t = self.pb, self.pb.disc, self.tables
@@ -142,6 +152,8 @@ class DeviceRelinearisation:
     """The plan on the outer system of a ``GpuLinearSolver`` and the Picard iterate in HBM."""
 
     def __init__(self, pb, outer, recipes, plan=None):
+        """``recipes``: the blocks every re-linearisation rewrites, per system
+        (``blocks.instationary_relinearisation_recipes``)."""
         self.pb, self.outer = pb, outer
         self.plan = RelinearisationPlan(pb) if plan is None else plan
         self._lib = outer._lib
@@ -176,10 +188,13 @@ class DeviceRelinearisation:
         self.outer._ck(self._lib.kkt_relinearise_device(self.outer.handle, self.outer.handle,
                                                         self.d_v, 0, None))
 
-    def relinearise(self, system, name):
+    def relinearise(self, system, name, recipes=None):
         """Rewrite ``system``'s recipe blocks (``name``: "outer", "inner" or "commutator") from
-        the last assembly."""
+        the last assembly.  ``recipes``: another list for this call (the first build composes
+        every block, ``blocks.instationary_build_recipes``)."""
         arr, n = self.recipes[name]
+        if recipes is not None:
+            arr, n = _recipe_array(recipes, 1 if name == "commutator" else 0), len(recipes)
         system._ck(self._lib.kkt_relinearise_device(system.handle, self.outer.handle, None, n, arr))
 
     def residual(self, d_out, rhs):

@@ -169,6 +169,17 @@ int kkt_add_block(kkt_handle h, int quadrant, int i, int j,
                   int64_t nrows, int64_t ncols,
                   const int32_t *indptr, const int32_t *indices,
                   const double *values, int64_t share_id);
+/* The structure of a block whose values are produced on the device.  Registers block (i, j) as
+ * kkt_add_block does with share_id < 0 -- shared index arrays, SELL layout, a value array of its
+ * own -- but uploads no values: the array is zero-filled and the block is *unset*.
+ * kkt_finalize accepts unset blocks.  While a handle holds one, kkt_apply*, kkt_pc_apply*,
+ * kkt_solve*, kkt_time_* and kkt_set_pc_schur / kkt_set_pc_stokes (on the handle, its inner or its
+ * commutator handle) return KKT_ERR_STATE before anything is launched; kkt_last_error names the
+ * first such block as (quadrant, i, j).  A block becomes set when kkt_relinearise_device composes
+ * into it or kkt_update_block_values writes it.  kkt_info.blocks_unset counts them. */
+int kkt_add_block_structure(kkt_handle h, int quadrant, int i, int j,
+                            int64_t nrows, int64_t ncols,
+                            const int32_t *indptr, const int32_t *indices);
 /* New values on the stored structure of a block (re-linearisation in a Picard loop,
  * control.py:3377-3590); valid after kkt_finalize.  A built-in preconditioner whose matrices
  * are sums with block values is marked stale and rebuilt once, on the device, at its next
@@ -379,7 +390,8 @@ int kkt_set_relinearisation(kkt_handle h, const kkt_relin_desc *desc);
 
 /* One block a recipe rewrites: block (quadrant; i, j) = alpha D_level(^T) + gamma M, with D, M
  * on the velocity (space 0, both components) or pressure (space 1) pattern -- the `comb`
- * coefficients of blocks.instationary_blocks (control.py:2889-2978, 3851-3885). */
+ * coefficients of blocks.instationary_blocks (control.py:2889-2978, 3851-3885).  alpha = 0: the
+ * constant block gamma M (its `mass` coefficients); D is not read. */
 typedef struct kkt_relin_recipe {
     int quadrant, i, j;
     int space;
@@ -571,6 +583,8 @@ typedef struct kkt_info {
     int64_t apply_launches;     /* kernel launches of one kkt_apply (block rows only) */
     int64_t apply_switched;     /* ... of which run the width-switched kernel for ragged
                                    structures (P2 / Stokes blocks; option "ragged_switch") */
+    int64_t blocks_unset;       /* blocks added by kkt_add_block_structure that no composition or
+                                   update has written yet */
 } kkt_info;
 int kkt_get_info(kkt_handle h, kkt_info *info);
 
