@@ -170,6 +170,9 @@ SIGNATURES = {
     "kkt_picard_iterate": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4),
     "kkt_picard_residual_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_f64p]),
     "kkt_picard_update_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kkt_debug_relin_array": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int64]),
+    "kkt_debug_block_values": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_f64p,
+                                         C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "kkt_time_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                  C.POINTER(C.c_float)]),
     "kkt_time_pc_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

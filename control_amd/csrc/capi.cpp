@@ -386,6 +386,34 @@ int kkt_picard_residual_device(kkt_handle plan, double *d_out, int rhs, double *
 int kkt_picard_update_device(kkt_handle plan, double *d_u) {
     KKT_TRY(plan, relin_update(S, d_u));
 }
+int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap) {
+    KKT_TRY(plan, relin_debug_array(S, which, out, cap));
+}
+int kkt_debug_block_values(kkt_handle h, int quadrant, int i, int j, double *out, int64_t cap,
+                           int64_t *nnz, int *padding_zero) {
+    KKT_TRY(h, {
+        if (!nnz || !padding_zero) fail(KKT_ERR_ARG, "kkt_debug_block_values: null argument");
+        auto it = S.blocks.find(std::make_tuple(quadrant, i, j));
+        if (it == S.blocks.end()) fail(KKT_ERR_ARG, "kkt_debug_block_values: no such block");
+        const ValueArray &va = S.values[it->second.va];
+        const Pattern &P = S.patterns[va.pattern];
+        *nnz = P.nnz;
+        if (!out) return KKT_OK;
+        if (cap < P.nnz) fail(KKT_ERR_ARG, "kkt_debug_block_values: buffer too small");
+        S.sync();
+        std::vector<int32_t> map((size_t)P.npadded);
+        std::vector<double> vals((size_t)P.npadded);
+        HIPCHK(hipMemcpy(map.data(), P.d_sell2csr, P.npadded * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(vals.data(), va.d_vals, P.npadded * 8, hipMemcpyDeviceToHost));
+        *padding_zero = 1;
+        for (int64_t p = 0; p < P.npadded; ++p) {
+            if (map[p] >= 0)
+                out[map[p]] = vals[p];
+            else if (vals[p] != 0.0 || std::signbit(vals[p]))
+                *padding_zero = 0;
+        }
+    });
+}
 
 static void time_loop(System &S, bool pc, const double *d_x, double *d_y, int reps, float *ms) {
     if (reps < 1 || !ms) fail(KKT_ERR_ARG, "bad timing arguments");

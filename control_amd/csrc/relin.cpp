@@ -295,6 +295,18 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
     HIPCHK(hipStreamSynchronize(S.stream));
 }
 
+void relin_debug_array(System &S, int which, double *out, int64_t cap) {
+    RelinPlan &P = plan_of(S);
+    if (!P.assembled) fail(KKT_ERR_STATE, "kkt_debug_relin_array: nothing assembled yet");
+    const double *src[4] = {P.d_Ev, P.d_Ep, P.d_D2, P.d_Dp};
+    const int64_t per_level[4] = {P.ne * RELIN_EV, P.ne * RELIN_EP, P.nnz2, P.nnz1};
+    if (which < 0 || which > 3) fail(KKT_ERR_ARG, "kkt_debug_relin_array: no such array");
+    const int64_t n = per_level[which] * P.n_t;
+    if (!out || cap < n) fail(KKT_ERR_ARG, "kkt_debug_relin_array: buffer too small");
+    HIPCHK(hipStreamSynchronize(S.stream));
+    HIPCHK(hipMemcpy(out, src[which], n * 8, hipMemcpyDeviceToHost));
+}
+
 void relin_update(System &S, double *d_u) {
     RelinPlan &P = plan_of(S);
     if (!d_u) fail(KKT_ERR_ARG, "kkt_picard_update_device: null update");

@@ -85,5 +85,7 @@ void relin_state(System &S, int download, double *v, double *zeta, double *p, do
 void relin_iterate(System &S, double **v, double **zeta, double **p, double **mu);
 void relin_residual(System &S, double *d_out, int rhs, double *norm);
 void relin_update(System &S, double *d_u);
+// kkt_debug_relin_array: Ev, Ep, D2 or Dp of the last assembly, copied to the host
+void relin_debug_array(System &S, int which, double *out, int64_t cap);
 
 }  // namespace kkt

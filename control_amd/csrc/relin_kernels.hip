@@ -101,6 +101,8 @@ void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v)
 
 // One thread per (stored position, level): the contributions in ascending element-entry order
 // (np.bincount's order), then nu K + C with separate roundings (fem / picard D_v on the host).
+// `contract(off)` is what keeps the product and the sum apart: hipcc contracts by default, and
+// its __dmul_rn / __dadd_rn are plain operators that fuse into an fma like any others.
 __global__ __launch_bounds__(256) void relin_gather_kernel(
     const int32_t *__restrict__ cptr, const int32_t *__restrict__ clist,
     const double *__restrict__ E, int64_t per_level, const double *__restrict__ K, double nu,
@@ -108,11 +110,13 @@ __global__ __launch_bounds__(256) void relin_gather_kernel(
     const int64_t total = nnz * n_t;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
          t += (int64_t)gridDim.x * blockDim.x) {
+#pragma clang fp contract(off)
         const int64_t l = t / nnz, k = t - l * nnz;
         const double *El = E + l * per_level;
         double acc = 0.0;
-        for (int32_t j = cptr[k]; j < cptr[k + 1]; ++j) acc = __dadd_rn(acc, El[clist[j]]);
-        D[t] = __dadd_rn(__dmul_rn(nu, K[k]), acc);
+        for (int32_t j = cptr[k]; j < cptr[k + 1]; ++j) acc += El[clist[j]];
+        const double nuK = nu * K[k];
+        D[t] = nuK + acc;
     }
 }
 
@@ -126,7 +130,8 @@ void launch_relin_gather(hipStream_t s, const RelinPlan &P) {
 }
 
 // blockIdx.y selects the target block; each SELL slot gets alpha D(^T) + gamma M (blocks.py
-// _axpby: two products, one sum), Dirichlet columns zeroed as kkt_update_block_values does.
+// _axpby: two products, one sum, kept apart by `contract(off)` as in the gather), Dirichlet
+// columns zeroed as kkt_update_block_values does.
 // alpha == 0 (uniform over the block: the job is read through the scalar path): the constant
 // block gamma M (blocks.py `mass`: one product), D and the transpose permutation are not read.
 __global__ __launch_bounds__(256) void relin_compose_kernel(const ComposeJob *__restrict__ jobs) {
@@ -134,15 +139,17 @@ __global__ __launch_bounds__(256) void relin_compose_kernel(const ComposeJob *__
     const bool constant = J.alpha == 0.0;
     for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < J.npadded;
          p += (int64_t)gridDim.x * blockDim.x) {
+#pragma clang fp contract(off)
         const int32_t k = J.sell2csr[p];
         double v = 0.0;
         if (k >= 0) {
             const int64_t ks = k >= J.nnz_s ? k - J.nnz_s : k;
             if (constant) {
-                v = __dmul_rn(J.gamma, J.M[ks]);
+                v = J.gamma * J.M[ks];
             } else {
                 const int64_t kd = J.tperm ? J.tperm[ks] : ks;
-                v = __dadd_rn(__dmul_rn(J.alpha, J.D[kd]), __dmul_rn(J.gamma, J.M[ks]));
+                const double aD = J.alpha * J.D[kd], gM = J.gamma * J.M[ks];
+                v = aD + gM;
             }
             if (J.colmask && J.colmask[J.col[p]]) v = 0.0;
         }

@@ -449,6 +449,19 @@ class MultiBlockSystem:
                      power=int(r[3]), coarse=bool(r[4]), solves=int(r[5]))
                 for r in self._records(self._lib.kkt_debug_pc_matrices, 6)]
 
+    def block_values(self, quadrant, i, j):
+        """``kkt_debug_block_values``: ``(values, padding_zero)`` of a stored block -- its values
+        in the CSR order of its pattern, and whether every padding slot of the SELL array
+        holds ``0.0``."""
+        nnz, pad = C.c_int64(), C.c_int()
+        self._ck(self._lib.kkt_debug_block_values(self._h, quadrant, i, j, None, 0,
+                                                  C.byref(nnz), C.byref(pad)))
+        out = np.empty(nnz.value)
+        self._ck(self._lib.kkt_debug_block_values(self._h, quadrant, i, j,
+                                                  out.ctypes.data_as(_lib.c_f64p), out.size,
+                                                  C.byref(nnz), C.byref(pad)))
+        return out, bool(pad.value)
+
     def coarse_matrices(self):
         """``kkt_debug_coarse_matrices``: the Galerkin matrices P^T A P of the last coarse set-up,
         shape ``(matrices, n_coarse, n_coarse)`` (needs option ``coarse_keep`` = ``1``)."""

@@ -205,3 +205,15 @@ class DeviceRelinearisation:
 
     def update(self, d_u):
         self.outer._ck(self._lib.kkt_picard_update_device(self.outer.handle, d_u))
+
+    def debug_array(self, which):
+        """``kkt_debug_relin_array``: ``"Ev"`` (n_t, ne, 6, 6), ``"Ep"`` (n_t, ne, 3, 3), ``"D2"``
+        (n_t, nnz2) or ``"Dp"`` (n_t, nnz1) of the last assembly."""
+        n_t, ne = self.pb.n_t, len(self.plan.V)
+        shape = {"Ev": (n_t, ne, 6, 6), "Ep": (n_t, ne, 3, 3), "D2": (n_t, self.plan.K2.nnz),
+                 "Dp": (n_t, self.plan.Kp.nnz)}[which]
+        out = np.empty(shape)
+        self.outer._ck(self._lib.kkt_debug_relin_array(
+            self.outer.handle, ("Ev", "Ep", "D2", "Dp").index(which),
+            out.ctypes.data_as(_lib.c_f64p), out.size))
+        return out

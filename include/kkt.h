@@ -426,6 +426,20 @@ int kkt_picard_residual_device(kkt_handle plan, double *d_out, int rhs, double *
  * the initial guess of the next linearised solve. */
 int kkt_picard_update_device(kkt_handle plan, double *d_u);
 
+/* Test hooks of the device re-linearisation: plain copies of what the kernels left, no launches.
+ * kkt_debug_relin_array downloads one array of the plan's last assembly (cap: doubles available
+ * at out): the element matrices Ev (n_t x ne x 36) and Ep (n_t x ne x 9), or the assembled
+ * D2 (n_t x nnz2) and Dp (n_t x nnz1).  KKT_ERR_STATE before any assembly, KKT_ERR_ARG when cap
+ * is too small. */
+enum { KKT_RELIN_EV = 0, KKT_RELIN_EP = 1, KKT_RELIN_D2 = 2, KKT_RELIN_DP = 3 };
+int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
+/* The stored values of block (quadrant, i, j) in the CSR order of its pattern, read from the
+ * SELL value array through the pattern's slot -> CSR map.  *nnz: the stored entries (out == NULL:
+ * only that); *padding_zero: 1 when every padding slot of the value array holds 0.0.  A value
+ * array that several blocks share is read as it is. */
+int kkt_debug_block_values(kkt_handle h, int quadrant, int i, int j, double *out, int64_t cap,
+                           int64_t *nnz, int *padding_zero);
+
 /* `reps` back-to-back kkt_apply_device / kkt_pc_apply_device launches timed with HIP
  * events on the library's own stream; *ms = total elapsed milliseconds. */
 int kkt_time_apply(kkt_handle h, const double *d_x, double *d_y, int reps, float *ms);

@@ -137,7 +137,8 @@ def test_device_residual_matches_host(CN):
     assert abs(norm - np.linalg.norm(ref)) <= 1e-12 * np.linalg.norm(ref)
 
 
-def _compare_loops(pb, make, **kw):
+def _compare_loops(pb, make, norm_floor=0.0, **kw):
+    """``norm_floor``: an absolute allowance on the residual norms, relative to the first one."""
     ref = picard.incompressible_non_linear_solve(pb, make("host"), print_error_non_linear=False,
                                                  **kw)
     out = picard.incompressible_non_linear_solve(pb, make("device"), device=True,
@@ -146,7 +147,7 @@ def _compare_loops(pb, make, **kw):
     assert out["linear_iterations"] == ref["linear_iterations"]
     assert out["converged"] == ref["converged"]
     for a, b in zip(out["norms"], ref["norms"]):
-        assert abs(a - b) <= 1e-8 * b
+        assert abs(a - b) <= 1e-8 * b + norm_floor * ref["norms"][0]
     for key in ("v", "zeta", "p", "mu"):
         assert out[key].shape == ref[key].shape
         assert np.abs(out[key] - ref[key]).max() <= 1e-9 * max(1.0, np.abs(ref[key]).max()), key
@@ -172,7 +173,10 @@ def test_device_loop_manufactured():
           "monitor_convergence": False}
     auto = (-1, 0.0, 0.0)
     specs = dict(mass=(20, 0.3924, 2.0598), schur=auto, kp=auto, mp=(20, 0.5, 2.0))
-    ref, out = _compare_loops(pb, lambda r: _solver(pb, r, specs=specs, sp=sp), v=v0,
+    # the loop drives the residual six decades below its first norm (1.37 to 8e-7): what is left is
+    # a difference of terms of the first norm's size, and two evaluations of it agree no better than
+    # the 1e-12 of that size that test_device_residual_matches_host asks of one evaluation
+    ref, out = _compare_loops(pb, lambda r: _solver(pb, r, specs=specs, sp=sp), norm_floor=1e-12, v=v0,
                               max_non_linear_iter=10, relative_non_linear_tol=1.0e-6,
                               absolute_non_linear_tol=1.0e-6)
     assert out["converged"]
