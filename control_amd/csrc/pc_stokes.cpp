@@ -25,14 +25,16 @@ static RowOp base_op(const Pattern &P) {
     return op;
 }
 
-static RowLaunch upload_launch(DevPool &mem, const Pattern &P, std::vector<RowOp> &ops) {
+static RowLaunch upload_launch(DevPool &mem, const Pattern &P, std::vector<RowOp> &ops,
+                               bool shared_rows) {
     RowLaunch L;
     L.nops = (int)ops.size();
     L.max_slices = P.nslices;
     L.R = P.R;
     L.uniform_w = P.uniform_w;
     // every op applies one and the same matrix: the four-blocks-per-thread form applies
-    L.shared_matrix = !ops.empty();
+    // (unless option "shared_rows" = "0")
+    L.shared_matrix = shared_rows && !ops.empty();
     for (const RowOp &op : ops)
         L.shared_matrix = L.shared_matrix && op.nterms == 1 && op.t[0].vals == ops[0].t[0].vals &&
                           op.col == ops[0].col && op.rowmask == ops[0].rowmask;
@@ -81,7 +83,7 @@ void StokesPC::emit_cheb(std::vector<ChainStep> &dst, const DevMat &A, int its, 
         op.c3 = scale;
         ops[k] = op;
     }
-    dst.push_back(ChainStep{upload_launch(mem_, P, ops)});
+    dst.push_back(ChainStep{upload_launch(mem_, P, ops, S_.opts.shared_rows)});
     if (its <= 1) return;
     const double alpha = 1.0 - scale * emin, mu = 1.0 / alpha, omegaprod = 2.0 / alpha;
     double c_km1 = 1.0, c_k = mu;
@@ -104,7 +106,7 @@ void StokesPC::emit_cheb(std::vector<ChainStep> &dst, const DevMat &A, int its, 
             op.c3 = scale * omega;
             ops[k] = op;
         }
-        dst.push_back(ChainStep{upload_launch(mem_, P, ops)});
+        dst.push_back(ChainStep{upload_launch(mem_, P, ops, S_.opts.shared_rows)});
         c_km1 = c_k;
         c_k = c_kp1;
     }
@@ -213,7 +215,7 @@ void StokesPC::emit_kp_two_grid(int its, double emin, double emax, const double 
                 op.z = vabs(blk(b, k));
                 ops[k] = op;
             }
-            kp_steps_.push_back(ChainStep{upload_launch(mem_, P, ops)});
+            kp_steps_.push_back(ChainStep{upload_launch(mem_, P, ops, S_.opts.shared_rows)});
             r = kp_r_;
         }
         ChainStep cs;
@@ -245,7 +247,7 @@ void StokesPC::emit_kp_two_grid(int its, double emin, double emax, const double 
                 op.c3 = step == 1 ? scale : c3[step];
                 ops[k] = op;
             }
-            kp_steps_.push_back(ChainStep{upload_launch(mem_, P, ops)});
+            kp_steps_.push_back(ChainStep{upload_launch(mem_, P, ops, S_.opts.shared_rows)});
         }
         xcur = target(its);
     }
@@ -332,7 +334,7 @@ StokesPC::StokesPC(System &outer, System &inner, System &commutator, const kkt_p
             }
             ops.push_back(op);
         }
-        lin_.push_back(upload_launch(mem_, P, ops));
+        lin_.push_back(upload_launch(mem_, P, ops, S_.opts.shared_rows));
     }
     int kp_its = d.kp_its;
     double kp_emin = d.kp_emin, kp_emax = d.kp_emax;

@@ -72,8 +72,10 @@ def stokes_problem(n=4, n_t=4, beta=1.0e-2, T=2.0, CN=False, share=True):
 
 
 def stokes_gpu(p, specs=STOKES_SPECS, options=None, comm=None, device=0, coarse=None,
-               kp_coarse=None):
-    """Outer system, velocity KKT system and pressure commutator on the GPU + the StokesPC."""
+               kp_coarse=None, b_scale=None, post_scale=None):
+    """Outer system, velocity KKT system and pressure commutator on the GPU + the StokesPC.
+    ``b_scale`` / ``post_scale``: the two scalings of the pressure stage, ``tau`` and
+    ``1 / tau^2`` unless given."""
     from .multiblock import (ChebSpec, CoarseSpace, ConstantNullspace, DirichletBCNullspace,
                              MultiBlockSystem, SchurPC, StokesPC)
     th, m, CN, bl = p["th"], p["m"], p["CN"], p["blocks"]
@@ -105,7 +107,8 @@ def stokes_gpu(p, specs=STOKES_SPECS, options=None, comm=None, device=0, coarse=
         kp.coarse = CoarseSpace(kp_coarse[0], int(kp_coarse[1]))
     gpc = StokesPC(inner=inner, inner_pc=inner_pc, commutator=commutator, B=th.B, K_p=th.K_p,
                    M_p=th.M_p, kp=kp, mp=ChebSpec(*specs["mp"]),
-                   n_p_blocks=m, b_scale=p["tau"], post_scale=1.0 / p["tau"]**2, cn=CN)
+                   n_p_blocks=m, b_scale=p["tau"] if b_scale is None else b_scale,
+                   post_scale=1.0 / p["tau"]**2 if post_scale is None else post_scale, cn=CN)
     return outer, gpc
 
 

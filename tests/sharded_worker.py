@@ -239,3 +239,54 @@ def run_rank_coarse(rank, world, conns, out_q):
     except Exception as e:
         import traceback
         out_q.put((rank, "error", traceback.format_exc() + repr(e)))
+
+
+def run_rank_stokes_pressure_stage(rank, world, conns, out_q, CN=False):
+    """The pressure stage of the StokesPC on a time shard (tests/stokes_stage_ref.py): m = world
+    + 1 levels, so the last rank holds a single one.  Both input kinds: the rank's pressure rows
+    against the one-rank extended-precision reference under the criterion of
+    tests/test_gpu_stokes_pressure_stage.py.  The reference takes the u_0 of THIS run, gathered
+    from the ranks: the sharded nested GMRES sums its inner products rank by rank, so its u_0 is
+    not the one-rank run's bit for bit (and backward Euler amplifies the difference).  With the
+    zero velocity right-hand side u_0 = 0 on every rank and the whole shard equals the one-rank
+    GPU run bit for bit; with the random one the distance to it is reported."""
+    try:
+        import common
+        import stokes_stage_ref as ref
+        from control_amd.dist import CallbackComm, PipeTransport, shard_range
+        c = ref.case(4, world + 1, CN, kp_its=9, mp_its=8)
+        p = ref.problem(c)
+        m, nv = p["m"], p["th"].n_v
+        lo, hi = shard_range(m, rank, world)
+        tr = PipeTransport(rank, world, conns)
+        comm = CallbackComm(rank, world, tr.allreduce, tr.sendrecv)
+        outer, gpc = ref.stage_gpu(c, comm=comm)
+        one, one_pc = ref.stage_gpu(c)
+        pick = list(range(lo, hi)) + list(range(m + lo, m + hi))
+        k0 = 2 * (hi - lo) * nv
+
+        def shard(v):   # global flat -> [v_lo.., zeta_lo.. | mu_lo.., p_lo..]
+            v0, v1 = ref.split(p, np.asarray(v))
+            return np.concatenate([v0[pick].ravel(), v1[pick].ravel()])
+
+        out = dict(levels=hi - lo)
+        for kind, x in zip(("zero_b0", "random"), ref.inputs(c)):
+            y = outer.pc_apply(shard(x), gpc)
+            y_one = shard(one.pc_apply(x, one_pc))
+            u0 = np.zeros((2 * m, nv))
+            u0[pick] = y[:k0].reshape(-1, nv)
+            u0[:, p["th"].boundary_v] = 0.0
+            tr.allreduce(u0.reshape(-1), 0)       # (sums with exact zeros: a gather)
+            if kind == "zero_b0":
+                out["u0_zero"] = not u0.any()
+            px, po, _ = ref.references(c, x, u0)
+            d = float(common.rel_err(po[pick], px[pick]))
+            e = float(common.rel_err(y[k0:], px[pick]))
+            out[kind] = dict(d=d, e=e, bound=ref.bound(d, c),
+                             ratio=e / max(d, ref.EPS * ref.its_total(c)),
+                             bitwise=bool(np.array_equal(y, y_one)),
+                             e_one=float(common.rel_err(y, y_one)))
+        out_q.put((rank, "ok", out))
+    except Exception as e:
+        import traceback
+        out_q.put((rank, "error", traceback.format_exc() + repr(e)))
