@@ -112,10 +112,11 @@ int kkt_create(kkt_handle *out, int device_id) {
             fail(KKT_ERR_HIP, "no HIP device available: libkkt has no CPU path");
         if (device_id < 0 || device_id >= ndev) fail(KKT_ERR_ARG, "device id out of range");
         HIPCHK(hipSetDevice(device_id));
-        kkt_system *h = new kkt_system();
+        auto h = std::make_unique<kkt_system>();
         h->S.device = device_id;
-        HIPCHK(hipStreamCreateWithFlags(&h->S.stream, hipStreamNonBlocking));
-        *out = h;
+        h->S.own_stream = Stream::create();
+        h->S.stream = h->S.own_stream;
+        *out = h.release();
         return KKT_OK;
     } catch (const Error &e) {
         g_create_error = e.msg;
@@ -213,7 +214,7 @@ int kkt_set_pc_schur(kkt_handle h, const kkt_pc_desc *desc) {
         S.require_values("kkt_set_pc_schur");
         S.pc.reset();
         S.pc_cb = nullptr;
-        S.pc.reset(new SchurPC(S, *desc));
+        S.pc = std::make_unique<SchurPC>(S, *desc);
         S.pc_stale = false;
     });
 }
@@ -227,7 +228,7 @@ int kkt_set_pc_stokes(kkt_handle h, kkt_handle inner, kkt_handle commutator,
         commutator->S.require_values("kkt_set_pc_stokes (commutator handle)");
         S.pc.reset();
         S.pc_cb = nullptr;
-        S.pc.reset(new StokesPC(S, inner->S, commutator->S, *desc));
+        S.pc = std::make_unique<StokesPC>(S, inner->S, commutator->S, *desc);
     });
 }
 
@@ -417,9 +418,7 @@ int kkt_debug_block_values(kkt_handle h, int quadrant, int i, int j, double *out
 
 static void time_loop(System &S, bool pc, const double *d_x, double *d_y, int reps, float *ms) {
     if (reps < 1 || !ms) fail(KKT_ERR_ARG, "bad timing arguments");
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
+    const Event e0 = Event::create(true), e1 = Event::create(true);
     HIPCHK(hipEventRecord(e0, S.stream));
     for (int r = 0; r < reps; ++r) {
         if (pc)
@@ -430,8 +429,6 @@ static void time_loop(System &S, bool pc, const double *d_x, double *d_y, int re
     HIPCHK(hipEventRecord(e1, S.stream));
     HIPCHK(hipEventSynchronize(e1));
     HIPCHK(hipEventElapsedTime(ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
 }
 int kkt_time_apply(kkt_handle h, const double *d_x, double *d_y, int reps, float *ms) {
     KKT_TRY(h, time_loop(S, false, d_x, d_y, reps, ms));

@@ -55,8 +55,7 @@ void System::ensure_workspace(int restart, bool flexible) {
     if (!d_red_scratch) d_red_scratch = mem.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX);
     d_hcol = ws_mem.alloc<double>(restart + 16);
     d_coef = ws_mem.alloc<double>(restart + 16);
-    if (h_pinned) (void)hipHostFree(h_pinned);
-    HIPCHK(hipHostMalloc((void **)&h_pinned, (restart + 16) * sizeof(double), 0));
+    h_pinned = PinnedBuf<double>::alloc(restart + 16);
     ws_restart = restart;
     ws_flexible = flexible;
 }

@@ -69,12 +69,6 @@ SchurPC::SchurPC(System &S, const kkt_pc_desc &d) : S_(S), d_(d) {
     build();
 }
 
-SchurPC::~SchurPC() {
-    segments_.clear();   // the graphs before the events and the stream they were captured on
-    for (hipEvent_t e : events_) (void)hipEventDestroy(e);
-    if (side_) (void)hipStreamDestroy(side_);
-}
-
 void SchurPC::clear_program() {
     segments_.clear();   // the graphs first: their nodes point into the program's memory
     program_mem_.release();
@@ -852,17 +846,14 @@ void SchurPC::time_programs(float *ms, int *launches, int64_t *phases) {
     *ms = 0.f;
     *launches = 0;
     *phases = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> evs;
+    std::vector<std::pair<Event, Event>> evs;
     size_t k = 0;
     while (k < steps_.size()) {
         if (steps_[k].kind == PcStep::PROG || steps_[k].kind == PcStep::TILE) {
-            hipEvent_t a, b;
-            HIPCHK(hipEventCreate(&a));
-            HIPCHK(hipEventCreate(&b));
-            HIPCHK(hipEventRecord(a, st));
+            evs.emplace_back(Event::create(true), Event::create(true));
+            HIPCHK(hipEventRecord(evs.back().first, st));
             replay(k, k + 1);
-            HIPCHK(hipEventRecord(b, st));
-            evs.push_back({a, b});
+            HIPCHK(hipEventRecord(evs.back().second, st));
             *launches += 1;
             *phases += steps_[k].nphases;
         } else {
@@ -875,8 +866,6 @@ void SchurPC::time_programs(float *ms, int *launches, int64_t *phases) {
         float t = 0.f;
         HIPCHK(hipEventElapsedTime(&t, e.first, e.second));
         *ms += t;
-        (void)hipEventDestroy(e.first);
-        (void)hipEventDestroy(e.second);
     }
 }
 
@@ -892,8 +881,8 @@ void PcBase::time_stages(kkt_pc_stage_times *out) {
 void SchurPC::time_stages(kkt_pc_stage_times *out) {
     hipStream_t st = S_.stream;
     *out = kkt_pc_stage_times{};
-    std::vector<hipEvent_t> ev(steps_.size() + 1);
-    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+    std::vector<Event> ev(steps_.size() + 1);
+    for (Event &e : ev) e = Event::create(true);
     HIPCHK(hipEventRecord(ev[0], st));
     for (size_t k = 0; k < steps_.size(); ++k) {
         replay(k, k + 1);
@@ -923,7 +912,6 @@ void SchurPC::time_stages(kkt_pc_stage_times *out) {
                 out->batched_launches += 1;
         }
     }
-    for (auto &e : ev) (void)hipEventDestroy(e);
 }
 
 bool SchurPC::timed_out(std::string *why) {
@@ -2235,14 +2223,8 @@ void SchurPC::emit_comm(const double *send, int dst, double *recv, int src) {
 void SchurPC::replay(size_t first, size_t last) {
     const bool xcd = S_.opts.pc_xcd;
     Bases B{{nullptr, nullptr, nullptr, nullptr}};
-    if (n_events_ > 0 && !side_) {
-        HIPCHK(hipStreamCreateWithFlags(&side_, hipStreamNonBlocking));
-    }
-    while ((int)events_.size() < n_events_) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        events_.push_back(e);
-    }
+    if (n_events_ > 0 && !side_) side_ = Stream::create();
+    while ((int)events_.size() < n_events_) events_.push_back(Event::create(false));
     for (size_t k = first; k < last; ++k) {
         const PcStep &s = steps_[k];
         hipStream_t st = s.lane == 0 ? S_.stream : side_;
@@ -2358,22 +2340,7 @@ void SchurPC::run() {
             replay(g.first, g.last);
             continue;
         }
-        if (!g.exec) {
-            hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                replay(g.first, g.last);
-                e = hipStreamEndCapture(st, &g.graph);
-                if (e == hipSuccess) e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
-            }
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                g.exec = nullptr;
-                use_graph_ = false;   // plain launches of the same kernels
-                replay(g.first, g.last);
-                continue;
-            }
-        }
-        HIPCHK(hipGraphLaunch(g.exec, st));
+        run_captured(st, g, use_graph_, [&] { replay(g.first, g.last); });
     }
 }
 

@@ -119,7 +119,6 @@ class PcBase {
 class SchurPC : public PcBase {
    public:
     SchurPC(System &S, const kkt_pc_desc &d);
-    ~SchurPC() override;
     // u = pc_fn(b) on the fixed internal vectors in_ / out_ (bc-corrected by the caller)
     void run() override;
     double *in() override { return in_; }
@@ -146,10 +145,17 @@ class SchurPC : public PcBase {
    private:
     System &S_;
     kkt_pc_desc d_;
+    // Lifetimes go by declaration order (members are destroyed in reverse): the side stream, then
+    // the events, then the device memory, and segments_' graphs after all of them, so that the
+    // graphs go first and what their nodes name -- buffers, events, the stream -- goes after.
+    // Side lane: work that does not depend on the sweep in flight (the mass solves and the
+    // right-hand-side products of later time levels) runs on a second stream while the
+    // latency-bound sweep program occupies a quarter of the wave slots.
+    Stream side_;                 // made by the first replay() of a program with events
+    std::vector<Event> events_;
     // Device memory by lifetime: the handle's; the current values' (mats_ and the coarse
     // inverses: values_changed() releases it); the current program's (steps_, tile tables, the
-    // interleaved iterates: clear_program() releases it).  Declared before everything that points
-    // into them -- segments_' graphs above all -- so that they are destroyed last.
+    // interleaved iterates: clear_program() releases it).
     DevPool handle_mem_, values_mem_, program_mem_;
     std::vector<int32_t> m_indptr_, m_indices_, bc_idx_;
     std::vector<double> m_values_;
@@ -214,12 +220,7 @@ class SchurPC : public PcBase {
     };
     std::vector<Segment> segments_;
     bool use_graph_ = true;
-    // Side lane: work that does not depend on the sweep in flight (the mass solves and the
-    // right-hand-side products of later time levels) runs on a second stream while the
-    // latency-bound sweep program occupies a quarter of the wave slots.
-    bool use_lanes_ = false;
-    hipStream_t side_ = nullptr;
-    std::vector<hipEvent_t> events_;
+    bool use_lanes_ = false;      // side lane (side_, events_)
     int cur_lane_ = 0;
     int n_events_ = 0;
     int emit_record(int lane);          // returns the event index
@@ -362,7 +363,9 @@ class StokesPC : public PcBase {
     double *in_ = nullptr, *out_ = nullptr, *h_ = nullptr, *m_ = nullptr, *g_ = nullptr;
     double *P_[3] = {nullptr, nullptr, nullptr};
     double *halo_a_ = nullptr, *halo_b_ = nullptr;   // CN on time shards: neighbour blocks of the T scans
-    DevPool mem_;   // declared before the chains: their graphs go first
+    // Lifetimes go by declaration order (members are destroyed in reverse): the device memory
+    // before the chains, so that their graphs go first and the buffers their nodes name after.
+    DevPool mem_;
     // a step of a pressure-space chain: a batched row launch, or -- two-grid K_p solve -- the
     // Galerkin correction x_out = x_in + P E^-1 P^T r of every block
     struct ChainStep {
@@ -375,7 +378,7 @@ class StokesPC : public PcBase {
     std::vector<ChainStep> kp_steps_, mp_steps_;
     // the two Chebyshev chains (hundreds of small launches on fixed buffers) replayed as graphs
     struct Chain : GraphExec {
-        bool failed = false;
+        bool usable = true;   // false once a capture failed: plain launches from then on
     } kp_chain_, mp_chain_;
     void run_chain(Chain &c, const std::vector<ChainStep> &steps);
     // two-grid K_p solve

@@ -459,26 +459,10 @@ void StokesPC::run_chain(Chain &c, const std::vector<ChainStep> &steps) {
                 launch_rowops(st, L.d_ops, L.nops, L.max_slices, L.R, B, 1, L.uniform_w);
         }
     };
-    if (S_.opts.no_graph || c.failed || steps.size() < 8) {
+    if (S_.opts.no_graph || !c.usable || steps.size() < 8)
         launches();
-        return;
-    }
-    if (!c.exec) {
-        hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            launches();
-            e = hipStreamEndCapture(st, &c.graph);
-            if (e == hipSuccess) e = hipGraphInstantiate(&c.exec, c.graph, nullptr, nullptr, 0);
-        }
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            c.exec = nullptr;
-            c.failed = true;          // plain launches of the same kernels from now on
-            launches();
-            return;
-        }
-    }
-    HIPCHK(hipGraphLaunch(c.exec, st));
+    else
+        run_captured(st, c, c.usable, launches);
 }
 
 void StokesPC::check() {

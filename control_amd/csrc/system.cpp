@@ -33,11 +33,7 @@ void StageClock::begin(hipStream_t s) {
 }
 void StageClock::mark(hipStream_t s, int stage) {
     if (!on) return;
-    if (used == pool.size()) {
-        hipEvent_t e;
-        HIPCHK(hipEventCreate(&e));
-        pool.push_back(e);
-    }
+    if (used == pool.size()) pool.push_back(Event::create(true));
     HIPCHK(hipEventRecord(pool[used], s));
     stage_of.push_back(stage);
     ++used;
@@ -59,24 +55,9 @@ void StageClock::finish(kkt_stage_times &out) {
     out.other_ms = acc[OTHER];
     out.total_ms = acc[OP] + acc[PC] + acc[ORTH] + acc[ALLREDUCE] + acc[OTHER];
 }
-StageClock::~StageClock() {
-    for (hipEvent_t e : pool) (void)hipEventDestroy(e);
-}
-
-System::~System() {
-    // device memory is released with the process or by hipDeviceReset; explicit frees keep
-    // long-lived hosts (Picard loops creating many systems) from accumulating HBM
-    (void)hipSetDevice(device);
-    pc.reset();
-    comm.reset();
-    ws_mem.release();   // after pc and comm, before the streams
-    mem.release();
-    if (h_pinned) (void)hipHostFree(h_pinned);
-    if (ev_x_ready) (void)hipEventDestroy(ev_x_ready);
-    if (ev_halo_ready) (void)hipEventDestroy(ev_halo_ready);
-    if (comm_stream) (void)hipStreamDestroy(comm_stream);
-    if (stream) (void)hipStreamDestroy(stream);
-}
+// The members release everything (system.hpp names the order); the caller's thread may have
+// another device current, which no declaration order can express.
+System::~System() { (void)hipSetDevice(device); }
 
 void System::set_layout(int n_blocks_00, int n_blocks_11, int64_t nx0_, int64_t nx1_, int CN_,
                         int s00, int s11) {
@@ -895,9 +876,9 @@ void System::apply(const double *d_x, double *d_y) {
     if (sharded) {
         // the exchange runs on the transport's stream, behind whatever produced x ...
         if (!comm_stream) {
-            HIPCHK(hipStreamCreateWithFlags(&comm_stream, hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&ev_x_ready, hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&ev_halo_ready, hipEventDisableTiming));
+            comm_stream = Stream::create();
+            ev_x_ready = Event::create(false);
+            ev_halo_ready = Event::create(false);
         }
         HIPCHK(hipEventRecord(ev_x_ready, stream));
         HIPCHK(hipStreamWaitEvent(comm_stream, ev_x_ready, 0));

@@ -136,18 +136,26 @@ struct KrylovCfg {
 struct StageClock {
     enum { OP = 0, PC = 1, ORTH = 2, ALLREDUCE = 3, OTHER = 4, NSTAGES = 5 };
     bool on = false;
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;
     std::vector<int> stage_of;     // stage of the interval that ends at event k (k >= 1)
     size_t used = 0;
     void begin(hipStream_t s);
     void mark(hipStream_t s, int stage);
     void finish(kkt_stage_times &out);   // synchronises on the last event
-    ~StageClock();
 };
 
+// Lifetimes go by declaration order (members are destroyed in reverse): the streams first, so that
+// they outlive everything queued on them, `stream` before all; then the events, the pinned buffer
+// and the clock's events; then the device pools; then comm and pc, whose graphs and buffers go
+// before the pools, events and streams their nodes name.
 struct System {
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream own_stream;                  // kkt_create
+    hipStream_t stream = nullptr;       // own_stream, or comm_stream while apply() exchanges halos
+    Stream comm_stream;                 // halo exchange, overlapped with interior rows (lazy)
+    Event ev_x_ready, ev_halo_ready;
+    PinnedBuf<double> h_pinned;         // Krylov workspace, host side (ensure_workspace)
+    StageClock clock;
     std::string err;
 
     // layout (global)
@@ -195,8 +203,6 @@ struct System {
     // apply plan
     std::vector<RowLaunch> apply_launches;
     int first_halo_launch = 0;    // launches [first_halo_launch, end) hold the rows that read a halo
-    hipStream_t comm_stream = nullptr;              // halo exchange, overlapped with interior rows
-    hipEvent_t ev_x_ready = nullptr, ev_halo_ready = nullptr;
     std::vector<std::vector<RowOp>> h_apply_ops;   // host copies (value pointers are re-pointed
                                                    // when an update un-shares a value array)
     std::map<std::tuple<int, int, int>, std::tuple<int, int, int>> block_term;   // -> launch, op, term
@@ -223,6 +229,7 @@ struct System {
     std::vector<double> coarse_E;      // its Galerkin matrices (option "coarse_keep" = "1")
     std::vector<double> coarse_Einv;   // ... and their inverses
 
+    std::unique_ptr<Comm> comm;
     // preconditioner
     std::unique_ptr<PcBase> pc;
     bool pc_stale = false;   // block values changed since the preconditioner was built
@@ -230,7 +237,6 @@ struct System {
     void *pc_cb_user = nullptr;
     bool pc_cb_failed = false;
 
-    std::unique_ptr<Comm> comm;
     std::unique_ptr<RelinPlan> relin;   // kkt_set_relinearisation (relin.hpp)
 
     KrylovCfg ksp;
@@ -238,7 +244,6 @@ struct System {
     // execution options (kkt_set_option); a key that was never set has its built-in default
     // (the library does not read the environment)
     Options opts;
-    StageClock clock;
     kkt_stage_times stage_times{};
     std::vector<double> tile_coords;   // kkt_set_tile_coordinates: N_x x tile_dim, or empty
     int tile_dim = 0;
@@ -247,10 +252,9 @@ struct System {
     bool ws_flexible = false;
     double *d_V = nullptr, *d_Z = nullptr, *d_w = nullptr, *d_t1 = nullptr, *d_t2 = nullptr;
     double *d_red_scratch = nullptr, *d_hcol = nullptr, *d_coef = nullptr;
-    double *h_pinned = nullptr;
 
     System() = default;
-    ~System();
+    ~System();   // selects the device for the members' destructors
 
     // -- definition
     void set_layout(int n_blocks_00, int n_blocks_11, int64_t nx0_, int64_t nx1_, int CN_,

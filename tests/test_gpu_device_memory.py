@@ -10,7 +10,8 @@ the granule skips the test (not measured), it does not pass it.
 
 Before the owner types of csrc/devmem.hpp the error leg lost 2 MiB about every second cycle (the
 error leaves a constructor whose destructor held the frees) and the other two legs were flat:
-profiles/device_memory_owners.md."""
+profiles/device_memory_owners.md.  The leg over streams, events and pinned memory is a guard:
+whether those show in hipMemGetInfo at all is not known (profiles/host_resource_owners.md)."""
 import ctypes
 import time
 
@@ -19,6 +20,7 @@ import pytest
 import scipy.sparse as sp
 
 import common
+from control_amd import _lib
 from control_amd._lib import KktError
 from control_amd.coarse import multilinear_coarse_space
 from test_gpu_coarse_setup import _convection_problem
@@ -93,6 +95,52 @@ def test_create_and_destroy_returns_the_memory():
         g.close()
 
     _check("create / destroy", cycle)
+
+
+def test_create_and_destroy_returns_streams_events_and_pinned_memory():
+    """Every owner of csrc/devmem.hpp that is no device buffer, in one create / destroy cycle:
+    "stage_timers" makes the clock's event pool, a solve the pinned buffer, the three timing entry
+    points their function-local events, and "lanes" the side stream and its events -- on 16 or
+    more time levels only (pc.cpp build_BE), so a second, small handle with 16 levels (plain
+    launches, as tests/test_gpu_sweep_forms.py runs the lanes) joins the two-grid one of the other
+    legs."""
+    p = common.heat_problem(n=32, n_t=6, beta=1e-4)
+    q = common.heat_problem(n=8, n_t=16, beta=1e-4)
+    xq = common.rng_vector(2 * q["m"] * q["sd"].n_dofs)
+    P = sp.csr_matrix(multilinear_coarse_space(p["sd"].coords, p["nodes"], cells=4))
+    m, nx = p["m"], p["sd"].n_dofs
+    x = common.rng_vector(2 * m * nx)
+    params = {"linear_solver": "fgmres", "fgmres_restart": 10, "maximum_iterations": 5,
+              "relative_tolerance": 1e-9, "absolute_tolerance": 0.0,
+              "monitor_convergence": False, "preconditioner": True}
+
+    def cycle(k):
+        g = common.gpu_system(p, options={"lanes": "1", "stage_timers": "1"})
+        pc = common.gpu_pc(p, MASS, SCHUR, coarse=(P, 2))
+        g.pc_apply(x, pc)
+        b = x.reshape(2 * m, nx)
+        g.solve(np.zeros((m, nx)), np.zeros((m, nx)), b[:m].copy(), b[m:].copy(),
+                solver_parameters=params, pc_fn=pc)
+        lib, h = g._lib, g.handle
+        d_x, d_y = ctypes.c_void_p(), ctypes.c_void_p()
+        g._ck(lib.kkt_vec_alloc(h, ctypes.byref(d_x)))
+        g._ck(lib.kkt_vec_alloc(h, ctypes.byref(d_y)))
+        g._ck(lib.kkt_vec_upload(h, d_x, _lib.f64(x)[1]))
+        stages, ms = _lib.PcStageTimes(), ctypes.c_float()
+        launches, phases = ctypes.c_int(), ctypes.c_int64()
+        g._ck(lib.kkt_time_pc_stages(h, d_x, d_y, ctypes.byref(stages)))
+        g._ck(lib.kkt_time_pc_sweeps(h, d_x, d_y, ctypes.byref(ms), ctypes.byref(launches),
+                                     ctypes.byref(phases)))
+        g._ck(lib.kkt_time_pc_apply(h, d_x, d_y, 2, ctypes.byref(ms)))
+        g._ck(lib.kkt_vec_free(h, d_x))
+        g._ck(lib.kkt_vec_free(h, d_y))
+        g.close()
+        g = common.gpu_system(q, options={"lanes": "1", "persistent": "0"})
+        g.pc_apply(xq, common.gpu_pc(q, MASS, SCHUR))
+        assert any(f["lane"] == 1 for f in g.pc_forms())
+        g.close()
+
+    _check("streams, events, pinned memory", cycle)
 
 
 def test_rebuilds_on_one_handle_do_not_grow():
