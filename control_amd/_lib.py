@@ -168,6 +168,7 @@ SIGNATURES = {
                                          C.POINTER(RelinRecipe)]),
     "kkt_picard_state": (C.c_int, [C.c_void_p, C.c_int, c_f64p, c_f64p, c_f64p, c_f64p]),
     "kkt_picard_iterate": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 4),
+    "kkt_picard_window": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "kkt_picard_residual_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_f64p]),
     "kkt_picard_update_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kkt_debug_relin_array": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int64]),

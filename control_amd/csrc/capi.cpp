@@ -377,6 +377,9 @@ int kkt_picard_state(kkt_handle plan, int download, double *v, double *zeta, dou
                      double *mu) {
     KKT_TRY(plan, relin_state(S, download, v, zeta, p, mu));
 }
+int kkt_picard_window(kkt_handle plan, int out[8]) {
+    KKT_TRY(plan, relin_window(S, out));
+}
 int kkt_picard_iterate(kkt_handle plan, double **d_v, double **d_zeta, double **d_p,
                        double **d_mu) {
     KKT_TRY(plan, relin_iterate(S, d_v, d_zeta, d_p, d_mu));

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <string>
 
+#include "comm.hpp"
 #include "system.hpp"
 
 namespace kkt {
@@ -51,13 +52,14 @@ static void check_perm(const int32_t *t, int64_t nnz, const char *what) {
 void relin_set(System &S, const kkt_relin_desc *d) {
     need(d != nullptr, "null descriptor");
     need(S.finalized, "the handle must be finalized");
-    need(!S.sharded, "time-sharded handles are not supported");
     need(d->nq == RELIN_NQ, "nq must be 7 (Radon's rule)");
     need(d->n_t >= 2 && d->ne > 0 && d->n2 > 0 && d->n1 > 0, "sizes must be positive");
     const int m = d->cn ? d->n_t - 1 : d->n_t;
     const int64_t nv = 2 * d->n2;
     need(S.n0 == 2 * m && S.n1 == 2 * m && S.nx0 == nv && S.nx1 == d->n1 && S.CN == (d->cn != 0),
          "the handle is not the outer system of these spaces and time levels");
+    need(!S.sharded || (S.families == 2 && S.mf == m),
+         "a time-sharded handle must shard the two block families of the outer system by level");
     need(d->V && d->W && d->phi && d->gphi && d->lam && d->glam && d->K2 && d->M2 && d->Kp &&
              d->Mp && d->b_values && d->data && (d->n_bc == 0 || d->bc_idx),
          "null array");
@@ -86,6 +88,25 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     P->nu = d->nu;
     P->tau = d->tau;
     P->beta = d->beta;
+    // the rank's block rows and the level windows its rows read (relin.hpp)
+    const int lo = S.sharded ? S.lo : 0, hi = S.sharded ? S.hi : m, nl = hi - lo;
+    P->lo = lo;
+    P->nl = nl;
+    if (P->CN) {
+        P->v_l0 = P->z_l0 = P->D_l0 = lo;
+        P->v_n = P->z_n = P->D_n = nl + 1;
+        P->v_halo = lo > 0;
+        P->z_halo = hi < m;
+    } else {
+        P->v_halo = lo > 0;
+        P->z_halo = hi < m;
+        P->v_l0 = lo - (P->v_halo ? 1 : 0);
+        P->v_n = hi - P->v_l0;
+        P->z_l0 = lo;
+        P->z_n = nl + (P->z_halo ? 1 : 0);
+        P->D_l0 = lo;
+        P->D_n = nl;
+    }
     const int64_t ne = d->ne, nq = RELIN_NQ;
     P->d_V = P->mem.upload(d->V, ne * 6);
     P->d_W = P->mem.upload(d->W, ne * nq);
@@ -131,19 +152,27 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     std::vector<uint8_t> bc(nv, 0);
     for (int64_t k = 0; k < d->n_bc; ++k) bc[d->bc_idx[k]] = 1;
     P->d_bc = P->mem.upload(bc.data(), nv);
-    P->d_data = P->mem.upload(d->data, 2 * (int64_t)m * nv);
-    P->d_Ev = P->mem.alloc<double>(ne * RELIN_EV * d->n_t);
-    P->d_Ep = P->mem.alloc<double>(ne * RELIN_EP * d->n_t);
-    P->d_D2 = P->mem.alloc<double>(d->nnz2 * d->n_t);
-    P->d_Dp = P->mem.alloc<double>(d->nnz1 * d->n_t);
-    P->d_v = P->mem.alloc<double>(d->n_t * nv);
-    P->d_zeta = P->mem.alloc<double>(d->n_t * nv);
-    P->d_p = P->mem.alloc<double>((int64_t)m * d->n1);
-    P->d_mu = P->mem.alloc<double>((int64_t)m * d->n1);
-    HIPCHK(hipMemset(P->d_v, 0, d->n_t * nv * 8));
-    HIPCHK(hipMemset(P->d_zeta, 0, d->n_t * nv * 8));
-    HIPCHK(hipMemset(P->d_p, 0, m * d->n1 * 8));
-    HIPCHK(hipMemset(P->d_mu, 0, m * d->n1 * 8));
+    // the data rows of the owned blocks: lo..hi-1 of the adjoint rows, m+lo..m+hi-1 of the state rows
+    P->d_data = P->mem.alloc<double>(2 * (int64_t)nl * nv);
+    for (int f = 0; f < 2; ++f)
+        HIPCHK(hipMemcpy(P->d_data + (int64_t)f * nl * nv, d->data + ((int64_t)f * m + lo) * nv,
+                         (int64_t)nl * nv * 8, hipMemcpyHostToDevice));
+    if (S.sharded && P->CN) {
+        P->d_rhalo = P->mem.alloc<double>(2 * nv + 2 * d->n1);
+        HIPCHK(hipMemset(P->d_rhalo, 0, (2 * nv + 2 * d->n1) * 8));
+    }
+    P->d_Ev = P->mem.alloc<double>(ne * RELIN_EV * P->D_n);
+    P->d_Ep = P->mem.alloc<double>(ne * RELIN_EP * P->D_n);
+    P->d_D2 = P->mem.alloc<double>(d->nnz2 * P->D_n);
+    P->d_Dp = P->mem.alloc<double>(d->nnz1 * P->D_n);
+    P->d_v = P->mem.alloc<double>(P->v_n * nv);
+    P->d_zeta = P->mem.alloc<double>(P->z_n * nv);
+    P->d_p = P->mem.alloc<double>((int64_t)nl * d->n1);
+    P->d_mu = P->mem.alloc<double>((int64_t)nl * d->n1);
+    HIPCHK(hipMemset(P->d_v, 0, P->v_n * nv * 8));
+    HIPCHK(hipMemset(P->d_zeta, 0, P->z_n * nv * 8));
+    HIPCHK(hipMemset(P->d_p, 0, nl * d->n1 * 8));
+    HIPCHK(hipMemset(P->d_mu, 0, nl * d->n1 * 8));
     P->d_red = P->mem.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX + 2);
     S.relin = std::move(P);
 }
@@ -153,22 +182,47 @@ static RelinPlan &plan_of(System &S) {
     return *S.relin;
 }
 
+// One level of v up and one of zeta down, after the update and before the assembly: v of my
+// last block (BE level hi - 1, CN level hi) is the first level of the window above, zeta of my
+// first block the last level of the window below.  Levels are contiguous: nothing is packed.
+void relin_exchange(System &S) {
+    RelinPlan &P = plan_of(S);
+    if (!S.sharded) return;
+    if (!S.comm) fail(KKT_ERR_STATE, "time-sharded system without a transport");
+    const int up = P.z_halo ? S.rank + 1 : -1, dn = P.v_halo ? S.rank - 1 : -1;
+    const int v_last = P.lo + P.nl - 1 + (P.CN ? 1 : 0);
+    S.comm->sendrecv(P.d_v + (int64_t)(v_last - P.v_l0) * P.nv, P.nv, up, P.d_v, P.nv, dn, S.stream);
+    S.comm->sendrecv(P.d_zeta, P.nv, dn, P.d_zeta + (int64_t)(P.z_n - 1) * P.nv, P.nv, up,
+                     S.stream);
+}
+
 void relin_apply(System &T, System &PS, const double *d_v, int n, const kkt_relin_recipe *rec) {
     RelinPlan &P = plan_of(PS);
     if (n < 0 || (n > 0 && !rec)) fail(KKT_ERR_ARG, "kkt_relinearise_device: bad recipe list");
     if (T.device != PS.device) fail(KKT_ERR_ARG, "kkt_relinearise_device: plan on another device");
-    if (!T.finalized || T.sharded)
-        fail(KKT_ERR_ARG, "kkt_relinearise_device: the target must be finalized and not sharded");
+    if (!T.finalized) fail(KKT_ERR_ARG, "kkt_relinearise_device: the target must be finalized");
+    if (T.sharded != PS.sharded || (T.sharded && (T.lo != PS.lo || T.hi != PS.hi)))
+        fail(KKT_ERR_ARG, "kkt_relinearise_device: the target is not sharded as the plan's handle");
+    if (d_v && PS.sharded && d_v != P.d_v)
+        fail(KKT_ERR_ARG, "kkt_relinearise_device: a time shard assembles at the plan's iterate "
+                          "(kkt_picard_iterate)");
     // validate every recipe before anything is written
     std::vector<ComposeJob> jobs;
     int64_t max_padded = 0;
     for (int r = 0; r < n; ++r) {
         const kkt_relin_recipe &c = rec[r];
         const std::string at = "kkt_relinearise_device: recipe " + std::to_string(r) + ": ";
+        const std::string blk = "block (" + std::to_string(c.quadrant) + "; " +
+                                std::to_string(c.i) + ", " + std::to_string(c.j) + ")";
+        if (T.sharded && c.i >= 0 && !T.owns(c.i))
+            fail(KKT_ERR_ARG, at + blk + ": its block row is not owned by this rank");
         auto it = T.blocks.find(std::make_tuple(c.quadrant, c.i, c.j));
         if (it == T.blocks.end()) fail(KKT_ERR_ARG, at + "no such block");
         if (c.space != 0 && c.space != 1) fail(KKT_ERR_ARG, at + "space must be 0 or 1");
         if (c.level < 0 || c.level >= P.n_t) fail(KKT_ERR_ARG, at + "level out of range");
+        if (c.alpha != 0.0 && (c.level < P.D_l0 || c.level >= P.D_l0 + P.D_n))
+            fail(KKT_ERR_ARG, at + blk + ": level " + std::to_string(c.level) +
+                                  " is outside this rank's window of D");
         const int pat = T.values[it->second.va].pattern;
         const Pattern &Q = T.patterns[pat];
         const auto key = std::make_tuple((const void *)&T, pat, c.space);
@@ -199,12 +253,12 @@ void relin_apply(System &T, System &PS, const double *d_v, int n, const kkt_reli
         J.alpha = c.alpha;
         J.gamma = c.gamma;
         if (c.space == 0) {
-            J.D = P.d_D2 + (int64_t)c.level * P.nnz2;
+            J.D = P.d_D2 + (int64_t)(c.level - P.D_l0) * P.nnz2;
             J.M = P.d_M2;
             J.tperm = c.transpose ? P.d_t2 : nullptr;
             J.nnz_s = P.nnz2;
         } else {
-            J.D = P.d_Dp + (int64_t)c.level * P.nnz1;
+            J.D = P.d_Dp + (int64_t)(c.level - P.D_l0) * P.nnz1;
             J.M = P.d_Mp;
             J.tperm = c.transpose ? P.d_tp : nullptr;
             J.nnz_s = P.nnz1 + 1;   // no second component
@@ -213,6 +267,7 @@ void relin_apply(System &T, System &PS, const double *d_v, int n, const kkt_reli
         max_padded = std::max(max_padded, Q.npadded);
     }
     if (d_v) {
+        relin_exchange(PS);
         launch_relin_elements(PS.stream, P, d_v);
         launch_relin_gather(PS.stream, P);
         HIPCHK(hipGetLastError());
@@ -251,12 +306,27 @@ void relin_apply(System &T, System &PS, const double *d_v, int n, const kkt_reli
     T.pc_stale = true;
 }
 
+// Host arrays of the global shapes.  Upload: the rank's windows, halo levels included.
+// Download: the levels the rank owns (BE: v, zeta of its blocks; CN: v one level up), and the
+// fixed levels -- CN's v_0, zeta of the last level -- on the rank whose window holds them; the
+// rest of the host arrays is left as it is.
 void relin_state(System &S, int download, double *v, double *zeta, double *p, double *mu) {
     RelinPlan &P = plan_of(S);
-    const int64_t nvl = P.n_t * P.nv, npl = (int64_t)P.m * P.n1;
-    double *dev[4] = {P.d_v, P.d_zeta, P.d_p, P.d_mu};
-    double *host[4] = {v, zeta, p, mu};
-    const int64_t len[4] = {nvl, nvl, npl, npl};
+    const int hi = P.lo + P.nl;
+    int v0 = P.v_l0, v1 = P.v_l0 + P.v_n, z0 = P.z_l0, z1 = P.z_l0 + P.z_n;
+    if (download) {
+        v0 = P.CN ? (P.lo == 0 ? 0 : P.lo + 1) : P.lo;
+        v1 = P.CN ? hi + 1 : hi;
+        z1 = P.CN && hi == P.m ? hi + 1 : hi;
+    }
+    double *dev[4] = {P.d_v + (int64_t)(v0 - P.v_l0) * P.nv,
+                      P.d_zeta + (int64_t)(z0 - P.z_l0) * P.nv, P.d_p, P.d_mu};
+    double *host[4] = {v ? v + (int64_t)v0 * P.nv : nullptr,
+                       zeta ? zeta + (int64_t)z0 * P.nv : nullptr,
+                       p ? p + (int64_t)P.lo * P.n1 : nullptr,
+                       mu ? mu + (int64_t)P.lo * P.n1 : nullptr};
+    const int64_t len[4] = {(v1 - v0) * P.nv, (z1 - z0) * P.nv, (int64_t)P.nl * P.n1,
+                            (int64_t)P.nl * P.n1};
     for (int k = 0; k < 4; ++k) {
         if (!host[k]) continue;
         if (download)
@@ -265,6 +335,14 @@ void relin_state(System &S, int download, double *v, double *zeta, double *p, do
             HIPCHK(hipMemcpyAsync(dev[k], host[k], len[k] * 8, hipMemcpyHostToDevice, S.stream));
     }
     HIPCHK(hipStreamSynchronize(S.stream));
+}
+
+void relin_window(System &S, int out[8]) {
+    RelinPlan &P = plan_of(S);
+    if (!out) fail(KKT_ERR_ARG, "kkt_picard_window: null argument");
+    const int w[8] = {P.v_l0, P.v_l0 + P.v_n, P.z_l0, P.z_l0 + P.z_n, P.D_l0, P.D_l0 + P.D_n,
+                      P.lo, P.lo + P.nl};
+    std::copy(w, w + 8, out);
 }
 
 void relin_iterate(System &S, double **v, double **zeta, double **p, double **mu) {
@@ -288,7 +366,22 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
     VecList V{};
     V.v[0] = r;
     launch_mdot(S.stream, r, V, 1, S.n_local, P.d_red + 2, P.d_red + 1);
+    if (S.sharded) {   // every rank holds the same sum, and so the same norm
+        if (!S.comm) fail(KKT_ERR_STATE, "time-sharded system without a transport");
+        S.comm->allreduce_sum(P.d_red + 1, 1, S.stream);
+    }
     launch_norm2_finish(S.stream, P.d_red + 1, P.d_red);
+    if (rhs && S.sharded && P.CN) {
+        // the raw rows the time transforms read across the shard boundary (the pattern of
+        // comm_exchange_row_halos): T_1 families send their first row down, T_2 their last up
+        const int up = P.z_halo ? S.rank + 1 : -1, dn = P.v_halo ? S.rank - 1 : -1;
+        const int64_t nv = P.nv, n1 = P.n1, nl = P.nl;
+        double *rp = r + 2 * nl * nv, *h = P.d_rhalo;
+        S.comm->sendrecv(r, nv, dn, h, nv, up, S.stream);
+        S.comm->sendrecv(r + (2 * nl - 1) * nv, nv, up, h + nv, nv, dn, S.stream);
+        S.comm->sendrecv(rp + (nl - 1) * n1, n1, up, h + 2 * nv, n1, dn, S.stream);
+        S.comm->sendrecv(rp + nl * n1, n1, dn, h + 2 * nv + n1, n1, up, S.stream);
+    }
     if (rhs) launch_relin_rhs(S.stream, P, r, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(norm, P.d_red, sizeof(double), hipMemcpyDeviceToHost, S.stream));
@@ -297,11 +390,12 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
 
 void relin_debug_array(System &S, int which, double *out, int64_t cap) {
     RelinPlan &P = plan_of(S);
-    if (!P.assembled) fail(KKT_ERR_STATE, "kkt_debug_relin_array: nothing assembled yet");
-    const double *src[4] = {P.d_Ev, P.d_Ep, P.d_D2, P.d_Dp};
-    const int64_t per_level[4] = {P.ne * RELIN_EV, P.ne * RELIN_EP, P.nnz2, P.nnz1};
-    if (which < 0 || which > 3) fail(KKT_ERR_ARG, "kkt_debug_relin_array: no such array");
-    const int64_t n = per_level[which] * P.n_t;
+    if (which < 0 || which > 5) fail(KKT_ERR_ARG, "kkt_debug_relin_array: no such array");
+    if (which < 4 && !P.assembled)
+        fail(KKT_ERR_STATE, "kkt_debug_relin_array: nothing assembled yet");
+    const double *src[6] = {P.d_Ev, P.d_Ep, P.d_D2, P.d_Dp, P.d_v, P.d_zeta};
+    const int64_t per_level[6] = {P.ne * RELIN_EV, P.ne * RELIN_EP, P.nnz2, P.nnz1, P.nv, P.nv};
+    const int64_t n = per_level[which] * (which < 4 ? P.D_n : which == 4 ? P.v_n : P.z_n);
     if (!out || cap < n) fail(KKT_ERR_ARG, "kkt_debug_relin_array: buffer too small");
     HIPCHK(hipStreamSynchronize(S.stream));
     HIPCHK(hipMemcpy(out, src[which], n * 8, hipMemcpyDeviceToHost));

@@ -35,8 +35,17 @@ struct ComposeJob {
 };
 
 struct RelinPlan {
-    int n_t = 0, m = 0;
+    int n_t = 0, m = 0;   // global: time levels, unknown blocks per family
     bool CN = false;
+    // Level windows.  The rank owns the block rows [lo, lo + nl) of both families (one rank: all
+    // m) and holds the levels its rows read: v from level v_l0 (v_n of them), zeta from z_l0, D
+    // and the element matrices from D_l0; p, mu and the data rows are the owned blocks'.
+    //   BE  v [lo - 1, hi)   zeta [lo, hi]   D [lo, hi)    (level -1 and level n_t do not exist)
+    //   CN  v [lo, hi]       zeta [lo, hi]   D [lo, hi]
+    // The levels outside the rank's own are halos: v's first from the rank below, zeta's last
+    // from the rank above (relin_exchange), CN's D_lo assembled here from the halo v.
+    int lo = 0, nl = 0, v_l0 = 0, v_n = 0, z_l0 = 0, z_n = 0, D_l0 = 0, D_n = 0;
+    bool v_halo = false, z_halo = false;   // the first v / last zeta level belongs to a neighbour
     int64_t ne = 0, n2 = 0, n1 = 0, nv = 0, nnz2 = 0, nnz1 = 0;
     double nu = 0.0, tau = 0.0, beta = 0.0;
     DevPool mem;   // everything below but the job table
@@ -53,11 +62,14 @@ struct RelinPlan {
     int32_t *d_Bip = nullptr, *d_Bix = nullptr, *d_BTip = nullptr, *d_BTix = nullptr;
     double *d_Bv = nullptr, *d_BTv = nullptr;
     uint8_t *d_bc = nullptr;   // nv bytes: Dirichlet velocity dofs
-    double *d_data = nullptr;  // 2m x nv data rows of the velocity residual
-    // work: element matrices and the assembled D per level
+    double *d_data = nullptr;  // 2 nl x nv data rows of the velocity residual (the owned rows)
+    // CN on a time shard: the neighbours' raw residual rows the time transforms read, velocity
+    // [adjoint: block hi | state: block lo - 1] (nv each), pressure [v: lo - 1 | zeta: hi] (n1)
+    double *d_rhalo = nullptr;
+    // work: element matrices and the assembled D per level of the D window
     double *d_Ev = nullptr, *d_Ep = nullptr, *d_D2 = nullptr, *d_Dp = nullptr;
     bool assembled = false;
-    // the iterate: v, zeta (n_t x nv), p, mu (m x n1)
+    // the iterate: v (v_n x nv), zeta (z_n x nv), p, mu (nl x n1)
     double *d_v = nullptr, *d_zeta = nullptr, *d_p = nullptr, *d_mu = nullptr;
     double *d_red = nullptr;   // reduction scratch + result
     DevBuf<ComposeJob> d_jobs;   // regrown with the largest job count seen
@@ -66,7 +78,8 @@ struct RelinPlan {
     std::set<std::tuple<const void *, int, int>> checked;
 };
 
-// element matrices of every (element, level): Ev[(l ne + e) 36 + 6a + b], Ep[... 9 + 3c + d]
+// element matrices of every (element, level of the D window): Ev[(s ne + e) 36 + 6a + b],
+// Ep[... 9 + 3c + d], s = level - D_l0; d_v: the plan's v window
 void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v);
 // D[l nnz + k] = nu K[k] + sum of the contributions of position k in list order
 void launch_relin_gather(hipStream_t s, const RelinPlan &P);
@@ -85,7 +98,12 @@ void relin_state(System &S, int download, double *v, double *zeta, double *p, do
 void relin_iterate(System &S, double **v, double **zeta, double **p, double **mu);
 void relin_residual(System &S, double *d_out, int rhs, double *norm);
 void relin_update(System &S, double *d_u);
-// kkt_debug_relin_array: Ev, Ep, D2 or Dp of the last assembly, copied to the host
+// kkt_debug_relin_array: Ev, Ep, D2 or Dp of the last assembly (the D window), or the v / zeta
+// window of the iterate, copied to the host
 void relin_debug_array(System &S, int which, double *out, int64_t cap);
+// kkt_picard_window: [v_l0, v_end, z_l0, z_end, D_l0, D_end, lo, hi), half-open ranges
+void relin_window(System &S, int out[8]);
+// the iterate's halo levels from the neighbour ranks (a time shard; one rank: nothing)
+void relin_exchange(System &S);
 
 }  // namespace kkt

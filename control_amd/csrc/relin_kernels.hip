@@ -93,10 +93,11 @@ __global__ __launch_bounds__(256) void relin_elements_kernel(
     }
 }
 
+// d_v: the v window; slot s of the D window takes its wind from level D_l0 + s of it
 void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v) {
-    hipLaunchKernelGGL(relin_elements_kernel, dim3(relin_grid(P.ne * P.n_t, 256 * 64)), dim3(256),
-                       0, s, d_v, P.ne, P.n2, P.n_t, P.d_V, P.d_W, P.d_phi, P.d_gphi, P.d_lam,
-                       P.d_glam, P.d_Ev, P.d_Ep);
+    hipLaunchKernelGGL(relin_elements_kernel, dim3(relin_grid(P.ne * P.D_n, 256 * 64)), dim3(256),
+                       0, s, d_v + (int64_t)(P.D_l0 - P.v_l0) * P.nv, P.ne, P.n2, P.D_n, P.d_V,
+                       P.d_W, P.d_phi, P.d_gphi, P.d_lam, P.d_glam, P.d_Ev, P.d_Ep);
 }
 
 // One thread per (stored position, level): the contributions in ascending element-entry order
@@ -121,12 +122,12 @@ __global__ __launch_bounds__(256) void relin_gather_kernel(
 }
 
 void launch_relin_gather(hipStream_t s, const RelinPlan &P) {
-    hipLaunchKernelGGL(relin_gather_kernel, dim3(relin_grid(P.nnz2 * P.n_t, 256 * 64)), dim3(256),
+    hipLaunchKernelGGL(relin_gather_kernel, dim3(relin_grid(P.nnz2 * P.D_n, 256 * 64)), dim3(256),
                        0, s, P.d_cptr2, P.d_clist2, P.d_Ev, P.ne * RELIN_EV, P.d_K2, P.nu, P.nnz2,
-                       P.n_t, P.d_D2);
-    hipLaunchKernelGGL(relin_gather_kernel, dim3(relin_grid(P.nnz1 * P.n_t, 256 * 64)), dim3(256),
+                       P.D_n, P.d_D2);
+    hipLaunchKernelGGL(relin_gather_kernel, dim3(relin_grid(P.nnz1 * P.D_n, 256 * 64)), dim3(256),
                        0, s, P.d_cptrp, P.d_clistp, P.d_Ep, P.ne * RELIN_EP, P.d_Kp, P.nu, P.nnz1,
-                       P.n_t, P.d_Dp);
+                       P.D_n, P.d_Dp);
 }
 
 // blockIdx.y selects the target block; each SELL slot gets alpha D(^T) + gamma M (blocks.py
@@ -177,14 +178,18 @@ struct RelinArgs {
     const double *M2, *D2, *Bv, *BTv, *data, *v, *zeta, *p, *mu;
     const uint8_t *bc;
     int64_t n2, nv, n1, nnz2;
-    int n_t, m, cn;
+    // Level windows of a time shard: the rank owns the block rows [lo, lo + nl) of both families
+    // (data, p, mu, the residual: local row blocks f nl + i - lo); v, zeta and D2 start at the
+    // global levels v_l0, z_l0 and D_l0.  n_t and m are global, and so are the stencil's guards.
+    int n_t, m, cn, lo, nl, v_l0, z_l0, D_l0;
     double tau, beta;
 };
 
-// Velocity rows (picard.non_linear_res_eval): one thread per (row block, dof).  Row blocks
-// 0..m-1 are the adjoint rows (r00), m..2m-1 the state rows (r01); Dirichlet rows are zero.
+// Velocity rows (picard.non_linear_res_eval): one thread per (row block, dof).  Local row blocks
+// 0..nl-1 are the adjoint rows (r00) of the blocks lo.., nl..2nl-1 the state rows (r01);
+// Dirichlet rows are zero.  i: the global block row.
 __global__ __launch_bounds__(256) void relin_residual_v_kernel(RelinArgs A, double *__restrict__ r) {
-    const int rb = blockIdx.y, fam = rb >= A.m, i = fam ? rb - A.m : rb;
+    const int rb = blockIdx.y, fam = rb >= A.nl, il = fam ? rb - A.nl : rb, i = A.lo + il;
     for (int64_t R = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; R < A.nv;
          R += (int64_t)gridDim.x * blockDim.x) {
         double out = 0.0;
@@ -194,39 +199,42 @@ __global__ __launch_bounds__(256) void relin_residual_v_kernel(RelinArgs A, doub
                 return relin_row(A.ip2, A.ix2, A.M2, nullptr, row, lev + off);
             };
             auto Dx = [&](int l, const double *lev) {
-                return relin_row(A.ip2, A.ix2, A.D2 + l * A.nnz2, nullptr, row, lev + off);
+                return relin_row(A.ip2, A.ix2, A.D2 + (l - A.D_l0) * A.nnz2, nullptr, row,
+                                 lev + off);
             };
             auto DTx = [&](int l, const double *lev) {
-                return relin_row(A.ip2, A.ix2, A.D2 + l * A.nnz2, A.t2, row, lev + off);
+                return relin_row(A.ip2, A.ix2, A.D2 + (l - A.D_l0) * A.nnz2, A.t2, row, lev + off);
             };
             auto BTx = [&](const double *lev) {
                 return relin_row(A.BTip, A.BTix, A.BTv, nullptr, R, lev);
             };
-            const double *v = A.v, *z = A.zeta;
             const int64_t nv = A.nv;
+            // global level l of v and zeta: its slot in the window
+            auto v = [&](int l) { return A.v + (l - A.v_l0) * nv; };
+            auto z = [&](int l) { return A.zeta + (l - A.z_l0) * nv; };
             const double tau = A.tau, d = A.data[rb * nv + R];
             if (!A.cn) {
                 if (!fam) {
-                    const double Dz = tau * DTx(i, z + i * nv) + Mx(z + i * nv);
+                    const double Dz = tau * DTx(i, z(i)) + Mx(z(i));
                     out = d - Dz;
-                    if (i < A.n_t - 1) out += -tau * Mx(v + i * nv) + Mx(z + (i + 1) * nv);
-                    out -= tau * BTx(A.mu + i * A.n1);
+                    if (i < A.n_t - 1) out += -tau * Mx(v(i)) + Mx(z(i + 1));
+                    out -= tau * BTx(A.mu + il * A.n1);
                 } else {
-                    const double Dv = tau * Dx(i, v + i * nv) + Mx(v + i * nv);
+                    const double Dv = tau * Dx(i, v(i)) + Mx(v(i));
                     out = d - Dv;
-                    if (i >= 1) out += Mx(v + (i - 1) * nv) + (tau / A.beta) * Mx(z + i * nv);
-                    out -= tau * BTx(A.p + i * A.n1);
+                    if (i >= 1) out += Mx(v(i - 1)) + (tau / A.beta) * Mx(z(i));
+                    out -= tau * BTx(A.p + il * A.n1);
                 }
             } else {
                 const double h = 0.5 * tau;
-                const double *v0 = v + i * nv, *v1 = v + (i + 1) * nv;
-                const double *z0 = z + i * nv, *z1 = z + (i + 1) * nv;
+                const double *v0 = v(i), *v1 = v(i + 1);
+                const double *z0 = z(i), *z1 = z(i + 1);
                 if (!fam) {
                     out = d - h * (Mx(v0) + Mx(v1)) - (h * DTx(i, z0) + Mx(z0)) -
-                          (h * DTx(i + 1, z1) - Mx(z1)) - tau * BTx(A.mu + i * A.n1);
+                          (h * DTx(i + 1, z1) - Mx(z1)) - tau * BTx(A.mu + il * A.n1);
                 } else {
                     out = d - (h * Dx(i, v0) - Mx(v0)) - (h * Dx(i + 1, v1) + Mx(v1)) +
-                          (h / A.beta) * (Mx(z0) + Mx(z1)) - tau * BTx(A.p + i * A.n1);
+                          (h / A.beta) * (Mx(z0) + Mx(z1)) - tau * BTx(A.p + il * A.n1);
                 }
             }
         }
@@ -234,10 +242,11 @@ __global__ __launch_bounds__(256) void relin_residual_v_kernel(RelinArgs A, doub
     }
 }
 
-// Pressure rows: -B v (row blocks 0..m-1; CN: the level i + 1) and -B zeta.
+// Pressure rows: -B v (local row blocks 0..nl-1; CN: the level i + 1) and -B zeta.
 __global__ __launch_bounds__(256) void relin_residual_p_kernel(RelinArgs A, double *__restrict__ r) {
-    const int rb = blockIdx.y, fam = rb >= A.m, i = fam ? rb - A.m : rb;
-    const double *x = fam ? A.zeta + i * A.nv : A.v + (A.cn ? i + 1 : i) * A.nv;
+    const int rb = blockIdx.y, fam = rb >= A.nl, i = A.lo + (fam ? rb - A.nl : rb);
+    const double *x = fam ? A.zeta + (i - A.z_l0) * A.nv
+                          : A.v + ((A.cn ? i + 1 : i) - A.v_l0) * A.nv;
     for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < A.n1;
          q += (int64_t)gridDim.x * blockDim.x)
         r[rb * A.n1 + q] = -relin_row(A.Bip, A.Bix, A.Bv, nullptr, q, x);
@@ -251,47 +260,68 @@ static RelinArgs relin_args(const RelinPlan &P) {
     A.v = P.d_v; A.zeta = P.d_zeta; A.p = P.d_p; A.mu = P.d_mu; A.bc = P.d_bc;
     A.n2 = P.n2; A.nv = P.nv; A.n1 = P.n1; A.nnz2 = P.nnz2;
     A.n_t = P.n_t; A.m = P.m; A.cn = P.CN;
+    A.lo = P.lo; A.nl = P.nl; A.v_l0 = P.v_l0; A.z_l0 = P.z_l0; A.D_l0 = P.D_l0;
     A.tau = P.tau; A.beta = P.beta;
     return A;
 }
 
 void launch_relin_residual(hipStream_t s, const RelinPlan &P, double *d_r) {
     const RelinArgs A = relin_args(P);
-    hipLaunchKernelGGL(relin_residual_v_kernel, dim3(relin_grid(P.nv, 512), 2 * P.m), dim3(256), 0,
+    hipLaunchKernelGGL(relin_residual_v_kernel, dim3(relin_grid(P.nv, 512), 2 * P.nl), dim3(256), 0,
                        s, A, d_r);
-    hipLaunchKernelGGL(relin_residual_p_kernel, dim3(relin_grid(P.n1, 512), 2 * P.m), dim3(256), 0,
-                       s, A, d_r + 2 * P.m * P.nv);
+    hipLaunchKernelGGL(relin_residual_p_kernel, dim3(relin_grid(P.n1, 512), 2 * P.nl), dim3(256), 0,
+                       s, A, d_r + 2 * (int64_t)P.nl * P.nv);
 }
 
 // b from r: velocity rows as they are, pressure rows times tau; CN: T_1 on the adjoint rows and
-// on the zeta pressure rows, T_2 on the state rows and the v pressure rows (picard.py)
+// on the zeta pressure rows, T_2 on the state rows and the v pressure rows (picard.py).  r holds
+// the rank's 2 nl row blocks per variable; the transforms' terms from the block rows hi and
+// lo - 1 are the neighbour ranks' raw rows in `halo` ([velocity | pressure][family], RelinPlan::
+// d_rhalo); the guards are those of the global system.
+struct RhsHalo {
+    const double *h[2][2];
+};
+
 __global__ __launch_bounds__(256) void relin_rhs_kernel(const double *__restrict__ r,
-                                                        double *__restrict__ b, int m,
-                                                        int64_t nv, int64_t n1, int cn,
-                                                        double tau) {
-    const int64_t n0 = 2 * (int64_t)m * nv, n = n0 + 2 * (int64_t)m * n1;
+                                                        double *__restrict__ b, int m, int lo,
+                                                        int nl, int64_t nv, int64_t n1, int cn,
+                                                        double tau, RhsHalo halo) {
+    const int64_t n0 = 2 * (int64_t)nl * nv, n = n0 + 2 * (int64_t)nl * n1;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n;
          t += (int64_t)gridDim.x * blockDim.x) {
         const bool pres = t >= n0;
         const int64_t nx = pres ? n1 : nv, u = pres ? t - n0 : t;
         const int64_t rb = u / nx;
-        const int fam = rb >= m, i = (int)(fam ? rb - m : rb);
+        const int fam = rb >= nl, il = (int)(fam ? rb - nl : rb), i = lo + il;
         const double c = pres ? tau : 1.0;
         double out = pres ? c * r[t] : r[t];
         if (cn) {
             // T_1 (i + 1 into i): adjoint rows, zeta pressure rows; T_2 (i - 1 into i): the others
             const bool t1 = fam == (int)pres;
-            if (t1 && i + 1 < m) out += pres ? c * r[t + nx] : r[t + nx];
-            if (!t1 && i >= 1) out += pres ? c * r[t - nx] : r[t - nx];
+            const double *hrow = (pres ? (fam ? halo.h[1][1] : halo.h[1][0])
+                                       : (fam ? halo.h[0][1] : halo.h[0][0])) + (u - rb * nx);
+            if (t1 && i + 1 < m) {
+                const double *nb = il + 1 < nl ? r + t + nx : hrow;
+                out += pres ? c * nb[0] : nb[0];
+            }
+            if (!t1 && i >= 1) {
+                const double *nb = il >= 1 ? r + t - nx : hrow;
+                out += pres ? c * nb[0] : nb[0];
+            }
         }
         b[t] = out;
     }
 }
 
 void launch_relin_rhs(hipStream_t s, const RelinPlan &P, const double *d_r, double *d_b) {
-    const int64_t n = 2 * P.m * (P.nv + P.n1);
-    hipLaunchKernelGGL(relin_rhs_kernel, dim3(relin_grid(n)), dim3(256), 0, s, d_r, d_b, P.m, P.nv,
-                       P.n1, (int)P.CN, P.tau);
+    const int64_t n = 2 * P.nl * (P.nv + P.n1);
+    RhsHalo H;
+    H.h[0][0] = P.d_rhalo;
+    H.h[0][1] = P.d_rhalo + P.nv;
+    H.h[1][0] = P.d_rhalo + 2 * P.nv;
+    H.h[1][1] = P.d_rhalo + 2 * P.nv + P.n1;
+    hipLaunchKernelGGL(relin_rhs_kernel, dim3(relin_grid(n)), dim3(256), 0, s, d_r, d_b, P.m, P.lo,
+                       P.nl, P.nv, P.n1, (int)P.CN, P.tau, H);
 }
 
 __global__ __launch_bounds__(256) void relin_update_kernel(double *__restrict__ u,
@@ -328,12 +358,15 @@ __global__ __launch_bounds__(256) void relin_zero_bc_kernel(double *__restrict__
         if (bc[t % nv]) zeta[t] = 0.0;
 }
 
+// the kernel's block rows are the rank's own: v and zeta are passed from the slot of level lo
 void launch_relin_update(hipStream_t s, const RelinPlan &P, double *d_u) {
-    const int64_t n = 2 * P.m * (P.nv + P.n1);
-    hipLaunchKernelGGL(relin_update_kernel, dim3(relin_grid(n)), dim3(256), 0, s, d_u, P.d_v,
-                       P.d_zeta, P.d_mu, P.d_p, P.m, P.nv, P.n1, (int)P.CN);
-    hipLaunchKernelGGL(relin_zero_bc_kernel, dim3(relin_grid(P.n_t * P.nv)), dim3(256), 0, s,
-                       P.d_zeta, P.d_bc, P.n_t * P.nv, P.nv);
+    const int64_t n = 2 * P.nl * (P.nv + P.n1);
+    hipLaunchKernelGGL(relin_update_kernel, dim3(relin_grid(n)), dim3(256), 0, s, d_u,
+                       P.d_v + (int64_t)(P.lo - P.v_l0) * P.nv,
+                       P.d_zeta + (int64_t)(P.lo - P.z_l0) * P.nv, P.d_mu, P.d_p, P.nl, P.nv, P.n1,
+                       (int)P.CN);
+    hipLaunchKernelGGL(relin_zero_bc_kernel, dim3(relin_grid(P.z_n * P.nv)), dim3(256), 0, s,
+                       P.d_zeta, P.d_bc, P.z_n * P.nv, P.nv);
 }
 
 }  // namespace kkt

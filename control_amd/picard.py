@@ -181,23 +181,31 @@ class GpuLinearSolver:
         Picard iterate in HBM -- the first linear solve builds the three systems (``build``),
         every later re-linearisation re-assembles the convection blocks, the
         residual and the update on the GPU (``control_amd.relinearise``).  Needs the element
-        data of ``fem.rectangle_p2p1`` and a single GPU.
+        data of ``fem.rectangle_p2p1``.  With ``comm`` every rank keeps, assembles, evaluates and
+        updates its own time levels only and trades one level of ``v`` and one of ``zeta`` (CN:
+        and the boundary residual rows) with its neighbours per iteration; ``host_allreduce``
+        then only gathers the fields once at the end.
 
         ``build="device"`` (with ``relinearise="device"``): the first build crosses to the GPU
         as patterns, the constant matrices of the plan and the starting iterate only --
         ``_build_device`` registers every block of the three systems by its structure
         (``PatternOnly``; ``tau B`` / ``tau B^T`` excepted: one value set each) and the device
         composes them all (``blocks.instationary_build_recipes``).  No ``D_v`` / ``D_p`` assembly
-        and no block sums on the host."""
+        and no block sums on the host.  Not with ``comm``: registering the blocks of a time
+        shard by pattern is not supported."""
         if relinearise not in ("host", "device"):
             raise ValueError("relinearise must be 'host' or 'device'")
         if build not in ("host", "device"):
             raise ValueError("build must be 'host' or 'device'")
         if build == "device" and relinearise != "device":
             raise ValueError("build='device' needs relinearise='device'")
+        if comm is not None and comm.world > 1 and not callable(getattr(comm, "attach", None)):
+            raise ValueError("comm must be a transport of control_amd.dist (it attaches itself to "
+                             "the three systems)")
+        if build == "device" and comm is not None and comm.world > 1:
+            raise ValueError("build='device' does not support time-sharded solvers (comm): "
+                             "use build='host' with relinearise='device'")
         if relinearise == "device":
-            if comm is not None:
-                raise ValueError("relinearise='device' does not support time-sharded solvers")
             if getattr(pb.disc, "elem", None) is None:
                 raise ValueError("relinearise='device' needs a discretisation with element data "
                                  "(fem.rectangle_p2p1)")
@@ -373,9 +381,11 @@ class GpuLinearSolver:
         m, lo, hi = bl["m"], self.inner._lo, self.inner._hi
         pick = list(range(lo, hi)) + list(range(m + lo, m + hi))
         l_0, l_1 = np.zeros_like(b_0[pick]), np.zeros_like(b_1[pick])
+        t0 = time.perf_counter()
         ksp = self.outer.solve(l_0, l_1, np.ascontiguousarray(b_0[pick]),
                                np.ascontiguousarray(b_1[pick]),
                                solver_parameters=self.solver_parameters, pc_fn=self.pc)
+        self.solve_times.append((t0, time.perf_counter()))
         u_0[pick], u_1[pick] = l_0, l_1
         for u in (u_0, u_1):            # the other ranks' rows are zero here: a sum gathers
             flat = u.reshape(-1)
@@ -391,12 +401,17 @@ class GpuLinearSolver:
             from .relinearise import DeviceRelinearisation
             pb = self.pb
             recipes = instationary_relinearisation_recipes(pb.tau, pb.beta, pb.n_t, pb.CN)
-            self._device = DeviceRelinearisation(pb, self.outer, recipes)
+            m = recipes["m"]        # (outer block rows: both families by their time level)
+            recipes = {name: [r for r in recipes[name] if self._owns(r[1] % m)]
+                       for name in ("outer", "inner", "commutator")}
+            self._device = DeviceRelinearisation(pb, self.outer, recipes,
+                                                 host_allreduce=self.host_allreduce)
         return self._device
 
     def device_relinearise(self):
         """Rewrite the linearised blocks of the outer, inner and commutator systems from the
-        plan's last assembly (``_update`` of the host path)."""
+        plan's last assembly (``_update`` of the host path; a time shard: the blocks of its own
+        rows, as ``_update``'s ``own``)."""
         dev = self.device_plan()
         dev.relinearise(self.outer, "outer")
         dev.relinearise(self.inner, "inner")
@@ -414,7 +429,8 @@ def _device_non_linear_solve(pb, ls, v, zeta, p, mu, max_non_linear_iter, rtol, 
                              print_error_non_linear):
     """``incompressible_non_linear_solve`` with the iterate in HBM: per iteration one assembly
     of the convection blocks, one residual (the host reads its norm), one linearised solve and
-    one update, all on the device."""
+    one update, all on the device -- on a time-sharded solver every rank on its own levels, the
+    norm the same on all of them."""
     import ctypes as C
     th, n_t = pb.disc, pb.n_t
     fresh = ls.outer is None

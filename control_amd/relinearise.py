@@ -149,12 +149,20 @@ def _recipe_array(recipes, space):
 
 
 class DeviceRelinearisation:
-    """The plan on the outer system of a ``GpuLinearSolver`` and the Picard iterate in HBM."""
+    """The plan on the outer system of a ``GpuLinearSolver`` and the Picard iterate in HBM.
 
-    def __init__(self, pb, outer, recipes, plan=None):
+    On a time-sharded outer system every rank keeps its own levels of the iterate, of the element
+    matrices and of ``D`` (``window``), assembles, evaluates the residual of and updates those, and
+    trades one level of ``v`` and one of ``zeta`` with its neighbours before every assembly;
+    ``assemble``, ``residual`` and ``get_state`` are then collective."""
+
+    def __init__(self, pb, outer, recipes, plan=None, host_allreduce=None):
         """``recipes``: the blocks every re-linearisation rewrites, per system
-        (``blocks.instationary_relinearisation_recipes``)."""
+        (``blocks.instationary_relinearisation_recipes``); on a time shard those of the rank's own
+        block rows, with their global indices.  ``host_allreduce(array, op)`` (a time shard):
+        what ``get_state`` gathers the iterate with."""
         self.pb, self.outer = pb, outer
+        self.host_allreduce = host_allreduce
         self.plan = RelinearisationPlan(pb) if plan is None else plan
         self._lib = outer._lib
         d, keep = self.plan.descriptor()
@@ -165,6 +173,10 @@ class DeviceRelinearisation:
         ptr = [C.c_void_p() for _ in range(4)]
         outer._ck(self._lib.kkt_picard_iterate(outer.handle, *[C.byref(p) for p in ptr]))
         self.d_v = ptr[0]
+        w = (C.c_int * 8)()
+        outer._ck(self._lib.kkt_picard_window(outer.handle, w))
+        #: half-open ranges of global levels held in HBM: v, zeta, D, and the owned block rows
+        self.window = {k: (w[2 * n], w[2 * n + 1]) for n, k in enumerate(("v", "zeta", "D", "blocks"))}
 
     def set_state(self, v, zeta, p, mu):
         th, n_t, m = self.pb.disc, self.pb.n_t, self.plan.m
@@ -176,15 +188,23 @@ class DeviceRelinearisation:
                                                   *[a.ctypes.data_as(_lib.c_f64p) for a in arrs]))
 
     def get_state(self):
+        """The whole iterate on the host.  A time shard downloads the levels it owns into zeros
+        and the ranks' arrays are summed (``host_allreduce``): every rank returns the same."""
         th, pb, m = self.pb.disc, self.pb, self.plan.m
-        out = [np.empty((pb.n_t, th.n_v)), np.empty((pb.n_t, th.n_v)), np.empty((m, th.n_p)),
-               np.empty((m, th.n_p))]
+        out = [np.zeros((pb.n_t, th.n_v)), np.zeros((pb.n_t, th.n_v)), np.zeros((m, th.n_p)),
+               np.zeros((m, th.n_p))]
         self.outer._ck(self._lib.kkt_picard_state(self.outer.handle, 1,
                                                   *[a.ctypes.data_as(_lib.c_f64p) for a in out]))
+        if self.window["blocks"] != (0, m):
+            if self.host_allreduce is None:
+                raise ValueError("a time-sharded plan needs host_allreduce to gather the iterate")
+            for a in out:            # the other ranks' levels are zero here: a sum gathers
+                self.host_allreduce(a.reshape(-1), 0)
         return out
 
     def assemble(self):
-        """D_v, D_p of every level at the device iterate's v."""
+        """D_v, D_p of every level of the D window at the device iterate's v (a time shard first
+        refreshes its halo levels from the neighbour ranks)."""
         self.outer._ck(self._lib.kkt_relinearise_device(self.outer.handle, self.outer.handle,
                                                         self.d_v, 0, None))
 
@@ -208,12 +228,14 @@ class DeviceRelinearisation:
 
     def debug_array(self, which):
         """``kkt_debug_relin_array``: ``"Ev"`` (n_t, ne, 6, 6), ``"Ep"`` (n_t, ne, 3, 3), ``"D2"``
-        (n_t, nnz2) or ``"Dp"`` (n_t, nnz1) of the last assembly."""
-        n_t, ne = self.pb.n_t, len(self.plan.V)
-        shape = {"Ev": (n_t, ne, 6, 6), "Ep": (n_t, ne, 3, 3), "D2": (n_t, self.plan.K2.nnz),
-                 "Dp": (n_t, self.plan.Kp.nnz)}[which]
+        (n_t, nnz2) or ``"Dp"`` (n_t, nnz1) of the last assembly -- on a time shard the levels of
+        ``window["D"]``; ``"v"`` / ``"zeta"``: the iterate's windows, halo levels included."""
+        ne, n_v = len(self.plan.V), self.pb.disc.n_v
+        n_D, n_v_lev, n_z_lev = (b - a for a, b in (self.window[k] for k in ("D", "v", "zeta")))
+        shape = {"Ev": (n_D, ne, 6, 6), "Ep": (n_D, ne, 3, 3), "D2": (n_D, self.plan.K2.nnz),
+                 "Dp": (n_D, self.plan.Kp.nnz), "v": (n_v_lev, n_v), "zeta": (n_z_lev, n_v)}[which]
         out = np.empty(shape)
         self.outer._ck(self._lib.kkt_debug_relin_array(
-            self.outer.handle, ("Ev", "Ep", "D2", "Dp").index(which),
+            self.outer.handle, ("Ev", "Ep", "D2", "Dp", "v", "zeta").index(which),
             out.ctypes.data_as(_lib.c_f64p), out.size))
         return out

@@ -362,7 +362,17 @@ int kkt_sync(kkt_handle h);
  * level.  B: the divergence block (n1 x 2 n2, sorted CSR).  data: the 2m x 2 n2 velocity rows
  * of the residual at the zero iterate (desired state, forces, the initial condition); bc_idx:
  * Dirichlet velocity dofs.  Arrays are copied; KKT_ERR_ARG on sizes, ranges or patterns that do
- * not fit. */
+ * not fit.
+ *
+ * On a time-sharded handle (kkt_set_shard with two families: the outer system) the descriptor is
+ * the same global one on every rank, and the plan keeps the rank's part only.  With [lo, hi) the
+ * rank's unknown blocks (kkt_shard_range of m) it holds the levels its block rows read:
+ *   backward Euler   v [lo - 1, hi), zeta [lo, hi], D [lo, hi)   (no level -1, no level n_t)
+ *   Crank-Nicolson   v [lo, hi],     zeta [lo, hi], D [lo, hi]
+ * p, mu and the data rows of its blocks.  The first v level and the last zeta level are halos:
+ * kkt_relinearise_device refreshes them from the neighbour ranks before it assembles (one level
+ * of v up, one of zeta down), and assembles CN's D_lo from the halo v.  kkt_picard_window reports
+ * the windows. */
 typedef struct kkt_relin_desc {
     int n_t, cn, nq;              /* time levels, Crank-Nicolson (1) or backward Euler, nq = 7 */
     int64_t ne, n2, n1;           /* triangles, P2 nodes (one component), P1 nodes */
@@ -399,39 +409,56 @@ typedef struct kkt_relin_recipe {
     int transpose;
     double alpha, gamma;
 } kkt_relin_recipe;
-/* Rewrites the recipes' blocks of handle h from the plan on handle `plan`.  d_v (device,
- * n_t x 2 n2, component-major levels) != NULL first re-assembles D at that velocity; NULL
+/* Rewrites the recipes' blocks of handle h from the plan on handle `plan`.  d_v (device, the
+ * levels of the plan's v window x 2 n2, component-major; one rank: all n_t; a time shard: the
+ * plan's own iterate) != NULL first re-assembles D at that velocity (collective on a time shard:
+ * the halo levels travel first); NULL
  * composes from the last assembly (so the outer, inner and commutator handles of one
  * linearisation share one).  n = 0 only assembles.  The blocks are written on the device as
  * kkt_update_block_values would write them (Dirichlet columns zeroed, a value array shared with
  * other blocks is first made private) and a built-in preconditioner is marked stale.  The
- * target pattern must be the plan's. */
+ * target pattern must be the plan's.  Time shards: h is sharded as the plan's handle, recipes
+ * keep their global (i, j) and level, and one whose block row the rank does not own, or whose
+ * level lies outside the rank's D window, is KKT_ERR_ARG naming the block. */
 int kkt_relinearise_device(kkt_handle h, kkt_handle plan, const double *d_v, int n,
                            const kkt_relin_recipe *recipes);
 /* The plan's iterate (v, zeta: n_t x 2 n2; p, mu: m x n1) in HBM: host copies in (download 0)
- * or out (download 1), and its device addresses (any out pointer may be NULL). */
+ * or out (download 1), and its device addresses (any out pointer may be NULL).  The host arrays
+ * always have the global shapes.  A time shard uploads its windows from them, halo levels
+ * included, and downloads only what it owns -- its blocks' levels, and the fixed levels (CN: v_0;
+ * zeta of the last level) on the rank whose window holds them -- leaving the rest untouched; the
+ * device addresses are those of the windows' first levels.
+ * kkt_picard_window: out = [v, zeta, D, block rows] as half-open ranges [first, end) of global
+ * levels (one rank: [0, n_t) three times and [0, m)). */
 int kkt_picard_state(kkt_handle plan, int download, double *v, double *zeta, double *p,
                      double *mu);
 int kkt_picard_iterate(kkt_handle plan, double **d_v, double **d_zeta, double **d_p,
                        double **d_mu);
+int kkt_picard_window(kkt_handle plan, int out[8]);
 /* Non-linear residual at the plan's iterate, with D of the last assembly (assemble at the
  * iterate's v first).  rhs = 0: d_out (one local vector of the plan's handle) receives the
  * residual rows [r00, r01, r10, r11] of picard.non_linear_res_eval, Dirichlet rows zero;
  * rhs = 1: the right-hand side of the linearised solve (pressure rows times tau, CN: T_1 / T_2,
  * control.py:4266-4269).  *norm (host) = ||[r00, r01, r10, r11]||_2 by the deterministic
- * reduction. */
+ * reduction.  Time shards (collective): the rank's rows [lo, hi) of the four families, each
+ * bit for bit the row of the one-rank result; CN takes the transforms' terms across the shard
+ * boundary from the neighbours' raw rows; the norm is the all-reduced sum of the ranks' sums of
+ * squares, the same on every rank. */
 int kkt_picard_residual_device(kkt_handle plan, double *d_out, int rhs, double *norm);
 /* v, zeta, mu, p += the blocks of the update d_u (one local vector; CN: v from level 1);
  * then zeta = 0 on the Dirichlet dofs of every level (control.py:5127-5147).  d_u is zeroed:
- * the initial guess of the next linearised solve. */
+ * the initial guess of the next linearised solve.  Time shards: the rank's own levels; its halo
+ * levels are refreshed by the next assembly. */
 int kkt_picard_update_device(kkt_handle plan, double *d_u);
 
 /* Test hooks of the device re-linearisation: plain copies of what the kernels left, no launches.
  * kkt_debug_relin_array downloads one array of the plan's last assembly (cap: doubles available
  * at out): the element matrices Ev (n_t x ne x 36) and Ep (n_t x ne x 9), or the assembled
- * D2 (n_t x nnz2) and Dp (n_t x nnz1).  KKT_ERR_STATE before any assembly, KKT_ERR_ARG when cap
- * is too small. */
-enum { KKT_RELIN_EV = 0, KKT_RELIN_EP = 1, KKT_RELIN_D2 = 2, KKT_RELIN_DP = 3 };
+ * D2 (n_t x nnz2) and Dp (n_t x nnz1) -- on a time shard the levels of the D window, in order.
+ * KKT_ERR_STATE before any assembly, KKT_ERR_ARG when cap is too small.  KKT_RELIN_V and
+ * KKT_RELIN_ZETA: the v and zeta windows of the iterate as they are, halo levels included. */
+enum { KKT_RELIN_EV = 0, KKT_RELIN_EP = 1, KKT_RELIN_D2 = 2, KKT_RELIN_DP = 3, KKT_RELIN_V = 4,
+       KKT_RELIN_ZETA = 5 };
 int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
 /* The stored values of block (quadrant, i, j) in the CSR order of its pattern, read from the
  * SELL value array through the pattern's slot -> CSR map.  *nnz: the stored entries (out == NULL:
