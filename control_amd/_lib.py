@@ -114,6 +114,12 @@ class RelinRecipe(C.Structure):
                [("alpha", C.c_double), ("gamma", C.c_double)]
 
 
+# kkt_debug_krylov_op: the operations (KKT_KRYLOV_*) and the padding value (KKT_KRYLOV_PAD)
+KRYLOV_OPS = {name: k for k, name in enumerate(
+    ("mdot", "orthogonalise", "build_solution", "scale_inv", "axpby", "copy", "fill", "norm2",
+     "maxpy"))}
+KRYLOV_PAD = -6.02214076e23
+
 PC_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, c_f64p, c_f64p, c_f64p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int, C.c_int)
 SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int64, C.c_int,
@@ -187,6 +193,8 @@ SIGNATURES = {
     "kkt_debug_coarse_matrices": (C.c_int, [C.c_void_p, c_f64p, C.c_int64]),
     "kkt_debug_coarse_inverses": (C.c_int, [C.c_void_p, c_f64p, C.c_int64]),
     "kkt_debug_dense_inverse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p]),
+    "kkt_debug_krylov_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, c_f64p, c_f64p,
+                                      c_f64p, C.c_double, C.c_double, c_f64p, c_f64p, c_f64p]),
     "kkt_debug_set_steplock": (C.c_int, [C.c_void_p, C.POINTER(StepLock)]),
     "kkt_debug_apply_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "kkt_debug_pc_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),

@@ -492,6 +492,12 @@ int kkt_debug_dense_inverse(kkt_handle h, int n, int nmat, const double *a, doub
     });
 }
 
+int kkt_debug_krylov_op(kkt_handle h, int op, int64_t n, int nv, const double *w, const double *V,
+                        const double *coef, double a, double b, double *w_out,
+                        double *scalars_out, double *arena_out) {
+    KKT_TRY(h, S.debug_krylov_op(op, n, nv, w, V, coef, a, b, w_out, scalars_out, arena_out));
+}
+
 int kkt_debug_set_steplock(kkt_handle h, const kkt_steplock *lock) {
     KKT_TRY(h, {
         if (!lock) {

@@ -7,6 +7,7 @@
 //                        because the initial guess is flagged non-zero (:743).
 // All vector work is HIP kernels on the system's stream; the host sees one small
 // device-to-host copy per iteration (the new Hessenberg column and the norm).
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -37,6 +38,118 @@ void System::norm2(const double *w, double *d_out) {
     const double *V[1] = {w};
     mdot(w, V, 1, d_out + 1);
     launch_norm2_finish(stream, d_out + 1, d_out);
+}
+
+// w += sign * sum_i coef[i] V_i in passes of MDOT_MAX vectors, ascending
+void System::maxpy_groups(double *w, const double *const *V, int nv, const double *d_coef,
+                          double sign) {
+    for (int g = 0; g < nv; g += MDOT_MAX) {
+        const int mm = std::min(MDOT_MAX, nv - g);
+        VecList L{};
+        for (int i = 0; i < mm; ++i) L.v[i] = V[g + i];
+        launch_maxpy(stream, w, L, d_coef + g, sign, mm, n_local);
+    }
+}
+
+// classical Gram-Schmidt: h = V^T w; w -= V h; tt = ||w||
+void System::orthogonalise(double *w, const double *const *V, int nv, double *d_h) {
+    clock.mark(stream, StageClock::OTHER);
+    mdot(w, V, nv, d_h);
+    // the last update pass also leaves the partial sums of ||w||^2 (one pass over w
+    // less; same chunks and summation order as mdot_stage1, so tt is bitwise the norm a
+    // separate pass would give)
+    double *d_tt = d_h + nv;   // [tt, ||w||^2, flag]
+    for (int g = 0; g < nv; g += MDOT_MAX) {
+        const int mm = std::min(MDOT_MAX, nv - g);
+        VecList L{};
+        for (int i = 0; i < mm; ++i) L.v[i] = V[g + i];
+        if (g + MDOT_MAX >= nv)   // the last group
+            launch_maxpy_norm(stream, w, L, d_h + g, -1.0, mm, n_local, d_red_scratch,
+                              d_tt + 1);
+        else
+            launch_maxpy(stream, w, L, d_h + g, -1.0, mm, n_local);
+    }
+    clock.mark(stream, StageClock::ORTH);
+    // time shards: the preconditioner's time-out word rides on this all-reduce, so that
+    // every rank sees a time-out of any rank in the same iteration
+    const unsigned *d_flag = (sharded && pc) ? pc->err_word() : nullptr;
+    if (sharded) {
+        launch_flag_to_double(stream, d_flag, d_tt + 2);
+        comm->allreduce_sum(d_tt + 1, 2, stream);
+        clock.mark(stream, StageClock::ALLREDUCE);
+    }
+    launch_norm2_finish(stream, d_tt + 1, d_tt);
+    // (norm2_finish writes d_tt[0] and leaves d_tt[1]; the flag sits in d_tt[2])
+}
+
+// kkt_debug_krylov_op: one vector operation of the Krylov loops on host data, through the members
+// and launchers above.  The vectors sit as the solves keep them: one allocation, slot k at
+// k * stride doubles with stride = (n + 31) & ~31 (the double2 accesses rely on that spacing), w in
+// slot 0, V_i in slot 1 + i, the padding of every slot filled with KKT_KRYLOV_PAD; the reduction
+// scratch is REDUCE_BLOCKS * MDOT_MAX doubles.  Everything is released on return, and the
+// handle's own length and scratch are put back.
+void System::debug_krylov_op(int op, int64_t n, int nv, const double *w, const double *V,
+                             const double *coef, double a, double b, double *w_out,
+                             double *scalars_out, double *arena_out) {
+    if (n < 1 || nv < 0 || !w || !w_out || !scalars_out || (nv > 0 && !V))
+        fail(KKT_ERR_ARG, "bad krylov op arguments");
+    const bool needs_coef = op == KKT_KRYLOV_BUILD_SOLUTION || op == KKT_KRYLOV_MAXPY;
+    const bool needs_v = op == KKT_KRYLOV_ORTHOGONALISE || op == KKT_KRYLOV_AXPBY;
+    if (op < KKT_KRYLOV_MDOT || op > KKT_KRYLOV_MAXPY || (needs_coef && nv > 0 && !coef) ||
+        (needs_v && nv < 1))
+        fail(KKT_ERR_ARG, "bad krylov op arguments");
+    if (sharded) fail(KKT_ERR_STATE, "kkt_debug_krylov_op on a time-sharded handle");
+    const size_t stride = (size_t)((n + 31) & ~(int64_t)31), slots = (size_t)nv + 1;
+    std::vector<double> host(slots * stride, KKT_KRYLOV_PAD);
+    std::copy(w, w + n, host.begin());
+    for (int i = 0; i < nv; ++i) std::copy(V + (size_t)i * n, V + (size_t)(i + 1) * n,
+                                           host.begin() + (size_t)(i + 1) * stride);
+    DevBuf<double> arena = DevBuf<double>::upload(host.data(), host.size());
+    DevBuf<double> scratch = DevBuf<double>::alloc((size_t)REDUCE_BLOCKS * MDOT_MAX);
+    std::vector<double> hs((size_t)nv + 3, 0.0);
+    if (op == KKT_KRYLOV_SCALE_INV) hs[0] = a;
+    DevBuf<double> d_s = DevBuf<double>::upload(hs.data(), hs.size());
+    DevBuf<double> d_c = DevBuf<double>::upload(coef, needs_coef ? (size_t)nv : 0);
+    double *dw = arena.get();
+    std::vector<const double *> Vl(nv);
+    for (int i = 0; i < nv; ++i) Vl[i] = dw + (size_t)(i + 1) * stride;
+
+    struct Restore {
+        System &S;
+        int64_t n_local;
+        double *d_red_scratch;
+        bool clock_on;
+        ~Restore() {
+            S.n_local = n_local;
+            S.d_red_scratch = d_red_scratch;
+            S.clock.on = clock_on;
+        }
+    } restore{*this, n_local, d_red_scratch, clock.on};
+    n_local = n;
+    d_red_scratch = scratch.get();
+    clock.on = false;
+    switch (op) {
+        case KKT_KRYLOV_MDOT: mdot(dw, Vl.data(), nv, d_s.get()); break;
+        case KKT_KRYLOV_ORTHOGONALISE: orthogonalise(dw, Vl.data(), nv, d_s.get()); break;
+        case KKT_KRYLOV_BUILD_SOLUTION: maxpy_groups(dw, Vl.data(), nv, d_c.get(), 1.0); break;
+        case KKT_KRYLOV_MAXPY: maxpy_groups(dw, Vl.data(), nv, d_c.get(), a); break;
+        case KKT_KRYLOV_SCALE_INV: launch_scale_inv(stream, dw, dw, d_s.get(), n); break;
+        case KKT_KRYLOV_AXPBY: launch_axpby(stream, dw, a, Vl[0], b, n); break;
+        case KKT_KRYLOV_COPY: launch_copy(stream, dw, nv > 0 ? Vl[0] : dw, n); break;
+        case KKT_KRYLOV_FILL: launch_fill(stream, dw, a, n); break;
+        case KKT_KRYLOV_NORM2: norm2(dw, d_s.get()); break;
+    }
+    HIPCHK(hipGetLastError());
+    sync();
+    HIPCHK(hipMemcpy(hs.data(), d_s.get(), hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (op == KKT_KRYLOV_SCALE_INV) hs[0] = 0.0;
+    std::copy(hs.begin(), hs.begin() + nv + 2, scalars_out);
+    if (arena_out) {
+        HIPCHK(hipMemcpy(arena_out, dw, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+        std::copy(arena_out, arena_out + n, w_out);
+    } else {
+        HIPCHK(hipMemcpy(w_out, dw, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    }
 }
 
 void System::ensure_workspace(int restart, bool flexible) {
@@ -477,33 +590,8 @@ void System::solve_once(const double *d_b, double *d_u, int *its_out, int *reaso
             // classical Gram-Schmidt: h = V^T w; w -= V h; tt = ||w||
             std::vector<const double *> Vl(it + 1);
             for (int k = 0; k <= it; ++k) Vl[k] = Vp(k);
-            clock.mark(stream, StageClock::OTHER);
-            mdot(w, Vl.data(), it + 1, d_hcol);
-            // the last update pass also leaves the partial sums of ||w||^2 (one pass over w
-            // less; same chunks and summation order as mdot_stage1, so tt is bitwise the norm a
-            // separate pass would give)
-            double *d_tt = d_hcol + (it + 1);   // [tt, scratch]
-            for (int g = 0; g <= it; g += MDOT_MAX) {
-                const int mm = std::min(MDOT_MAX, it + 1 - g);
-                VecList L{};
-                for (int i = 0; i < mm; ++i) L.v[i] = Vl[g + i];
-                if (g + MDOT_MAX > it)
-                    launch_maxpy_norm(stream, w, L, d_hcol + g, -1.0, mm, n_local, d_red_scratch,
-                                      d_tt + 1);
-                else
-                    launch_maxpy(stream, w, L, d_hcol + g, -1.0, mm, n_local);
-            }
-            clock.mark(stream, StageClock::ORTH);
-            // time shards: the preconditioner's time-out word rides on this all-reduce, so that
-            // every rank sees a time-out of any rank in the same iteration
-            const unsigned *d_flag = (sharded && pc) ? pc->err_word() : nullptr;
-            if (sharded) {
-                launch_flag_to_double(stream, d_flag, d_tt + 2);
-                comm->allreduce_sum(d_tt + 1, 2, stream);
-                clock.mark(stream, StageClock::ALLREDUCE);
-            }
-            launch_norm2_finish(stream, d_tt + 1, d_tt);
-            // (norm2_finish writes d_tt[0] and leaves d_tt[1]; the flag sits in d_tt[2])
+            double *d_tt = d_hcol + (it + 1);   // [tt, ||w||^2, time-out flag (time shards)]
+            orthogonalise(w, Vl.data(), it + 1, d_hcol);
             read_scalars(d_hcol, it + 2 + (sharded ? 2 : 0));
             if (pc) {
                 std::string why;
@@ -573,12 +661,9 @@ void System::solve_once(const double *d_b, double *d_u, int *its_out, int *reaso
                 launch_fill(stream, d_t1, 0.0, n_local);
                 acc = d_t1;
             }
-            for (int g = 0; g < it; g += MDOT_MAX) {
-                const int mm = std::min(MDOT_MAX, it - g);
-                VecList L{};
-                for (int i = 0; i < mm; ++i) L.v[i] = flexible ? Zp(g + i) : Vp(g + i);
-                launch_maxpy(stream, acc, L, d_coef + g, 1.0, mm, n_local);
-            }
+            std::vector<const double *> Bl(it);
+            for (int k = 0; k < it; ++k) Bl[k] = flexible ? Zp(k) : Vp(k);
+            maxpy_groups(acc, Bl.data(), it, d_coef, 1.0);
             if (right && !flexible) {
                 pc_apply(d_t1, d_t2);
                 launch_axpby(stream, d_u, 1.0, d_t2, 1.0, n_local);

@@ -312,6 +312,15 @@ struct System {
     // reductions over the whole (distributed) vector; results in device memory
     void mdot(const double *w, const double *const *V, int nv, double *d_out);
     void norm2(const double *w, double *d_out);   // d_out[0] = ||w||_2, d_out[1] scratch
+    // the Gram-Schmidt step of GMRES: d_h[0..nv) = V^T w, w -= V h in passes of MDOT_MAX vectors,
+    // d_h[nv] = ||w||, d_h[nv + 1] = ||w||^2 (time shards: d_h[nv + 2] = the time-out flag)
+    void orthogonalise(double *w, const double *const *V, int nv, double *d_h);
+    // w += sign * sum_i d_coef[i] V_i in passes of MDOT_MAX vectors (KSPGMRESBuildSoln: sign = 1)
+    void maxpy_groups(double *w, const double *const *V, int nv, const double *d_coef, double sign);
+    // kkt_debug_krylov_op (include/kkt.h)
+    void debug_krylov_op(int op, int64_t n, int nv, const double *w, const double *V,
+                         const double *coef, double a, double b, double *w_out,
+                         double *scalars_out, double *arena_out);
     // y = P x: lhs_right / lhs_left of every block's nullspace (preconditioner.py:92-106)
     void ns_project(double *y, const double *x);
     // y = P u + (I - P) b on top of u stored in `u` (preconditioner.py:114-116)

@@ -526,6 +526,35 @@ int kkt_debug_coarse_matrices(kkt_handle h, double *out, int64_t cap);
 int kkt_debug_coarse_inverses(kkt_handle h, double *out, int64_t cap);
 int kkt_debug_dense_inverse(kkt_handle h, int n, int nmat, const double *a, double *inv, int *bad);
 
+/* Test hook of the Krylov vector kernels: one operation of the GMRES / MINRES loops on host data,
+ * through the members and launchers the solves call.  Independent of the handle's layout: works
+ * on a created handle, before or after kkt_finalize (not on a time-sharded one).  w: n doubles;
+ * V: nv vectors of n doubles, contiguous; coef: nv doubles (BUILD_SOLUTION, MAXPY).  On the
+ * device the vectors sit as the solves keep them, in one allocation at a stride of (n + 31) & ~31
+ * doubles: w in slot 0, V_i in slot 1 + i, the padding of every slot set to KKT_KRYLOV_PAD.
+ * w_out (n doubles) receives slot 0 after the operation, scalars_out (nv + 2 doubles, zero where
+ * the operation writes nothing) its scalar results, arena_out (NULL, or (nv + 1) * stride
+ * doubles) the whole allocation.
+ *   MDOT            scalars[i] = <w, V_i>
+ *   ORTHOGONALISE   the classical Gram-Schmidt step (nv >= 1): scalars[i] = h_i = <w, V_i>,
+ *                   w -= sum h_i V_i, scalars[nv] = ||w||, scalars[nv + 1] = ||w||^2
+ *   BUILD_SOLUTION  w += sum coef_i V_i, grouped as KSPGMRESBuildSoln
+ *   SCALE_INV       w = w * (1 / a)
+ *   AXPBY           w = a V_0 + b w (nv >= 1)
+ *   COPY            w = V_0; nv == 0: w = w, which launches nothing
+ *   FILL            w = a
+ *   NORM2           scalars[0] = ||w||, scalars[1] = ||w||^2
+ *   MAXPY           w += a sum coef_i V_i by the plain grouped passes alone (a = -1: the update of
+ *                   ORTHOGONALISE without the fused norm)
+ * KKT_ERR_ARG for n < 1, nv < 0, an unknown op or a null array the operation reads or writes. */
+enum { KKT_KRYLOV_MDOT = 0, KKT_KRYLOV_ORTHOGONALISE = 1, KKT_KRYLOV_BUILD_SOLUTION = 2,
+       KKT_KRYLOV_SCALE_INV = 3, KKT_KRYLOV_AXPBY = 4, KKT_KRYLOV_COPY = 5, KKT_KRYLOV_FILL = 6,
+       KKT_KRYLOV_NORM2 = 7, KKT_KRYLOV_MAXPY = 8 };
+#define KKT_KRYLOV_PAD (-6.02214076e23)
+int kkt_debug_krylov_op(kkt_handle h, int op, int64_t n, int nv, const double *w, const double *V,
+                        const double *coef, double a, double b, double *w_out,
+                        double *scalars_out, double *arena_out);
+
 /* Step-locked parity hook (tests): while set, kkt_solve / kkt_solve_device with gmres or
  * fgmres replace their Krylov basis v_0 .. v_it by the caller's vectors before inner step `it`
  * of global step s (s < n_steps), and record what the step produced from them: the classical
