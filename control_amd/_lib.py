@@ -61,7 +61,14 @@ class Info(C.Structure):
                  "sweep_its", "apply_launches", "apply_switched", "blocks_unset")]
 
     def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
+        return {n: getattr(self, n) for cls in reversed(type(self).__mro__)
+                for n, _ in cls.__dict__.get("_fields_", ())}
+
+
+class InfoRings(Info):
+    """``kkt_info`` as the library fills it today: the fields of ``Info`` (whose list is pinned
+    where it stood when ``blocks_unset`` was appended) followed by what was appended since."""
+    _fields_ = [("sweep_coarse_rings", C.c_int64)]
 
 
 class StageTimes(C.Structure):

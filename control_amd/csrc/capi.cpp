@@ -95,6 +95,7 @@ static const OptionKey option_keys[] = {
     {"coarse_setup", "batched | columns", set_coarse_setup},
     {"coarse_keep", "0 | 1", set_switch<&Options::coarse_keep>},
     {"coarse_blocks", "0 | 1", set_switch<&Options::coarse_blocks>},
+    {"coarse_rings", "0 | 1", set_switch<&Options::coarse_rings>},
     {"stage_timers", "0 | 1", set_switch<&Options::stage_timers>},
     {"verbose", "0 | 1", set_switch<&Options::verbose>},
     {"stamps", "0 | 1", set_switch<&Options::stamps>},

@@ -171,22 +171,29 @@ struct alignas(128) TileLevel {
 // Coarse corrections inside the tile program (two-grid form of the sub-solves): what a tile needs
 // to restrict its own rows' residual to the coarse functions they touch (J_t), to publish those
 // partial sums, to assemble the whole coarse residual from every tile's partials in a fixed order,
-// to apply its rows of (P^T A P)^-1 and to prolong onto its own rows.  Device-resident plan,
-// built by SchurPC from the tile plan and P (csrc/pc.cpp, build_tile_coarse).
+// to apply its rows of (P^T A P)^-1 and to prolong onto its own rows -- and, with `ring_prolong`,
+// onto its ring rows as well, from the products of J_t+ = J_t followed by the coarse functions
+// that only ring rows touch (no hand-off after a correction then).  Device-resident plan: lists
+// from tiles.cpp (build_tile_coarse_lists), uploaded by SchurPC (csrc/pc.cpp, build_tile_coarse).
 struct TileCoarseDev {
-    int32_t nc, jmax, n0max, nslots;
-    int32_t nr_max;               // most restriction (= prolongation) entries of a tile
+    int32_t nc, jmax, pstride, nslots;
+    int32_t nr_max;               // most restriction (= own-row prolongation) entries of a tile
     int32_t cache_lists;          // 1: every tile copies its entries into LDS (they fit)
     int32_t cache_einv;           // 1: ... and keeps the rows of (P^T A P)^-1 it owns there
     int32_t nown;                 // most coarse functions a tile owns: ceil(nc / ntiles)
+    int32_t jxmax;                // max |J_t+|: stride of jglob (= jmax when the lists have no rings)
+    int32_t np_max;               // most prolongation entries of a tile, ring rows included
+    int32_t ring_prolong;         // 1: tiles prolong onto their rings (needs cache_lists)
     const int32_t *nj;            // [ntiles] number of coarse functions the own rows touch
-    const int32_t *jglob;         // [ntiles][jmax] their global numbers
+    const int32_t *njx;           // [ntiles] ... and with those only ring rows touch, >= nj
+    const int32_t *jglob;         // [ntiles][jxmax] their global numbers, J_t first
     const int32_t *slot0;         // [ntiles] first slot of the tile's partial sums
     const int32_t *r_ip;          // [ntiles * jmax + 1] restriction lists, per (tile, k) ...
     const uint16_t *r_row;        // ... local own row
     const double *r_w;            // ... and weight, ascending rows
-    const int32_t *p_ip;          // [ntiles * n0max + 1] prolongation entries of the own rows ...
-    const uint16_t *p_k;          // ... index into the tile's J_t
+    const int32_t *p_ip;          // [ntiles * pstride + 1] prolongation entries of the local rows
+                                  // (own rows first; ring rows have entries only in lists with rings) ...
+    const uint16_t *p_k;          // ... index into the tile's J_t+
     const double *p_w;
     const int32_t *c_ip;          // [nc + 1] slots that contribute to a coarse function ...
     const int32_t *c_slot;        // ... ascending (tile order)
@@ -232,7 +239,14 @@ bool tile_sweep_fuses_update(int W, int max_terms);   // update terms of any lev
 size_t tile_sweep_lds_bytes(int nk_pad, int its, int coarse_nc = 0, int coarse_nslots = 0,
                             int coarse_jmax = 0, int coarse_nr_max = 0,
                             int coarse_einv_rows = 0,
-                            int coarse_einv_width = 0);   // rows of the coarse inverse kept in LDS
+                            int coarse_einv_width = 0,   // rows of the coarse inverse kept in LDS
+                            int coarse_ring_entries = 0,  // ring form: entries of the ring rows ...
+                            int coarse_jxmax = 0);        // ... and max |J_t+| (0: no ring form)
+// the footprint of a coarse plan as the kernel lays it out: `cache` 0 nothing cached, 1 the lists,
+// 2 also the rows of the coarse inverse; `rings`: the ring form (needs cache >= 1)
+size_t tile_sweep_lds_bytes(int nk_pad, int its, const TileCoarseDev &c, int cache, bool rings);
+// ... with the plan's own settings
+size_t tile_sweep_lds_bytes(int nk_pad, int its, const TileCoarseDev &c);
 // workgroups of `threads` that are certainly co-resident (one per CU)
 int tile_sweep_max_tiles(int W, int rpt, int threads, size_t lds_bytes, int hslots,
                          bool coarse = false);

@@ -116,6 +116,7 @@ void SchurPC::values_changed() {
         std::fprintf(stderr, "[kkt] Chebyshev sub-solves: degree %d; %lld Lanczos steps spent on "
                      "%zu matrices\n", schur_its_, (long long)spectrum_steps_, mats_.size());
     S_.info.sweep_form = 0;
+    S_.info.sweep_coarse_rings = 0;
     S_.info.sweep_tiles = S_.info.sweep_threads = S_.info.sweep_depth = S_.info.sweep_row_slots = 0;
     S_.info.sweep_its = schur_its_;
     fuse_programs();
@@ -347,20 +348,28 @@ bool SchurPC::prepare_tiles() {
     if (coarse_cycles_ > 0 && tile_sweep_coarse_available(tp.W, tp.rpt, threads, tp.hslots) &&
         build_tile_coarse()) {
         // the tiles' P entries go into LDS when everything fits in 150 KB, else they stay in memory
-        // (and, room permitting, its rows of the coarse inverse: cache = 2)
-        for (int cache = 2; cache >= 0 && !tile_coarse_ok_; --cache) {
-            const size_t lds_c = tile_sweep_lds_bytes(tp.nk_pad, max_its, h_tile_coarse_.nc,
-                                                      h_tile_coarse_.nslots, h_tile_coarse_.jmax,
-                                                      cache ? h_tile_coarse_.nr_max : 0,
-                                                      cache == 2 ? h_tile_coarse_.nown : 0,
-                                                      h_tile_coarse_.ew);
+        // (and, room permitting, its rows of the coarse inverse: cache = 2; and the ring rows'
+        // entries: the ring form).  Short of room the rings are given up before the rows of the
+        // inverse (those save 6 us of an exchange, tile_kernels.hip; a hand-off costs 2-3.4) --
+        // but where the rows do not fit anyway, the rings are taken if they do.
+        for (int pick = 0; pick < 5 && !tile_coarse_ok_; ++pick) {
+            const int cache = pick < 2 ? 2 : pick < 4 ? 1 : 0;
+            const bool rings = pick == 0 || pick == 2;
+            if (rings && !tile_coarse_rings_built_) continue;
+            const size_t lds_c = tile_sweep_lds_bytes(tp.nk_pad, max_its, h_tile_coarse_, cache, rings);
             if (lds_c <= 150 * 1024 &&
                 tp.ntiles <= tile_sweep_max_tiles(tp.W, tp.rpt, threads, lds_c, tp.hslots, true)) {
                 tile_coarse_ok_ = true;
                 h_tile_coarse_.cache_lists = cache >= 1;
                 h_tile_coarse_.cache_einv = cache == 2;
+                h_tile_coarse_.ring_prolong = rings;
                 HIPCHK(hipMemcpy(d_tile_coarse_, &h_tile_coarse_, sizeof h_tile_coarse_,
                                  hipMemcpyHostToDevice));
+                if (S_.opts.verbose)
+                    std::fprintf(stderr, "[kkt] tile sweep program, coarse corrections: %zu bytes of "
+                                 "LDS for %d sweeps (lists %s, coarse inverse rows %s), "
+                                 "sweep_coarse_rings %d\n", lds_c, max_its, cache >= 1 ? "cached" : "in memory",
+                                 cache == 2 ? "cached" : "in memory", (int)rings);
             }
         }
     }
@@ -378,71 +387,20 @@ bool SchurPC::prepare_tiles() {
     return true;
 }
 
-// Coarse corrections inside the tile program: per tile, the coarse functions its own rows touch
-// (J_t) with their restriction lists, the prolongation entries of its own rows, the slots of its
-// partial sums; per coarse function, the slots that contribute to it (ascending tile order).
+// Coarse corrections inside the tile program: the lists of tiles.cpp (build_tile_coarse_lists)
+// on the device, the granule buffers of the exchanges, the column ranges of the coarse inverse.
 bool SchurPC::build_tile_coarse() {
     const TilePlan &tp = tile_plan_;
     const int nt = tp.ntiles, nc = coarse_.nc;
-    if (nt < 1 || nc < 1) return false;
-    std::vector<int32_t> nj(nt, 0), slot0(nt, 0);
-    std::vector<std::vector<int32_t>> J(nt);
-    int n0max = 0;
-    for (int t = 0; t < nt; ++t) {
-        const int n0 = tp.n[(size_t)t * (TILE_MAX_DEPTH + 1)];
-        n0max = std::max(n0max, n0);
-        std::vector<int32_t> &j = J[t];
-        for (int l = 0; l < n0; ++l) {
-            const int32_t g = tp.grow[(size_t)t * tp.nk_pad + l];
-            for (int32_t q = p_indptr_[g]; q < p_indptr_[g + 1]; ++q) j.push_back(p_indices_[q]);
-        }
-        std::sort(j.begin(), j.end());
-        j.erase(std::unique(j.begin(), j.end()), j.end());
-        nj[t] = (int32_t)j.size();
-    }
-    int jmax = 0, nslots = 0;
-    for (int t = 0; t < nt; ++t) {
-        jmax = std::max(jmax, nj[t]);
-        slot0[t] = nslots;
-        nslots += nj[t];
-    }
-    if (jmax < 1 || jmax > 65535 || nslots > 65536) return false;
-    std::vector<int32_t> jglob((size_t)nt * jmax, -1), r_ip((size_t)nt * jmax + 1, 0),
-        p_ip((size_t)nt * n0max + 1, 0), c_ip(nc + 1, 0), c_slot;
-    std::vector<uint16_t> r_row, p_k;
-    std::vector<double> r_w, p_w;
-    std::vector<std::vector<int32_t>> contrib(nc);
-    for (int t = 0; t < nt; ++t) {
-        const int n0 = tp.n[(size_t)t * (TILE_MAX_DEPTH + 1)];
-        const std::vector<int32_t> &j = J[t];
-        std::vector<std::vector<std::pair<uint16_t, double>>> lists(j.size());
-        for (int l = 0; l < n0; ++l) {
-            const int32_t g = tp.grow[(size_t)t * tp.nk_pad + l];
-            for (int32_t q = p_indptr_[g]; q < p_indptr_[g + 1]; ++q) {
-                const int k = (int)(std::lower_bound(j.begin(), j.end(), p_indices_[q]) - j.begin());
-                lists[k].push_back({(uint16_t)l, p_values_[q]});
-                p_k.push_back((uint16_t)k);
-                p_w.push_back(p_values_[q]);
-            }
-            p_ip[(size_t)t * n0max + l + 1] = (int32_t)p_k.size();
-        }
-        for (int l = n0; l < n0max; ++l) p_ip[(size_t)t * n0max + l + 1] = (int32_t)p_k.size();
-        for (size_t k = 0; k < (size_t)jmax; ++k) {
-            if (k < j.size()) {
-                jglob[(size_t)t * jmax + k] = j[k];
-                contrib[j[k]].push_back(slot0[t] + (int)k);
-                for (auto &e : lists[k]) {
-                    r_row.push_back(e.first);
-                    r_w.push_back(e.second);
-                }
-            }
-            r_ip[(size_t)t * jmax + k + 1] = (int32_t)r_row.size();
-        }
-    }
-    for (int j = 0; j < nc; ++j) {
-        for (int32_t sl : contrib[j]) c_slot.push_back(sl);
-        c_ip[j + 1] = (int32_t)c_slot.size();
-    }
+    TileCoarseLists L;
+    if (!build_tile_coarse_lists(tp, nc, p_indptr_.data(), p_indices_.data(), p_values_.data(),
+                                 S_.opts.coarse_rings, L))
+        return false;
+    const int jmax = L.jmax, nslots = L.nslots;
+    std::vector<int32_t> &nj = L.nj, &njx = L.njx, &slot0 = L.slot0, &jglob = L.jglob, &r_ip = L.r_ip,
+                         &p_ip = L.p_ip, &c_ip = L.c_ip, &c_slot = L.c_slot;
+    std::vector<uint16_t> &r_row = L.r_row, &p_k = L.p_k;
+    std::vector<double> &r_w = L.r_w, &p_w = L.p_w;
     // handle memory: prepare_tiles() runs once per handle, and so does this
     auto up = [&](const auto &v) {
         return handle_mem_.upload(v.data(), std::max<size_t>(1, v.size()));
@@ -450,15 +408,15 @@ bool SchurPC::build_tile_coarse() {
     TileCoarseDev &D = h_tile_coarse_;
     D.nc = nc;
     D.jmax = jmax;
-    D.n0max = n0max;
+    D.pstride = L.pstride;
     D.nslots = nslots;
-    {
-        int nrm = 1;
-        for (int t = 0; t < nt; ++t)
-            nrm = std::max(nrm, r_ip[(size_t)t * jmax + nj[t]] - r_ip[(size_t)t * jmax]);
-        D.nr_max = nrm;
-    }
+    D.nr_max = L.nr_max;
+    D.jxmax = L.jxmax;
+    D.np_max = L.np_max;
+    D.ring_prolong = 0;           // prepare_tiles(): where the longer lists fit on chip
+    tile_coarse_rings_built_ = L.rings;
     D.nj = up(nj);
+    D.njx = up(njx);
     D.jglob = up(jglob);
     D.slot0 = up(slot0);
     D.r_ip = up(r_ip);
@@ -547,7 +505,11 @@ bool SchurPC::build_tile_coarse() {
     d_tile_coarse_ = handle_mem_.upload(&D, 1);
     if (S_.opts.verbose)
         std::fprintf(stderr, "[kkt] tile sweep program, coarse corrections: %d coarse functions, at most "
-                     "%d per tile, %d partial-sum slots\n", nc, jmax, nslots);
+                     "%d per tile (%d with the rings'), %d partial-sum slots; prolongation entries of a "
+                     "tile: at most %d on own rows, %d with the rings (%s)\n", nc, jmax, L.jxmax,
+                     nslots, L.nr_max, L.np_max,
+                     L.rings ? "lists with rings" : S_.opts.coarse_rings ? "no rings: long rows of P"
+                                                                         : "no rings: coarse_rings = 0");
     return true;
 }
 
@@ -570,13 +532,7 @@ bool SchurPC::fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out) {
     if (coarse && !tile_coarse_ok_) return false;
     {
         // residency and the dynamic-LDS attribute were checked for tile_lds_checked_ bytes
-        const size_t need = coarse ? tile_sweep_lds_bytes(tile_plan_.nk_pad, its, h_tile_coarse_.nc,
-                                                          h_tile_coarse_.nslots, h_tile_coarse_.jmax,
-                                                          h_tile_coarse_.cache_lists
-                                                              ? h_tile_coarse_.nr_max : 0,
-                                                          h_tile_coarse_.cache_einv
-                                                              ? h_tile_coarse_.nown : 0,
-                                                          h_tile_coarse_.ew)
+        const size_t need = coarse ? tile_sweep_lds_bytes(tile_plan_.nk_pad, its, h_tile_coarse_)
                                    : tile_sweep_lds_bytes(tile_plan_.nk_pad, its);
         if (need > tile_lds_checked_) {
             if (need > 150 * 1024 ||
@@ -810,6 +766,10 @@ void SchurPC::fuse_programs() {
     S_.info.sweep_threads = form == 3 ? tile_plan_.threads : 0;
     S_.info.sweep_depth = form == 3 ? tile_plan_.depth : 0;
     S_.info.sweep_row_slots = form == 3 ? tile_plan_.rpt : 0;
+    bool rings = false;
+    for (const PcStep &s : steps_)
+        if (s.kind == PcStep::TILE && s.coarse) rings = h_tile_coarse_.ring_prolong != 0;
+    S_.info.sweep_coarse_rings = rings ? 1 : 0;
 }
 
 // The form replay() gives each row step, sweep program and tile launch (kkt_debug_pc_forms)

@@ -257,6 +257,7 @@ class SchurPC : public PcBase {
     TileCoarseDev h_tile_coarse_{};     // host copy (device pointers inside)
     TileCoarseDev *d_tile_coarse_ = nullptr;
     bool tile_coarse_ok_ = false;
+    bool tile_coarse_rings_built_ = false;   // the lists hold the ring rows' entries
     uint32_t tile_cepoch_cursor_ = 0;
     bool build_tile_coarse();
     unsigned long long *d_tg_[4] = {nullptr, nullptr, nullptr, nullptr};

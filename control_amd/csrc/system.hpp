@@ -37,6 +37,7 @@ struct Options {
     int prog_waves = 0, tile_depth = 0, tile_waves = 0;          // 0: chosen by shape / modelled
     bool coarse_columns = false;                                  // "coarse_setup" = "columns"
     bool coarse_keep = false, coarse_blocks = true;
+    bool coarse_rings = true;     // two-grid tile sweeps: tiles prolong onto their rings themselves
     // diagnostics and test hooks
     bool stage_timers = false, verbose = false, stamps = false;
     int tile_poll_delay = 24, debug_drop_handoff = 0;

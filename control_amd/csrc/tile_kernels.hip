@@ -221,16 +221,23 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     double *dump = scoef + 3 * (size_t)(COARSE ? (its > 0 ? its : 1) : (its > 1 ? its - 1 : 1));
     // coarse corrections: every tile's partial sums, the coarse residual, this tile's corrections
     double *SL = dump + 1, *RC = nullptr, *EC = nullptr;
-    int c_nc = 0, c_jmax = 0, c_n0max = 0, c_nslots = 0, c_nj = 0, c_slot0 = 0;
+    int c_nc = 0, c_jmax = 0, c_pstride = 0, c_nslots = 0, c_nj = 0, c_slot0 = 0;
+    // ring form (TileCoarseDev::ring_prolong): the products of J_t+ are polled (c_njp of them,
+    // else the c_nj of J_t), at most c_jx per tile
+    bool c_rings = false;
+    int c_njp = 0, c_jx = 0;
     unsigned cepoch = A.cepoch0;
     if constexpr (COARSE) {
         const TileCoarseDev *cd = A.coarse;
         c_nc = cd->nc;
         c_jmax = cd->jmax;
-        c_n0max = cd->n0max;
+        c_pstride = cd->pstride;
         c_nslots = cd->nslots;
         c_nj = cd->nj[tile];
         c_slot0 = cd->slot0[tile];
+        c_rings = cd->ring_prolong != 0;
+        c_njp = c_rings ? cd->njx[tile] : c_nj;
+        c_jx = c_rings ? cd->jxmax : c_jmax;
         RC = SL + c_nslots;
         EC = RC + c_nc;
     }
@@ -239,6 +246,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     // restriction lists and prolongation entries, the slot -> coarse function map
     double *RWc = nullptr, *PWc = nullptr;
     int *CSLc = nullptr, *CIPc = nullptr, *RIPc = nullptr, *JGc = nullptr;
+    int *PIPc = nullptr;     // ring form: entry offsets of all nk local rows (nk + 1 of them)
     uint16_t *RROWc = nullptr, *PKc = nullptr;
     int pe0[RPT], pe1[RPT];
     bool c_cached = true;    // the tile's P entries are in LDS (3-D: 8 per row, they stay in memory)
@@ -265,22 +273,26 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
             c_hi0 = cd->e_hi[j0];
         }
         c_cached = cd->cache_lists != 0;
+        // (the layout tile_sweep_lds_bytes() counts)
         const int nrm = c_cached ? cd->nr_max : 0;
-        RWc = EC + c_jmax;
+        const int npm = c_rings ? cd->np_max : nrm;
+        RWc = EC + c_jx;
         PWc = RWc + nrm;
-        CSLc = reinterpret_cast<int *>(PWc + nrm);
+        CSLc = reinterpret_cast<int *>(PWc + npm);
         CIPc = CSLc + c_nslots;
         RIPc = CIPc + (c_nc + 1);
         JGc = RIPc + (c_jmax + 1);
-        RROWc = reinterpret_cast<uint16_t *>(JGc + c_jmax);
+        PIPc = JGc + c_jx;
+        RROWc = reinterpret_cast<uint16_t *>(PIPc + (c_rings ? nkp + 1 : 0));
         PKc = RROWc + nrm;
         c_einv_cache = cd->cache_einv != 0;
         // (8-byte aligned: behind the 2-byte lists, rounded up)
         EINVc = reinterpret_cast<double *>(
-            (reinterpret_cast<uintptr_t>(PKc + nrm) + 7) & ~(uintptr_t)7);
+            (reinterpret_cast<uintptr_t>(PKc + npm) + 7) & ~(uintptr_t)7);
         const gci_p rip = (gci_p)cd->r_ip + (size_t)tile * c_jmax;
-        const gci_p pip = (gci_p)cd->p_ip + (size_t)tile * c_n0max;
-        const int re0 = rip[0], re1 = rip[c_nj], pq0 = pip[0], pq1 = pip[nt[0]];
+        const gci_p pip = (gci_p)cd->p_ip + (size_t)tile * c_pstride;
+        // (ring form: the ring rows' entries lie behind the own rows')
+        const int re0 = rip[0], re1 = rip[c_nj], pq0 = pip[0], pq1 = pip[c_rings ? nk : nt[0]];
         c_re0 = re0;
         c_pq0 = pq0;
         const gcu16_p rrow = (gcu16_p)cd->r_row, pk = (gcu16_p)cd->p_k;
@@ -298,9 +310,11 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         const gci_p cslot = (gci_p)cd->c_slot, cip = (gci_p)cd->c_ip;
         for (int i = tid; i < c_nslots; i += T) CSLc[i] = cslot[i];
         for (int i = tid; i <= c_nc; i += T) CIPc[i] = cip[i];
-        const gci_p jg = (gci_p)cd->jglob + (size_t)tile * c_jmax;
+        const gci_p jg = (gci_p)cd->jglob + (size_t)tile * cd->jxmax;
         for (int i = tid; i <= c_nj; i += T) RIPc[i] = rip[i] - re0;
-        for (int i = tid; i < c_nj; i += T) JGc[i] = jg[i];
+        for (int i = tid; i < c_njp; i += T) JGc[i] = jg[i];
+        if (c_rings)
+            for (int i = tid; i <= nk; i += T) PIPc[i] = pip[i] - pq0;
 #pragma unroll
         for (int sl = 0; sl < RPT; ++sl) {
             const int r = sl * T + tid;
@@ -815,7 +829,10 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                         if (r < n0) Xo[r] = b[sl];          // zero guess: r = b
                     }
                 } else {
-                    if (cr == 0) {                          // the first ring must be valid
+                    // the first ring must be valid; ring form: every ring, the correction is
+                    // added to them (the same condition in every tile: they all take the same
+                    // sequence of hand-offs, which the alternation of the granule buffers needs)
+                    if (cr == 0 || (c_rings && cr < depth)) {
                         handoff(false);
                         cr = depth;
                     }
@@ -976,14 +993,15 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                     }
                     KKT_XS(5);      // owned products + publish
                     // ---- the products for the functions the own rows touch, from their owners
-                    for (int k0 = 0; k0 < c_nj; k0 += T) {
+                    // (ring form: and for those its ring rows touch)
+                    for (int k0 = 0; k0 < c_njp; k0 += T) {
                         const int k = k0 + tid;
                         u32x4 g = u32x4{0u, 0u, 0u, 0u};
                         unsigned spins = 0;
                         while (true) {
                             asm volatile("" ::: "memory");
                             bool ok = true;
-                            if (k < c_nj && (g.y != cepoch || g.w != cepoch)) {
+                            if (k < c_njp && (g.y != cepoch || g.w != cepoch)) {
                                 g = __builtin_amdgcn_raw_buffer_load_b128(re_, JGc[k] * 16, 0, 16);
                                 ok = g.y == cepoch && g.w == cepoch;
                             }
@@ -996,7 +1014,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                                     A.err[8] = (unsigned)tile;
                                     A.err[9] = cepoch;
                                     A.err[10] = 0xfffeu;            // products of a coarse exchange
-                                    A.err[11] = (unsigned)(k < c_nj ? JGc[k] : 0);
+                                    A.err[11] = (unsigned)(k < c_njp ? JGc[k] : 0);
                                     A.err[12] = g.y;
                                     A.err[13] = g.w;
                                     A.err[16] = 2u;
@@ -1005,7 +1023,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                             }
                             __builtin_amdgcn_s_sleep(1);
                         }
-                        if (k < c_nj)
+                        if (k < c_njp)
                             EC[k] = __longlong_as_double((long long)(
                                 (unsigned long long)g.x | ((unsigned long long)g.z << 32)));
                     }
@@ -1014,6 +1032,18 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                     KKT_XS(6);      // products polled + barrier
                     // ---- prolongation onto the own rows of the current iterate
                     double *Xc = X + cur * nkp;
+                    if (c_rings) {
+                        // ... and onto the ring rows: a ring row's chain is its owner's (entries
+                        // in the order of P's row, the owners' products), so the value is the one
+                        // a hand-off would fetch.  Later cycles: the hand-off in front of the
+                        // residual left the current iterate on every ring.
+                        for (int l = tid; l < nk; l += T) {
+                            double a = 0.0;
+                            for (int e = PIPc[l]; e < PIPc[l + 1]; ++e)
+                                a = __builtin_fma(PWc[e], EC[PKc[e]], a);
+                            Xc[l] = cyc == 0 ? a : Xc[l] + a;
+                        }
+                    } else {
 #pragma unroll
                     for (int sl = 0; sl < RPT; ++sl) {
                         const int r = sl * T + tid;
@@ -1031,6 +1061,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                             Xc[r] = cyc == 0 ? a : Xc[r] + a;
                         }
                     }
+                    }
                 }
                 // (the barrier inside the hand-off orders these stores before anyone's gathers)
                 lds_barrier();
@@ -1039,7 +1070,8 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                     if (tid == 0) sstat[7] += now - t_mark;
                     t_mark = now;
                 }
-                handoff(false);
+                // (ring form: every local row holds the corrected iterate already)
+                if (!c_rings) handoff(false);
                 cr = depth;
                 // ---- smoothing sweeps from the corrected iterate
                 for (int s = 1; s <= its; ++s) {
@@ -1312,18 +1344,39 @@ bool tile_sweep_fuses_update(int W, int max_terms) {
 }
 
 size_t tile_sweep_lds_bytes(int nk_pad, int its, int coarse_nc, int coarse_nslots, int coarse_jmax,
-                            int coarse_nr_max, int coarse_einv_rows, int coarse_einv_width) {
+                            int coarse_nr_max, int coarse_einv_rows, int coarse_einv_width,
+                            int coarse_ring_entries, int coarse_jxmax) {
     if (coarse_nc > 0 && coarse_einv_rows > 0)
         return tile_sweep_lds_bytes(nk_pad, its, coarse_nc, coarse_nslots, coarse_jmax,
-                                    coarse_nr_max, 0) +
+                                    coarse_nr_max, 0, 0, coarse_ring_entries, coarse_jxmax) +
                (size_t)coarse_einv_rows * (coarse_einv_width > 0 ? coarse_einv_width : coarse_nc) *
                    sizeof(double) + 8;
-    if (coarse_nc > 0)
+    if (coarse_nc > 0) {
+        // ring form: products of J_t+ instead of J_t, the ring rows' entries behind the own rows',
+        // per-row entry offsets of all local rows
+        const bool rings = coarse_jxmax > 0;
+        const size_t jx = rings ? (size_t)coarse_jxmax : (size_t)coarse_jmax;
+        const size_t np = (size_t)coarse_nr_max + (rings ? (size_t)coarse_ring_entries : 0);
+        const size_t pip = rings ? (size_t)nk_pad + 1 : 0;
         return (2 * (size_t)nk_pad + 3 * (size_t)std::max(1, its) + 1 + (size_t)coarse_nslots +
-                (size_t)coarse_nc + (size_t)coarse_jmax + 2 * (size_t)coarse_nr_max) * sizeof(double) +
-               ((size_t)coarse_nslots + (size_t)coarse_nc + 1 + 2 * (size_t)coarse_jmax + 1) * sizeof(int) +
-               2 * (size_t)coarse_nr_max * sizeof(uint16_t) + 16;
+                (size_t)coarse_nc + jx + (size_t)coarse_nr_max + np) * sizeof(double) +
+               ((size_t)coarse_nslots + (size_t)coarse_nc + 1 + (size_t)coarse_jmax + 1 + jx + pip) *
+                   sizeof(int) +
+               ((size_t)coarse_nr_max + np) * sizeof(uint16_t) + 16;
+    }
     return (2 * (size_t)nk_pad + 3 * (size_t)std::max(1, its - 1) + 1) * sizeof(double);
+}
+
+size_t tile_sweep_lds_bytes(int nk_pad, int its, const TileCoarseDev &c, int cache, bool rings) {
+    const bool r = rings && cache >= 1;
+    return tile_sweep_lds_bytes(nk_pad, its, c.nc, c.nslots, c.jmax, cache >= 1 ? c.nr_max : 0,
+                                cache == 2 ? c.nown : 0, c.ew, r ? c.np_max - c.nr_max : 0,
+                                r ? c.jxmax : 0);
+}
+
+size_t tile_sweep_lds_bytes(int nk_pad, int its, const TileCoarseDev &c) {
+    return tile_sweep_lds_bytes(nk_pad, its, c, c.cache_einv ? 2 : c.cache_lists ? 1 : 0,
+                                c.ring_prolong != 0);
 }
 
 int tile_sweep_max_rpt(int W, int threads) {
@@ -1390,11 +1443,7 @@ void launch_tile_sweep(hipStream_t s, const TileArgs &a, const TileLevel *d_leve
             }
         chk(hipGetLastError(), "clearing the granule buffers");
     }
-    const size_t lds = h_coarse ? tile_sweep_lds_bytes(a.nk_pad, a.its, h_coarse->nc,
-                                                       h_coarse->nslots, h_coarse->jmax,
-                                                       h_coarse->cache_lists ? h_coarse->nr_max : 0,
-                                                       h_coarse->cache_einv ? h_coarse->nown : 0,
-                                                       h_coarse->ew)
+    const size_t lds = h_coarse ? tile_sweep_lds_bytes(a.nk_pad, a.its, *h_coarse)
                                 : tile_sweep_lds_bytes(a.nk_pad, a.its);
     tile_fn f = pick_tile(a.W, a.rpt, threads, a.fused_update != 0, a.hslots, h_coarse != nullptr);
     if (!f) throw TileLaunchError{"tile sweep program: no kernel variant for this plan"};

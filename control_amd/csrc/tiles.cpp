@@ -382,4 +382,111 @@ bool build_tile_plan(const Pattern &P, int ntiles, int depth, int threads, int m
     return true;
 }
 
+bool build_tile_coarse_lists(const TilePlan &tp, int nc, const int32_t *p_indptr,
+                             const int32_t *p_indices, const double *p_values, bool want_rings,
+                             TileCoarseLists &out) {
+    out = TileCoarseLists{};
+    const int nt = tp.ntiles, depth = tp.depth;
+    if (nt < 1 || nc < 1 || depth < 1) return false;
+    auto ntile = [&](int t, int j) { return tp.n[(size_t)t * (TILE_MAX_DEPTH + 1) + j]; };
+    auto grow = [&](int t, int l) { return tp.grow[(size_t)t * tp.nk_pad + l]; };
+    // rings only where a row of P is short (tiles.hpp)
+    bool rings = want_rings;
+    for (int t = 0; t < nt && rings; ++t)
+        for (int l = 0; l < ntile(t, depth) && rings; ++l) {
+            const int32_t g = grow(t, l);
+            if (p_indptr[g + 1] - p_indptr[g] > 4) rings = false;
+        }
+    out.nc = nc;
+    out.rings = rings;
+    out.pstride = tp.nk_pad;
+    out.nj.assign(nt, 0);
+    out.njx.assign(nt, 0);
+    out.slot0.assign(nt, 0);
+    // J_t (own rows), then what only ring rows touch: J_t+ = J[t] followed by JR[t]
+    std::vector<std::vector<int32_t>> J(nt), JR(nt);
+    for (int t = 0; t < nt; ++t) {
+        const int n0 = ntile(t, 0), nk = ntile(t, depth);
+        std::vector<int32_t> &j = J[t], &jr = JR[t];
+        for (int l = 0; l < n0; ++l) {
+            const int32_t g = grow(t, l);
+            for (int32_t q = p_indptr[g]; q < p_indptr[g + 1]; ++q) j.push_back(p_indices[q]);
+        }
+        std::sort(j.begin(), j.end());
+        j.erase(std::unique(j.begin(), j.end()), j.end());
+        if (rings) {
+            for (int l = n0; l < nk; ++l) {
+                const int32_t g = grow(t, l);
+                for (int32_t q = p_indptr[g]; q < p_indptr[g + 1]; ++q)
+                    if (!std::binary_search(j.begin(), j.end(), p_indices[q]))
+                        jr.push_back(p_indices[q]);
+            }
+            std::sort(jr.begin(), jr.end());
+            jr.erase(std::unique(jr.begin(), jr.end()), jr.end());
+        }
+        out.nj[t] = (int32_t)j.size();
+        out.njx[t] = (int32_t)(j.size() + jr.size());
+    }
+    int jmax = 0, jxmax = 0, nslots = 0;
+    for (int t = 0; t < nt; ++t) {
+        jmax = std::max(jmax, (int)out.nj[t]);
+        jxmax = std::max(jxmax, (int)out.njx[t]);
+        out.slot0[t] = nslots;
+        nslots += out.nj[t];
+    }
+    if (jmax < 1 || jxmax > 65535 || nslots > 65536) return false;
+    out.jmax = jmax;
+    out.jxmax = jxmax;
+    out.nslots = nslots;
+    out.jglob.assign((size_t)nt * jxmax, -1);
+    out.r_ip.assign((size_t)nt * jmax + 1, 0);
+    out.p_ip.assign((size_t)nt * out.pstride + 1, 0);
+    out.c_ip.assign(nc + 1, 0);
+    std::vector<std::vector<int32_t>> contrib(nc);
+    for (int t = 0; t < nt; ++t) {
+        const int n0 = ntile(t, 0), nk = ntile(t, depth);
+        const std::vector<int32_t> &j = J[t], &jr = JR[t];
+        const size_t p_first = out.p_k.size(), r_first = out.r_row.size();
+        std::vector<std::vector<std::pair<uint16_t, double>>> lists(j.size());
+        for (int l = 0; l < out.pstride; ++l) {
+            if (l < n0 || (rings && l < nk)) {
+                const int32_t g = grow(t, l);
+                for (int32_t q = p_indptr[g]; q < p_indptr[g + 1]; ++q) {
+                    const auto at = std::lower_bound(j.begin(), j.end(), p_indices[q]);
+                    int k;
+                    if (at != j.end() && *at == p_indices[q])
+                        k = (int)(at - j.begin());
+                    else      // (own rows never get here: J_t holds all they touch)
+                        k = (int)(j.size() +
+                                  (std::lower_bound(jr.begin(), jr.end(), p_indices[q]) - jr.begin()));
+                    if (l < n0) lists[k].push_back({(uint16_t)l, p_values[q]});
+                    out.p_k.push_back((uint16_t)k);
+                    out.p_w.push_back(p_values[q]);
+                }
+            }
+            out.p_ip[(size_t)t * out.pstride + l + 1] = (int32_t)out.p_k.size();
+        }
+        for (size_t k = 0; k < (size_t)jxmax; ++k)
+            if (k < j.size() + jr.size())
+                out.jglob[(size_t)t * jxmax + k] = k < j.size() ? j[k] : jr[k - j.size()];
+        for (size_t k = 0; k < (size_t)jmax; ++k) {
+            if (k < j.size()) {
+                contrib[j[k]].push_back(out.slot0[t] + (int)k);
+                for (auto &e : lists[k]) {
+                    out.r_row.push_back(e.first);
+                    out.r_w.push_back(e.second);
+                }
+            }
+            out.r_ip[(size_t)t * jmax + k + 1] = (int32_t)out.r_row.size();
+        }
+        out.nr_max = std::max(out.nr_max, (int)(out.r_row.size() - r_first));
+        out.np_max = std::max(out.np_max, (int)(out.p_k.size() - p_first));
+    }
+    for (int j = 0; j < nc; ++j) {
+        for (int32_t sl : contrib[j]) out.c_slot.push_back(sl);
+        out.c_ip[j + 1] = (int32_t)out.c_slot.size();
+    }
+    return true;
+}
+
 }  // namespace kkt

@@ -63,4 +63,37 @@ bool build_tile_plan(const Pattern &P, int ntiles, int depth, int threads, int m
 // `max_hslots` (may be null: rpt + 1): ring-entry slots per thread the kernel variant with `rpt`
 // row slots has; a plan whose rings need more is not made (a deeper one would lose the tile form).
 
+// Lists of the coarse corrections inside the tile program (kernels.hpp, TileCoarseDev), host side.
+// Per tile t: J_t, the coarse functions its own rows touch (ascending), with their restriction
+// lists and the slots of its partial sums; per coarse function the slots that contribute to it
+// (ascending tile order: the summation order of the coarse residual).  The prolongation entries
+// cover the own rows and, with `rings`, the ring rows n[0] <= l < n[depth] as well: the list of
+// coarse functions is then J_t+ = J_t followed by the functions only ring rows touch (ascending),
+// and p_k indexes J_t+.  Entries of a row keep the order of P's CSR row.
+struct TileCoarseLists {
+    int nc = 0, nslots = 0;
+    int jmax = 0;         // max |J_t|
+    int jxmax = 0;        // max |J_t+| (= jmax without rings): stride of jglob
+    int nr_max = 1;       // most restriction (= own-row prolongation) entries of a tile
+    int np_max = 1;       // most prolongation entries of a tile, ring rows included
+    int pstride = 0;      // stride of p_ip: the plan's nk_pad
+    bool rings = false;   // the ring rows' entries are there
+    std::vector<int32_t> nj, njx, slot0;   // [ntiles]
+    std::vector<int32_t> jglob;            // [ntiles][jxmax], -1 behind njx[t]
+    std::vector<int32_t> r_ip;             // [ntiles * jmax + 1]
+    std::vector<uint16_t> r_row;
+    std::vector<double> r_w;
+    std::vector<int32_t> p_ip;             // [ntiles * pstride + 1]
+    std::vector<uint16_t> p_k;
+    std::vector<double> p_w;
+    std::vector<int32_t> c_ip, c_slot;     // [nc + 1], [nslots]
+};
+// P (n x nc) as CSR.  `want_rings`: add the ring rows' entries where a tile prolonging onto its
+// rings is cheaper than fetching them -- rows of P with at most 4 entries (multilinear spaces in
+// 2-D; in 3-D a row has 8 and the rings are several times the own rows: today's form stays).
+// False when the lists do not fit the kernel's 16-bit indices.
+bool build_tile_coarse_lists(const TilePlan &tp, int nc, const int32_t *p_indptr,
+                             const int32_t *p_indices, const double *p_values, bool want_rings,
+                             TileCoarseLists &out);
+
 }  // namespace kkt

@@ -211,7 +211,7 @@ def _array_of(v, n, nx):
 _ENV_OPTION_KEYS = ("sell_r", "sell_sort", "no_graph", "persistent", "prog_mode", "prog_waves",
                     "prog_steps", "tile_depth", "tile_waves", "lanes", "lane_chunks",
                     "kernarg_ops", "shared_rows", "verbose", "stamps", "tile_poll_delay",
-                    "tile_unfused", "stage_timers", "sell_sigma", "interleave")
+                    "tile_unfused", "stage_timers", "sell_sigma", "interleave", "coarse_rings")
 
 
 # ------------------------------------------------------------------ the block system
@@ -364,7 +364,7 @@ class MultiBlockSystem:
         self._pc_state = None
 
     def info(self):
-        inf = _lib.Info()
+        inf = _lib.InfoRings()       # (the whole struct: kkt_get_info writes every field)
         self._ck(self._lib.kkt_get_info(self._h, C.byref(inf)))
         return inf.as_dict()
 

@@ -114,6 +114,10 @@ const char *kkt_last_error(kkt_handle h);
  *   "coarse_blocks" "1" | "0"      batched set-up: one inverse per component block of a
  *                                  vector-valued space (the rows keep their full layout, exact
  *                                  zeros outside the block); "0": invert P^T A P as one matrix
+ *   "coarse_rings"  "1" | "0"      two-grid sub-solves in the tile form: a tile prolongs the
+ *                                  coarse correction onto its ring rows itself instead of fetching
+ *                                  them in a hand-off after every correction (same results; "0":
+ *                                  the hand-off; see kkt_info.sweep_coarse_rings)
  *   "stage_timers"  "0" | "1"      HIP events around the stages of every Krylov iteration
  *                                  (kkt_get_stage_times)
  *   "verbose"       "0" | "1"      set-up decisions on stderr
@@ -655,6 +659,10 @@ typedef struct kkt_info {
                                    structures (P2 / Stokes blocks; option "ragged_switch") */
     int64_t blocks_unset;       /* blocks added by kkt_add_block_structure that no composition or
                                    update has written yet */
+    int64_t sweep_coarse_rings; /* 1: the tile program that was built prolongs coarse corrections
+                                   onto the tiles' rings (option "coarse_rings", where the lists
+                                   fit on chip); 0: it fetches them in a hand-off, or no two-grid
+                                   tile program was built */
 } kkt_info;
 int kkt_get_info(kkt_handle h, kkt_info *info);
 
