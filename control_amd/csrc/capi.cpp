@@ -66,6 +66,12 @@ static bool set_coarse_setup(Options &o, const char *v) {
     return o.coarse_columns || std::strcmp(v, "batched") == 0;
 }
 
+static bool set_mass_tile_waves(Options &o, const char *v) {
+    if (std::strcmp(v, "0") != 0 && std::strcmp(v, "4") != 0 && std::strcmp(v, "8") != 0) return false;
+    o.mass_tile_waves = v[0] - '0';
+    return true;
+}
+
 struct OptionKey {
     const char *key, *accepted;
     bool (*set)(Options &, const char *);
@@ -96,6 +102,11 @@ static const OptionKey option_keys[] = {
     {"coarse_keep", "0 | 1", set_switch<&Options::coarse_keep>},
     {"coarse_blocks", "0 | 1", set_switch<&Options::coarse_blocks>},
     {"coarse_rings", "0 | 1", set_switch<&Options::coarse_rings>},
+    {"mass_tiles", "0 | 1", set_switch<&Options::mass_tiles>},
+    {"mass_tile_depth", "0..8", set_int<&Options::mass_tile_depth, 0, MASS_TILE_MAX_DEPTH>},
+    {"mass_tile_rows", "0..65536", set_int<&Options::mass_tile_rows, 0, 65536>},
+    {"mass_tile_levels", "0..4096", set_int<&Options::mass_tile_levels, 0, 4096>},
+    {"mass_tile_waves", "0 | 4 | 8", set_mass_tile_waves},
     {"stage_timers", "0 | 1", set_switch<&Options::stage_timers>},
     {"verbose", "0 | 1", set_switch<&Options::verbose>},
     {"stamps", "0 | 1", set_switch<&Options::stamps>},

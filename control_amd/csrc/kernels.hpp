@@ -255,6 +255,40 @@ void launch_tile_sweep(hipStream_t s, const TileArgs &a, const TileLevel *d_leve
                        const int32_t *d_gpos, const uint8_t *d_rowmask, int ntiles, int threads,
                        size_t granule_words, const TileCoarseDev *h_coarse = nullptr);
 
+// ---- batched one-matrix Chebyshev solves, several steps per launch out of LDS
+// (mass_tile_kernels.hip; plan: tiles.hpp with depth = K)
+constexpr int MASS_TILE_MAX_DEPTH = 8;
+// a group of (at most) four time levels: right-hand sides, outputs and the last step's factors
+struct MassTileGroup {
+    const double *b[4];
+    double *out[4];
+    double post1[4], post2[4];
+    int32_t nlev, pad_;
+};
+// One launch: steps s0 + 1 .. s0 + k of every solve.  Iterates between launches: four levels
+// interleaved by global row (element (row r, level l) of group g at 4 (g nx + r) + l), read from
+// the pair in_*, written to the pair out_* (another pair: other tiles read their rings from in_*).
+struct MassTileArgs {
+    const int32_t *n, *grow, *gpos;   // the plan's tables (TilePlan::d_*)
+    const uint16_t *lcol;
+    const int32_t *masked;            // the Dirichlet rows (the last launch writes their zeros)
+    const double *vals, *dinv;
+    const MassTileGroup *groups;
+    const double *in_new, *in_old;    // p_{s0}, p_{s0 - 1} (unused where s0 is too small)
+    double *out_new, *out_old;        // p_{s0 + k}, p_{s0 + k - 1} (not the last launch)
+    int64_t nx;
+    int32_t nmasked, ngroups, nk_pad, W;
+    int32_t s0, k, last, pad_;
+    double coef[MASS_TILE_MAX_DEPTH][3];   // c1, c2, c3 of steps s0 + 1 .. s0 + k
+};
+int mass_tile_kernel_width(int W);     // the variant's width for rows of W entries (0: none)
+int mass_tile_max_rpt(int threads);    // row slots per thread the variants of a workgroup size have
+size_t mass_tile_lds_bytes(int nk_pad);
+// workgroups per CU of the variant for this plan (0: none or it does not fit); raises its LDS limit
+int mass_tile_prepare(int W, int rpt, int threads, size_t lds_bytes);
+void launch_mass_tile(hipStream_t s, const MassTileArgs &a, int ntiles, int grid_y, int rpt,
+                      int threads);
+
 // ---- value-array preparation
 void launch_csr_to_sell(hipStream_t s, const double *csr_vals, const int32_t *sell2csr,
                         double *sell_vals, int64_t n_padded);

@@ -73,6 +73,9 @@ void SchurPC::clear_program() {
     segments_.clear();   // the graphs first: their nodes point into the program's memory
     program_mem_.release();
     il_cap_ = 0;
+    mt_cap_ = 0;
+    mass_solves_.clear();
+    mass_launches_.clear();
     sweep_levels_.clear();
     steps_.clear();
     n_events_ = 0;
@@ -632,8 +635,192 @@ bool SchurPC::fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out) {
 // Replace every run of >= 4 consecutive single-block steps (the time sweeps) by one
 // persistent launch: the tile form (tile_kernels.hip: `depth` steps per hand-off) where it
 // fits, else a row program with neighbour synchronisation (kernels.hip, pc_row_program*).
+// Tile plan of the batched one-matrix solves (mass_tile_kernels.hip): once per handle.  Its own
+// tile count and depth K -- the sweeps' plan (one tile per CU, a few hundred rows) computes 2.25 x
+// the rows at depth 4 and is the wrong shape here.
+bool SchurPC::prepare_mass_tiles() {
+    if (mass_tried_) return mass_ok_;
+    mass_tried_ = true;
+    const Pattern &P = S_.patterns[m_pat_];
+    if (P.R != 2 || mass_tile_kernel_width(P.max_width) == 0) return false;
+    int dev_id = 0;
+    if (hipGetDevice(&dev_id) != hipSuccess ||
+        hipDeviceGetAttribute(&mass_cus_, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess ||
+        mass_cus_ < 1)
+        return false;
+    std::vector<uint8_t> hmask;
+    if (!bc_idx_.empty()) {
+        hmask.assign(P.nrows, 0);
+        for (int32_t k : bc_idx_) hmask[k] = 1;
+    }
+    int64_t live = 0;
+    for (int64_t r = 0; r < P.nrows; ++r) live += hmask.empty() || !hmask[r];
+    if (live < 1) return false;
+    const double *tc = (S_.tile_dim > 0 && (int64_t)S_.tile_coords.size() == P.nrows * S_.tile_dim)
+                           ? S_.tile_coords.data() : nullptr;
+    // defaults: what won on 256^2 P1 x 64 levels among K = 2 .. 6 and 192 .. 1 024 own rows
+    // (profiles/mass_tiles.md): 5 steps on tiles of 512 rows, 256 threads with four row slots, two
+    // workgroups per CU
+    const bool chosen = S_.opts.mass_tile_depth > 0 || S_.opts.mass_tile_rows > 0;
+    const int K = S_.opts.mass_tile_depth > 0 ? S_.opts.mass_tile_depth : 5;
+    const int rows = S_.opts.mass_tile_rows > 0 ? S_.opts.mass_tile_rows : 512;
+    const int ntiles = (int)std::max<int64_t>(1, (live + rows - 1) / rows);
+    // the rings are loaded by a loop, not by slots per thread: no limit on their size
+    auto any_halo = [](int, int, int) { return 1 << 20; };
+    bool ok = false;
+    for (int threads : {256, 512}) {
+        if (S_.opts.mass_tile_waves && threads != 64 * S_.opts.mass_tile_waves) continue;
+        if (build_tile_plan(P, ntiles, K, threads, mass_tile_max_rpt(threads), mass_plan_,
+                            hmask.empty() ? nullptr : hmask.data(), 0, tc, S_.tile_dim, any_halo)) {
+            ok = true;
+            break;
+        }
+    }
+    if (!ok) return false;
+    const TilePlan &tp = mass_plan_;
+    const size_t lds = mass_tile_lds_bytes(tp.nk_pad);
+    mass_per_cu_ = mass_tile_prepare(tp.W, tp.rpt, tp.threads, lds);
+    if (mass_per_cu_ < 1) return false;
+    // Cost rule: bytes a launch of K steps moves per tile and level group -- two iterates on
+    // n[K] rows in, the right-hand sides on n[K-1] rows, two iterates on the own rows out, 32 bytes
+    // per row and group each -- against K plain steps at 40 bytes per unknown.  The form also pays
+    // the redundant rows' LDS gathers, so it must move less than 0.6 of the plain bytes.
+    // (a caller who sets the depth or the tile size has chosen: the rule is not asked)
+    double tile_bytes = 0.0, plain_bytes = 0.0;
+    for (int t = 0; t < tp.ntiles; ++t) {
+        const int32_t *nt = &tp.n[(size_t)t * (TILE_MAX_DEPTH + 1)];
+        tile_bytes += 64.0 * nt[K] + 32.0 * nt[K - 1] + 64.0 * nt[0];
+        plain_bytes += 160.0 * K * nt[0];
+    }
+    const double ratio = tile_bytes / std::max(1.0, plain_bytes);
+    const bool pays = ratio < 0.6;
+    if (S_.opts.verbose)
+        std::fprintf(stderr, "[kkt] mass tile form: %d tiles x %d threads, K %d, W %d, %d row slots; "
+                     "largest tile: %lld own rows, %lld computed rows; redundancy %.2f; %zu bytes of "
+                     "LDS, %d workgroups per CU; modelled bytes %.2f of the plain steps'%s\n",
+                     tp.ntiles, tp.threads, K, tp.W, tp.rpt, (long long)tp.max_own,
+                     (long long)tp.max_rows, tp.mean_redundancy, lds, mass_per_cu_, ratio,
+                     pays || chosen ? "" : ": off");
+    if (!pays && !chosen) return false;
+    mass_plan_.upload(handle_mem_);
+    if (!bc_idx_.empty()) d_masked_ = handle_mem_.upload(bc_idx_.data(), bc_idx_.size());
+    mass_ok_ = true;
+    return true;
+}
+
+// Replace every run of ROWS_IL steps of one batched solve by ceil(its / K) TILE_CHEB steps.
+void SchurPC::fuse_mass_tiles() {
+    if (!S_.opts.mass_tiles || S_.opts.lanes || mass_solves_.empty()) return;
+    bool any = false;
+    for (const MassSolve &ms : mass_solves_) any = any || ms.its >= 2;
+    if (!any || !prepare_mass_tiles()) return;
+    const TilePlan &tp = mass_plan_;
+    const int K = tp.depth;
+    std::vector<PcStep> out;
+    std::vector<size_t> new_index(steps_.size() + 1, 0);
+    size_t k = 0, q = 0;
+    while (k < steps_.size()) {
+        while (q < mass_solves_.size() && mass_solves_[q].first < k) ++q;
+        const MassSolve *ms = q < mass_solves_.size() && mass_solves_[q].first == k ? &mass_solves_[q] : nullptr;
+        bool run = ms && ms->its >= 2 && k + ms->its <= steps_.size();
+        for (int i = 0; run && i < ms->its; ++i) run = steps_[k + i].kind == PcStep::ROWS_IL;
+        if (!run) {
+            new_index[k] = out.size();
+            out.push_back(steps_[k++]);
+            continue;
+        }
+        const size_t m = ms->sv.size();
+        const int ng = (int)((m + 3) / 4);
+        const size_t need = (size_t)ng * 4 * (size_t)nx_;
+        if (need > mt_cap_) {
+            for (int i = 0; i < 4; ++i) {
+                mt_P_[i] = program_mem_.alloc<double>(need + 32);
+                HIPCHK(hipMemsetAsync(mt_P_[i], 0, (need + 32) * sizeof(double), S_.stream));
+            }
+            mt_cap_ = need;
+        }
+        std::vector<MassTileGroup> groups(ng);
+        for (int g = 0; g < ng; ++g) {
+            MassTileGroup G{};
+            G.nlev = (int32_t)std::min<size_t>(4, m - (size_t)g * 4);
+            for (int l = 0; l < 4; ++l) {
+                const bool live = l < G.nlev;
+                const Solve *sv = live ? &ms->sv[(size_t)g * 4 + l] : nullptr;
+                G.b[l] = live ? sv->b : nullptr;
+                G.out[l] = live ? sv->out : nullptr;
+                G.post1[l] = live ? sv->post1 : 1.0;
+                G.post2[l] = live ? sv->post2 : 1.0;
+            }
+            groups[g] = G;
+        }
+        const MassTileGroup *d_groups = program_mem_.upload(groups.data(), groups.size());
+        // level groups per workgroup: as many workgroups as the chip holds at once, unless chosen
+        int gpw = S_.opts.mass_tile_levels > 0 ? (S_.opts.mass_tile_levels + 3) / 4 : 0;
+        if (gpw <= 0) {
+            const int64_t slots = (int64_t)mass_per_cu_ * mass_cus_;
+            const int gy = (int)std::max<int64_t>(1, std::min<int64_t>(ng, slots / tp.ntiles));
+            gpw = (ng + gy - 1) / gy;
+        }
+        const int grid_y = (ng + gpw - 1) / gpw;
+        const int nl = (ms->its + K - 1) / K;
+        for (int i = 0; i < ms->its; ++i) new_index[k + i] = out.size();
+        for (int j = 0; j < nl; ++j) {
+            MassLaunch ml;
+            MassTileArgs &a = ml.a;
+            a = MassTileArgs{};
+            a.n = tp.d_n;
+            a.grow = tp.d_grow;
+            a.gpos = tp.d_gpos;
+            a.lcol = tp.d_lcol;
+            a.masked = d_masked_;
+            a.nmasked = (int32_t)bc_idx_.size();
+            a.vals = ms->sv[0].vals;
+            a.dinv = ms->sv[0].dinv;
+            a.groups = d_groups;
+            const int wr = j & 1, rd = wr ^ 1;
+            a.in_new = mt_P_[2 * rd];
+            a.in_old = mt_P_[2 * rd + 1];
+            a.out_new = mt_P_[2 * wr];
+            a.out_old = mt_P_[2 * wr + 1];
+            a.nx = nx_;
+            a.ngroups = ng;
+            a.nk_pad = tp.nk_pad;
+            a.W = tp.W;
+            a.s0 = j * K;
+            a.k = std::min(K, ms->its - a.s0);
+            a.last = j + 1 == nl ? 1 : 0;
+            for (int i = 0; i < a.k; ++i) {
+                const TileCoef &c = ms->coef[a.s0 + i];
+                a.coef[i][0] = c.c1;
+                a.coef[i][1] = c.c2;
+                a.coef[i][2] = c.c3;
+            }
+            ml.grid_y = grid_y;
+            PcStep s;
+            s.kind = PcStep::TILE_CHEB;
+            s.mt = (int)mass_launches_.size();
+            s.lane = steps_[k].lane;
+            mass_launches_.push_back(ml);
+            out.push_back(s);
+        }
+        if (S_.opts.verbose)
+            std::fprintf(stderr, "[kkt] mass tile form: a solve of %d steps on %zu levels as %d "
+                         "launches of %d x %d workgroups (%d level groups each)\n", ms->its, m, nl,
+                         tp.ntiles, grid_y, gpw);
+        k += ms->its;
+    }
+    new_index[steps_.size()] = out.size();
+    // (the sweep levels name their steps by index)
+    for (SweepLevel &lv : sweep_levels_) {
+        lv.first = new_index[lv.first];
+        lv.last = new_index[lv.last];
+    }
+    steps_.swap(out);
+}
+
 void SchurPC::fuse_programs() {
     if (!use_programs_) return;
+    fuse_mass_tiles();
     if (!d_err_) {
         d_err_ = handle_mem_.alloc<unsigned>(64 + 16 * 1024);   // word 0: error bits; rest: diagnostics
         HIPCHK(hipMemset(d_err_, 0, (64 + 16 * 1024) * sizeof(unsigned)));
@@ -783,6 +970,9 @@ void SchurPC::plain_forms(std::vector<int32_t> &out) const {
             out.insert(out.end(), {form, s.rows.uniform_w, s.rows.R, s.lane, s.rows.nops, 0});
         } else if (s.kind == PcStep::ROWS_IL) {
             out.insert(out.end(), {KKT_PC_ROWS_INTERLEAVED, s.il_w, 2, s.lane, s.il_groups, 0});
+        } else if (s.kind == PcStep::TILE_CHEB) {
+            out.insert(out.end(), {KKT_PC_TILE_CHEB, mass_plan_.W, mass_plan_.rpt, s.lane,
+                                   mass_launches_[s.mt].a.k, mass_plan_.threads});
         } else if (s.kind == PcStep::PROG) {
             out.insert(out.end(), {KKT_PC_PROGRAM, P.uniform_w, P.R, s.lane, s.nphases,
                                    s.gmode == 2 ? 2 : s.granule ? 1 : 0});
@@ -868,7 +1058,8 @@ void SchurPC::time_stages(kkt_pc_stage_times *out) {
             out->comm_steps += 1;
         } else {
             out->batched_ms += ms;
-            if (s.kind == PcStep::ROWS || s.kind == PcStep::TIME || s.kind == PcStep::ROWS_IL)
+            if (s.kind == PcStep::ROWS || s.kind == PcStep::TIME || s.kind == PcStep::ROWS_IL ||
+                s.kind == PcStep::TILE_CHEB)
                 out->batched_launches += 1;
         }
     }
@@ -1779,6 +1970,10 @@ bool SchurPC::emit_solves_interleaved(const std::vector<Solve> &sv, int its, dou
     auto buf = [&](int step, int g) -> double * {
         return il_P_[(step - 1) % 3] + (size_t)g * 4 * (size_t)nx_;
     };
+    MassSolve rec;      // for fuse_mass_tiles()
+    rec.first = steps_.size();
+    rec.its = its;
+    rec.sv = sv;
     for (int step = 1; step <= its; ++step) {
         double k1 = 0.0, k2 = 0.0, k3 = scale;
         if (step >= 2) {
@@ -1790,6 +1985,7 @@ bool SchurPC::emit_solves_interleaved(const std::vector<Solve> &sv, int its, dou
             c_km1 = c_k;
             c_k = c_kp1;
         }
+        rec.coef.push_back(TileCoef{k1, k2, k3});
         const bool last = step == its;
         std::vector<IlOp> ops(ng);
         for (int g = 0; g < ng; ++g) {
@@ -1830,6 +2026,7 @@ bool SchurPC::emit_solves_interleaved(const std::vector<Solve> &sv, int its, dou
         s.lane = cur_lane_;
         steps_.push_back(s);
     }
+    mass_solves_.push_back(std::move(rec));
     return true;
 }
 
@@ -2206,6 +2403,16 @@ void SchurPC::replay(size_t first, size_t last) {
             case PcStep::ROWS_IL:
                 launch_rowops_il(st, s.d_il, s.il_groups, s.il_slices, s.il_w, xcd);
                 break;
+            case PcStep::TILE_CHEB: {
+                const MassLaunch &ml = mass_launches_[s.mt];
+                try {
+                    launch_mass_tile(st, ml.a, mass_plan_.ntiles, ml.grid_y, mass_plan_.rpt,
+                                     mass_plan_.threads);
+                } catch (const TileLaunchError &e) {
+                    fail(KKT_ERR_HIP, e.msg);
+                }
+                break;
+            }
             case PcStep::TIME:
                 launch_time_transform(st, s.y, s.x, s.tkind, s.n, s.nx, s.lo_halo, s.hi_halo);
                 break;

@@ -28,7 +28,8 @@ double jacobi_skew_radius(System &S, int pattern, const double *skew_vals, const
                           const uint8_t *rowmask, int max_steps, int *steps_out);
 
 struct PcStep {
-    enum Kind { ROWS, TIME, COPY, COMM, PROG, TILE, EV_RECORD, EV_WAIT, COARSE, ROWS_IL } kind;
+    enum Kind { ROWS, TIME, COPY, COMM, PROG, TILE, EV_RECORD, EV_WAIT, COARSE, ROWS_IL, TILE_CHEB } kind;
+    int mt = -1;                    // TILE_CHEB: index into the mass tile launches (K steps of a batched solve)
     IlOp *d_il = nullptr;           // ROWS_IL: one IlOp per group of four time levels
     int il_groups = 0, il_slices = 0, il_w = 0;
     const double *einv = nullptr;   // COARSE: y = (x or 0) + P E^-1 P^T cr
@@ -307,6 +308,29 @@ class SchurPC : public PcBase {
     };
     // batched solves on one matrix with the iterates of four levels interleaved (kernels.hpp IlOp)
     bool emit_solves_interleaved(const std::vector<Solve> &sv, int its, double emin, double emax);
+    // ... and several of their steps per launch out of LDS (mass_tile_kernels.hip): the runs of
+    // ROWS_IL steps the function above emitted, as it recorded them, are replaced by
+    // ceil(its / K) TILE_CHEB steps on a tile plan of the form's own (depth K)
+    struct MassSolve {
+        size_t first = 0;               // steps_[first, first + its) are the solve's ROWS_IL steps
+        int its = 0;
+        std::vector<Solve> sv;
+        std::vector<TileCoef> coef;     // steps 1 .. its
+    };
+    std::vector<MassSolve> mass_solves_;
+    struct MassLaunch {
+        MassTileArgs a;
+        int grid_y = 1;
+    };
+    std::vector<MassLaunch> mass_launches_;
+    TilePlan mass_plan_;
+    bool mass_tried_ = false, mass_ok_ = false;
+    int mass_per_cu_ = 0, mass_cus_ = 0;
+    int32_t *d_masked_ = nullptr;
+    double *mt_P_[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t mt_cap_ = 0;
+    bool prepare_mass_tiles();
+    void fuse_mass_tiles();
     void emit_solves(const std::vector<Solve> &sv, int its, double emin, double emax,
                      double *const P[3], int64_t pstride, bool first_done = false,
                      std::vector<TileCoef> *coef_out = nullptr, double eimag = 0.0,

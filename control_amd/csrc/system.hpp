@@ -38,6 +38,9 @@ struct Options {
     bool coarse_columns = false;                                  // "coarse_setup" = "columns"
     bool coarse_keep = false, coarse_blocks = true;
     bool coarse_rings = true;     // two-grid tile sweeps: tiles prolong onto their rings themselves
+    // batched mass solves, several Chebyshev steps per launch out of LDS (0: chosen)
+    bool mass_tiles = true;
+    int mass_tile_depth = 0, mass_tile_rows = 0, mass_tile_levels = 0, mass_tile_waves = 0;
     // diagnostics and test hooks
     bool stage_timers = false, verbose = false, stamps = false;
     int tile_poll_delay = 24, debug_drop_handoff = 0;

@@ -211,7 +211,9 @@ def _array_of(v, n, nx):
 _ENV_OPTION_KEYS = ("sell_r", "sell_sort", "no_graph", "persistent", "prog_mode", "prog_waves",
                     "prog_steps", "tile_depth", "tile_waves", "lanes", "lane_chunks",
                     "kernarg_ops", "shared_rows", "verbose", "stamps", "tile_poll_delay",
-                    "tile_unfused", "stage_timers", "sell_sigma", "interleave", "coarse_rings")
+                    "tile_unfused", "stage_timers", "sell_sigma", "interleave", "coarse_rings",
+                    "mass_tiles", "mass_tile_depth", "mass_tile_rows", "mass_tile_levels",
+                    "mass_tile_waves")
 
 
 # ------------------------------------------------------------------ the block system
@@ -398,9 +400,11 @@ class MultiBlockSystem:
         """``kkt_debug_pc_forms``: one dict per row step, sweep program and tile launch of the
         built-in preconditioner (built by the first ``pc_apply``), in replay order -- ``form`` (0
         plain rows, 1 shared matrix, 2 kernel-argument single op, 3 interleaved levels, 4 row
-        program, 5 tile program), ``width``, ``slots`` (R; tile: row slots per thread), ``lane``
-        (1: side stream), ``count`` (row ops; program: phases; tile: threads) and ``variant``
-        (program: 0 counters, 1 data-flow, 2 data-flow any width; tile: 1 fused | 2 coarse)."""
+        program, 5 tile program, 6 several steps of a batched mass solve on tiles), ``width``,
+        ``slots`` (R; tile forms: row slots per thread), ``lane`` (1: side stream), ``count`` (row
+        ops; program: phases; tile: threads; form 6: Chebyshev steps in the launch) and ``variant``
+        (program: 0 counters, 1 data-flow, 2 data-flow any width; tile: 1 fused | 2 coarse; form 6:
+        threads)."""
         return self._forms(self._lib.kkt_debug_pc_forms,
                            ("form", "width", "slots", "lane", "count", "variant"))
 

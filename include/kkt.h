@@ -118,6 +118,17 @@ const char *kkt_last_error(kkt_handle h);
  *                                  coarse correction onto its ring rows itself instead of fetching
  *                                  them in a hand-off after every correction (same results; "0":
  *                                  the hand-off; see kkt_info.sweep_coarse_rings)
+ *   "mass_tiles"    "1" | "0"      batched one-matrix solves (the mass solves) as several Chebyshev
+ *                                  steps per launch out of LDS on a tile plan of their own, where
+ *                                  the sweeps are programs ("persistent"), "lanes" is off, the
+ *                                  rows have at most 9 entries and the plan's rings pay; "0": one
+ *                                  launch per step (same results)
+ *   "mass_tile_depth"  "0".."8"    ... steps per launch (0: chosen)
+ *   "mass_tile_rows"   "0".."65536"  ... own rows per tile (0: chosen).  A caller who sets the
+ *                                  depth or the rows gets the form wherever a plan fits.
+ *   "mass_tile_levels" "0".."4096" ... time levels a workgroup serves (groups of four; 0: as
+ *                                  many workgroups as the device holds at once)
+ *   "mass_tile_waves"  "0" | "4" | "8"   ... waves per workgroup (0: 4 where the rows fit)
  *   "stage_timers"  "0" | "1"      HIP events around the stages of every Krylov iteration
  *                                  (kkt_get_stage_times)
  *   "verbose"       "0" | "1"      set-up decisions on stderr
@@ -596,11 +607,14 @@ int kkt_debug_set_steplock(kkt_handle h, const kkt_steplock *lock);
  *     PROGRAM (a persistent row program): width = uniform_w, slots = R, count = phases, variant
  *       0 counters ("flags"), 1 data-flow fixed width, 2 data-flow any width ("w");
  *     TILE: width = W of the tile kernel, slots = row slots per thread, count = threads per
- *       workgroup, variant = 1 (level update fused) | 2 (coarse corrections).
+ *       workgroup, variant = 1 (level update fused) | 2 (coarse corrections);
+ *     TILE_CHEB (several steps of a batched one-matrix solve out of LDS): width = W of the form's
+ *       tile plan, slots = row slots per thread, count = Chebyshev steps in this launch, variant =
+ *       threads per workgroup.
  *   0 records before kkt_set_pc_schur. */
 enum { KKT_APPLY_FORM_INTS = 4, KKT_PC_FORM_INTS = 6 };
 enum { KKT_PC_ROWS_PLAIN = 0, KKT_PC_ROWS_SHARED = 1, KKT_PC_ROWS_KERNARG = 2,
-       KKT_PC_ROWS_INTERLEAVED = 3, KKT_PC_PROGRAM = 4, KKT_PC_TILE = 5 };
+       KKT_PC_ROWS_INTERLEAVED = 3, KKT_PC_PROGRAM = 4, KKT_PC_TILE = 5, KKT_PC_TILE_CHEB = 6 };
 int kkt_debug_apply_forms(kkt_handle h, int32_t *out, int cap);
 int kkt_debug_pc_forms(kkt_handle h, int32_t *out, int cap);
 
