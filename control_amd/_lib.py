@@ -121,6 +121,15 @@ class RelinRecipe(C.Structure):
                [("alpha", C.c_double), ("gamma", C.c_double)]
 
 
+class ReactionDesc(C.Structure):
+    _fields_ = ([("n_t", C.c_int), ("cn", C.c_int), ("nq", C.c_int), ("ne", C.c_int64),
+                 ("n1", C.c_int64), ("tau", C.c_double), ("beta", C.c_double),
+                 ("cells", c_i32p), ("W", c_f64p), ("lam", c_f64p), ("nnz", C.c_int64)]
+                + [(n, c_i32p) for n in ("indptr", "indices", "tperm", "cptr", "clist")]
+                + [("L", c_f64p), ("M", c_f64p), ("degree", C.c_int), ("c", C.c_double * 5),
+                   ("n_bc", C.c_int64), ("bc_idx", c_i32p), ("data", c_f64p)])
+
+
 # kkt_debug_krylov_op: the operations (KKT_KRYLOV_*) and the padding value (KKT_KRYLOV_PAD)
 KRYLOV_OPS = {name: k for k, name in enumerate(
     ("mdot", "orthogonalise", "build_solution", "scale_inv", "axpby", "copy", "fill", "norm2",
@@ -185,6 +194,14 @@ SIGNATURES = {
     "kkt_picard_residual_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_f64p]),
     "kkt_picard_update_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kkt_debug_relin_array": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int64]),
+    "kkt_set_reaction_relinearisation": (C.c_int, [C.c_void_p, C.POINTER(ReactionDesc)]),
+    "kkt_reaction_relinearise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                           C.POINTER(RelinRecipe)]),
+    "kkt_reaction_state": (C.c_int, [C.c_void_p, C.c_int, c_f64p, c_f64p]),
+    "kkt_reaction_iterate": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 2),
+    "kkt_reaction_residual_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_f64p]),
+    "kkt_reaction_update_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kkt_debug_reaction_array": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int64]),
     "kkt_debug_block_values": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_f64p,
                                          C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "kkt_time_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

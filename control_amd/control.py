@@ -20,6 +20,7 @@ import scipy.sparse as sp
 
 from .blocks import (conform_to, instationary_blocks, instationary_incompressible_blocks,
                      stationary_blocks, stationary_incompressible_blocks)
+from .fem import ReactionTerm
 
 __all__ = ["Instationary", "Stationary", "GpuBackend", "suggest_chebyshev", "coarse_space"]
 
@@ -240,6 +241,8 @@ class Instationary:
         self._disc = disc
         self._forward = forward_operator or (lambda v, t: disc.K)
         self._jacobian = forward_jacobian
+        if forward_jacobian is None and isinstance(forward_operator, ReactionTerm):
+            self._jacobian = forward_operator.jacobian
         self._Gauss_Newton = False
         self._desired_state, self._force_f = desired_state, force_f
         self._beta = float(beta)
@@ -473,9 +476,26 @@ class Instationary:
     def non_linear_solve(self, *, P=None, solver_parameters=None, lambda_v_bounds=None,
                          max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                          absolute_non_linear_tol=1.0e-8, print_error_non_linear=False,
-                         backend=None, Multigrid=False):
+                         backend=None, Multigrid=False, device=False):
         """``control.py:3377-3560``: Picard loop around ``linear_solve``; returns the residual
-        norms (initial one first).  ``Multigrid``: as in ``linear_solve``."""
+        norms (initial one first).  ``Multigrid``: as in ``linear_solve``.
+
+        ``device=True``: the same loop with the iterate in HBM (``control_amd.reaction``): one
+        block system and one preconditioner live through the loop, re-linearisation, residual and
+        update run on the GPU, the host reads one norm per iteration and the fields once at the
+        end; the linear iteration counts land in ``self.non_linear_info["linear_iterations"]``.
+        Needs a ``fem.ReactionTerm`` as forward operator, no ``P=`` and a scalar discretisation
+        (``ValueError`` otherwise, before the GPU is touched).  Limits: one GPU, and the
+        time-invariant linear part ``L`` of the term only."""
+        if device:
+            from .reaction import device_non_linear_solve
+            return device_non_linear_solve(
+                self, P=P, solver_parameters=solver_parameters, lambda_v_bounds=lambda_v_bounds,
+                max_non_linear_iter=max_non_linear_iter,
+                relative_non_linear_tol=relative_non_linear_tol,
+                absolute_non_linear_tol=absolute_non_linear_tol,
+                print_error_non_linear=print_error_non_linear, backend=backend,
+                Multigrid=Multigrid)
         disc, n_t, CN = self._disc, self._n_t, self._CN
         v_0 = (np.zeros(disc.n_dofs) if self._initial_condition is None
                else np.asarray(self._initial_condition(disc.coords), dtype=np.float64))

@@ -8,6 +8,7 @@
 
 #include "comm.hpp"
 #include "pc.hpp"
+#include "reaction.hpp"
 #include "relin.hpp"
 #include "system.hpp"
 #include "tiles.hpp"
@@ -404,6 +405,31 @@ int kkt_picard_update_device(kkt_handle plan, double *d_u) {
 }
 int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap) {
     KKT_TRY(plan, relin_debug_array(S, which, out, cap));
+}
+int kkt_set_reaction_relinearisation(kkt_handle h, const kkt_reaction_desc *desc) {
+    KKT_TRY(h, reaction_set(S, desc));
+}
+int kkt_reaction_relinearise(kkt_handle h, kkt_handle plan, int assemble, int n,
+                             const kkt_relin_recipe *recipes) {
+    KKT_TRY(h, {
+        if (!plan) fail(KKT_ERR_ARG, "kkt_reaction_relinearise: null plan handle");
+        reaction_apply(S, plan->S, assemble, n, recipes);
+    });
+}
+int kkt_reaction_state(kkt_handle plan, int download, double *v, double *zeta) {
+    KKT_TRY(plan, reaction_state(S, download, v, zeta));
+}
+int kkt_reaction_iterate(kkt_handle plan, double **d_v, double **d_zeta) {
+    KKT_TRY(plan, reaction_iterate(S, d_v, d_zeta));
+}
+int kkt_reaction_residual_device(kkt_handle plan, double *d_out, int rhs, double *norm) {
+    KKT_TRY(plan, reaction_residual(S, d_out, rhs, norm));
+}
+int kkt_reaction_update_device(kkt_handle plan, double *d_u) {
+    KKT_TRY(plan, reaction_update(S, d_u));
+}
+int kkt_debug_reaction_array(kkt_handle plan, int which, double *out, int64_t cap) {
+    KKT_TRY(plan, reaction_debug_array(S, which, out, cap));
 }
 int kkt_debug_block_values(kkt_handle h, int quadrant, int i, int j, double *out, int64_t cap,
                            int64_t *nnz, int *padding_zero) {

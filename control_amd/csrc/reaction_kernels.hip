@@ -1,0 +1,251 @@
+// Kernels of the scalar reaction re-linearisation (reaction.hpp): P1 element matrices of a
+// polynomial reaction coefficient, the Picard residual of the heat-type optimality system, its
+// Crank-Nicolson right-hand side and the update of the iterate.  gfx950, wave64; every store is a
+// plain vector store, and no floating-point atomics: every sum runs in a fixed order.  Gather and
+// composition are relin_kernels.hip's.
+#include <hip/hip_runtime.h>
+
+#include "reaction.hpp"
+
+namespace kkt {
+
+static inline int reaction_grid(int64_t n, int cap) {
+    int64_t g = (n + 255) / 256;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
+constexpr int REACTION_ELEMENT_BLOCKS = 1024;   // grid caps: the rest is grid-stride
+constexpr int REACTION_ROW_BLOCKS = 512;
+constexpr int REACTION_VECTOR_BLOCKS = 256 * 8;
+
+// One thread per (element, level): E[a][b] = sum_q (W_eq g(s_q)) lam_qa lam_qb with
+// s_q = lam_q0 v_0 + lam_q1 v_1 + lam_q2 v_2 summed left to right, g by Horner from c[degree]
+// down, q ascending from 0.0 (fem.ReactionTerm.element_matrices on the host).  `contract(off)`
+// keeps every product and sum a rounding of its own: hipcc contracts by default.
+__global__ __launch_bounds__(256) void reaction_elements_kernel(
+    const double *__restrict__ v, int64_t ne, int64_t n1, int n_t,
+    const int32_t *__restrict__ cells, const double *__restrict__ W,
+    const double *__restrict__ lam, ReactionCoef C, double *__restrict__ E) {
+    const int64_t total = ne * n_t;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
+         t += (int64_t)gridDim.x * blockDim.x) {
+#pragma clang fp contract(off)
+        const int64_t l = t / ne, e = t - l * ne;
+        const double *vl = v + l * n1;
+        const double v0 = vl[cells[e * 3]], v1 = vl[cells[e * 3 + 1]], v2 = vl[cells[e * 3 + 2]];
+        double acc[RELIN_EP];
+#pragma unroll
+        for (int k = 0; k < RELIN_EP; ++k) acc[k] = 0.0;
+#pragma unroll
+        for (int q = 0; q < RELIN_NQ; ++q) {
+            const double l0 = lam[q * 3], l1 = lam[q * 3 + 1], l2 = lam[q * 3 + 2];
+            const double p0 = l0 * v0, p1 = l1 * v1, p2 = l2 * v2;
+            const double s01 = p0 + p1;
+            const double s = s01 + p2;
+            double g = C.c[C.degree];
+            for (int k = C.degree - 1; k >= 0; --k) {
+                const double gs = g * s;
+                g = gs + C.c[k];
+            }
+            const double wg = W[e * RELIN_NQ + q] * g;
+            const double la[3] = {l0, l1, l2};
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const double wa = wg * la[a];
+#pragma unroll
+                for (int b = 0; b < 3; ++b) {
+                    const double term = wa * la[b];
+                    acc[a * 3 + b] = acc[a * 3 + b] + term;
+                }
+            }
+        }
+        double *o = E + t * RELIN_EP;
+#pragma unroll
+        for (int k = 0; k < RELIN_EP; ++k) o[k] = acc[k];
+    }
+}
+
+void launch_reaction_elements(hipStream_t s, const ReactionPlan &P) {
+    hipLaunchKernelGGL(reaction_elements_kernel,
+                       dim3(reaction_grid(P.ne * P.n_t, REACTION_ELEMENT_BLOCKS)), dim3(256), 0, s,
+                       P.d_v, P.ne, P.n1, P.n_t, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
+}
+
+// sum_k A[k] x[col[k]] over CSR row r from 0.0 in stored order (tperm: the transposed matrix on
+// the symmetric pattern) -- SciPy's order for A @ x and A.T @ x
+__device__ inline double reaction_row(const int32_t *__restrict__ ip, const int32_t *__restrict__ ix,
+                                      const double *__restrict__ A,
+                                      const int32_t *__restrict__ tperm, int64_t r,
+                                      const double *__restrict__ x) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int32_t k = ip[r]; k < ip[r + 1]; ++k) {
+        const double p = (tperm ? A[tperm[k]] : A[k]) * x[ix[k]];
+        acc = acc + p;
+    }
+    return acc;
+}
+
+// M @ (x + y): the vectors are added first, as the host does
+__device__ inline double reaction_row_sum(const int32_t *__restrict__ ip,
+                                          const int32_t *__restrict__ ix,
+                                          const double *__restrict__ A, int64_t r,
+                                          const double *__restrict__ x,
+                                          const double *__restrict__ y) {
+#pragma clang fp contract(off)
+    double acc = 0.0;
+    for (int32_t k = ip[r]; k < ip[r + 1]; ++k) {
+        const double xy = x[ix[k]] + y[ix[k]];
+        const double p = A[k] * xy;
+        acc = acc + p;
+    }
+    return acc;
+}
+
+struct ReactionArgs {
+    const int32_t *ip, *ix, *tperm;
+    const double *M, *D, *data, *v, *zeta;
+    const uint8_t *bc;
+    int64_t n1, nnz;
+    int n_t, m, cn;
+    double tau, beta;
+};
+
+// One thread per (row block, dof): row blocks 0..m-1 are the adjoint rows r0, m..2m-1 the state
+// rows r1 of Instationary.non_linear_res_eval, with its bracketing; Dirichlet rows are zero.
+__global__ __launch_bounds__(256) void reaction_residual_kernel(ReactionArgs A,
+                                                                double *__restrict__ r) {
+    const int rb = blockIdx.y, fam = rb >= A.m, i = fam ? rb - A.m : rb;
+    for (int64_t R = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; R < A.n1;
+         R += (int64_t)gridDim.x * blockDim.x) {
+#pragma clang fp contract(off)
+        double out = 0.0;
+        if (!A.bc[R]) {
+            auto Mx = [&](const double *x) { return reaction_row(A.ip, A.ix, A.M, nullptr, R, x); };
+            auto Dx = [&](int l, const double *x) {
+                return reaction_row(A.ip, A.ix, A.D + (int64_t)l * A.nnz, nullptr, R, x);
+            };
+            auto DTx = [&](int l, const double *x) {
+                return reaction_row(A.ip, A.ix, A.D + (int64_t)l * A.nnz, A.tperm, R, x);
+            };
+            auto v = [&](int l) { return A.v + (int64_t)l * A.n1; };
+            auto z = [&](int l) { return A.zeta + (int64_t)l * A.n1; };
+            const double tau = A.tau, d = A.data[(int64_t)rb * A.n1 + R];
+            if (!A.cn) {
+                if (!fam) {
+                    const double tDz = tau * DTx(i, z(i));
+                    const double Dz = tDz + Mx(z(i));
+                    if (i < A.n_t - 1) {
+                        const double tMv = tau * Mx(v(i));
+                        const double a = d - tMv;
+                        const double b = a - Dz;
+                        out = b + Mx(z(i + 1));
+                    } else {
+                        out = -Dz;
+                    }
+                } else {
+                    const double tDv = tau * Dx(i, v(i));
+                    const double Dv = tDv + Mx(v(i));
+                    if (i == 0) {
+                        out = d - Dv;
+                    } else {
+                        const double a = d + Mx(v(i - 1));
+                        const double b = a - Dv;
+                        const double c = (tau / A.beta) * Mx(z(i));
+                        out = b + c;
+                    }
+                }
+            } else {
+                const double h = 0.5 * tau;
+                if (!fam) {
+                    const double hMv = h * reaction_row_sum(A.ip, A.ix, A.M, R, v(i), v(i + 1));
+                    const double a = d - hMv;
+                    const double hD0 = h * DTx(i, z(i));
+                    const double t0 = hD0 + Mx(z(i));
+                    const double b = a - t0;
+                    const double hD1 = h * DTx(i + 1, z(i + 1));
+                    const double t1 = hD1 - Mx(z(i + 1));
+                    out = b - t1;
+                } else {
+                    const double hD0 = h * Dx(i, v(i));
+                    const double t0 = hD0 - Mx(v(i));
+                    const double a = d - t0;
+                    const double hD1 = h * Dx(i + 1, v(i + 1));
+                    const double t1 = hD1 + Mx(v(i + 1));
+                    const double b = a - t1;
+                    const double c =
+                        (h / A.beta) * reaction_row_sum(A.ip, A.ix, A.M, R, z(i), z(i + 1));
+                    out = b + c;
+                }
+            }
+        }
+        r[(int64_t)rb * A.n1 + R] = out;
+    }
+}
+
+void launch_reaction_residual(hipStream_t s, const ReactionPlan &P, double *d_r) {
+    ReactionArgs A;
+    A.ip = P.d_ip; A.ix = P.d_ix; A.tperm = P.d_tperm;
+    A.M = P.d_M; A.D = P.d_D; A.data = P.d_data; A.v = P.d_v; A.zeta = P.d_zeta; A.bc = P.d_bc;
+    A.n1 = P.n1; A.nnz = P.nnz; A.n_t = P.n_t; A.m = P.m; A.cn = P.CN;
+    A.tau = P.tau; A.beta = P.beta;
+    hipLaunchKernelGGL(reaction_residual_kernel,
+                       dim3(reaction_grid(P.n1, REACTION_ROW_BLOCKS), 2 * P.m), dim3(256), 0, s, A,
+                       d_r);
+}
+
+// Crank-Nicolson: T_1 on the adjoint rows (row i + 1 into i), T_2 on the state rows (i - 1 into i)
+__global__ __launch_bounds__(256) void reaction_rhs_kernel(const double *__restrict__ r,
+                                                           double *__restrict__ b, int m,
+                                                           int64_t n1) {
+    const int64_t n = 2 * (int64_t)m * n1;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t rb = t / n1;
+        double out = r[t];
+        if (rb < m) {
+            if (rb + 1 < m) out += r[t + n1];
+        } else if (rb > m) {
+            out += r[t - n1];
+        }
+        b[t] = out;
+    }
+}
+
+void launch_reaction_rhs(hipStream_t s, const ReactionPlan &P, const double *d_r, double *d_b) {
+    const int64_t n = 2 * (int64_t)P.m * P.n1;
+    hipLaunchKernelGGL(reaction_rhs_kernel, dim3(reaction_grid(n, REACTION_VECTOR_BLOCKS)),
+                       dim3(256), 0, s, d_r, d_b, P.m, P.n1);
+}
+
+// unknown block i: v at level i (Crank-Nicolson: i + 1), zeta at level i.  v keeps its boundary
+// values on the Dirichlet dofs, zeta is zero there.
+__global__ __launch_bounds__(256) void reaction_update_kernel(double *__restrict__ u,
+                                                              double *__restrict__ v,
+                                                              double *__restrict__ zeta,
+                                                              const uint8_t *__restrict__ bc, int m,
+                                                              int64_t n1, int cn) {
+    const int64_t n0 = (int64_t)m * n1, n = 2 * n0;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t rb = t / n1, R = t - rb * n1;
+        const bool fixed = bc[R] != 0;
+        if (rb < m) {
+            if (!fixed) v[(rb + cn) * n1 + R] += u[t];
+        } else {
+            const int64_t at = (rb - m) * n1 + R;
+            zeta[at] = fixed ? 0.0 : zeta[at] + u[t];
+        }
+        u[t] = 0.0;   // consumed: the next solve starts from zero
+    }
+}
+
+void launch_reaction_update(hipStream_t s, const ReactionPlan &P, double *d_u) {
+    const int64_t n = 2 * (int64_t)P.m * P.n1;
+    hipLaunchKernelGGL(reaction_update_kernel, dim3(reaction_grid(n, REACTION_VECTOR_BLOCKS)),
+                       dim3(256), 0, s, d_u, P.d_v, P.d_zeta, P.d_bc, P.m, P.n1, (int)P.CN);
+}
+
+}  // namespace kkt

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "comm.hpp"
+#include "reaction.hpp"
 #include "system.hpp"
 
 namespace kkt {
@@ -52,6 +53,9 @@ static void check_perm(const int32_t *t, int64_t nnz, const char *what) {
 void relin_set(System &S, const kkt_relin_desc *d) {
     need(d != nullptr, "null descriptor");
     need(S.finalized, "the handle must be finalized");
+    if (S.reaction)
+        fail(KKT_ERR_STATE, "kkt_set_relinearisation: the handle carries a reaction plan "
+                            "(kkt_set_reaction_relinearisation)");
     need(d->nq == RELIN_NQ, "nq must be 7 (Radon's rule)");
     need(d->n_t >= 2 && d->ne > 0 && d->n2 > 0 && d->n1 > 0, "sizes must be positive");
     const int m = d->cn ? d->n_t - 1 : d->n_t;

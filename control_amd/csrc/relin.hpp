@@ -83,6 +83,11 @@ struct RelinPlan {
 void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v);
 // D[l nnz + k] = nu K[k] + sum of the contributions of position k in list order
 void launch_relin_gather(hipStream_t s, const RelinPlan &P);
+// one pattern: D[l nnz + k] = nu K[k] + the contributions of position k (n_t levels of E, per_level
+// doubles each)
+void launch_relin_gather_one(hipStream_t s, const int32_t *cptr, const int32_t *clist,
+                             const double *E, int64_t per_level, const double *K, double nu,
+                             int64_t nnz, int n_t, double *D);
 void launch_relin_compose(hipStream_t s, const ComposeJob *d_jobs, int njobs, int64_t max_padded);
 // velocity and pressure rows of the residual in the outer system's vector layout
 void launch_relin_residual(hipStream_t s, const RelinPlan &P, double *d_r);

@@ -130,6 +130,14 @@ void launch_relin_gather(hipStream_t s, const RelinPlan &P) {
                        P.D_n, P.d_Dp);
 }
 
+// the same kernel under the same grid rule for one pattern of another plan (reaction.cpp)
+void launch_relin_gather_one(hipStream_t s, const int32_t *cptr, const int32_t *clist,
+                             const double *E, int64_t per_level, const double *K, double nu,
+                             int64_t nnz, int n_t, double *D) {
+    hipLaunchKernelGGL(relin_gather_kernel, dim3(relin_grid(nnz * n_t, 256 * 64)), dim3(256), 0, s,
+                       cptr, clist, E, per_level, K, nu, nnz, n_t, D);
+}
+
 // blockIdx.y selects the target block; each SELL slot gets alpha D(^T) + gamma M (blocks.py
 // _axpby: two products, one sum, kept apart by `contract(off)` as in the gather), Dirichlet
 // columns zeroed as kkt_update_block_values does.

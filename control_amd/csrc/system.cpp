@@ -11,6 +11,7 @@
 
 #include "comm.hpp"
 #include "pc.hpp"
+#include "reaction.hpp"
 #include "relin.hpp"
 
 namespace kkt {

@@ -127,6 +127,7 @@ struct TimeGroup {   // CN transform applied to a contiguous range of local bloc
 class PcBase;
 class Comm;
 struct RelinPlan;
+struct ReactionPlan;
 
 struct KrylovCfg {
     int type = KKT_KSP_FGMRES;
@@ -242,6 +243,7 @@ struct System {
     bool pc_cb_failed = false;
 
     std::unique_ptr<RelinPlan> relin;   // kkt_set_relinearisation (relin.hpp)
+    std::unique_ptr<ReactionPlan> reaction;   // kkt_set_reaction_relinearisation (reaction.hpp)
 
     KrylovCfg ksp;
     kkt_steplock steplock{};   // test hook (kkt_debug_set_steplock); n_steps == 0: off

@@ -25,6 +25,7 @@ __all__ = [
     "unit_cube_p1",
     "unit_square_q2",
     "rectangle_p1",
+    "ReactionTerm",
 ]
 
 
@@ -90,6 +91,108 @@ def _p1_convection(self, wind) -> sp.csr_matrix:
 
 
 SpatialDiscretisation.convection = _p1_convection
+
+
+def _radon_rule():
+    """``(lam, wq)`` of Radon's 7-point rule, the tables of ``weighted_mass``."""
+    s15 = np.sqrt(15.0)
+    a1, a2 = (6.0 - s15) / 21.0, (6.0 + s15) / 21.0
+    w1, w2 = (155.0 - s15) / 1200.0, (155.0 + s15) / 1200.0
+    lam = np.array([[1 / 3, 1 / 3, 1 / 3],
+                    [a1, a1, 1 - 2 * a1], [a1, 1 - 2 * a1, a1], [1 - 2 * a1, a1, a1],
+                    [a2, a2, 1 - 2 * a2], [a2, 1 - 2 * a2, a2], [1 - 2 * a2, a2, a2]])
+    wq = np.array([9.0 / 40.0, w1, w1, w1, w2, w2, w2])
+    return lam, wq
+
+
+class ReactionTerm:
+    """The forward form ``(L u, w) + (g(v_old) u, w)`` with a polynomial reaction coefficient
+    ``g(s) = sum_k c_k s^k`` (``coefficients = (c_0, ..., c_p)``, ``p <= 4``) on P1 triangles --
+    the reference's non-linear scalar problem is ``grad v . grad w + (2 + 0.5 v^2) v w``
+    (``test/test_control.py:715-719``): ``ReactionTerm(disc, (2, 0, 0.5))``.
+
+    ``L`` is ``nu * disc.K``, or any CSR matrix ``linear`` inside the structure of ``disc.M``
+    (``disc.K + disc.convection(wind)``: a non-symmetric linear part).  ``term(v, t)`` is the
+    Picard matrix, ``term.jacobian(v, t)`` the Gateaux derivative of ``g(v) v`` in ``v``: the same
+    form with the coefficients ``(k + 1) c_k``.  Declaring the term instead of passing a callable
+    is what lets ``Instationary.non_linear_solve(device=True)`` re-linearise on the GPU.
+
+    The element matrix is stated operation by operation, and the device kernel evaluates the same
+    statement (``csrc/reaction_kernels.hip``): over Radon's 7 points ``q``, ascending,
+
+        s_q = (lam_q0 v_0 + lam_q1 v_1) + lam_q2 v_2
+        g   = c_p;  g = g s_q + c_k  for k = p - 1, ..., 0            (Horner)
+        E[a][b] = sum_q ((W_eq g) lam_qa) lam_qb   from 0.0,  W_eq = wq_q area_e
+
+    every product and sum rounded separately.  The entries are summed into the structure of ``M``
+    by ``np.bincount`` (ascending element-entry order), and ``D = L + C`` with one rounding."""
+
+    MAX_DEGREE = 4
+
+    def __init__(self, disc, coefficients, *, nu=1.0, linear=None):
+        from .blocks import conform_to
+        cells = getattr(disc, "cells", None)
+        if cells is None or np.ndim(cells) != 2 or np.shape(cells)[1] != 3:
+            raise ValueError("ReactionTerm needs a P1 triangle discretisation (disc.cells)")
+        self.coefficients = tuple(float(c) for c in coefficients)
+        if not 1 <= len(self.coefficients) <= self.MAX_DEGREE + 1:
+            raise ValueError(f"ReactionTerm: the degree must be 0 .. {self.MAX_DEGREE}")
+        self.disc = disc
+        self.M = _canonical_csr(disc.M)
+        self.L = conform_to(nu * disc.K if linear is None else linear, self.M)
+        self.cells = np.ascontiguousarray(cells, dtype=np.int32)
+        self.lam, self.wq = _radon_rule()
+        X = disc.coords[self.cells]
+        d1, d2 = X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]
+        self.area = 0.5 * np.abs(d1[:, 0] * d2[:, 1] - d1[:, 1] * d2[:, 0])
+        self.W = self.wq[None, :] * self.area[:, None]
+        rows = np.repeat(self.cells, 3, axis=1).ravel()
+        cols = np.tile(self.cells, (1, 3)).ravel()
+        #: position in the structure of ``M`` of every flat element entry ``e * 9 + 3 a + b``
+        self.scatter = self.M.indptr[rows].astype(np.int64) + _row_positions(self.M, rows, cols)
+
+    @property
+    def degree(self):
+        return len(self.coefficients) - 1
+
+    @property
+    def jacobian_coefficients(self):
+        return tuple((k + 1) * c for k, c in enumerate(self.coefficients))
+
+    def element_matrices(self, v, coefficients=None):
+        """``E`` (n_cells, 3, 3) at the nodal values ``v``: the statement above, an explicit
+        loop over the points, vectorised over the cells."""
+        c = self.coefficients if coefficients is None else tuple(coefficients)
+        lam, W = self.lam, self.W
+        vc = np.asarray(v, dtype=np.float64)[self.cells]
+        v0, v1, v2 = vc[:, 0], vc[:, 1], vc[:, 2]
+        E = np.zeros((len(self.cells), 3, 3))
+        for q in range(len(self.wq)):
+            s = (lam[q, 0] * v0 + lam[q, 1] * v1) + lam[q, 2] * v2
+            g = np.full(len(s), c[-1])
+            for k in range(len(c) - 2, -1, -1):
+                g = g * s + c[k]
+            wg = W[:, q] * g
+            for a in range(3):
+                wa = wg * lam[q, a]
+                for b in range(3):
+                    E[:, a, b] += wa * lam[q, b]
+        return E
+
+    def reaction_values(self, v, coefficients=None):
+        """``C``: the element matrices summed into the structure of ``M`` (its ``data``)."""
+        return np.bincount(self.scatter, weights=self.element_matrices(v, coefficients).ravel(),
+                           minlength=self.M.nnz)
+
+    def _matrix(self, v, coefficients):
+        return sp.csr_matrix((self.L.data + self.reaction_values(v, coefficients),
+                              self.M.indices, self.M.indptr), shape=self.M.shape)
+
+    def __call__(self, v, t):
+        return self._matrix(v, self.coefficients)
+
+    def jacobian(self, v, t):
+        return self._matrix(v, self.jacobian_coefficients)
 
 
 def _canonical_csr(A: sp.spmatrix) -> sp.csr_matrix:

@@ -1,0 +1,278 @@
+"""The scalar Picard / Gauss-Newton loop on the device (``kkt_set_reaction_relinearisation``,
+DESIGN.md section 6.6a): ``Instationary.non_linear_solve(device=True)`` for a forward operator
+declared as a ``fem.ReactionTerm``.
+
+Host side: ``ReactionPlan`` -- the element tables of the term, the contribution lists that make
+the device assembly deterministic (``relinearise.contribution_lists``), the transpose permutation
+and the constant data rows of the residual -- and ``DeviceReaction``, a thin binding of the device
+entry points.  ``device_non_linear_solve`` is the loop of ``Instationary.non_linear_solve`` with
+one block system and one preconditioner kept alive and the iterate in HBM.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .fem import ReactionTerm
+from .relinearise import _recipe_array, contribution_lists, transpose_permutation
+
+__all__ = ["ReactionPlan", "DeviceReaction", "device_non_linear_solve"]
+
+_ARRAYS = ("E", "D", "v", "zeta")
+
+
+def _check(ctl, P=None):
+    """The ``ValueError``s of ``non_linear_solve(device=True)``: nothing here touches the GPU."""
+    if not isinstance(ctl._forward, ReactionTerm):
+        raise ValueError("device=True needs the forward operator declared as a fem.ReactionTerm")
+    if P is not None:
+        raise ValueError("device=True does not take P=: a host callback as preconditioner would "
+                         "bring every application back to the host")
+    if ctl._th is not None:
+        raise ValueError("device=True is the scalar driver's: not for a Taylor-Hood discretisation")
+    if ctl._forward.disc is not ctl._disc:
+        raise ValueError("the ReactionTerm was declared on another discretisation")
+
+
+class ReactionPlan:
+    """Everything ``kkt_set_reaction_relinearisation`` uploads, built once per problem on the
+    host from an ``Instationary`` whose forward operator is a ``fem.ReactionTerm``."""
+
+    def __init__(self, ctl):
+        _check(ctl)
+        term, disc = ctl._forward, ctl._disc
+        self.ctl, self.term = ctl, term
+        self.n_t, self.CN = ctl._n_t, ctl._CN
+        self.m = self.n_t - 1 if self.CN else self.n_t
+        _, _, self.tau = ctl._times()
+        self.beta = ctl._beta
+        #: the coefficients every D of the loop is built from (``construct_D_v``)
+        self.coefficients = term.jacobian_coefficients if ctl._Gauss_Newton else term.coefficients
+        self.lists = contribution_lists(term.cells, term.M)
+        self.tperm = transpose_permutation(term.M)
+        self.data = self._data_rows()
+
+    def _data_rows(self):
+        """The rows of ``non_linear_res_eval`` at the zero iterate: what does not depend on
+        ``(v, zeta)`` -- desired state, forces, and backward Euler's initial-condition row
+        ``tau D(v_0) v_0 + M v_0``.  Boundary values live in the iterate (``v`` keeps them on the
+        Dirichlet dofs), and the Dirichlet rows of the residual are zero."""
+        ctl, disc, n_t, tau = self.ctl, self.ctl._disc, self.n_t, self.tau
+        v_d, f = ctl.construct_v_d(), ctl.construct_f()
+        if self.CN:
+            h = 0.5 * tau
+            r0 = np.stack([h * (v_d[i] + v_d[i + 1]) for i in range(self.m)])
+            r1 = np.stack([h * (f[i] + f[i + 1]) for i in range(self.m)])
+        else:
+            t_0 = ctl._time_interval[0]
+            v_0 = (np.zeros(disc.n_dofs) if ctl._initial_condition is None
+                   else np.asarray(ctl._initial_condition(disc.coords), dtype=np.float64))
+            r0 = tau * v_d
+            r0[n_t - 1] = 0.0
+            r1 = tau * f
+            r1[0] = tau * (ctl.construct_D_v(v_0, t_0) @ v_0) + disc.M @ v_0
+        r0[:, disc.boundary] = 0.0
+        r1[:, disc.boundary] = 0.0
+        return np.ascontiguousarray(np.concatenate([r0, r1]))
+
+    def pattern(self):
+        """``(indptr, indices)`` of every block: the structure of ``M``."""
+        M = self.term.M
+        return M.indptr.astype(np.int32), M.indices.astype(np.int32)
+
+    def descriptor(self):
+        """``kkt_reaction_desc`` over this plan's arrays (valid while ``keep`` lives)."""
+        term, disc = self.term, self.ctl._disc
+        keep = []
+
+        def i32(a):
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            keep.append(a)
+            return a.ctypes.data_as(_lib.c_i32p)
+
+        def f64(a):
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            keep.append(a)
+            return a.ctypes.data_as(_lib.c_f64p)
+        c = (C.c_double * 5)(*self.coefficients)
+        d = _lib.ReactionDesc(
+            n_t=self.n_t, cn=int(self.CN), nq=term.W.shape[1], ne=len(term.cells),
+            n1=disc.n_dofs, tau=float(self.tau), beta=float(self.beta), cells=i32(term.cells),
+            W=f64(term.W), lam=f64(term.lam), nnz=term.M.nnz, indptr=i32(term.M.indptr),
+            indices=i32(term.M.indices), tperm=i32(self.tperm), cptr=i32(self.lists[0]),
+            clist=i32(self.lists[1]), L=f64(term.L.data), M=f64(term.M.data),
+            degree=len(self.coefficients) - 1, c=c, n_bc=len(disc.boundary),
+            bc_idx=i32(disc.boundary), data=f64(self.data))
+        return d, keep
+
+
+class DeviceReaction:
+    """The plan on a scalar instationary ``MultiBlockSystem`` and the iterate in HBM."""
+
+    def __init__(self, ctl, system, recipes=None, plan=None):
+        """``recipes``: the blocks every re-linearisation rewrites (default: the ``"inner"`` list
+        of ``blocks.instationary_relinearisation_recipes``)."""
+        from .blocks import instationary_relinearisation_recipes
+        self.plan = ReactionPlan(ctl) if plan is None else plan
+        self.ctl, self.system, self._lib = ctl, system, system._lib
+        d, keep = self.plan.descriptor()
+        system._ck(self._lib.kkt_set_reaction_relinearisation(system.handle, C.byref(d)))
+        del keep
+        if recipes is None:
+            p = self.plan
+            recipes = instationary_relinearisation_recipes(p.tau, p.beta, p.n_t, p.CN)["inner"]
+        self.recipes = (_recipe_array(recipes, 0), len(recipes))
+
+    def _shape(self):
+        return (self.plan.n_t, self.ctl._disc.n_dofs)
+
+    def set_state(self, v, zeta):
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (v, zeta)]
+        for a in arrs:
+            if a.shape != self._shape():
+                raise ValueError(f"iterate block of shape {a.shape}, expected {self._shape()}")
+        self.system._ck(self._lib.kkt_reaction_state(
+            self.system.handle, 0, *[a.ctypes.data_as(_lib.c_f64p) for a in arrs]))
+
+    def get_state(self):
+        out = [np.zeros(self._shape()), np.zeros(self._shape())]
+        self.system._ck(self._lib.kkt_reaction_state(
+            self.system.handle, 1, *[a.ctypes.data_as(_lib.c_f64p) for a in out]))
+        return out
+
+    def assemble(self):
+        """Element matrices and ``D`` of every level at the device iterate's ``v``."""
+        self.system._ck(self._lib.kkt_reaction_relinearise(self.system.handle, self.system.handle,
+                                                           1, 0, None))
+
+    def relinearise(self, system=None, recipes=None):
+        """Rewrite the recipe blocks of ``system`` (default: the plan's own) from the last
+        assembly.  ``recipes``: another list for this call (the first build composes every
+        block, ``blocks.instationary_build_recipes``)."""
+        system = self.system if system is None else system
+        arr, n = self.recipes if recipes is None else (_recipe_array(recipes, 0), len(recipes))
+        system._ck(self._lib.kkt_reaction_relinearise(system.handle, self.system.handle, 0, n, arr))
+
+    def residual(self, d_out, rhs):
+        norm = C.c_double()
+        self.system._ck(self._lib.kkt_reaction_residual_device(self.system.handle, d_out,
+                                                               int(rhs), C.byref(norm)))
+        return norm.value
+
+    def update(self, d_u):
+        self.system._ck(self._lib.kkt_reaction_update_device(self.system.handle, d_u))
+
+    def debug_array(self, which):
+        """``kkt_debug_reaction_array``: ``"E"`` (n_t, ne, 3, 3) or ``"D"`` (n_t, nnz) of the last
+        assembly, ``"v"`` / ``"zeta"`` (n_t, n) of the iterate."""
+        n_t, n = self._shape()
+        shape = {"E": (n_t, len(self.plan.term.cells), 3, 3), "D": (n_t, self.plan.term.M.nnz),
+                 "v": (n_t, n), "zeta": (n_t, n)}[which]
+        out = np.empty(shape)
+        self.system._ck(self._lib.kkt_debug_reaction_array(
+            self.system.handle, _ARRAYS.index(which), out.ctypes.data_as(_lib.c_f64p), out.size))
+        return out
+
+
+def build_system(ctl, backend, plan):
+    """The scalar block system from patterns: every block of ``blocks.instationary_blocks`` is a
+    ``PatternOnly`` of the structure of ``M``, in the row-major dict order of the host path.
+    Returns ``(system, block dicts)``; the blocks are unset until the device composes them."""
+    from .blocks import instationary_build_recipes
+    from .multiblock import PatternOnly
+    disc, m = ctl._disc, plan.m
+    full = instationary_build_recipes(plan.tau, plan.beta, plan.n_t, plan.CN)["inner"]
+    n = disc.n_dofs
+    pat = PatternOnly(*plan.pattern(), (n, n))
+    quads = [{(i, j): None for i in range(m) for j in range(m)} for _ in range(4)]
+    for (q, i, j, *_) in full:
+        quads[q][(i, j)] = pat
+    ns = tuple(backend.DirichletBCNullspace(disc.boundary) for _ in range(m))
+    system = backend.MultiBlockSystem(n, n, *quads, n_blocks_00=m, n_blocks_11=m, nullspace_0=ns,
+                                      nullspace_1=ns, CN=plan.CN)
+    return system, quads, full
+
+
+def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bounds=None,
+                            max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
+                            absolute_non_linear_tol=1.0e-8, print_error_non_linear=False,
+                            backend=None, Multigrid=False):
+    """``Instationary.non_linear_solve`` with the iterate in HBM.  One ``MultiBlockSystem`` is
+    built from patterns and composed on the device, one ``SchurPC`` is attached to it; every
+    iteration then assembles, evaluates the residual (the host reads its norm), re-composes the
+    blocks that carry ``D`` (the preconditioner is marked stale and rebuilt by the next solve),
+    solves and updates on the GPU.  The stopping logic is the host loop's."""
+    from .control import GpuBackend, _multigrid_kw
+    _check(ctl, P)
+    backend = backend or GpuBackend()
+    if not isinstance(backend, GpuBackend):
+        raise ValueError("device=True runs on a GpuBackend")
+    disc, n_t, CN = ctl._disc, ctl._n_t, ctl._CN
+    nodes = disc.boundary
+    v_0 = (np.zeros(disc.n_dofs) if ctl._initial_condition is None
+           else np.asarray(ctl._initial_condition(disc.coords), dtype=np.float64))
+    v_old, zeta_old = ctl._v.copy(), ctl._zeta.copy()
+    if CN:
+        v_old[0] = v_0                                           # control.py:3425-3426
+    zeta_old[n_t - 1] = 0.0
+    # the values the iterate keeps on the Dirichlet dofs from the first update on (:3490-3493)
+    v_fixed = v_old.copy()
+    for i in range(n_t):
+        v_fixed[i, nodes] = ctl._bc_values(i)[nodes]
+    lift = not np.array_equal(v_fixed, v_old)
+
+    plan = ReactionPlan(ctl)
+    system, quads, full = build_system(ctl, backend, plan)
+    dev = DeviceReaction(ctl, system, plan=plan)
+    dev.set_state(v_old, zeta_old)
+    dev.assemble()
+    dev.relinearise(recipes=full)
+    pc_fn = backend.construct_pc("CN" if CN else "BE", plan.term.M, quads[1], quads[2], n_t,
+                                 plan.tau, plan.beta, nodes, lambda_v_bounds or (0.5, 2.0),
+                                 1.0e-3, **_multigrid_kw(disc, Multigrid))
+    if solver_parameters is None:                                # control.py:3260-3266
+        solver_parameters = {"linear_solver": "gmres", "gmres_restart": 10,
+                             "maximum_iterations": 50, "relative_tolerance": 1.0e-6,
+                             "absolute_tolerance": 0.0, "monitor_convergence": False}
+    lib = system._lib
+    d_b, d_u = C.c_void_p(), C.c_void_p()
+    system._ck(lib.kkt_vec_alloc(system.handle, C.byref(d_b)))
+    lin_its = []
+    try:
+        system._ck(lib.kkt_vec_alloc(system.handle, C.byref(d_u)))   # zeroed
+        norm_0 = dev.residual(d_b, rhs=True)
+        norm_k, k, norms = norm_0, 0, [norm_0]
+        fresh = True
+        while (norm_k > relative_non_linear_tol * norm_0
+               and norm_k > absolute_non_linear_tol):
+            if not fresh:
+                dev.relinearise()
+            fresh = False
+            ksp = system.solve_device(d_b, d_u, solver_parameters=solver_parameters, pc_fn=pc_fn)
+            lin_its.append(ksp.getIterationNumber())
+            dev.update(d_u)
+            if lift:     # the starting iterate did not carry the boundary values: once
+                v_new, zeta_new = dev.get_state()
+                v_new[:, nodes] = v_fixed[:, nodes]
+                dev.set_state(v_new, zeta_new)
+                lift = False
+            dev.assemble()
+            norm_k = dev.residual(d_b, rhs=True)
+            norms.append(norm_k)
+            k += 1
+            if print_error_non_linear:
+                print(f"Non-linear solver: iteration {k:d}, non-linear residual norm "
+                      f"{norm_k:.16e}")
+            if k + 1 > max_non_linear_iter:
+                break
+        v_new, zeta_new = dev.get_state()
+    finally:
+        lib.kkt_vec_free(system.handle, d_b)
+        if d_u:
+            lib.kkt_vec_free(system.handle, d_u)
+        system.close()
+    ctl._v, ctl._zeta = v_new, zeta_new
+    ctl.non_linear_info = {"linear_iterations": lin_its}
+    return norms

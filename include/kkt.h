@@ -475,6 +475,66 @@ int kkt_picard_update_device(kkt_handle plan, double *d_u);
 enum { KKT_RELIN_EV = 0, KKT_RELIN_EP = 1, KKT_RELIN_D2 = 2, KKT_RELIN_DP = 3, KKT_RELIN_V = 4,
        KKT_RELIN_ZETA = 5 };
 int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
+/* ---- Device re-linearisation of the scalar reaction problem.
+ *
+ * The forward operator is (L u, w) + (g(v_old) u, w) on P1 triangles with the polynomial
+ * g(s) = sum_k c[k] s^k, degree <= 4 (fem.ReactionTerm).  Per (element, level) the element matrix
+ *   E[a][b] = sum_q (W_eq g(s_q)) lam_qa lam_qb,   s_q = lam_q0 v_0 + lam_q1 v_1 + lam_q2 v_2,
+ * over Radon's 7 points, q ascending from 0.0, g by Horner from c[degree] down, every product and
+ * sum rounded separately; the entries are gathered into the scalar pattern through the
+ * contribution lists (flat entry e * 9 + 3 a + b, ascending: np.bincount's order) and
+ * D = L + C with one rounding per entry.  The handle must be a scalar instationary layout
+ * (n_blocks_00 = n_blocks_11 = m, nx0 = nx1 = n1; m = n_t, Crank-Nicolson n_t - 1), finalized,
+ * on one rank.  A handle carries at most one plan, of this kind or of kkt_set_relinearisation's:
+ * setting the other kind is KKT_ERR_STATE.  data: the 2m x n1 rows [adjoint | state] of
+ * Instationary.non_linear_res_eval at the zero iterate (desired state, forces, backward Euler's
+ * initial-condition row tau D(v_0) v_0 + M v_0), Dirichlet rows zero.  c: the Gauss-Newton
+ * coefficients (k + 1) c_k when that linearisation is on.  Arrays are copied; patterns, lists and
+ * permutations are validated as kkt_set_relinearisation validates its own (KKT_ERR_ARG naming what
+ * does not fit). */
+typedef struct kkt_reaction_desc {
+    int n_t, cn, nq;              /* time levels, Crank-Nicolson (1) or backward Euler, nq = 7 */
+    int64_t ne, n1;               /* triangles, P1 nodes */
+    double tau, beta;
+    const int32_t *cells;         /* ne x 3 nodes per triangle */
+    const double *W;              /* ne x nq quadrature weights times the area */
+    const double *lam;            /* nq x 3 barycentric coordinates of the points */
+    int64_t nnz;                  /* the scalar pattern (that of M) */
+    const int32_t *indptr, *indices, *tperm, *cptr, *clist;
+    const double *L, *M;          /* nnz values: the linear part and the mass matrix */
+    int degree;
+    double c[5];
+    int64_t n_bc;
+    const int32_t *bc_idx;
+    const double *data;
+} kkt_reaction_desc;
+int kkt_set_reaction_relinearisation(kkt_handle h, const kkt_reaction_desc *desc);
+/* assemble != 0 first forms the element matrices and D of all n_t levels at the plan's iterate;
+ * then the n recipes (space = 0) rewrite blocks of handle h exactly as kkt_relinearise_device
+ * does: Dirichlet columns zeroed, shared value arrays made private first, alpha = 0 recipes give
+ * gamma M, a built-in preconditioner is marked stale.  n = 0 only assembles. */
+int kkt_reaction_relinearise(kkt_handle h, kkt_handle plan, int assemble, int n,
+                             const kkt_relin_recipe *recipes);
+/* The iterate (v, zeta: n_t x n1) in HBM: host copies in (download 0) or out (download 1), and
+ * its device addresses (either out pointer may be NULL). */
+int kkt_reaction_state(kkt_handle plan, int download, double *v, double *zeta);
+int kkt_reaction_iterate(kkt_handle plan, double **d_v, double **d_zeta);
+/* The rows [r0, r1] of Instationary.non_linear_res_eval at the plan's iterate with D of the last
+ * assembly (backward Euler: n_t rows per family, Crank-Nicolson n_t - 1), Dirichlet rows zero, in
+ * d_out (one local vector of the plan's handle); rhs = 1: the right-hand side of the linearised
+ * solve (Crank-Nicolson: T_1 on the adjoint rows, T_2 on the state rows).  *norm (host): the
+ * 2-norm of the untransformed rows by the deterministic reduction.  KKT_ERR_STATE before any
+ * assembly. */
+int kkt_reaction_residual_device(kkt_handle plan, double *d_out, int rhs, double *norm);
+/* v, zeta += the blocks of the update d_u (Crank-Nicolson: v from level 1, zeta levels
+ * 0 .. n_t - 2); v is left untouched on the Dirichlet dofs (they hold the boundary values), zeta
+ * is zero there; d_u is zeroed: the initial guess of the next solve. */
+int kkt_reaction_update_device(kkt_handle plan, double *d_u);
+/* Test hook: the element matrices E (n_t x ne x 9) or D (n_t x nnz) of the last assembly
+ * (KKT_ERR_STATE before one), or v / zeta (n_t x n1) of the iterate, copied to the host; cap:
+ * doubles available at out (KKT_ERR_ARG when too small). */
+enum { KKT_REACTION_E = 0, KKT_REACTION_D = 1, KKT_REACTION_V = 2, KKT_REACTION_ZETA = 3 };
+int kkt_debug_reaction_array(kkt_handle plan, int which, double *out, int64_t cap);
 /* The stored values of block (quadrant, i, j) in the CSR order of its pattern, read from the
  * SELL value array through the pattern's slot -> CSR map.  *nnz: the stored entries (out == NULL:
  * only that); *padding_zero: 1 when every padding slot of the value array holds 0.0.  A value
