@@ -1,18 +1,14 @@
 // Device re-linearisation of the scalar reaction problem (include/kkt.h,
 // kkt_set_reaction_relinearisation): P1 element matrices of a polynomial reaction coefficient,
-// their gather and composition into block values (relin.hpp's kernels), the Picard residual and
-// the update of the iterate.  DESIGN.md section 6.6a.
+// their gather and composition into block values (compose.hpp), the Picard residual and the
+// update of the iterate.  DESIGN.md section 6.6a.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
-#include <set>
-#include <utility>
-#include <vector>
-
 #include "../../include/kkt.h"
+#include "compose.hpp"
 #include "devmem.hpp"
-#include "relin.hpp"
 
 namespace kkt {
 
@@ -34,7 +30,6 @@ struct ReactionPlan {
     DevPool mem;   // everything below but the job table
     int32_t *d_cells = nullptr;
     double *d_W = nullptr, *d_lam = nullptr;
-    std::vector<int32_t> h_ip, h_ix;   // the scalar pattern (target patterns are proven equal to it)
     int32_t *d_ip = nullptr, *d_ix = nullptr, *d_tperm = nullptr, *d_cptr = nullptr,
             *d_clist = nullptr;
     double *d_L = nullptr, *d_M = nullptr;
@@ -45,9 +40,7 @@ struct ReactionPlan {
     bool assembled = false;
     double *d_v = nullptr, *d_zeta = nullptr;   // the iterate, n_t x n1 each
     double *d_red = nullptr;                    // reduction scratch + result
-    DevBuf<ComposeJob> d_jobs;                  // regrown with the largest job count seen
-    int jobs_cap = 0;
-    std::set<std::pair<const void *, int>> checked;   // (system, pattern id) equal to the plan's
+    Composer compose;                           // one space: the scalar pattern
 };
 
 // E[(l ne + e) 9 + 3a + b] of every (element, level) at the iterate's v

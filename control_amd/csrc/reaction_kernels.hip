@@ -9,13 +9,6 @@
 
 namespace kkt {
 
-static inline int reaction_grid(int64_t n, int cap) {
-    int64_t g = (n + 255) / 256;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 constexpr int REACTION_ELEMENT_BLOCKS = 1024;   // grid caps: the rest is grid-stride
 constexpr int REACTION_ROW_BLOCKS = 512;
 constexpr int REACTION_VECTOR_BLOCKS = 256 * 8;
@@ -69,7 +62,7 @@ __global__ __launch_bounds__(256) void reaction_elements_kernel(
 
 void launch_reaction_elements(hipStream_t s, const ReactionPlan &P) {
     hipLaunchKernelGGL(reaction_elements_kernel,
-                       dim3(reaction_grid(P.ne * P.n_t, REACTION_ELEMENT_BLOCKS)), dim3(256), 0, s,
+                       dim3(grid_of(P.ne * P.n_t, REACTION_ELEMENT_BLOCKS)), dim3(256), 0, s,
                        P.d_v, P.ne, P.n1, P.n_t, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
 }
 
@@ -192,7 +185,7 @@ void launch_reaction_residual(hipStream_t s, const ReactionPlan &P, double *d_r)
     A.n1 = P.n1; A.nnz = P.nnz; A.n_t = P.n_t; A.m = P.m; A.cn = P.CN;
     A.tau = P.tau; A.beta = P.beta;
     hipLaunchKernelGGL(reaction_residual_kernel,
-                       dim3(reaction_grid(P.n1, REACTION_ROW_BLOCKS), 2 * P.m), dim3(256), 0, s, A,
+                       dim3(grid_of(P.n1, REACTION_ROW_BLOCKS), 2 * P.m), dim3(256), 0, s, A,
                        d_r);
 }
 
@@ -216,7 +209,7 @@ __global__ __launch_bounds__(256) void reaction_rhs_kernel(const double *__restr
 
 void launch_reaction_rhs(hipStream_t s, const ReactionPlan &P, const double *d_r, double *d_b) {
     const int64_t n = 2 * (int64_t)P.m * P.n1;
-    hipLaunchKernelGGL(reaction_rhs_kernel, dim3(reaction_grid(n, REACTION_VECTOR_BLOCKS)),
+    hipLaunchKernelGGL(reaction_rhs_kernel, dim3(grid_of(n, REACTION_VECTOR_BLOCKS)),
                        dim3(256), 0, s, d_r, d_b, P.m, P.n1);
 }
 
@@ -244,7 +237,7 @@ __global__ __launch_bounds__(256) void reaction_update_kernel(double *__restrict
 
 void launch_reaction_update(hipStream_t s, const ReactionPlan &P, double *d_u) {
     const int64_t n = 2 * (int64_t)P.m * P.n1;
-    hipLaunchKernelGGL(reaction_update_kernel, dim3(reaction_grid(n, REACTION_VECTOR_BLOCKS)),
+    hipLaunchKernelGGL(reaction_update_kernel, dim3(grid_of(n, REACTION_VECTOR_BLOCKS)),
                        dim3(256), 0, s, d_u, P.d_v, P.d_zeta, P.d_bc, P.m, P.n1, (int)P.CN);
 }
 

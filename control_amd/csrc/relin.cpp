@@ -1,5 +1,6 @@
 // Host side of the device re-linearisation (include/kkt.h, kkt_set_relinearisation): plan
-// upload and validation, composition jobs, residual and update.  Kernels: relin_kernels.hip.
+// upload and validation, assembly, residual and update.  Kernels: relin_kernels.hip; checks and
+// composition: compose.hpp.
 #include "relin.hpp"
 
 #include <algorithm>
@@ -13,41 +14,6 @@ namespace kkt {
 
 static void need(bool ok, const std::string &msg) {
     if (!ok) fail(KKT_ERR_ARG, "kkt_set_relinearisation: " + msg);
-}
-
-// sorted CSR with nrows rows over ncols columns
-static void check_csr(const int32_t *ip, const int32_t *ix, int64_t nrows, int64_t ncols,
-                      int64_t nnz, const char *what) {
-    need(ip && ix, std::string(what) + ": null pattern");
-    need(ip[0] == 0 && ip[nrows] == nnz, std::string(what) + ": indptr does not span nnz");
-    for (int64_t r = 0; r < nrows; ++r) {
-        need(ip[r] <= ip[r + 1], std::string(what) + ": indptr decreases");
-        for (int32_t k = ip[r]; k < ip[r + 1]; ++k) {
-            need(ix[k] >= 0 && ix[k] < ncols, std::string(what) + ": column out of range");
-            need(k == ip[r] || ix[k - 1] < ix[k], std::string(what) + ": columns not sorted");
-        }
-    }
-}
-
-static void check_lists(const int32_t *cptr, const int32_t *clist, int64_t nnz, int64_t n_entries,
-                        const char *what) {
-    need(cptr && clist, std::string(what) + ": null contribution list");
-    need(cptr[0] == 0 && cptr[nnz] == n_entries,
-         std::string(what) + ": the lists must hold every element entry once");
-    for (int64_t k = 0; k < nnz; ++k) {
-        need(cptr[k] <= cptr[k + 1], std::string(what) + ": list pointer decreases");
-        for (int32_t j = cptr[k]; j < cptr[k + 1]; ++j)
-            need(clist[j] >= 0 && clist[j] < n_entries &&
-                     (j == cptr[k] || clist[j - 1] < clist[j]),
-                 std::string(what) + ": list entries out of range or not ascending");
-    }
-}
-
-static void check_perm(const int32_t *t, int64_t nnz, const char *what) {
-    need(t != nullptr, std::string(what) + ": null transpose permutation");
-    for (int64_t k = 0; k < nnz; ++k)
-        need(t[k] >= 0 && t[k] < nnz && t[t[k]] == k,
-             std::string(what) + ": not a transpose permutation");
 }
 
 void relin_set(System &S, const kkt_relin_desc *d) {
@@ -67,17 +33,16 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     need(d->V && d->W && d->phi && d->gphi && d->lam && d->glam && d->K2 && d->M2 && d->Kp &&
              d->Mp && d->b_values && d->data && (d->n_bc == 0 || d->bc_idx),
          "null array");
-    for (int64_t k = 0; k < d->ne * 6; ++k)
-        need(d->V[k] >= 0 && d->V[k] < d->n2, "V: node out of range");
-    check_csr(d->v_indptr, d->v_indices, d->n2, d->n2, d->nnz2, "P2 pattern");
-    check_csr(d->p_indptr, d->p_indices, d->n1, d->n1, d->nnz1, "P1 pattern");
-    check_csr(d->b_indptr, d->b_indices, d->n1, nv, d->nnz_b, "B");
-    check_perm(d->v_tperm, d->nnz2, "P2 pattern");
-    check_perm(d->p_tperm, d->nnz1, "P1 pattern");
-    check_lists(d->v_cptr, d->v_clist, d->nnz2, d->ne * RELIN_EV, "P2");
-    check_lists(d->p_cptr, d->p_clist, d->nnz1, d->ne * RELIN_EP, "P1");
-    for (int64_t k = 0; k < d->n_bc; ++k)
-        need(d->bc_idx[k] >= 0 && d->bc_idx[k] < nv, "bc_idx out of range");
+    const std::string api = "kkt_set_relinearisation: ";
+    check_range(api + "V", d->V, d->ne * 6, d->n2);
+    check_csr(api + "P2 pattern", d->v_indptr, d->v_indices, d->n2, d->n2, d->nnz2);
+    check_csr(api + "P1 pattern", d->p_indptr, d->p_indices, d->n1, d->n1, d->nnz1);
+    check_csr(api + "B", d->b_indptr, d->b_indices, d->n1, nv, d->nnz_b);
+    check_perm(api + "P2 pattern", d->v_tperm, d->nnz2);
+    check_perm(api + "P1 pattern", d->p_tperm, d->nnz1);
+    check_lists(api + "P2", d->v_cptr, d->v_clist, d->nnz2, d->ne * RELIN_EV);
+    check_lists(api + "P1", d->p_cptr, d->p_clist, d->nnz1, d->ne * RELIN_EP);
+    check_range(api + "bc_idx", d->bc_idx, d->n_bc, nv);
 
     auto P = std::make_unique<RelinPlan>();
     P->n_t = d->n_t;
@@ -118,10 +83,6 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     P->d_gphi = P->mem.upload(d->gphi, ne * nq * 12);
     P->d_lam = P->mem.upload(d->lam, nq * 3);
     P->d_glam = P->mem.upload(d->glam, ne * 6);
-    P->h_ip2.assign(d->v_indptr, d->v_indptr + d->n2 + 1);
-    P->h_ix2.assign(d->v_indices, d->v_indices + d->nnz2);
-    P->h_ipp.assign(d->p_indptr, d->p_indptr + d->n1 + 1);
-    P->h_ixp.assign(d->p_indices, d->p_indices + d->nnz1);
     P->d_ip2 = P->mem.upload(d->v_indptr, d->n2 + 1);
     P->d_ix2 = P->mem.upload(d->v_indices, d->nnz2);
     P->d_t2 = P->mem.upload(d->v_tperm, d->nnz2);
@@ -178,6 +139,15 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     HIPCHK(hipMemset(P->d_p, 0, nl * d->n1 * 8));
     HIPCHK(hipMemset(P->d_mu, 0, nl * d->n1 * 8));
     P->d_red = P->mem.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX + 2);
+    P->compose.n_t = d->n_t;
+    using I32 = std::vector<int32_t>;
+    P->compose.spaces = {
+        {"velocity", I32(d->v_indptr, d->v_indptr + d->n2 + 1),
+         I32(d->v_indices, d->v_indices + d->nnz2), d->nnz2, 2, P->d_D2, P->D_l0, P->D_n, P->d_M2,
+         P->d_t2},
+        {"pressure", I32(d->p_indptr, d->p_indptr + d->n1 + 1),
+         I32(d->p_indices, d->p_indices + d->nnz1), d->nnz1, 1, P->d_Dp, P->D_l0, P->D_n, P->d_Mp,
+         P->d_tp}};
     S.relin = std::move(P);
 }
 
@@ -210,66 +180,8 @@ void relin_apply(System &T, System &PS, const double *d_v, int n, const kkt_reli
     if (d_v && PS.sharded && d_v != P.d_v)
         fail(KKT_ERR_ARG, "kkt_relinearise_device: a time shard assembles at the plan's iterate "
                           "(kkt_picard_iterate)");
-    // validate every recipe before anything is written
-    std::vector<ComposeJob> jobs;
-    int64_t max_padded = 0;
-    for (int r = 0; r < n; ++r) {
-        const kkt_relin_recipe &c = rec[r];
-        const std::string at = "kkt_relinearise_device: recipe " + std::to_string(r) + ": ";
-        const std::string blk = "block (" + std::to_string(c.quadrant) + "; " +
-                                std::to_string(c.i) + ", " + std::to_string(c.j) + ")";
-        if (T.sharded && c.i >= 0 && !T.owns(c.i))
-            fail(KKT_ERR_ARG, at + blk + ": its block row is not owned by this rank");
-        auto it = T.blocks.find(std::make_tuple(c.quadrant, c.i, c.j));
-        if (it == T.blocks.end()) fail(KKT_ERR_ARG, at + "no such block");
-        if (c.space != 0 && c.space != 1) fail(KKT_ERR_ARG, at + "space must be 0 or 1");
-        if (c.level < 0 || c.level >= P.n_t) fail(KKT_ERR_ARG, at + "level out of range");
-        if (c.alpha != 0.0 && (c.level < P.D_l0 || c.level >= P.D_l0 + P.D_n))
-            fail(KKT_ERR_ARG, at + blk + ": level " + std::to_string(c.level) +
-                                  " is outside this rank's window of D");
-        const int pat = T.values[it->second.va].pattern;
-        const Pattern &Q = T.patterns[pat];
-        const auto key = std::make_tuple((const void *)&T, pat, c.space);
-        if (!P.checked.count(key)) {
-            bool same;
-            if (c.space == 0) {
-                const int64_t n2 = P.n2, nnz2 = P.nnz2;
-                same = Q.nrows == 2 * n2 && Q.ncols == 2 * n2 && Q.nnz == 2 * nnz2;
-                for (int64_t row = 0; same && row <= 2 * n2; ++row)
-                    same = Q.h_indptr[row] ==
-                           (row <= n2 ? P.h_ip2[row] : nnz2 + P.h_ip2[row - n2]);
-                for (int64_t k = 0; same && k < 2 * nnz2; ++k)
-                    same = Q.h_indices[k] ==
-                           (k < nnz2 ? P.h_ix2[k] : n2 + P.h_ix2[k - nnz2]);
-            } else {
-                same = Q.nrows == P.n1 && Q.ncols == P.n1 && Q.nnz == P.nnz1 &&
-                       Q.h_indptr == P.h_ipp && Q.h_indices == P.h_ixp;
-            }
-            if (!same)
-                fail(KKT_ERR_ARG, at + "the block's pattern is not the plan's " +
-                                      (c.space == 0 ? "velocity" : "pressure") + " pattern");
-            P.checked.insert(key);
-        }
-        ComposeJob J{};
-        J.sell2csr = Q.d_sell2csr;
-        J.col = Q.d_col;
-        J.npadded = Q.npadded;
-        J.alpha = c.alpha;
-        J.gamma = c.gamma;
-        if (c.space == 0) {
-            J.D = P.d_D2 + (int64_t)(c.level - P.D_l0) * P.nnz2;
-            J.M = P.d_M2;
-            J.tperm = c.transpose ? P.d_t2 : nullptr;
-            J.nnz_s = P.nnz2;
-        } else {
-            J.D = P.d_Dp + (int64_t)(c.level - P.D_l0) * P.nnz1;
-            J.M = P.d_Mp;
-            J.tperm = c.transpose ? P.d_tp : nullptr;
-            J.nnz_s = P.nnz1 + 1;   // no second component
-        }
-        jobs.push_back(J);
-        max_padded = std::max(max_padded, Q.npadded);
-    }
+    // every recipe is validated before anything is written
+    std::vector<ComposeJob> jobs = compose_jobs("kkt_relinearise_device", T, P.compose, n, rec);
     if (d_v) {
         relin_exchange(PS);
         launch_relin_elements(PS.stream, P, d_v);
@@ -280,34 +192,7 @@ void relin_apply(System &T, System &PS, const double *d_v, int n, const kkt_reli
     }
     if (n == 0) return;
     if (!P.assembled) fail(KKT_ERR_STATE, "kkt_relinearise_device: nothing assembled yet (d_v NULL)");
-    // copy on write: a value array shared with another block becomes private first
-    for (int r = 0; r < n; ++r) {
-        Block &blk = T.blocks.at(std::make_tuple(rec[r].quadrant, rec[r].i, rec[r].j));
-        int users = 0;
-        for (auto &kv : T.blocks) users += kv.second.va == blk.va;
-        if (users > 1) {
-            const Pattern &Q = T.patterns[T.values[blk.va].pattern];
-            T.give_private_values(rec[r].quadrant, rec[r].i, rec[r].j,
-                                  DevBuf<double>::alloc(Q.npadded));
-        }
-        const ValueArray &va = T.values[blk.va];
-        jobs[r].dst = va.d_vals;
-        jobs[r].colmask = va.colmask_set >= 0 ? T.bc_sets[va.colmask_set].d_mask : nullptr;
-    }
-    if (P.jobs_cap < n) {
-        P.d_jobs.reset();
-        P.d_jobs = DevBuf<ComposeJob>::alloc(n);
-        P.jobs_cap = n;
-    }
-    // the job table is shared by every target of the plan: the copy and the launch run in order
-    // on the target's stream, and the host waits before the table is reused
-    HIPCHK(hipMemcpyAsync(P.d_jobs.get(), jobs.data(), n * sizeof(ComposeJob), hipMemcpyHostToDevice,
-                          T.stream));
-    launch_relin_compose(T.stream, P.d_jobs.get(), n, max_padded);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(T.stream));
-    for (int r = 0; r < n; ++r) T.mark_set(rec[r].quadrant, rec[r].i, rec[r].j);
-    T.pc_stale = true;
+    compose_run(T, P.compose, jobs, rec);
 }
 
 // Host arrays of the global shapes.  Upload: the rank's windows, halo levels included.
@@ -323,22 +208,14 @@ void relin_state(System &S, int download, double *v, double *zeta, double *p, do
         v1 = P.CN ? hi + 1 : hi;
         z1 = P.CN && hi == P.m ? hi + 1 : hi;
     }
-    double *dev[4] = {P.d_v + (int64_t)(v0 - P.v_l0) * P.nv,
-                      P.d_zeta + (int64_t)(z0 - P.z_l0) * P.nv, P.d_p, P.d_mu};
-    double *host[4] = {v ? v + (int64_t)v0 * P.nv : nullptr,
-                       zeta ? zeta + (int64_t)z0 * P.nv : nullptr,
-                       p ? p + (int64_t)P.lo * P.n1 : nullptr,
-                       mu ? mu + (int64_t)P.lo * P.n1 : nullptr};
-    const int64_t len[4] = {(v1 - v0) * P.nv, (z1 - z0) * P.nv, (int64_t)P.nl * P.n1,
-                            (int64_t)P.nl * P.n1};
-    for (int k = 0; k < 4; ++k) {
-        if (!host[k]) continue;
-        if (download)
-            HIPCHK(hipMemcpyAsync(host[k], dev[k], len[k] * 8, hipMemcpyDeviceToHost, S.stream));
-        else
-            HIPCHK(hipMemcpyAsync(dev[k], host[k], len[k] * 8, hipMemcpyHostToDevice, S.stream));
-    }
-    HIPCHK(hipStreamSynchronize(S.stream));
+    const int64_t rows = (int64_t)P.nl * P.n1;
+    copy_spans(S.stream, download != 0,
+               {{P.d_v + (int64_t)(v0 - P.v_l0) * P.nv, v ? v + (int64_t)v0 * P.nv : nullptr,
+                 (v1 - v0) * P.nv},
+                {P.d_zeta + (int64_t)(z0 - P.z_l0) * P.nv,
+                 zeta ? zeta + (int64_t)z0 * P.nv : nullptr, (z1 - z0) * P.nv},
+                {P.d_p, p ? p + (int64_t)P.lo * P.n1 : nullptr, rows},
+                {P.d_mu, mu ? mu + (int64_t)P.lo * P.n1 : nullptr, rows}});
 }
 
 void relin_window(System &S, int out[8]) {
@@ -361,20 +238,9 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
     RelinPlan &P = plan_of(S);
     if (!d_out || !norm) fail(KKT_ERR_ARG, "kkt_picard_residual_device: null argument");
     if (!P.assembled) fail(KKT_ERR_STATE, "kkt_picard_residual_device: D not assembled yet");
-    double *r = d_out;
-    if (rhs) {
-        if (!S.d_tmp_y) S.d_tmp_y = S.mem.adopt(S.new_vec());
-        r = S.d_tmp_y;
-    }
+    double *r = rhs ? raw_rows(S) : d_out;
     launch_relin_residual(S.stream, P, r);
-    VecList V{};
-    V.v[0] = r;
-    launch_mdot(S.stream, r, V, 1, S.n_local, P.d_red + 2, P.d_red + 1);
-    if (S.sharded) {   // every rank holds the same sum, and so the same norm
-        if (!S.comm) fail(KKT_ERR_STATE, "time-sharded system without a transport");
-        S.comm->allreduce_sum(P.d_red + 1, 1, S.stream);
-    }
-    launch_norm2_finish(S.stream, P.d_red + 1, P.d_red);
+    launch_residual_norm(S, r, P.d_red);
     if (rhs && S.sharded && P.CN) {
         // the raw rows the time transforms read across the shard boundary (the pattern of
         // comm_exchange_row_halos): T_1 families send their first row down, T_2 their last up
@@ -387,9 +253,7 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
         S.comm->sendrecv(rp + nl * n1, n1, dn, h + 2 * nv + n1, n1, up, S.stream);
     }
     if (rhs) launch_relin_rhs(S.stream, P, r, d_out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(norm, P.d_red, sizeof(double), hipMemcpyDeviceToHost, S.stream));
-    HIPCHK(hipStreamSynchronize(S.stream));
+    read_residual_norm(S, P.d_red, norm);
 }
 
 void relin_debug_array(System &S, int which, double *out, int64_t cap) {

@@ -5,34 +5,13 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
-#include <set>
-#include <tuple>
-#include <vector>
-
 #include "../../include/kkt.h"
+#include "compose.hpp"
 #include "devmem.hpp"
 
 namespace kkt {
 
 struct System;
-
-constexpr int RELIN_NQ = 7;        // Radon's 7-point rule
-constexpr int RELIN_EV = 36;       // P2 element matrix entries
-constexpr int RELIN_EP = 9;        // P1 element matrix entries
-
-// One target block of a composition: dst = alpha D(^T) + gamma M on a SELL value array.
-struct ComposeJob {
-    double *dst;
-    const int32_t *sell2csr;   // CSR position of every SELL slot (-1: padding)
-    const int32_t *col;        // SELL column of every slot
-    const uint8_t *colmask;    // Dirichlet columns zeroed (null: none)
-    int64_t npadded;
-    const double *D;           // the level's scalar values (CSR of the scalar pattern)
-    const double *M;           // scalar mass values
-    const int32_t *tperm;      // transpose permutation of the scalar pattern, null: D itself
-    int64_t nnz_s;             // scalar nnz: positions of the second component fold onto it
-    double alpha, gamma;
-};
 
 struct RelinPlan {
     int n_t = 0, m = 0;   // global: time levels, unknown blocks per family
@@ -53,7 +32,6 @@ struct RelinPlan {
     double *d_W = nullptr, *d_phi = nullptr, *d_gphi = nullptr, *d_lam = nullptr,
            *d_glam = nullptr;
     // scalar P2 pattern (one velocity component) and P1 pattern
-    std::vector<int32_t> h_ip2, h_ix2, h_ipp, h_ixp;
     int32_t *d_ip2 = nullptr, *d_ix2 = nullptr, *d_t2 = nullptr, *d_tp = nullptr;
     double *d_K2 = nullptr, *d_M2 = nullptr, *d_Kp = nullptr, *d_Mp = nullptr;
     // contribution lists: CSR over stored positions of flat element-entry indices, ascending
@@ -72,10 +50,7 @@ struct RelinPlan {
     // the iterate: v (v_n x nv), zeta (z_n x nv), p, mu (nl x n1)
     double *d_v = nullptr, *d_zeta = nullptr, *d_p = nullptr, *d_mu = nullptr;
     double *d_red = nullptr;   // reduction scratch + result
-    DevBuf<ComposeJob> d_jobs;   // regrown with the largest job count seen
-    int jobs_cap = 0;
-    // target patterns already proven equal to the plan's: (system, pattern id, space)
-    std::set<std::tuple<const void *, int, int>> checked;
+    Composer compose;   // spaces: velocity (two components of the P2 pattern), pressure
 };
 
 // element matrices of every (element, level of the D window): Ev[(s ne + e) 36 + 6a + b],
@@ -83,12 +58,6 @@ struct RelinPlan {
 void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v);
 // D[l nnz + k] = nu K[k] + sum of the contributions of position k in list order
 void launch_relin_gather(hipStream_t s, const RelinPlan &P);
-// one pattern: D[l nnz + k] = nu K[k] + the contributions of position k (n_t levels of E, per_level
-// doubles each)
-void launch_relin_gather_one(hipStream_t s, const int32_t *cptr, const int32_t *clist,
-                             const double *E, int64_t per_level, const double *K, double nu,
-                             int64_t nnz, int n_t, double *D);
-void launch_relin_compose(hipStream_t s, const ComposeJob *d_jobs, int njobs, int64_t max_padded);
 // velocity and pressure rows of the residual in the outer system's vector layout
 void launch_relin_residual(hipStream_t s, const RelinPlan &P, double *d_r);
 // the solve's right-hand side from the residual: pressure rows times tau, CN time transforms

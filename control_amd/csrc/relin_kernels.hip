@@ -8,13 +8,6 @@
 
 namespace kkt {
 
-static inline int relin_grid(int64_t n, int cap = 256 * 8) {
-    int64_t g = (n + 255) / 256;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 // One thread per (element, level): the velocity element matrix
 //   N[a][b] = sum_q W_eq phi_qa (w_q . grad phi_eqb)
 // and the pressure one  sum_q W_eq lam_qc (w_q . grad lam_ed)  (fem.py convection_v_data /
@@ -95,7 +88,7 @@ __global__ __launch_bounds__(256) void relin_elements_kernel(
 
 // d_v: the v window; slot s of the D window takes its wind from level D_l0 + s of it
 void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v) {
-    hipLaunchKernelGGL(relin_elements_kernel, dim3(relin_grid(P.ne * P.D_n, 256 * 64)), dim3(256),
+    hipLaunchKernelGGL(relin_elements_kernel, dim3(grid_of(P.ne * P.D_n, 256 * 64)), dim3(256),
                        0, s, d_v + (int64_t)(P.D_l0 - P.v_l0) * P.nv, P.ne, P.n2, P.D_n, P.d_V,
                        P.d_W, P.d_phi, P.d_gphi, P.d_lam, P.d_glam, P.d_Ev, P.d_Ep);
 }
@@ -122,10 +115,10 @@ __global__ __launch_bounds__(256) void relin_gather_kernel(
 }
 
 void launch_relin_gather(hipStream_t s, const RelinPlan &P) {
-    hipLaunchKernelGGL(relin_gather_kernel, dim3(relin_grid(P.nnz2 * P.D_n, 256 * 64)), dim3(256),
+    hipLaunchKernelGGL(relin_gather_kernel, dim3(grid_of(P.nnz2 * P.D_n, 256 * 64)), dim3(256),
                        0, s, P.d_cptr2, P.d_clist2, P.d_Ev, P.ne * RELIN_EV, P.d_K2, P.nu, P.nnz2,
                        P.D_n, P.d_D2);
-    hipLaunchKernelGGL(relin_gather_kernel, dim3(relin_grid(P.nnz1 * P.D_n, 256 * 64)), dim3(256),
+    hipLaunchKernelGGL(relin_gather_kernel, dim3(grid_of(P.nnz1 * P.D_n, 256 * 64)), dim3(256),
                        0, s, P.d_cptrp, P.d_clistp, P.d_Ep, P.ne * RELIN_EP, P.d_Kp, P.nu, P.nnz1,
                        P.D_n, P.d_Dp);
 }
@@ -134,7 +127,7 @@ void launch_relin_gather(hipStream_t s, const RelinPlan &P) {
 void launch_relin_gather_one(hipStream_t s, const int32_t *cptr, const int32_t *clist,
                              const double *E, int64_t per_level, const double *K, double nu,
                              int64_t nnz, int n_t, double *D) {
-    hipLaunchKernelGGL(relin_gather_kernel, dim3(relin_grid(nnz * n_t, 256 * 64)), dim3(256), 0, s,
+    hipLaunchKernelGGL(relin_gather_kernel, dim3(grid_of(nnz * n_t, 256 * 64)), dim3(256), 0, s,
                        cptr, clist, E, per_level, K, nu, nnz, n_t, D);
 }
 
@@ -168,7 +161,7 @@ __global__ __launch_bounds__(256) void relin_compose_kernel(const ComposeJob *__
 
 void launch_relin_compose(hipStream_t s, const ComposeJob *d_jobs, int njobs, int64_t max_padded) {
     if (njobs <= 0) return;
-    hipLaunchKernelGGL(relin_compose_kernel, dim3(relin_grid(max_padded, 256), njobs), dim3(256), 0,
+    hipLaunchKernelGGL(relin_compose_kernel, dim3(grid_of(max_padded, 256), njobs), dim3(256), 0,
                        s, d_jobs);
 }
 
@@ -275,9 +268,9 @@ static RelinArgs relin_args(const RelinPlan &P) {
 
 void launch_relin_residual(hipStream_t s, const RelinPlan &P, double *d_r) {
     const RelinArgs A = relin_args(P);
-    hipLaunchKernelGGL(relin_residual_v_kernel, dim3(relin_grid(P.nv, 512), 2 * P.nl), dim3(256), 0,
+    hipLaunchKernelGGL(relin_residual_v_kernel, dim3(grid_of(P.nv, 512), 2 * P.nl), dim3(256), 0,
                        s, A, d_r);
-    hipLaunchKernelGGL(relin_residual_p_kernel, dim3(relin_grid(P.n1, 512), 2 * P.nl), dim3(256), 0,
+    hipLaunchKernelGGL(relin_residual_p_kernel, dim3(grid_of(P.n1, 512), 2 * P.nl), dim3(256), 0,
                        s, A, d_r + 2 * (int64_t)P.nl * P.nv);
 }
 
@@ -328,8 +321,8 @@ void launch_relin_rhs(hipStream_t s, const RelinPlan &P, const double *d_r, doub
     H.h[0][1] = P.d_rhalo + P.nv;
     H.h[1][0] = P.d_rhalo + 2 * P.nv;
     H.h[1][1] = P.d_rhalo + 2 * P.nv + P.n1;
-    hipLaunchKernelGGL(relin_rhs_kernel, dim3(relin_grid(n)), dim3(256), 0, s, d_r, d_b, P.m, P.lo,
-                       P.nl, P.nv, P.n1, (int)P.CN, P.tau, H);
+    hipLaunchKernelGGL(relin_rhs_kernel, dim3(grid_of(n, 256 * 8)), dim3(256), 0, s, d_r, d_b, P.m,
+                       P.lo, P.nl, P.nv, P.n1, (int)P.CN, P.tau, H);
 }
 
 __global__ __launch_bounds__(256) void relin_update_kernel(double *__restrict__ u,
@@ -369,11 +362,11 @@ __global__ __launch_bounds__(256) void relin_zero_bc_kernel(double *__restrict__
 // the kernel's block rows are the rank's own: v and zeta are passed from the slot of level lo
 void launch_relin_update(hipStream_t s, const RelinPlan &P, double *d_u) {
     const int64_t n = 2 * P.nl * (P.nv + P.n1);
-    hipLaunchKernelGGL(relin_update_kernel, dim3(relin_grid(n)), dim3(256), 0, s, d_u,
+    hipLaunchKernelGGL(relin_update_kernel, dim3(grid_of(n, 256 * 8)), dim3(256), 0, s, d_u,
                        P.d_v + (int64_t)(P.lo - P.v_l0) * P.nv,
                        P.d_zeta + (int64_t)(P.lo - P.z_l0) * P.nv, P.d_mu, P.d_p, P.nl, P.nv, P.n1,
                        (int)P.CN);
-    hipLaunchKernelGGL(relin_zero_bc_kernel, dim3(relin_grid(P.z_n * P.nv)), dim3(256), 0, s,
+    hipLaunchKernelGGL(relin_zero_bc_kernel, dim3(grid_of(P.z_n * P.nv, 256 * 8)), dim3(256), 0, s,
                        P.d_zeta, P.d_bc, P.z_n * P.nv, P.nv);
 }
 

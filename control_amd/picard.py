@@ -431,45 +431,22 @@ def _device_non_linear_solve(pb, ls, v, zeta, p, mu, max_non_linear_iter, rtol, 
     of the convection blocks, one residual (the host reads its norm), one linearised solve and
     one update, all on the device -- on a time-sharded solver every rank on its own levels, the
     norm the same on all of them."""
-    import ctypes as C
-    th, n_t = pb.disc, pb.n_t
+    from .relinearise import device_picard_loop, device_vectors
     fresh = ls.outer is None
     if fresh:                # the first call builds the systems (host blocks or patterns)
         ls.setup(v, zeta, p, mu)
     dev = ls.device_plan()
     dev.set_state(v, zeta, p, mu)
-    lib, outer = ls.outer._lib, ls.outer
-    d_b, d_u = C.c_void_p(), C.c_void_p()
-    outer._ck(lib.kkt_vec_alloc(outer.handle, C.byref(d_b)))
-    try:
-        outer._ck(lib.kkt_vec_alloc(outer.handle, C.byref(d_u)))   # zeroed
+    with device_vectors(ls.outer) as (d_b, d_u):
         dev.assemble()
         norm_0 = dev.residual(d_b, rhs=True)
-        norm_k = norm_0
-        norms, lin_its = [norm_0], []
         if print_error_non_linear:
             print(f"Initial non-linear residual: {norm_0:.16e}")
-        k = 0
-        while norm_k > rtol * norm_0 and norm_k > atol:
-            if not fresh:
-                ls.device_relinearise()
-            fresh = False
-            lin_its.append(ls.device_solve(d_b, d_u))
-            dev.update(d_u)
-            dev.assemble()
-            norm_k = dev.residual(d_b, rhs=True)
-            norms.append(norm_k)
-            k += 1
-            if print_error_non_linear:
-                print(f"Non-linear solver: iteration {k:d}, non-linear residual norm "
-                      f"{norm_k:.16e}")
-            if k + 1 > max_non_linear_iter:
-                break
+        norms, lin_its = device_picard_loop(dev, d_b, d_u, norm_0, ls.device_solve,
+                                            ls.device_relinearise, fresh, rtol, atol,
+                                            max_non_linear_iter, print_error_non_linear)
         v, zeta, p, mu = dev.get_state()
-    finally:
-        lib.kkt_vec_free(outer.handle, d_b)
-        if d_u:
-            lib.kkt_vec_free(outer.handle, d_u)
+    norm_k = norms[-1]
     return dict(v=v, zeta=zeta, p=p, mu=mu, norms=norms, linear_iterations=lin_its,
                 converged=bool(norm_k <= rtol * norm_0 or norm_k <= atol))
 

@@ -16,7 +16,8 @@ import numpy as np
 
 from . import _lib
 from .fem import ReactionTerm
-from .relinearise import _recipe_array, contribution_lists, transpose_permutation
+from .relinearise import (_marshal, _recipe_array, contribution_lists, device_picard_loop,
+                          device_vectors, transpose_permutation)
 
 __all__ = ["ReactionPlan", "DeviceReaction", "device_non_linear_solve"]
 
@@ -85,17 +86,7 @@ class ReactionPlan:
     def descriptor(self):
         """``kkt_reaction_desc`` over this plan's arrays (valid while ``keep`` lives)."""
         term, disc = self.term, self.ctl._disc
-        keep = []
-
-        def i32(a):
-            a = np.ascontiguousarray(a, dtype=np.int32)
-            keep.append(a)
-            return a.ctypes.data_as(_lib.c_i32p)
-
-        def f64(a):
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            keep.append(a)
-            return a.ctypes.data_as(_lib.c_f64p)
+        i32, f64, keep = _marshal()
         c = (C.c_double * 5)(*self.coefficients)
         d = _lib.ReactionDesc(
             n_t=self.n_t, cn=int(self.CN), nq=term.W.shape[1], ne=len(term.cells),
@@ -236,42 +227,24 @@ def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bou
         solver_parameters = {"linear_solver": "gmres", "gmres_restart": 10,
                              "maximum_iterations": 50, "relative_tolerance": 1.0e-6,
                              "absolute_tolerance": 0.0, "monitor_convergence": False}
-    lib = system._lib
-    d_b, d_u = C.c_void_p(), C.c_void_p()
-    system._ck(lib.kkt_vec_alloc(system.handle, C.byref(d_b)))
-    lin_its = []
-    try:
-        system._ck(lib.kkt_vec_alloc(system.handle, C.byref(d_u)))   # zeroed
-        norm_0 = dev.residual(d_b, rhs=True)
-        norm_k, k, norms = norm_0, 0, [norm_0]
-        fresh = True
-        while (norm_k > relative_non_linear_tol * norm_0
-               and norm_k > absolute_non_linear_tol):
-            if not fresh:
-                dev.relinearise()
-            fresh = False
-            ksp = system.solve_device(d_b, d_u, solver_parameters=solver_parameters, pc_fn=pc_fn)
-            lin_its.append(ksp.getIterationNumber())
-            dev.update(d_u)
-            if lift:     # the starting iterate did not carry the boundary values: once
-                v_new, zeta_new = dev.get_state()
-                v_new[:, nodes] = v_fixed[:, nodes]
-                dev.set_state(v_new, zeta_new)
-                lift = False
-            dev.assemble()
-            norm_k = dev.residual(d_b, rhs=True)
-            norms.append(norm_k)
-            k += 1
-            if print_error_non_linear:
-                print(f"Non-linear solver: iteration {k:d}, non-linear residual norm "
-                      f"{norm_k:.16e}")
-            if k + 1 > max_non_linear_iter:
-                break
+
+    def solve(d_b, d_u):
+        ksp = system.solve_device(d_b, d_u, solver_parameters=solver_parameters, pc_fn=pc_fn)
+        return ksp.getIterationNumber()
+
+    def lift_boundary():     # the starting iterate did not carry the boundary values: once
         v_new, zeta_new = dev.get_state()
+        v_new[:, nodes] = v_fixed[:, nodes]
+        dev.set_state(v_new, zeta_new)
+    try:
+        with device_vectors(system) as (d_b, d_u):
+            norm_0 = dev.residual(d_b, rhs=True)
+            norms, lin_its = device_picard_loop(
+                dev, d_b, d_u, norm_0, solve, dev.relinearise, True, relative_non_linear_tol,
+                absolute_non_linear_tol, max_non_linear_iter, print_error_non_linear,
+                after_first_update=lift_boundary if lift else None)
+            v_new, zeta_new = dev.get_state()
     finally:
-        lib.kkt_vec_free(system.handle, d_b)
-        if d_u:
-            lib.kkt_vec_free(system.handle, d_u)
         system.close()
     ctl._v, ctl._zeta = v_new, zeta_new
     ctl.non_linear_info = {"linear_iterations": lin_its}

@@ -9,6 +9,7 @@ in which ``np.bincount`` sums them in ``fem.TaylorHoodDiscretisation.convection_
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -18,7 +19,7 @@ from . import _lib
 from .fem import _row_positions
 
 __all__ = ["contribution_lists", "gather", "transpose_permutation", "RelinearisationPlan",
-           "DeviceRelinearisation"]
+           "DeviceRelinearisation", "device_vectors", "device_picard_loop"]
 
 
 def contribution_lists(conn, pattern):
@@ -60,6 +61,18 @@ def transpose_permutation(A):
             and np.array_equal(T.indices, A.indices)):
         raise ValueError("the pattern is not structurally symmetric")
     return (T.data.astype(np.int64) - 1).astype(np.int32)
+
+
+def _marshal():
+    """``(i32, f64, keep)``: pointers for a descriptor, into contiguous arrays that ``keep``
+    holds alive."""
+    keep = []
+
+    def pointer(a, dtype, ctype):
+        keep.append(np.ascontiguousarray(a, dtype=dtype))
+        return keep[-1].ctypes.data_as(ctype)
+    return (lambda a: pointer(a, np.int32, _lib.c_i32p),
+            lambda a: pointer(a, np.float64, _lib.c_f64p), keep)
 
 
 class RelinearisationPlan:
@@ -113,17 +126,7 @@ class RelinearisationPlan:
     def descriptor(self):
         """``kkt_relin_desc`` over this plan's arrays (valid while the plan lives)."""
         pb, th, t = self.pb, self.pb.disc, self.tables
-        keep = []
-
-        def i32(a):
-            a = np.ascontiguousarray(a, dtype=np.int32)
-            keep.append(a)
-            return a.ctypes.data_as(_lib.c_i32p)
-
-        def f64(a):
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            keep.append(a)
-            return a.ctypes.data_as(_lib.c_f64p)
+        i32, f64, keep = _marshal()
         d = _lib.RelinDesc(
             n_t=pb.n_t, cn=int(bool(pb.CN)), nq=t["W"].shape[1], ne=len(self.V), n2=self.n2,
             n1=th.n_p, nu=float(pb.nu), tau=float(pb.tau), beta=float(pb.beta), V=i32(self.V),
@@ -239,3 +242,47 @@ class DeviceRelinearisation:
             self.outer.handle, ("Ev", "Ep", "D2", "Dp", "v", "zeta").index(which),
             out.ctypes.data_as(_lib.c_f64p), out.size))
         return out
+
+
+@contextlib.contextmanager
+def device_vectors(system):
+    """``(d_b, d_u)``: right-hand side and (zeroed) update of a device loop on ``system``."""
+    lib = system._lib
+    d_b, d_u = C.c_void_p(), C.c_void_p()
+    system._ck(lib.kkt_vec_alloc(system.handle, C.byref(d_b)))
+    try:
+        system._ck(lib.kkt_vec_alloc(system.handle, C.byref(d_u)))
+        yield d_b, d_u
+    finally:
+        lib.kkt_vec_free(system.handle, d_b)
+        if d_u:
+            lib.kkt_vec_free(system.handle, d_u)
+
+
+def device_picard_loop(dev, d_b, d_u, norm_0, solve, relinearise, fresh, rtol, atol, max_iter,
+                       verbose, after_first_update=None):
+    """The device Picard iterations from the assembled iterate of ``dev`` with right-hand side
+    ``d_b`` and residual norm ``norm_0``: re-linearise (unless the blocks are ``fresh`` from the
+    build), ``solve(d_b, d_u)`` (it returns the linear iterations), update, assemble, residual,
+    until the host loops' stopping rule holds.  ``after_first_update()`` runs once, before the
+    first re-assembly.  Returns the norms (``norm_0`` first) and the linear iteration counts."""
+    norm_k, k = norm_0, 0
+    norms, lin_its = [norm_0], []
+    while norm_k > rtol * norm_0 and norm_k > atol:
+        if not fresh:
+            relinearise()
+        fresh = False
+        lin_its.append(solve(d_b, d_u))
+        dev.update(d_u)
+        if k == 0 and after_first_update is not None:
+            after_first_update()
+        dev.assemble()
+        norm_k = dev.residual(d_b, rhs=True)
+        norms.append(norm_k)
+        k += 1
+        if verbose:
+            print(f"Non-linear solver: iteration {k:d}, non-linear residual norm "
+                  f"{norm_k:.16e}")
+        if k + 1 > max_iter:
+            break
+    return norms, lin_its

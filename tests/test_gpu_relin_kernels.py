@@ -21,7 +21,7 @@ import scipy.sparse as sp
 import common
 import relin_ref
 import structures
-from control_amd import blocks, fem, picard, relinearise
+from control_amd import _lib, blocks, fem, picard, relinearise
 from control_amd.multiblock import (ConstantNullspace, DirichletBCNullspace, MultiBlockSystem,
                                     PatternOnly)
 
@@ -32,7 +32,7 @@ ELEMENT_BAR = 32          # tests/test_relin_ref.py derives it
 MESHES = {"square": (2, 2, 2.0, 2.0), "anisotropic": (3, 2, 3.0, 1.0)}
 WINDS = ("normal", "decades", "zero_level", "zero_component")
 BETA = 2.0 ** -6
-# relin_grid(n, cap) in relin_kernels.hip: min(ceil(n / 256), cap) workgroups of 256 threads
+# grid_of(n, cap) in compose.hpp: min(ceil(n / 256), cap) workgroups of 256 threads
 RHS_UPDATE_CAP = 2048 * 256      # launch_relin_rhs / launch_relin_update (the default cap)
 COMPOSE_CAP = 256 * 256          # launch_relin_compose, over the padded slots of a block
 RESIDUAL_CAP = 512 * 256         # launch_relin_residual, over the rows of a row block
@@ -547,3 +547,43 @@ def test_tails_of_gather_and_residual():
     print(f"n = 128 rows past the cap: worst error / bound = {worst[0]:.3f} (device), "
           f"{worst[1]:.3f} (host)")
     assert worst[0] <= 1.0 and worst[1] <= 1.0
+
+
+# -------------------------------------------------------------------------------- refusals
+def test_errors():
+    """What ``kkt_relinearise_device`` refuses, and that a refused call writes nothing."""
+    pb = _problem(MESHES["square"], 3, False)
+    good = (0, 0, 0, 0, pb.tau, False, 1.0)
+    # composing before any assembly; the block stays unset
+    outer, dev = _bare(pb)
+    with pytest.raises(_lib.KktError) as err:
+        dev.relinearise(outer, "outer", recipes=[good])
+    assert err.value.code == -3
+    with pytest.raises(_lib.KktError) as err:
+        outer.mult(np.zeros(outer.local_size))
+    assert err.value.code == -3
+
+    ls, dev = _full(pb, _state(pb, np.random.default_rng(common.SEED + 8)))
+    full = blocks.instationary_build_recipes(pb.tau, pb.beta, pb.n_t, pb.CN)
+    lib, plan_handle = ls.outer._lib, ls.outer.handle
+    for name, system in (("outer", ls.outer), ("inner", ls.inner), ("commutator", ls.comm)):
+        space = 1 if name == "commutator" else 0
+        q, i, j, level, alpha, transpose, gamma = full[name][0]
+        before, _ = system.block_values(q, i, j)
+        assert np.any(before != 0.0)
+
+        def refused(recipe, as_space=space):
+            arr = relinearise._recipe_array([recipe], as_space)
+            code = lib.kkt_relinearise_device(system.handle, plan_handle, None, 1, arr)
+            message = lib.kkt_last_error(system.handle)
+            assert np.array_equal(system.block_values(q, i, j)[0], before)   # nothing written
+            return code, message
+
+        code, message = refused((q, i, 99, level, 0.7, transpose, 0.3))
+        assert code == -1 and message.startswith(b"kkt_relinearise_device: recipe 0: no such block")
+        assert refused((q, i, j, level, 0.7, transpose, 0.3), as_space=2)[0] == -1
+        assert refused((q, i, j, pb.n_t, 0.7, transpose, 0.3))[0] == -1
+        assert refused((q, i, j, -1, 0.7, transpose, 0.3))[0] == -1
+        # a block of the other space: its pattern is not the plan's pattern of the space asked for
+        code, message = refused((q, i, j, level, 0.7, transpose, 0.3), as_space=1 - space)
+        assert code == -1 and (b"velocity pattern", b"pressure pattern")[1 - space] in message
