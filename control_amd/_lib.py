@@ -217,6 +217,8 @@ SIGNATURES = {
     "kkt_debug_coarse_matrices": (C.c_int, [C.c_void_p, c_f64p, C.c_int64]),
     "kkt_debug_coarse_inverses": (C.c_int, [C.c_void_p, c_f64p, C.c_int64]),
     "kkt_debug_dense_inverse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p]),
+    "kkt_debug_coarse_correction": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, c_f64p, c_f64p,
+                                              c_f64p, c_f64p, c_f64p, c_f64p, c_i32p]),
     "kkt_debug_krylov_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, c_f64p, c_f64p,
                                       c_f64p, C.c_double, C.c_double, c_f64p, c_f64p, c_f64p]),
     "kkt_debug_set_steplock": (C.c_int, [C.c_void_p, C.POINTER(StepLock)]),

@@ -530,6 +530,13 @@ int kkt_debug_dense_inverse(kkt_handle h, int n, int nmat, const double *a, doub
     });
 }
 
+int kkt_debug_coarse_correction(kkt_handle h, int batched, int nb, int64_t vstride, const double *r,
+                                const double *x_in, const double *einv, double *rc, double *ec,
+                                double *x_out, int32_t *shape) {
+    KKT_TRY(h, kkt::coarse_correction_host(S, batched, nb, vstride, r, x_in, einv, rc, ec, x_out,
+                                           shape));
+}
+
 int kkt_debug_krylov_op(kkt_handle h, int op, int64_t n, int nv, const double *w, const double *V,
                         const double *coef, double a, double b, double *w_out,
                         double *scalars_out, double *arena_out) {

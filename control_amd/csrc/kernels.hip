@@ -2795,7 +2795,8 @@ void launch_galerkin_batched(hipStream_t s, const CoarseDev &c, const GalerkinDe
 //    columns, copies the pivot rows U = M[c0 .. c0+nb-1, j], and forms
 //    M[r, j] = (r outside the panel ? M[r, j] : 0) + sum_l W[r, l] U[l, j], a rank-nb update.
 // Columns of A left of the panel's end are never read again and are not updated.  Singularity:
-// |pivot| < 1e-13 max|diag A| (or not finite) records the smallest such column in bad[b].
+// |pivot| < 1e-13 max|diag A| (or not finite), or a non-finite entry in a panel column as the
+// panel kernel loads it, records the smallest such column in bad[b].
 constexpr int GJ_NB = 32;
 constexpr int GJ_PANEL_THREADS = 1024;
 struct GjArgs {
@@ -2838,10 +2839,14 @@ __global__ __launch_bounds__(GJ_PANEL_THREADS) void gj_panel_kernel(GjArgs g, in
     const int b = blockIdx.x, n = g.n, nb = min(GJ_NB, n - c0), t = threadIdx.x;
     const double *a = g.a + (size_t)b * n * n;
     double *Y = g.Y + (size_t)b * n * GJ_NB, *Z = g.Z + (size_t)b * n * GJ_NB;
+    // a non-finite entry is an offending column of its own: the pivot search skips a NaN, and
+    // where the multipliers under a pivot are zero the entry never reaches one (sparse E)
     for (int r = t; r < n; r += NT)
         for (int l = 0; l < nb; ++l) {
-            Y[(size_t)l * n + r] = a[(size_t)r * n + c0 + l];
+            const double v = a[(size_t)r * n + c0 + l];
+            Y[(size_t)l * n + r] = v;
             Z[(size_t)l * n + r] = r == c0 + l ? 1.0 : 0.0;
+            if (!isfinite(v)) atomicMin(&g.bad[b], c0 + l);
         }
     const double tol = 1e-13 * g.dmax[b];
     __syncthreads();
@@ -2890,7 +2895,7 @@ __global__ __launch_bounds__(GJ_PANEL_THREADS) void gj_panel_kernel(GjArgs g, in
         }
         if (t == 0) {
             g.piv[b * GJ_NB + cc] = p;
-            if (sing && g.bad[b] > c) g.bad[b] = c;
+            if (sing) atomicMin(&g.bad[b], c);
         }
         __syncthreads();
         for (int r = t; r < n; r += NT) {

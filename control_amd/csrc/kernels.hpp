@@ -393,7 +393,8 @@ void launch_galerkin_batched(hipStream_t s, const CoarseDev &c, const GalerkinDe
                              const double *const *d_vals, double *E, int nmat);
 // inv[b] = a_b^-1 for nmat n x n row-major matrices stored contiguously at a (destroyed): blocked
 // Gauss-Jordan with partial pivoting, 1 + 2 ceil(n / 32) launches for the whole batch (returned).
-// d_bad[b] = first column whose pivot is below 1e-13 max|diag a_b| (n: none).  scratch: at least
+// d_bad[b] = first column whose pivot is below 1e-13 max|diag a_b| or which holds a non-finite entry
+// when its panel is loaded (n: none).  scratch: at least
 // dense_inverse_batched_scratch(n, nmat) bytes.
 size_t dense_inverse_batched_scratch(int n, int nmat);
 int launch_dense_inverse_batched(hipStream_t s, double *a, double *const *d_inv, int n, int nmat,

@@ -1505,6 +1505,50 @@ void dense_inverse_host(System &S, int n, int nmat, const double *a, double *inv
     HIPCHK(hipStreamSynchronize(st));
 }
 
+void coarse_correction_host(System &S, int batched, int nb, int64_t vstride, const double *r,
+                            const double *x_in, const double *einv, double *rc, double *ec,
+                            double *x_out, int32_t *shape) {
+    CoarseDev c;
+    GalerkinDev g;
+    int64_t n = 0;
+    if (!S.pc || !S.pc->coarse_space(&c, &g, &n))
+        fail(KKT_ERR_STATE,
+             "kkt_debug_coarse_correction: no two-grid preconditioner built on this handle");
+    hipStream_t st = S.stream;
+    const int nc = c.nc;
+    if (shape) {
+        std::vector<int32_t> pt_ip((size_t)nc + 1);
+        HIPCHK(hipMemcpyAsync(pt_ip.data(), c.pt_ip, pt_ip.size() * sizeof(int32_t),
+                              hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        int32_t longest = 0;
+        for (int j = 0; j < nc; ++j) longest = std::max(longest, pt_ip[j + 1] - pt_ip[j]);
+        const int32_t v[KKT_COARSE_SHAPE_INTS] = {(int32_t)n, nc, g.R, g.uniform_w, g.pos != nullptr,
+                                                  g.mask != nullptr, g.block_n, longest};
+        std::copy(v, v + KKT_COARSE_SHAPE_INTS, shape);
+    }
+    if (nb == 0) return;
+    if (nb < 1 || (!batched && nb != 1) || vstride < n || !r || !einv || !rc || !ec || !x_out)
+        fail(KKT_ERR_ARG, "bad coarse correction arguments");
+    const size_t len = (size_t)nb * vstride;
+    DevPool tmp;
+    const double *d_r = tmp.upload(r, len);
+    const double *d_xin = x_in ? tmp.upload(x_in, len) : nullptr;
+    double *d_xout = tmp.upload(x_out, len);
+    const double *d_einv = tmp.upload(einv, (size_t)nc * nc);
+    c.rc = tmp.alloc<double>((size_t)nb * nc);      // its own scratch, nb vectors wide
+    c.ec = tmp.alloc<double>((size_t)nb * nc);
+    if (batched)
+        launch_coarse_correction_batched(st, c, d_einv, d_r, d_xin, d_xout, n, nb, vstride);
+    else
+        launch_coarse_correction(st, c, d_einv, d_r, d_xin, d_xout, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rc, c.rc, (size_t)nb * nc * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ec, c.ec, (size_t)nb * nc * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(x_out, d_xout, len * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+}
+
 double *SchurPC::coarse_inverse(const double *vals) {
     const int nc = coarse_.nc;
     double *d_inv = values_mem_.alloc<double>((size_t)nc * nc);
@@ -1754,6 +1798,13 @@ void SchurPC::note_solve(int sweep, int level, const Mat &m) {
 }
 
 void SchurPC::solve_records(std::vector<double> &out) const { out = solve_recs_; }
+bool SchurPC::coarse_space(CoarseDev *c, GalerkinDev *g, int64_t *n) const {
+    if (coarse_.nc <= 0) return false;
+    *c = coarse_;
+    *g = galerkin_;
+    *n = nx_;
+    return true;
+}
 
 void SchurPC::matrix_records(std::vector<double> &out) const {
     out.clear();

@@ -82,6 +82,10 @@ void coarse_setup(System &S, int pat, const CoarseDev &c, const GalerkinDev &g,
 
 // inv[b] = a_b^-1 for nmat host matrices through the batched device inverse (test hook)
 void dense_inverse_host(System &S, int n, int nmat, const double *a, double *inv, int *bad);
+// kkt_debug_coarse_correction (include/kkt.h)
+void coarse_correction_host(System &S, int batched, int nb, int64_t vstride, const double *r,
+                            const double *x_in, const double *einv, double *rc, double *ec,
+                            double *x_out, int32_t *shape);
 
 // A device-resident pc_fn: reads the nullspace-corrected right-hand side from in(), leaves
 // pc_fn(b) in out() (both n_local doubles, fixed buffers).
@@ -109,6 +113,9 @@ class PcBase {
     // KKT_PC_MATRIX_VALS per distinct sub-solve matrix (include/kkt.h)
     virtual void solve_records(std::vector<double> &) const {}
     virtual void matrix_records(std::vector<double> &) const {}
+    // kkt_debug_coarse_correction: the coarse space of the two-grid sub-solves, the Galerkin
+    // launch constants of its set-up and the rows of P (false: built without a coarse space)
+    virtual bool coarse_space(CoarseDev *, GalerkinDev *, int64_t *) const { return false; }
     // measurement: time the persistent programs of the next run() with events
     virtual void time_programs(float *ms, int *launches, int64_t *phases) {
         *ms = 0.f;
@@ -133,6 +140,7 @@ class SchurPC : public PcBase {
     void debug_read(unsigned long long *out, int n) override;   // diagnostic builds (KKT_STAMPS)
     void plain_forms(std::vector<int32_t> &out) const override;
     void solve_records(std::vector<double> &out) const override;
+    bool coarse_space(CoarseDev *c, GalerkinDev *g, int64_t *n) const override;
     void matrix_records(std::vector<double> &out) const override;
     void time_programs(float *ms, int *launches, int64_t *phases) override;
     int bc_set() const { return bc_set_; }
@@ -369,6 +377,7 @@ class StokesPC : public PcBase {
     void check() override;
     bool timed_out(std::string *why) override { return inner_.pc && inner_.pc->timed_out(why); }
     void solve_records(std::vector<double> &out) const override;
+    bool coarse_space(CoarseDev *c, GalerkinDev *g, int64_t *n) const override;
     bool fallback_plain() override { return inner_.pc && inner_.pc->fallback_plain(); }
     const unsigned *err_word() const override { return inner_.pc ? inner_.pc->err_word() : nullptr; }
 
@@ -408,6 +417,7 @@ class StokesPC : public PcBase {
     void run_chain(Chain &c, const std::vector<ChainStep> &steps);
     // two-grid K_p solve
     CoarseDev kp_coarse_;
+    GalerkinDev kp_galerkin_{};
     double *kp_einv_ = nullptr, *kp_r_ = nullptr, *kp_x0_ = nullptr;
     int kp_cycles_ = 0;
     void build_kp_coarse(const kkt_pc_stokes_desc &d);

@@ -173,6 +173,7 @@ void StokesPC::build_kp_coarse(const kkt_pc_stokes_desc &d) {
     g.mask = nullptr;
     g.R = P.R;
     g.uniform_w = P.uniform_w;
+    kp_galerkin_ = g;
     kp_einv_ = mem_.alloc<double>((size_t)nc * nc);
     coarse_setup(S_, Kp_.pat, c, g, {Kp_.vals}, {kp_einv_}, true, "K_p solve");
 }
@@ -386,6 +387,13 @@ StokesPC::StokesPC(System &outer, System &inner, System &commutator, const kkt_p
     HIPCHK(hipStreamSynchronize(S_.stream));
 }
 
+bool StokesPC::coarse_space(CoarseDev *c, GalerkinDev *g, int64_t *n) const {
+    if (kp_coarse_.nc <= 0) return false;
+    *c = kp_coarse_;
+    *g = kp_galerkin_;
+    *n = np_;
+    return true;
+}
 void StokesPC::solve_records(std::vector<double> &out) const {
     out = {(double)KKT_PC_SWEEP_KP, -1.0, -1.0, 0.0, kp_emin_, kp_emax_, 0.0, (double)kp_its_,
            (double)kp_est_};

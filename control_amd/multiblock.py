@@ -484,7 +484,8 @@ class MultiBlockSystem:
 
     def debug_dense_inverse(self, A):
         """``kkt_debug_dense_inverse``: inverses of a batch ``A`` (nmat, n, n) by the device's
-        blocked Gauss-Jordan, and per matrix the first column with a too small pivot (n: none)."""
+        blocked Gauss-Jordan, and per matrix the first column with a too small pivot or a non-finite
+        entry (n: none)."""
         A = np.ascontiguousarray(A, dtype=np.float64)
         nmat, n, _ = A.shape
         inv = np.empty_like(A)
@@ -493,6 +494,48 @@ class MultiBlockSystem:
                                                    inv.ctypes.data_as(_lib.c_f64p),
                                                    bad.ctypes.data_as(_lib.c_i32p)))
         return inv, bad
+
+    _COARSE_SHAPE = ("n", "n_coarse", "R", "uniform_w", "sorted", "masked", "block_n", "pt_longest")
+
+    def coarse_shape(self):
+        """The launch constants ``kkt_debug_coarse_correction`` reports for the coarse space of the
+        two-grid preconditioner last built on this handle: rows ``n`` of P, ``n_coarse``, and of
+        its Galerkin set-up ``R``, ``uniform_w`` (-1: ragged), ``sorted``, ``masked``, ``block_n``
+        (0: one block) and ``pt_longest``, the longest row of P^T."""
+        shape = np.zeros(len(self._COARSE_SHAPE), dtype=np.int32)
+        self._ck(self._lib.kkt_debug_coarse_correction(self._h, 0, 0, 0, None, None, None, None, None,
+                                                       None, shape.ctypes.data_as(_lib.c_i32p)))
+        return dict(zip(self._COARSE_SHAPE, map(int, shape)))
+
+    def debug_coarse_correction(self, r, einv, x_in=None, x_out=None, nb=1, vstride=None,
+                                batched=False):
+        """``kkt_debug_coarse_correction``: ``x_out = x_in + P einv P^T r`` by the plain correction
+        kernels on this handle's coarse space, for ``nb`` vectors ``vstride`` apart (``batched``:
+        the batched launches; else ``nb`` = 1).  ``x_out``: the prior contents of the output
+        (default zeros).  Returns ``(rc, ec, x_out)``, ``rc`` and ``ec`` of shape ``(nb, n_coarse)``."""
+        sh = self.coarse_shape()
+        vstride = sh["n"] if vstride is None else int(vstride)
+        ln = nb * vstride
+
+        def vec(v):
+            v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+            if v.size != ln:
+                raise ValueError(f"vectors must hold nb * vstride = {ln} doubles")
+            return v
+        r = vec(r)
+        x_in = None if x_in is None else vec(x_in)
+        out = np.zeros(ln) if x_out is None else vec(x_out).copy()
+        einv = np.ascontiguousarray(einv, dtype=np.float64)
+        if einv.shape != (sh["n_coarse"], sh["n_coarse"]):
+            raise ValueError("einv must be n_coarse x n_coarse")
+        rc = np.empty((nb, sh["n_coarse"]))
+        ec = np.empty((nb, sh["n_coarse"]))
+        self._ck(self._lib.kkt_debug_coarse_correction(
+            self._h, int(bool(batched)), nb, vstride, r.ctypes.data_as(_lib.c_f64p),
+            None if x_in is None else x_in.ctypes.data_as(_lib.c_f64p),
+            einv.ctypes.data_as(_lib.c_f64p), rc.ctypes.data_as(_lib.c_f64p),
+            ec.ctypes.data_as(_lib.c_f64p), out.ctypes.data_as(_lib.c_f64p), None))
+        return rc, ec, out
 
     def update_block_values(self, quadrant, i, j, A):
         """New values on a stored block's structure (Picard re-linearisation)."""

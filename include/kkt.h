@@ -594,12 +594,31 @@ int kkt_coarse_setup_stats(kkt_handle h, kkt_coarse_stats *out);
  * matrices P^T A P (before any deflation) on the host: kkt_debug_coarse_matrices copies them,
  * matrices x n_coarse^2 doubles row-major in set-up order (cap: doubles available at out).
  * kkt_debug_dense_inverse inverts nmat host matrices (n x n, row-major, contiguous) with the
- * batched device inverse; bad[b] = first column with a pivot below 1e-13 max|diag| (n: none). */
+ * batched device inverse; bad[b] = first column with a pivot below 1e-13 max|diag| or with a
+ * non-finite entry (n: none). */
 int kkt_debug_coarse_matrices(kkt_handle h, double *out, int64_t cap);
 /* ... and the inverses of the same set-up, in the same layout (the rows as the solves read them:
  * full n_coarse columns, zeros outside the diagonal blocks on the block path) */
 int kkt_debug_coarse_inverses(kkt_handle h, double *out, int64_t cap);
 int kkt_debug_dense_inverse(kkt_handle h, int n, int nmat, const double *a, double *inv, int *bad);
+/* Test hook of the plain coarse correction x_out = x_in + P E^-1 P^T r, on the coarse space of the
+ * two-grid preconditioner last built on this handle (kkt_set_pc_schur with a coarse space; with
+ * kkt_set_pc_stokes the space of the K_p solve), through the launchers the solves call: the
+ * one-vector launches (batched = 0, nb = 1) or the batched ones (batched = 1: nb vectors vstride
+ * doubles apart, vstride >= the rows n of P).  All arrays are host memory.  r and x_in (NULL: none)
+ * hold nb * vstride doubles; einv is the n_c x n_c row-major matrix to apply -- any matrix, not
+ * only an inverse the handle formed.  x_out (nb * vstride doubles) is read and written: entries the
+ * kernels do not write come back as given.  The hook owns its coarse scratch and returns it: rc =
+ * P^T r and ec = einv rc, nb * n_c doubles each.  shape (NULL, or KKT_COARSE_SHAPE_INTS values)
+ * receives the launch constants: rows n of P, n_c, then of the Galerkin set-up on that space R,
+ * uniform_w (-1: ragged slices), row-sorted storage (0 | 1), masked rows (0 | 1), block_n of the
+ * structure of P^T A P (0: one block), and the longest row of P^T.  nb = 0 fills shape and
+ * launches nothing.  KKT_ERR_STATE without such a preconditioner; KKT_ERR_ARG for nb < 0, nb != 1
+ * with batched = 0, vstride < n or a null array. */
+#define KKT_COARSE_SHAPE_INTS 8
+int kkt_debug_coarse_correction(kkt_handle h, int batched, int nb, int64_t vstride, const double *r,
+                                const double *x_in, const double *einv, double *rc, double *ec,
+                                double *x_out, int32_t *shape);
 
 /* Test hook of the Krylov vector kernels: one operation of the GMRES / MINRES loops on host data,
  * through the members and launchers the solves call.  Independent of the handle's layout: works
