@@ -136,6 +136,29 @@ KRYLOV_OPS = {name: k for k, name in enumerate(
      "maxpy"))}
 KRYLOV_PAD = -6.02214076e23
 
+# kkt_debug_block_op: the operations (KKT_BLOCK_*), the guard elements around every written array
+# (KKT_BLOCK_GUARD, set to KRYLOV_PAD; the flag's to BLOCK_FLAG_PAD) and the argument record
+BLOCK_OPS = {name: k for k, name in enumerate(
+    ("time_transform", "time_transform_mask", "mask_blocks", "const_correct", "const_center",
+     "csr_to_sell", "mask_columns", "vals_axpy", "vals_differ", "vals_sym_skew", "extract_dinv"))}
+BLOCK_GUARD = 64
+BLOCK_FLAG_PAD = 0xA5A5A5A5
+c_u8p = C.POINTER(C.c_uint8)
+c_i64p = C.POINTER(C.c_int64)
+c_u32p = C.POINTER(C.c_uint32)
+
+
+class BlockOp(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ("op", "kind", "in_place", "n")]
+                + [("nx", C.c_int64), ("len", C.c_int64), ("c", C.c_double)]
+                + [(n, c_f64p) for n in ("x", "x2", "lo_halo", "hi_halo")]
+                + [("mask", c_u8p), ("has_mask", c_i32p), ("alpha", c_f64p),
+                   ("job_off", c_i64p), ("job_nx", c_i64p)]
+                + [(n, c_f64p) for n in ("job_c1", "job_c2_one", "job_c2_alpha")]
+                + [(n, c_i32p) for n in ("idx", "idx2", "idx3")]
+                + [("y", c_f64p), ("y2", c_f64p), ("flag", c_u32p), ("inputs_changed", C.c_int32)])
+
+
 PC_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, c_f64p, c_f64p, c_f64p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int, C.c_int)
 SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int64, C.c_int,
@@ -221,6 +244,7 @@ SIGNATURES = {
                                               c_f64p, c_f64p, c_f64p, c_f64p, c_i32p]),
     "kkt_debug_krylov_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, c_f64p, c_f64p,
                                       c_f64p, C.c_double, C.c_double, c_f64p, c_f64p, c_f64p]),
+    "kkt_debug_block_op": (C.c_int, [C.c_void_p, C.POINTER(BlockOp)]),
     "kkt_debug_set_steplock": (C.c_int, [C.c_void_p, C.POINTER(StepLock)]),
     "kkt_debug_apply_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "kkt_debug_pc_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),

@@ -543,6 +543,10 @@ int kkt_debug_krylov_op(kkt_handle h, int op, int64_t n, int nv, const double *w
     KKT_TRY(h, S.debug_krylov_op(op, n, nv, w, V, coef, a, b, w_out, scalars_out, arena_out));
 }
 
+int kkt_debug_block_op(kkt_handle h, kkt_block_op *op) {
+    KKT_TRY(h, kkt::debug_block_op(S, op));
+}
+
 int kkt_debug_set_steplock(kkt_handle h, const kkt_steplock *lock) {
     KKT_TRY(h, {
         if (!lock) {

@@ -2006,11 +2006,17 @@ void launch_mask_columns(hipStream_t s, double *sell_vals, const int32_t *col,
                        sell_vals, col, colmask, n_padded);
 }
 
+// out = a + c * b with the product rounded before the sum, as "assemble(block + c * M)" rounds.
+// `contract(off)` is what keeps them apart: hipcc contracts by default, and its __dmul_rn /
+// __dadd_rn are plain operators that fuse into an fma like any others (they did here until
+// tests/test_gpu_block_kernels.py::test_vals_axpy_keeps_two_roundings compared the bits).
 __global__ void vals_axpy_kernel(double *__restrict__ out, const double *__restrict__ a,
                                  double c, const double *__restrict__ b, int64_t n) {
     for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < n;
          p += (int64_t)gridDim.x * blockDim.x) {
-        out[p] = __dadd_rn(a ? a[p] : 0.0, __dmul_rn(c, b[p]));
+#pragma clang fp contract(off)
+        const double cb = c * b[p];
+        out[p] = (a ? a[p] : 0.0) + cb;
     }
 }
 void launch_vals_axpy(hipStream_t s, double *out, const double *a, double c,
@@ -2255,43 +2261,10 @@ void launch_time_transform(hipStream_t s, double *y, const double *x, int kind, 
                        kind, n, nx, lo_halo, hi_halo);
 }
 
-// one workgroup per block: fixed-order sum (deterministic)
-__global__ void block_sums_kernel(const double *__restrict__ x, double *__restrict__ sums,
-                                  int64_t nx) {
-    __shared__ double sh[256];
-    const double *xb = x + (int64_t)blockIdx.x * nx;
-    double a = 0.0;
-    for (int64_t r = threadIdx.x; r < nx; r += 256) a += xb[r];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sums[blockIdx.x] = sh[0];
-}
-void launch_block_sums(hipStream_t s, const double *x, double *sums, int n, int64_t nx,
-                       double *) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(block_sums_kernel, dim3(n), dim3(256), 0, s, x, sums, nx);
-}
-__global__ void block_shift_kernel(double *__restrict__ y, const double *__restrict__ sums,
-                                   double coef, int64_t nx) {
-    const double sh = coef * sums[blockIdx.y];
-    double *yb = y + (int64_t)blockIdx.y * nx;
-    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < nx;
-         r += (int64_t)gridDim.x * blockDim.x)
-        yb[r] += sh;
-}
-void launch_block_shift(hipStream_t s, double *y, const double *sums, double coef, int n,
-                        int64_t nx) {
-    if (n <= 0) return;
-    dim3 grid(grid_for(nx, 256, 64), n);
-    hipLaunchKernelGGL(block_shift_kernel, grid, dim3(256), 0, s, y, sums, coef, nx);
-}
-
 // ConstantNullspace on all its blocks at once (preconditioner.py:137-152): sums of block j of
-// `a` (and of `b` when given) by one workgroup each, in a fixed order; then
+// `a` (and of `b` when given) by one workgroup each, in a fixed order (thread t adds the elements
+// t, t + 256, ... from +0.0, then a tree over the threads with strides 128, 64, ..., 1:
+// deterministic, and the order tests/blockops_ref.py restates); then
 // y_j = (y_j + c1_j * sum_a_j) + c2_j * sum_b_j, the two additions the per-block form made.
 __global__ void const_sums_kernel(const ConstJob *__restrict__ jobs, int njobs,
                                   const double *__restrict__ a, const double *__restrict__ b,

@@ -312,6 +312,9 @@ void launch_fill(hipStream_t s, double *y, double v, int64_t n);
 // y = a*x + b*y
 void launch_axpby(hipStream_t s, double *y, double a, const double *x, double b, int64_t n);
 // y[k*nx + r] = mask_k[r] ? (mx ? alpha_k * mx[k*nx + r] : 0) : x[k*nx + r]
+// Called in place (y == x: System::apply, the Krylov drivers' ns_project of an iterate) although
+// both are __restrict__: every thread reads x[p] before it writes y[p] and touches no other element,
+// which tests/test_gpu_block_kernels.py::test_mask_blocks pins bit for bit against the out-of-place call.
 struct MaskJob { const uint8_t *mask; double alpha; };
 void launch_mask_blocks(hipStream_t s, double *y, const double *x, const double *mx,
                         const MaskJob *d_jobs, int nblocks, int64_t nx);
@@ -324,11 +327,12 @@ void launch_time_transform_mask(hipStream_t s, double *y, const double *t, const
 // kind 1: T_1 (new_i = old_i + old_{i+1}); 2: T_2; 3: T_1^{-1}; 4: T_2^{-1}
 // (preconditioner.py:33-60, control.py:63-96).  `lo_halo`/`hi_halo` (may be null) stand
 // for the block before the first / after the last one on a time-sharded handle.
+// Called in place (y == x: StokesPC's launch_time_transform(st, h_, h_, ...)) although both are
+// __restrict__: a thread walks its own dof through the levels, reading every level before it writes
+// it; tests/test_gpu_block_kernels.py::test_time_transform pins it bit for bit against the
+// out-of-place call.
 void launch_time_transform(hipStream_t s, double *y, const double *x, int kind, int n,
                            int64_t nx, const double *lo_halo, const double *hi_halo);
-// y_k += shift_k for `n` blocks where shift_k = coef * sums[k] (ConstantNullspace)
-void launch_block_shift(hipStream_t s, double *y, const double *sums, double coef, int n,
-                        int64_t nx);
 // ConstantNullspace on every block that carries one, in two launches:
 // y_j -= mean(y_j); second == 1: y_j += mean(b_j); second == 2: y_j += alpha_j * mean(b_j)
 struct ConstJob { int64_t off, nx; double c1, c2_one, c2_alpha; };
@@ -336,8 +340,6 @@ void launch_const_correct(hipStream_t s, const ConstJob *d_jobs, int njobs, int6
                           double *y, const double *b, int second, double *sums);
 void launch_const_center(hipStream_t s, const ConstJob *d_jobs, int njobs, int64_t max_nx,
                          const double *x, double *xc, double *sums);
-void launch_block_sums(hipStream_t s, const double *x, double *sums, int n, int64_t nx,
-                       double *scratch);
 
 // ---- reductions (two fixed stages, no atomics: bitwise reproducible)
 struct VecList { const double *v[MDOT_MAX]; };

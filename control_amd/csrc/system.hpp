@@ -334,4 +334,7 @@ struct System {
     void sync() { HIPCHK(hipStreamSynchronize(stream)); }
 };
 
+// kkt_debug_block_op (include/kkt.h; csrc/blockops.cpp)
+void debug_block_op(System &S, kkt_block_op *op);
+
 }  // namespace kkt

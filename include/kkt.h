@@ -649,6 +649,66 @@ int kkt_debug_krylov_op(kkt_handle h, int op, int64_t n, int nv, const double *w
                         const double *coef, double a, double b, double *w_out,
                         double *scalars_out, double *arena_out);
 
+/* Test hook of the time-transform, nullspace and value set-up kernels: one launcher of
+ * csrc/kernels.hpp on host data, once, on the handle's stream.  Independent of the handle's layout:
+ * works on a created handle.  Every pointer is host memory; the hook uploads, launches, synchronises,
+ * downloads and releases.  What each operation reads (others ignored; "opt": may be NULL):
+ *   TIME_TRANSFORM       kind 1..4 (T_1, T_2, T_1^-1, T_2^-1), n levels of nx; x (n nx; in_place:
+ *                        ignored, the levels are taken from y and y is both operands of the launch);
+ *                        lo_halo, hi_halo (opt, nx: the level before the first / after the last); y
+ *   TIME_TRANSFORM_MASK  kind 1 | 2, n, nx; x = the raw rows t (n nx), x2 = xin (n nx; opt when no
+ *                        level has a mask); mask, has_mask, alpha; lo_halo, hi_halo (opt); y
+ *   MASK_BLOCKS          n blocks of nx; x (n nx; in_place as above), x2 = mx (opt); mask, has_mask,
+ *                        alpha; y
+ *   CONST_CORRECT        kind = second (0, 1, 2), n jobs on a vector of len; y (len, read and
+ *                        written), x2 = b (len; second != 0), job_*; y2 = sums (2 n)
+ *   CONST_CENTER         n jobs, len; x (len); job_*; y = xc (len), y2 = sums (n)
+ *   CSR_TO_SELL          nx padded entries; x = CSR values (len), idx = map (nx, -1 | < len); y
+ *   MASK_COLUMNS         nx; idx = col (nx, in [0, len)), mask = column mask (len bytes); y (nx,
+ *                        read and written)
+ *   VALS_AXPY            nx; x = a (opt), c, x2 = b; y
+ *   VALS_DIFFER          nx; x = a, x2 = b; flag
+ *   VALS_SYM_SKEW        nx; x = a, idx = tpos (nx, -1 | < nx); y = h, y2 = sk; flag
+ *   EXTRACT_DINV         kind = R (1 | 2), n slices of C = 64 R positions, len rows (without idx3:
+ *                        len <= n C); idx2 = slice_off (n + 1, from 0, ascending), nx =
+ *                        slice_off[n] C; idx = col (nx), x = vals (nx), idx3 = perm (opt, n C
+ *                        entries, -1 | < len), mask = row mask (opt, len bytes); y = dinv (len)
+ * mask: n * nx bytes, level i at i * nx (NULL: no level has a mask); has_mask (opt, n): 0 gives
+ * level i a null mask; alpha: n doubles (required with mask).  job_off, job_nx, job_c1,
+ * job_c2_one, job_c2_alpha: n entries each, the fields of the launch's job list (the launch's
+ * max_nx is the largest job_nx).
+ * Written arrays are guarded.  y and y2 hold KKT_BLOCK_GUARD doubles, the array, KKT_BLOCK_GUARD
+ * doubles; flag holds KKT_BLOCK_GUARD words, the flag, KKT_BLOCK_GUARD words.  The hook sets the
+ * guards to KKT_KRYLOV_PAD (flag: KKT_BLOCK_FLAG_PAD), uploads the whole allocation -- the array
+ * part as the caller filled it, so that elements a kernel must not touch can be recognised -- and
+ * returns the whole allocation.  Every array the launch only reads is downloaded again and
+ * compared with what went up: inputs_changed receives the number of arrays that differ.
+ * KKT_ERR_ARG (nothing launched) for an unknown op or kind, a null array the operation needs,
+ * in_place on another operation, sizes < 1, an index outside its array, a job that is not inside
+ * [0, len). */
+enum { KKT_BLOCK_TIME_TRANSFORM = 0, KKT_BLOCK_TIME_TRANSFORM_MASK = 1, KKT_BLOCK_MASK_BLOCKS = 2,
+       KKT_BLOCK_CONST_CORRECT = 3, KKT_BLOCK_CONST_CENTER = 4, KKT_BLOCK_CSR_TO_SELL = 5,
+       KKT_BLOCK_MASK_COLUMNS = 6, KKT_BLOCK_VALS_AXPY = 7, KKT_BLOCK_VALS_DIFFER = 8,
+       KKT_BLOCK_VALS_SYM_SKEW = 9, KKT_BLOCK_EXTRACT_DINV = 10 };
+#define KKT_BLOCK_GUARD 64
+#define KKT_BLOCK_FLAG_PAD 0xA5A5A5A5u
+typedef struct kkt_block_op {
+    int op, kind, in_place, n;
+    int64_t nx, len;
+    double c;
+    const double *x, *x2, *lo_halo, *hi_halo;
+    const uint8_t *mask;
+    const int32_t *has_mask;
+    const double *alpha;
+    const int64_t *job_off, *job_nx;
+    const double *job_c1, *job_c2_one, *job_c2_alpha;
+    const int32_t *idx, *idx2, *idx3;
+    double *y, *y2;
+    uint32_t *flag;
+    int32_t inputs_changed;
+} kkt_block_op;
+int kkt_debug_block_op(kkt_handle h, kkt_block_op *op);
+
 /* Step-locked parity hook (tests): while set, kkt_solve / kkt_solve_device with gmres or
  * fgmres replace their Krylov basis v_0 .. v_it by the caller's vectors before inner step `it`
  * of global step s (s < n_steps), and record what the step produced from them: the classical
