@@ -159,6 +159,30 @@ class BlockOp(C.Structure):
                 + [("y", c_f64p), ("y2", c_f64p), ("flag", c_u32p), ("inputs_changed", C.c_int32)])
 
 
+# kkt_debug_row_step: the forms (KKT_ROWSTEP_*), modes, kernel families it reports and its records
+ROWSTEP_FORMS = {name: k for k, name in enumerate(("rows", "single", "shared", "interleaved"))}
+ROWSTEP_LIN, ROWSTEP_CHEB = 0, 1
+ROWSTEP_FAMILIES = ("pc_rows", "pc_row_step", "pc_rows_shared", "pc_rows_shared_g", "pc_rows_il")
+ROWSTEP_MAX_TERMS = 8
+
+
+class RowStepOp(C.Structure):
+    _fields_ = ([("mode", C.c_int32), ("nterms", C.c_int32)]
+                + [(n, C.c_int32 * ROWSTEP_MAX_TERMS) for n in ("term_q", "term_i", "term_j",
+                                                                "term_x")]
+                + [(n, C.c_int32) for n in ("y", "y2", "yin", "z", "mx", "b", "pkm1", "pk")]
+                + [(n, C.c_double) for n in ("ca", "cy", "cz", "malpha", "c1", "c2", "c3",
+                                             "post1", "post2")])
+
+
+class RowStep(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("form", "q", "i", "j", "nops", "pc_xcd", "nvec", "pad_")]
+                + [("ops", C.POINTER(RowStepOp)), ("vecs", c_f64p), ("rowmask", c_u8p),
+                   ("dinv", c_f64p), ("il_x", c_f64p), ("il_pkm1", c_f64p), ("il_y", c_f64p)]
+                + [(n, C.c_int32) for n in ("family", "width", "launched", "inputs_changed", "R",
+                                            "uniform_w", "sorted", "nslices")])
+
+
 PC_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, c_f64p, c_f64p, c_f64p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int, C.c_int)
 SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int64, C.c_int,
@@ -245,6 +269,7 @@ SIGNATURES = {
     "kkt_debug_krylov_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, c_f64p, c_f64p,
                                       c_f64p, C.c_double, C.c_double, c_f64p, c_f64p, c_f64p]),
     "kkt_debug_block_op": (C.c_int, [C.c_void_p, C.POINTER(BlockOp)]),
+    "kkt_debug_row_step": (C.c_int, [C.c_void_p, C.POINTER(RowStep)]),
     "kkt_debug_set_steplock": (C.c_int, [C.c_void_p, C.POINTER(StepLock)]),
     "kkt_debug_apply_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "kkt_debug_pc_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),

@@ -547,6 +547,10 @@ int kkt_debug_block_op(kkt_handle h, kkt_block_op *op) {
     KKT_TRY(h, kkt::debug_block_op(S, op));
 }
 
+int kkt_debug_row_step(kkt_handle h, kkt_row_step *step) {
+    KKT_TRY(h, kkt::debug_row_step(S, step));
+}
+
 int kkt_debug_set_steplock(kkt_handle h, const kkt_steplock *lock) {
     KKT_TRY(h, {
         if (!lock) {

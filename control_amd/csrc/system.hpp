@@ -336,5 +336,7 @@ struct System {
 
 // kkt_debug_block_op (include/kkt.h; csrc/blockops.cpp)
 void debug_block_op(System &S, kkt_block_op *op);
+// kkt_debug_row_step (include/kkt.h; csrc/rowstep.cpp)
+void debug_row_step(System &S, kkt_row_step *step);
 
 }  // namespace kkt

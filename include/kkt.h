@@ -709,6 +709,67 @@ typedef struct kkt_block_op {
 } kkt_block_op;
 int kkt_debug_block_op(kkt_handle h, kkt_block_op *op);
 
+/* Test hook of the preconditioner's row steps: ONE launch of a launcher SchurPC::replay calls
+ * (csrc/kernels.hpp) on host data, on the handle's stream.  Needs a finalized handle: block
+ * (q, i, j) names the SELL pattern of every op of the call, and every term matrix is a stored block
+ * of that pattern (square: the vectors of a call all have its `nrows` elements).
+ *   form ROWS         launch_rowops, tag 1, nops >= 1 ops from device memory       (pc_rows)
+ *        SINGLE       the same with one op handed over by value (h_single)         (pc_row_step)
+ *        SHARED       launch_rowops_shared: every op has one term, all the same block; `launched`
+ *                     receives the launcher's return value (0: it declined, nothing ran)
+ *        INTERLEAVED  launch_rowops_il: nops time LEVELS in groups of four, as
+ *                     SchurPC::emit_solves_interleaved builds them.  ops[l] gives the level's b,
+ *                     post1, post2 and, on the last step, its output y; ops[0] the matrix (its
+ *                     one term's block, in every step; term_x is not read) and c1, c2, c3.  il_x / il_pkm1 (NULL: first / second step) hold the
+ *                     interleaved iterates, ceil(nops / 4) * 4 * nrows doubles, element (group g,
+ *                     row r, level l) at 4 (g nrows + r) + l; il_y (guarded like a vector of that
+ *                     length) receives the interleaved output, NULL: the last step, which writes
+ *                     the levels' y.
+ * Vectors are named by their index into `vecs` (-1: absent): nvec slots of KKT_BLOCK_GUARD + nrows
+ * + KKT_BLOCK_GUARD doubles.  The hook sets every guard to KKT_KRYLOV_PAD, uploads the whole table,
+ * and afterwards returns the slots the launch may write (y, y2) whole; every other slot, the mask,
+ * dinv, il_x and il_pkm1 are downloaded again and compared (inputs_changed: how many differ).
+ * An op reads term_x[t] through block (term_q[t], term_i[t], term_j[t]); mode KKT_ROWSTEP_LIN:
+ * y = ca acc + cy yin + cz z (masked rows: malpha mx, 0 without mx) and y2 = c3 dinv y;
+ * KKT_ROWSTEP_CHEB: y = post2 (post1 (c1 pkm1 + c2 pk + c3 dinv (b - acc))) (masked rows: 0).  An op
+ * without terms is given the all-zero slice offsets and uniform_w 0, as the emitters do.
+ * The one aliasing the emitters produce is allowed -- LIN with yin == y (the level update in place);
+ * KKT_ERR_ARG for any other vector that one op writes and the same or another op of the launch
+ * reads or writes, for a term block of another pattern, an index outside the table, a missing
+ * operand (CHEB: b, dinv; y2: dinv), SINGLE with nops != 1, SHARED or INTERLEAVED on R != 2 or with
+ * ops the production planner would not batch.  Nothing is launched then.
+ * Out: family (KKT_ROWSTEP_PC_*) and width -- the template instantiation the launcher's dispatch
+ * picks for this pattern (pc_rows / pc_row_step: WFIX; pc_rows_shared: W; pc_rows_shared_g and
+ * pc_rows_il: KC) -- and the pattern's R, uniform_w (-1: ragged), sorted (row-sorted storage) and
+ * nslices.  The launchers themselves report nothing: family and width are the hook's restatement
+ * of their dispatch (csrc/rowstep.cpp), not an observation of the kernel that ran; `launched` is
+ * the launcher's own return value. */
+enum { KKT_ROWSTEP_ROWS = 0, KKT_ROWSTEP_SINGLE = 1, KKT_ROWSTEP_SHARED = 2,
+       KKT_ROWSTEP_INTERLEAVED = 3 };
+enum { KKT_ROWSTEP_LIN = 0, KKT_ROWSTEP_CHEB = 1 };
+enum { KKT_ROWSTEP_PC_ROWS = 0, KKT_ROWSTEP_PC_ROW_STEP = 1, KKT_ROWSTEP_PC_ROWS_SHARED = 2,
+       KKT_ROWSTEP_PC_ROWS_SHARED_G = 3, KKT_ROWSTEP_PC_ROWS_IL = 4 };
+#define KKT_ROWSTEP_MAX_TERMS 8
+typedef struct kkt_row_step_op {
+    int32_t mode, nterms;
+    int32_t term_q[KKT_ROWSTEP_MAX_TERMS], term_i[KKT_ROWSTEP_MAX_TERMS],
+        term_j[KKT_ROWSTEP_MAX_TERMS], term_x[KKT_ROWSTEP_MAX_TERMS];
+    int32_t y, y2, yin, z, mx, b, pkm1, pk;
+    double ca, cy, cz, malpha, c1, c2, c3, post1, post2;
+} kkt_row_step_op;
+typedef struct kkt_row_step {
+    int32_t form, q, i, j, nops, pc_xcd, nvec, pad_;
+    const kkt_row_step_op *ops;
+    double *vecs;
+    const uint8_t *rowmask;     /* nrows bytes, or NULL */
+    const double *dinv;         /* nrows doubles, or NULL */
+    const double *il_x, *il_pkm1;
+    double *il_y;
+    /* out */
+    int32_t family, width, launched, inputs_changed, R, uniform_w, sorted, nslices;
+} kkt_row_step;
+int kkt_debug_row_step(kkt_handle h, kkt_row_step *step);
+
 /* Step-locked parity hook (tests): while set, kkt_solve / kkt_solve_device with gmres or
  * fgmres replace their Krylov basis v_0 .. v_it by the caller's vectors before inner step `it`
  * of global step s (s < n_steps), and record what the step produced from them: the classical

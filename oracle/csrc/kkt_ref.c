@@ -76,7 +76,13 @@ void ref_kkt_apply(const ref_sys_t *S, const double *x, double *y) {
     free(xc);
 }
 
-/* KSPSolve_Chebyshev (first kind) + PCJACOBI, zero guess, `its` steps; out may alias nothing */
+/* KSPSolve_Chebyshev (first kind) + PCJACOBI, zero guess, `its` steps; out may alias nothing.
+ * The three-term update below is written as the NumPy oracle evaluates it, every product rounded
+ * before it is added.  That is NOT the device's chain: the row kernels fuse `omega * pk` and
+ * `(scale * omega) * z` into the adds (csrc/kernels.hpp, RowOp; pinned by
+ * tests/test_gpu_row_steps.py), and this file is compiled with whatever contraction the host
+ * compiler applies.  The two agree to rounding, which is what the tolerance tests of this
+ * restatement ask. */
 static void cheb(const csr_t *A, const double *dinv, const double *b, double emin, double emax,
                  int its, double *out, double *w0, double *w1, double *w2, int par) {
     const int32_t n = A->nrows;
