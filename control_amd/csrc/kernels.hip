@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "epilogue.hpp"
+
 #include <cstddef>
 
 namespace kkt {
@@ -535,24 +537,20 @@ __device__ __forceinline__ void rowops_body(const RowOp &op, const TermFn &terms
             if (masked[q]) {
                 out[q] = pc ? op.malpha * e2[q] : 0.0;
             } else {
-                double v = op.ca * acc[q];
-                if (pa) v += op.cy * e0[q];
-                if (pb) v += op.cz * e1[q];
-                out[q] = v;
+                out[q] = epi_lin(op.ca, acc[q], pa != nullptr, op.cy, e0[q], pb != nullptr, op.cz,
+                                 e1[q]);
             }
             // optional second output: first Chebyshev step on the row just formed,
             // y2 = c3 * D^-1 y  (p_1 = scale D^-1 b with b = y)
-            out2[q] = op.c3 * (e3[q] * out[q]);
+            out2[q] = epi_first(op.c3, e3[q], out[q]);
         } else {
             // (1-w) p_{k-1} + w p_k + (scale w) D^-1 (b - A p_k): VecAXPBYPCZ order; masked
             // rows: the bc-assembled matrix on a bc-clean right-hand side gives exactly 0
             if (masked[q]) {
                 out[q] = 0.0;
             } else {
-                double v = pa ? op.c1 * e0[q] : 0.0;
-                if (pb) v += op.c2 * e1[q];
-                v += op.c3 * (e3[q] * (e2[q] - acc[q]));
-                out[q] = op.post2 * (op.post1 * v);
+                out[q] = epi_cheb(pa != nullptr, op.c1, e0[q], pb != nullptr, op.c2, e1[q], op.c3,
+                                  e3[q], e2[q], acc[q], op.post1, op.post2);
             }
         }
     }
@@ -1271,16 +1269,13 @@ __global__ __launch_bounds__(512) void pc_row_program_g(const RowOp *__restrict_
                 if (masked[q]) {
                     out = pc ? k_malpha * e2[q] : 0.0;
                 } else {
-                    out = k_ca * acc[q];
-                    if (pa) out += k_cy * e0[q];
-                    if (pb) out += k_cz * e1[q];
+                    out = epi_lin(k_ca, acc[q], pa != nullptr, k_cy, e0[q], pb != nullptr, k_cz,
+                                  e1[q]);
                 }
-                out2 = k_c3 * (e3[q] * out);
+                out2 = epi_first(k_c3, e3[q], out);
             } else if (!masked[q]) {
-                double t = pa ? k_c1 * e0[q] : 0.0;
-                if (pb) t += k_c2 * e1[q];
-                t += k_c3 * (e3[q] * (e2[q] - acc[q]));
-                out = k_post2 * (k_post1 * t);
+                out = epi_cheb(pa != nullptr, k_c1, e0[q], pb != nullptr, k_c2, e1[q], k_c3, e3[q],
+                               e2[q], acc[q], k_post1, k_post2);
             }
             outv[q] = out;
             out2v[q] = out2;
@@ -1519,18 +1514,15 @@ __global__ __launch_bounds__(256) void pc_rows_shared(const RowOp *__restrict__ 
                 if (masked[q]) {
                     out = pc ? op.malpha * e2[q] : 0.0;
                 } else {
-                    out = op.ca * acc[q];
-                    if (pa) out += op.cy * e0[q];
-                    if (pb) out += op.cz * e1[q];
+                    out = epi_lin(op.ca, acc[q], pa != nullptr, op.cy, e0[q], pb != nullptr, op.cz,
+                                  e1[q]);
                 }
-                out2 = op.c3 * (e3[q] * out);
+                out2 = epi_first(op.c3, e3[q], out);
             } else if (masked[q]) {
                 out = 0.0;
             } else {
-                double t = pa ? op.c1 * e0[q] : 0.0;
-                if (pb) t += op.c2 * e1[q];
-                t += op.c3 * (e3[q] * (e2[q] - acc[q]));
-                out = op.post2 * (op.post1 * t);
+                out = epi_cheb(pa != nullptr, op.c1, e0[q], pb != nullptr, op.c2, e1[q], op.c3, e3[q],
+                               e2[q], acc[q], op.post1, op.post2);
             }
             y[r] = out;
             if (y2) y2[r] = out2;
@@ -1646,18 +1638,14 @@ __global__ __launch_bounds__(256) void pc_rows_shared_g(const RowOp *__restrict_
                 if (masked[q]) {
                     out = pc ? op.malpha * e2 : 0.0;
                 } else {
-                    out = op.ca * acc[b][q];
-                    if (pa) out += op.cy * e0;
-                    if (pb) out += op.cz * e1;
+                    out = epi_lin(op.ca, acc[b][q], pa != nullptr, op.cy, e0, pb != nullptr, op.cz, e1);
                 }
-                out2 = op.c3 * (e3 * out);
+                out2 = epi_first(op.c3, e3, out);
             } else if (masked[q]) {
                 out = 0.0;
             } else {
-                double t = pa ? op.c1 * e0 : 0.0;
-                if (pb) t += op.c2 * e1;
-                t += op.c3 * (e3 * (e2 - acc[b][q]));
-                out = op.post2 * (op.post1 * t);
+                out = epi_cheb(pa != nullptr, op.c1, e0, pb != nullptr, op.c2, e1, op.c3, e3, e2,
+                               acc[b][q], op.post1, op.post2);
             }
             y[r] = out;
             if (y2) y2[r] = out2;
@@ -1762,10 +1750,8 @@ __global__ __launch_bounds__(256) void pc_rows_il(const IlOp *__restrict__ ops, 
 #pragma unroll
             for (int l = 0; l < 4; ++l) {
                 const double e2 = l < op.nlev ? ((gcd_p)op.b[l])[r] : 0.0;
-                double t = pkm1 ? op.c1 * p0_[l] : 0.0;
-                if (x4) t += op.c2 * p1_[l];
-                t += op.c3 * (e3 * (e2 - a_[l]));
-                o[l] = op.post2[l] * (op.post1[l] * t);
+                o[l] = epi_cheb(pkm1 != nullptr, op.c1, p0_[l], x4 != nullptr, op.c2, p1_[l], op.c3,
+                                e3, e2, a_[l], op.post1[l], op.post2[l]);
             }
         }
         if (op.out[0] != nullptr) {
@@ -1860,10 +1846,8 @@ __global__ __launch_bounds__(256) void kkt_spmv_rows_shared(const RowOp *__restr
             if (masked) {
                 out = pc ? op.malpha * pc[r] : 0.0;
             } else {
-                double vv = op.ca * acc[b][q];
-                if (pa) vv += op.cy * pa[r];
-                if (pb) vv += op.cz * pb[r];
-                out = vv;
+                out = epi_lin(op.ca, acc[b][q], pa != nullptr, op.cy, pa ? pa[r] : 0.0,
+                              pb != nullptr, op.cz, pb ? pb[r] : 0.0);
             }
             y[r] = out;
         }

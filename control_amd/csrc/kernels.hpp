@@ -37,20 +37,7 @@ enum EpiMode : int32_t { EPI_LIN = 0, EPI_CHEB = 1 };
 // many of them (blockIdx.y selects the RowOp).  acc = sum_t A_t x_t is accumulated
 // term-major with one fused-multiply-add chain per row, in CSR order within a term --
 // the order of the reference's sequence of MatMultAdd calls (preconditioner.py:406-432).
-//
-// Rounding sequence of the epilogues as built (hipcc contracts a product into the add that
-// follows it; the source says `*` and `+=`), pinned bit for bit per launch by
-// tests/test_gpu_row_steps.py against tests/rowstep_ref.py, candidate "ff" of both modes, for
-// pc_rows, pc_row_step, pc_rows_shared<W>, pc_rows_shared_g and pc_rows_il<8 | 4> alike:
-//   EPI_CHEB  v = fl(c1 pkm1)                     (0 without pkm1)
-//             v = fma(c2, pk, v)                  (with pk)
-//             v = fma(c3, fl(dinv fl(b - acc)), v)
-//             y = fl(post2 fl(post1 v))
-//   EPI_LIN   v = fl(ca acc);  v = fma(cy, yin, v) (with yin);  v = fma(cz, z, v) (with z)
-//             y2 = fl(c3 fl(dinv y))
-// Without pkm1 (without yin and z) the fma adds to a zero (there is none) and the candidates of
-// that sum coincide.  The other copies of the epilogue (row programs, tile and mass-tile kernels)
-// are held to these launches bit for bit by the sweep-form, mass-tile and coarse-ring tests.
+// The epilogues and their rounding sequence: epilogue.hpp, the one definition every kernel calls.
 struct RowOp {
     const int32_t *col;        // SELL column indices of the shared pattern
     const int32_t *slice_off;  // nslices + 1 offsets, in slots

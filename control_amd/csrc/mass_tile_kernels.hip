@@ -14,11 +14,13 @@
 // several level groups (the matrix is the same for every level).
 //
 // Arithmetic: per (row, level) the chain of pc_rows_il -- acc from 0 by fma over the row's entries
-// in SELL order (padding entries: value 0), then t = c1 p0, t += c2 p1, t += c3 (dinv (b - acc)),
-// out = post2 (post1 t), the same terms absent at steps 1 and 2 -- so results are bit-identical.
+// in SELL order (padding entries: value 0), then epi_cheb (epilogue.hpp) -- so results are
+// bit-identical.
 #include "kernels.hpp"
 
 #include <hip/hip_runtime.h>
+
+#include "epilogue.hpp"
 
 namespace kkt {
 
@@ -150,12 +152,9 @@ __global__ __launch_bounds__(T) void pc_tile_cheb(const MassTileArgs A) {
                     const double f1[4] = {q1.x, q1.y, q1.z, q1.w}, f2[4] = {q2.x, q2.y, q2.z, q2.w};
                     double o[4];
 #pragma unroll
-                    for (int l = 0; l < 4; ++l) {
-                        double t = has_old ? c1 * p0_[l] : 0.0;
-                        if (has_new) t += c2 * p1_[l];
-                        t += c3 * (dinv[sl] * (b_[l] - a_[l]));
-                        o[l] = f2[l] * (f1[l] * t);
-                    }
+                    for (int l = 0; l < 4; ++l)
+                        o[l] = epi_cheb(has_old, c1, p0_[l], has_new, c2, p1_[l], c3, dinv[sl], b_[l],
+                                        a_[l], f1[l], f2[l]);
                     // in place over the older iterate: only this thread reads or writes its row there
                     Xo[r] = d4{o[0], o[1], o[2], o[3]};
                 }

@@ -2,7 +2,8 @@
 // documents the arguments).  As blockops.cpp, nothing here computes and there is no second path:
 // the vectors go up, the launcher of kernels.hpp that SchurPC::replay calls runs once on the
 // handle's stream, the vectors come back.  Every vector sits between guards; what the launch only
-// reads is downloaded again and compared with what went up.
+// reads is downloaded again and compared with what went up.  The epilogue chain the launches run is
+// the one epilogue.hpp writes (candidate "ff" of tests/rowstep_ref.py), which the test asserts.
 #include <algorithm>
 #include <cstring>
 #include <vector>

@@ -23,6 +23,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "epilogue.hpp"
+
 #include <algorithm>
 #include <type_traits>
 
@@ -720,15 +722,9 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
 #pragma unroll
                 for (int sl = 0; sl < RPT; ++sl) {
                     const int r = sl * T + tid;
-                    double out;
-                    if (msk[sl]) {
-                        out = 0.0;
-                    } else {
-                        double t = L.ca * acc[sl];
-                        t += L.cy * b[sl];
-                        out = t;
-                    }
-                    const double out2 = L.p1_scale * (dinv[sl] * out);
+                    const double out =
+                        msk[sl] ? 0.0 : epi_lin(L.ca, acc[sl], true, L.cy, b[sl], false, 0.0, 0.0);
+                    const double out2 = epi_first(L.p1_scale, dinv[sl], out);
                     b[sl] = out;
                     if (r < nk1) Xo[r] = out2;
                     if (r < n0 && bo != nullptr) bo[gr[sl]] = out;
@@ -745,11 +741,9 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                 for (int sl = 0; sl < RPT; ++sl) {
                     const int r = sl * T + tid;
                     double out = 0.0;
-                    if (!msk[sl]) {
-                        double t = 0.0;
-                        t += L.p1_scale * (dinv[sl] * (b[sl] - 0.0));
-                        out = q2 * (q1 * t);
-                    }
+                    if (!msk[sl])
+                        out = epi_cheb(false, 0.0, 0.0, false, 0.0, 0.0, L.p1_scale, dinv[sl], b[sl],
+                                       0.0, q1, q2);
                     if (r < nk1) Xo[r] = out;
                 }
             }
@@ -803,11 +797,8 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                         double out = 0.0;
                         if (!msk[sl]) {
                             if (mode == 0) {
-                                const double e0 = Xo[r], e1 = Xc[r];
-                                double t = has_old ? cf1 * e0 : 0.0;
-                                t += cf2 * e1;
-                                t += cf3 * (dinv[sl] * (b[sl] - acc));
-                                out = q2 * (q1 * t);
+                                out = epi_cheb(has_old, cf1, Xo[r], true, cf2, Xc[r], cf3, dinv[sl],
+                                               b[sl], acc, q1, q2);
                             } else {
                                 out = b[sl] - acc;
                             }
@@ -1141,12 +1132,9 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                         if (r < nv) {
                             const double e0 = Xo[r], e1 = Xc[r];
                             double out = 0.0;
-                            if (!msk[sl]) {
-                                double t = has_old ? cf1 * e0 : 0.0;
-                                t += cf2 * e1;
-                                t += cf3 * (dinv[sl] * (b[sl] - acc));
-                                out = q2 * (q1 * t);
-                            }
+                            if (!msk[sl])
+                                out = epi_cheb(has_old, cf1, e0, true, cf2, e1, cf3, dinv[sl], b[sl],
+                                               acc, q1, q2);
                             Xo[r] = out;
                             // last step of a round: the own rows leave at once, with the number of
                             // the hand-off that follows (the rest of the step runs under their flight)
@@ -1189,6 +1177,15 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     #pragma unroll
                         for (int sl = 0; sl < NL; ++sl) {
                             const int r = sl * T + tid;
+                            // The one copy of the epilogue left in the kernels: it restates
+                            // epi_cheb(has_old, cf1, e0, true, cf2, e1, cf3, dinv, b, acc, q1, q2)
+                            // (epilogue.hpp) and is held to it bit for bit by the tile plans of
+                            // tests/test_gpu_sweep_forms.py.  With the call in its place the compiler
+                            // shares more code between the bodies of the slot counts: the 512-thread
+                            // kernels of W = 5 / 7 / 9 with two (three) slots come out one (two)
+                            // v_mul_f64 and v_fmac_f64 shorter -- 44 -> 43 and 22 -> 21 (W = 5, two
+                            // slots) up to 97 -> 95 and 38 -> 36 (W = 9, three) -- and a kernel here
+                            // must keep its instruction mix (profiles/one_epilogue.md).
                             // (boundary rows: a bit mask, not a branch or a select the compiler
                             // turns into one -- a branch per slot would put the chains of the slots
                             // one behind the other again)

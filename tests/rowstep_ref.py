@@ -7,8 +7,9 @@ The step, per row ``r``:
 * ``acc`` -- one fused multiply-add per stored entry from ``+0.0``, term-major and in CSR order
   inside a term, every fma exact (``fma``).  Padded slots add an exact zero, which leaves ``acc`` as
   it is, so they do not appear here.
-* the epilogue under a named *contraction candidate*: a way a compiler may fuse the sums of the
-  source expression without reassociating them.
+* the epilogue under a named *contraction candidate*: a way the sums of the expression can be fused
+  without reassociating them.  The library writes candidate ``ff`` (``csrc/epilogue.hpp``, explicit
+  fmas under ``contract(off)``); the others are the chains a different epilogue would produce.
 
   ``EPI_CHEB``  ``v = c1 pkm1; v += c2 pk; v += c3 (dinv (b - acc)); y = post2 (post1 v)``.  First
   letter, the sum ``c1 pkm1 + c2 pk``: ``u`` both products rounded, ``f`` = ``fma(c2, pk, fl(c1

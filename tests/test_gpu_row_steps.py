@@ -28,8 +28,8 @@ branch listed above ran.
 
 Measured on an MI355X (gfx950): all six kernels run candidate ``ff`` of both modes -- the first
 product rounded, every further addend one fma (``uf`` without ``pkm1``, ``fu`` with one of ``yin`` /
-``z``, ``uu`` where nothing is added) -- which is the chain the ``RowOp`` comment of ``kernels.hpp``
-states and the closing test asserts (``EXPECTED``).  Largest error / bound 0.714.  42 cases of 416 launches and the closing test: 3.5 s,
+``z``, ``uu`` where nothing is added) -- which is the chain ``csrc/epilogue.hpp`` writes out, fma by
+fma, for every kernel, and the closing test asserts (``EXPECTED``).  Largest error / bound 0.714.  42 cases of 416 launches and the closing test: 3.5 s,
 the slowest case (4225 rows, interleaved, ``pc_xcd`` on and off) 0.34 s.  A library whose
 ``pc_rows_il`` takes ``post1[0]`` for every level fails the seven interleaved cases (the last step's
 second level matches no candidate, 3e14 times the bound) and the closing test.
@@ -312,7 +312,7 @@ def test_every_row_step_branch_is_reached_with_one_candidate():
         assert len(common) == 1, (operands, {k: sorted(v) for k, v in per_kernel.items()})
         chosen[operands] = common.pop()
     print("candidate per operand set:", chosen)
-    # the chain the RowOp comment of kernels.hpp states: every product after the first fused into
+    # the chain csrc/epilogue.hpp writes: every product after the first fused into
     # its add ("ff"), reduced to "u" where the operand set leaves the letter no choice
     assert chosen == EXPECTED, chosen
     print(f"largest error / bound: {WORST['ratio']:.3f}")
