@@ -1769,7 +1769,7 @@ void launch_rowops_il(hipStream_t s, const IlOp *d_ops, int ngroups, int max_sli
     if (ngroups <= 0 || max_slices <= 0) return;
     const int gx = (max_slices + 3) / 4, xcd = pc_xcd ? 1 : 0;
     const dim3 grid(xcd ? (gx + 7) / 8 * 8 : gx, ngroups), block(256);
-    if (uniform_w > 0 && uniform_w <= 8)
+    if (il_kernel(uniform_w).width == 8)
         hipLaunchKernelGGL((pc_rows_il<8>), grid, block, 0, s, d_ops, xcd);
     else
         hipLaunchKernelGGL((pc_rows_il<4>), grid, block, 0, s, d_ops, xcd);
@@ -1871,10 +1871,11 @@ bool launch_rowops_grouped(hipStream_t s, const RowOp *d_ops, const int32_t *d_g
 bool launch_rowops_shared(hipStream_t s, const RowOp *d_ops, int nops, int max_slices, int R,
                           int uniform_w, bool pc_xcd) {
     constexpr int NB = 4;
-    if (R != 2 || nops < NB) return false;
+    const RowKernel k = shared_kernel(R, uniform_w, nops);
+    if (k.declined) return false;
     const int gx = (max_slices + 3) / 4, xcd = pc_xcd ? 1 : 0;
     const dim3 grid(xcd ? (gx + 7) / 8 * 8 : gx, (nops + NB - 1) / NB), block(256);
-    switch (uniform_w) {
+    switch (k.family == ROW_PC_ROWS_SHARED ? k.width : 0) {
 #define KKT_W(n) case n: hipLaunchKernelGGL((pc_rows_shared<n, NB>), grid, block, 0, s, d_ops, nops, xcd); return true;
         KKT_W(1) KKT_W(2) KKT_W(3) KKT_W(4) KKT_W(5) KKT_W(6) KKT_W(7) KKT_W(8)
 #undef KKT_W
@@ -1900,12 +1901,14 @@ void launch_rowops(hipStream_t s, const RowOp *d_ops, int nops, int max_slices, 
                    const Bases &bases, int tag, int uniform_w, const RowOp *h_single, XcdOrder xcd) {
     if (nops <= 0 || max_slices <= 0) return;
     dim3 grid((max_slices + 3) / 4, nops);
-    if (nops != 1) h_single = nullptr;
+    // tag 1 (the preconditioner's row steps): family and width are rows_kernel's answer
+    const RowKernel k = rows_kernel(R, uniform_w, nops, h_single != nullptr);
+    if (k.family != ROW_PC_ROW_STEP) h_single = nullptr;
     if (R != 2) {
         launch_one<1, 0>(s, grid, d_ops, bases, tag, h_single, xcd.fixed);
         return;
     }
-    switch (uniform_w) {
+    switch (tag == 0 ? uniform_w : k.width) {
 #define KKT_W(n) case n: launch_one<2, n>(s, grid, d_ops, bases, tag, h_single, xcd.fixed); break;
         KKT_W(1) KKT_W(2) KKT_W(3) KKT_W(4) KKT_W(5) KKT_W(6) KKT_W(7) KKT_W(8)
         KKT_W(9) KKT_W(10) KKT_W(11) KKT_W(12) KKT_W(13) KKT_W(14) KKT_W(15) KKT_W(16)

@@ -5,6 +5,8 @@
 
 #include <string>
 
+#include "chebyshev.hpp"
+
 namespace kkt {
 
 // thrown by launch_tile_sweep when a memset or the launch itself fails (never silently)
@@ -67,8 +69,32 @@ struct RowOp {
 // (On the fixed-width P1 launches the same relabelling was slower, profiles/DIARY_r01_r02.md
 // 8.1b: their traffic is 1.1 x the bytes already; the ragged launches fetched 1.4 x.)
 struct XcdOrder { bool ragged = false, fixed = false; };
-// (kkt_debug_row_step, csrc/rowstep.cpp, restates which kernel and instantiation launch_rowops with
-// tag 1, launch_rowops_shared and launch_rowops_il pick: a change of their dispatch goes there too)
+// Which kernel and instantiation a launch of the preconditioner's row steps gets: the launchers
+// below dispatch on these answers, and kkt_debug_row_step / kkt_debug_pc_forms report them.
+enum RowFamily : int32_t { ROW_PC_ROWS = 0, ROW_PC_ROW_STEP = 1, ROW_PC_ROWS_SHARED = 2,
+                           ROW_PC_ROWS_SHARED_G = 3, ROW_PC_ROWS_IL = 4 };
+struct RowKernel {
+    RowFamily family;
+    int width;               // the instantiation's width argument
+    bool declined = false;   // the launcher launches nothing and says so (launch_rowops_shared)
+};
+// launch_rowops with tag 1: pc_rows<R, WFIX>, or pc_row_step<R, WFIX> for one op that rides in the
+// kernel arguments; WFIX 0: the slot loop
+inline RowKernel rows_kernel(int R, int uniform_w, int nops, bool single) {
+    return {single && nops == 1 ? ROW_PC_ROW_STEP : ROW_PC_ROWS,
+            R == 2 && uniform_w >= 1 && uniform_w <= 16 ? uniform_w : 0};
+}
+// launch_rowops_shared: pc_rows_shared<W, 4>, or pc_rows_shared_g<4, 4> for any other width; it
+// serves R = 2 and at least four ops
+inline RowKernel shared_kernel(int R, int uniform_w, int nops) {
+    const bool declined = R != 2 || nops < 4;
+    if (uniform_w >= 1 && uniform_w <= 8) return {ROW_PC_ROWS_SHARED, uniform_w, declined};
+    return {ROW_PC_ROWS_SHARED_G, 4, declined};
+}
+// launch_rowops_il: pc_rows_il<8> or pc_rows_il<4>
+inline RowKernel il_kernel(int uniform_w) {
+    return {ROW_PC_ROWS_IL, uniform_w >= 1 && uniform_w <= 8 ? 8 : 4};
+}
 void launch_rowops(hipStream_t s, const RowOp *d_ops, int nops, int max_slices, int R,
                    const Bases &bases, int tag, int uniform_w,
                    const RowOp *h_single = nullptr, XcdOrder xcd = {});
@@ -151,7 +177,6 @@ void launch_row_program(hipStream_t s, const RowOp *d_ops, int nphases, int nwg,
 
 // ---- tile sweep program (tile_kernels.hip; plan: tiles.hpp)
 constexpr int TILE_DEPTH_MAX = 16;
-struct TileCoef { double c1, c2, c3; };
 // One time level of a sweep: optional update b = ca * (sum_t U_t x_prev) + cy * bin on the
 // boundary-masked rows, then `its` Jacobi-Chebyshev steps with the matrix `vals` on b, result in
 // `out` (control.py:2263-2295 / 2375-2406: "b_i += M u_{i-1}; solve").

@@ -9,10 +9,6 @@
 
 namespace kkt {
 
-static VRef vabs(const double *p) {
-    return p ? VRef{(int64_t)(uintptr_t)p, 0, 0} : VRef{0, -1, 0};
-}
-
 SchurPC::SchurPC(System &S, const kkt_pc_desc &d) : S_(S), d_(d) {
     if (!S.finalized) fail(KKT_ERR_STATE, "kkt_set_pc_schur needs a finalized system");
     if (d.kind < KKT_PC_STATIONARY || d.kind > KKT_PC_INSTATIONARY_CN)
@@ -964,9 +960,10 @@ void SchurPC::plain_forms(std::vector<int32_t> &out) const {
     const Pattern &P = S_.patterns[m_pat_];
     for (const PcStep &s : steps_) {
         if (s.kind == PcStep::ROWS) {
-            const int form = s.rows.shared_matrix && s.rows.R == 2 ? KKT_PC_ROWS_SHARED
-                             : s.rows.single                       ? KKT_PC_ROWS_KERNARG
-                                                                   : KKT_PC_ROWS_PLAIN;
+            const RowFamily f = row_launch_kernel(s.rows).family;
+            const int form = f == ROW_PC_ROWS       ? KKT_PC_ROWS_PLAIN
+                             : f == ROW_PC_ROW_STEP ? KKT_PC_ROWS_KERNARG
+                                                    : KKT_PC_ROWS_SHARED;
             out.insert(out.end(), {form, s.rows.uniform_w, s.rows.R, s.lane, s.rows.nops, 0});
         } else if (s.kind == PcStep::ROWS_IL) {
             out.insert(out.end(), {KKT_PC_ROWS_INTERLEAVED, s.il_w, 2, s.lane, s.il_groups, 0});
@@ -1137,10 +1134,6 @@ void SchurPC::build() {
     m_dinv_ = handle_mem_.alloc<double>(nx_);
     launch_extract_dinv(st, P.d_col, P.d_slice_off, m_vals_, mask_, m_dinv_, (int)nx_, P.nslices,
                         P.R, P.d_perm);
-    {
-        std::vector<int32_t> z(P.nslices + 1, 0);
-        zero_off_ = handle_mem_.upload(z.data(), z.size());
-    }
     auto vec = [&](int64_t blocks) {
         double *p = handle_mem_.alloc<double>(blocks * nx_ + 32);
         HIPCHK(hipMemsetAsync(p, 0, (blocks * nx_ + 32) * sizeof(double), st));
@@ -1292,22 +1285,7 @@ static int64_t coarse_columns(System &S, const Pattern &P, const CoarseDev &c, c
     const int64_t n = P.nrows;
     DevPool tmp;   // released on every way out
     double *x = tmp.alloc<double>(n + 32), *y = tmp.alloc<double>(n + 32);
-    RowOp op{};
-    op.col = P.d_col;
-    op.perm = P.d_perm;
-    op.slice_off = P.d_slice_off;
-    op.uniform_w = P.uniform_w;
-    op.nrows = (int32_t)n;
-    op.nslices = P.nslices;
-    op.nterms = 1;
-    op.mode = EPI_LIN;
-    op.t[0].vals = vals;
-    op.t[0].x = vabs(x);
-    op.y = vabs(y);
-    op.y2 = op.yin = op.z = op.mx = op.b = op.pk = op.pkm1 = vabs(nullptr);
-    op.ca = 1.0;
-    op.post1 = op.post2 = 1.0;
-    op.rowmask = mask;
+    const RowOp op = lin_op(P, n, mask, LinStep{{RowTerm{vals, x}}, y});
     RowOp *d_op = tmp.upload(&op, 1);
     const Bases B{{nullptr, nullptr, nullptr, nullptr}};
     for (int k = 0; k < nc; ++k) {
@@ -1583,32 +1561,6 @@ void SchurPC::emit_coarse(const double *r, const double *x_in, double *x_out, co
     steps_.push_back(s);
 }
 
-// coefficients (c1, c2, c3) of the Chebyshev steps 2 .. its (what emit_solves generates)
-static std::vector<TileCoef> cheb_coefficients(int its, double emin, double emax, double eimag) {
-    std::vector<TileCoef> out;
-    const double scale = 2.0 / (emax + emin);
-    const double alpha = 1.0 - scale * emin;
-    const double mu = 1.0 / alpha, omegaprod = 2.0 / alpha;
-    double c_km1 = 1.0, c_k = mu;
-    const double ell_d = 0.5 * (emax + emin), ell_a = 0.5 * (emax - emin);
-    const double ell_c2 = ell_a * ell_a - eimag * eimag;
-    double ell_alpha = 1.0 / ell_d;
-    for (int step = 2; step <= its; ++step) {
-        if (eimag > 0.0) {
-            ell_alpha = 1.0 / (ell_d - (step == 2 ? 0.5 : 0.25) * ell_c2 * ell_alpha);
-            const double beta = ell_d * ell_alpha - 1.0;
-            out.push_back(TileCoef{-beta, 1.0 + beta, ell_alpha});
-        } else {
-            const double c_kp1 = 2.0 * mu * c_k - c_km1;
-            const double omega = omegaprod * c_k / c_kp1;
-            out.push_back(TileCoef{1.0 - omega, omega, scale * omega});
-            c_km1 = c_k;
-            c_k = c_kp1;
-        }
-    }
-    return out;
-}
-
 // One sub-solve in its two-grid form: [update of the right-hand side;] cycles x [Galerkin
 // correction of the current iterate; `its` smoothing sweeps from it].
 void SchurPC::emit_coarse_solve(const Lin *upd, const Solve &sv, const Mat &F) {
@@ -1620,15 +1572,15 @@ void SchurPC::emit_coarse_solve(const Lin *upd, const Solve &sv, const Mat &F) {
         u.y2 = nullptr;
         emit_lin({u});
     }
-    const double scale = 2.0 / (F.emax + F.emin);
-    const std::vector<TileCoef> coef = cheb_coefficients(its, F.emin, F.emax, F.eimag);
+    const ChebCoefficients cheb = cheb_coefficients(its, F.emin, F.emax, F.eimag);
+    const double scale = cheb.scale;
     {
         // what the tile form runs as one two-grid level
         lv.its = its;
         lv.coarse = true;
         lv.einv = F.einv;
         lv.coef.push_back(TileCoef{0.0, 1.0, scale});
-        lv.coef.insert(lv.coef.end(), coef.begin(), coef.end());
+        lv.coef.insert(lv.coef.end(), cheb.steps.begin(), cheb.steps.end());
         TileLevel &L = lv.lev;
         L.vals = F.vals;
         L.dinv = F.dinv;
@@ -1676,7 +1628,7 @@ void SchurPC::emit_coarse_solve(const Lin *upd, const Solve &sv, const Mat &F) {
             const bool last = last_cycle && step == its;
             const double *pk = step == 1 ? p0 : target(step - 1);
             const double *pkm1 = step == 1 ? nullptr : (step == 2 ? p0 : target(step - 2));
-            const TileCoef k = step == 1 ? TileCoef{0.0, 1.0, scale} : coef[step - 2];
+            const TileCoef k = step == 1 ? TileCoef{0.0, 1.0, scale} : cheb.step(step);
             emit_cheb({Cheb{F.vals, F.dinv, sv.b, pk, pkm1, target(step), k.c1, k.c2, k.c3,
                             last ? sv.post1 : 1.0, last ? sv.post2 : 1.0}});
         }
@@ -1832,94 +1784,23 @@ int SchurPC::resolve_its(const Mat &typical) {
 }
 
 void SchurPC::push_rows(std::vector<RowOp> &r) {
-    const Pattern &P = S_.patterns[m_pat_];
     PcStep s;
     s.kind = PcStep::ROWS;
-    s.rows.nops = (int)r.size();
-    s.rows.max_slices = P.nslices;
-    s.rows.R = P.R;
-    s.rows.uniform_w = P.uniform_w;
-    s.rows.d_ops = program_mem_.upload(r.data(), r.size());
-    if (r.size() == 1) {
-        s.rows.single = S_.opts.kernarg_ops;
-        s.rows.h_op = r[0];
-    }
-    s.rows.shared_matrix = S_.opts.shared_rows && r.size() >= 4;
-    for (const RowOp &op : r)
-        s.rows.shared_matrix = s.rows.shared_matrix && op.nterms == 1 &&
-                               op.t[0].vals == r[0].t[0].vals && op.col == r[0].col &&
-                               op.rowmask == r[0].rowmask && op.t[0].x.base == 0;
+    s.rows = make_row_launch(program_mem_, S_.patterns[m_pat_], r, S_.opts.kernarg_ops,
+                             S_.opts.shared_rows);
     s.lane = cur_lane_;
     steps_.push_back(s);
 }
 
 void SchurPC::emit_lin(const std::vector<Lin> &ops) {
-    const Pattern &P = S_.patterns[m_pat_];
     std::vector<RowOp> r;
-    for (const Lin &l : ops) {
-        if ((int)l.terms.size() > MAX_TERMS) fail(KKT_ERR_STATE, "too many terms");
-        RowOp op{};
-        op.col = P.d_col;
-        op.perm = P.d_perm;
-        op.slice_off = l.terms.empty() ? zero_off_ : P.d_slice_off;
-        op.uniform_w = l.terms.empty() ? 0 : P.uniform_w;
-        op.nrows = (int32_t)nx_;
-        op.nslices = P.nslices;
-        op.nterms = (int32_t)l.terms.size();
-        op.mode = EPI_LIN;
-        for (size_t t = 0; t < l.terms.size(); ++t) {
-            op.t[t].vals = l.terms[t].vals;
-            op.t[t].x = vabs(l.terms[t].x);
-        }
-        op.y = vabs(l.y);
-        op.y2 = vabs(l.y2);
-        op.dinv = l.dinv;
-        op.c3 = l.c3;
-        op.ca = l.ca;
-        op.cy = l.cy;
-        op.cz = l.cz;
-        op.yin = vabs(l.yin);
-        op.z = vabs(l.z);
-        op.rowmask = mask_;
-        op.mx = vabs(nullptr);
-        op.b = op.pk = op.pkm1 = vabs(nullptr);
-        r.push_back(op);
-    }
+    for (const Lin &l : ops) r.push_back(lin_op(S_.patterns[m_pat_], nx_, mask_, l));
     push_rows(r);
 }
 
 void SchurPC::emit_cheb(const std::vector<Cheb> &ops) {
-    const Pattern &P = S_.patterns[m_pat_];
     std::vector<RowOp> r;
-    for (const Cheb &c : ops) {
-        RowOp op{};
-        op.col = P.d_col;
-        op.perm = P.d_perm;
-        op.slice_off = c.vals ? P.d_slice_off : zero_off_;
-        op.uniform_w = c.vals ? P.uniform_w : 0;
-        op.nrows = (int32_t)nx_;
-        op.nslices = P.nslices;
-        op.nterms = c.vals ? 1 : 0;
-        op.mode = EPI_CHEB;
-        if (c.vals) {
-            op.t[0].vals = c.vals;
-            op.t[0].x = vabs(c.pk);
-        }
-        op.y = vabs(c.y);
-        op.y2 = vabs(nullptr);
-        op.yin = op.z = op.mx = vabs(nullptr);
-        op.rowmask = mask_;
-        op.b = vabs(c.b);
-        op.pk = vabs(c.pk);
-        op.pkm1 = vabs(c.pkm1);
-        op.dinv = c.dinv;
-        op.c1 = c.c1;
-        op.c2 = c.c2;
-        op.c3 = c.c3;
-        op.post1 = c.post1;
-        op.post2 = c.post2;
-        r.push_back(op);
-    }
+    for (const Cheb &c : ops) r.push_back(cheb_op(S_.patterns[m_pat_], nx_, mask_, c));
     push_rows(r);
 }
 
@@ -2015,9 +1896,7 @@ bool SchurPC::emit_solves_interleaved(const std::vector<Solve> &sv, int its, dou
         }
         il_cap_ = need;
     }
-    const double scale = 2.0 / (emax + emin);
-    const double alpha = 1.0 - scale * emin, mu = 1.0 / alpha, omegaprod = 2.0 / alpha;
-    double c_km1 = 1.0, c_k = mu;
+    const ChebCoefficients cheb = cheb_coefficients(its, emin, emax);
     auto buf = [&](int step, int g) -> double * {
         return il_P_[(step - 1) % 3] + (size_t)g * 4 * (size_t)nx_;
     };
@@ -2026,47 +1905,21 @@ bool SchurPC::emit_solves_interleaved(const std::vector<Solve> &sv, int its, dou
     rec.its = its;
     rec.sv = sv;
     for (int step = 1; step <= its; ++step) {
-        double k1 = 0.0, k2 = 0.0, k3 = scale;
-        if (step >= 2) {
-            const double c_kp1 = 2.0 * mu * c_k - c_km1;
-            const double omega = omegaprod * c_k / c_kp1;
-            k1 = 1.0 - omega;
-            k2 = omega;
-            k3 = scale * omega;
-            c_km1 = c_k;
-            c_k = c_kp1;
-        }
-        rec.coef.push_back(TileCoef{k1, k2, k3});
+        const TileCoef k = step >= 2 ? cheb.step(step) : TileCoef{0.0, 0.0, cheb.scale};
+        rec.coef.push_back(k);
         const bool last = step == its;
         std::vector<IlOp> ops(ng);
         for (int g = 0; g < ng; ++g) {
-            IlOp op{};
-            op.col = P.d_col;
-            op.slice_off = P.d_slice_off;
-            op.perm = P.d_perm;
-            op.vals = sv[0].vals;
-            op.dinv = sv[0].dinv;
-            op.rowmask = mask_;
-            op.nrows = (int32_t)nx_;
-            op.nslices = P.nslices;
-            op.uniform_w = P.uniform_w;
-            op.nlev = (int32_t)std::min<size_t>(4, m - (size_t)g * 4);
-            for (int l = 0; l < op.nlev; ++l) {
-                op.b[l] = sv[(size_t)g * 4 + l].b;
-                op.out[l] = last ? sv[(size_t)g * 4 + l].out : nullptr;
+            const int nlev = (int)std::min<size_t>(4, m - (size_t)g * 4);
+            IlLevel lev[4];
+            for (int l = 0; l < nlev; ++l) {
+                const Solve &q = sv[(size_t)g * 4 + l];
+                lev[l] = IlLevel{q.b, last ? q.out : nullptr, last ? q.post1 : 1.0,
+                                 last ? q.post2 : 1.0};
             }
-            op.x = step >= 2 ? buf(step - 1, g) : nullptr;
-            op.pkm1 = step >= 3 ? buf(step - 2, g) : nullptr;
-            op.y = last ? nullptr : buf(step, g);
-            op.c1 = k1;
-            op.c2 = k2;
-            op.c3 = k3;
-            for (int l = 0; l < 4; ++l) {
-                const bool live = last && l < op.nlev;
-                op.post1[l] = live ? sv[(size_t)g * 4 + l].post1 : 1.0;
-                op.post2[l] = live ? sv[(size_t)g * 4 + l].post2 : 1.0;
-            }
-            ops[g] = op;
+            ops[g] = il_op(P, nx_, mask_, sv[0].vals, sv[0].dinv, lev, nlev,
+                           step >= 2 ? buf(step - 1, g) : nullptr,
+                           step >= 3 ? buf(step - 2, g) : nullptr, last ? nullptr : buf(step, g), k);
         }
         PcStep s;
         s.kind = PcStep::ROWS_IL;
@@ -2108,11 +1961,9 @@ void SchurPC::emit_solves(const std::vector<Solve> &sv, int its, double emin, do
         emit_cheb(ops);
         return;
     }
-    const double scale = 2.0 / (emax + emin);
-    const double alpha = 1.0 - scale * emin;
-    const double mu = 1.0 / alpha;
-    const double omegaprod = 2.0 / alpha;
-    double c_km1 = 1.0, c_k = mu;
+    // (eimag > 0: the coefficients of the ellipse, chebyshev.hpp)
+    const ChebCoefficients cheb = cheb_coefficients(its, emin, emax, eimag);
+    const double scale = cheb.scale;
     // step 1: p_1 = scale * D^-1 b
     auto target = [&](int step, size_t q) -> double * {
         return step == its ? sv[q].out : P[(step - 1) % 3] + (int64_t)q * pstride;
@@ -2125,42 +1976,17 @@ void SchurPC::emit_solves(const std::vector<Solve> &sv, int its, double emin, do
         }
         emit_cheb(ops);
     }
-    // eimag > 0: the spectrum lies in the ellipse with centre d = (emax + emin) / 2 and semi-axes
-    // a = (emax - emin) / 2, eimag (blocks with a convection term).  Manteuffel's recurrence
-    // (Numer. Math. 28, 1977) for the same three-term sweep: alpha_1 = 2d / (2d^2 - c^2),
-    // alpha_n = 1 / (d - (c^2 / 4) alpha_{n-1}), beta_n = d alpha_n - 1 with c^2 = a^2 - eimag^2,
-    // which may be negative -- only c^2 enters, the arithmetic stays real.  Restated in the
-    // oracle (chebyshev_ellipse_coefficients); for eimag == 0 PETSc's form below is kept, bit
-    // for bit what rounds 1 and 2 ran.
-    const double ell_d = 0.5 * (emax + emin), ell_a = 0.5 * (emax - emin);
-    const double ell_c2 = ell_a * ell_a - eimag * eimag;
-    double ell_alpha = 1.0 / ell_d;
     for (int step = 2; step <= its; ++step) {
-        double k1, k2, k3;
-        if (eimag > 0.0) {
-            ell_alpha = 1.0 / (ell_d - (step == 2 ? 0.5 : 0.25) * ell_c2 * ell_alpha);
-            const double beta = ell_d * ell_alpha - 1.0;
-            k1 = -beta;
-            k2 = 1.0 + beta;
-            k3 = ell_alpha;
-        } else {
-            const double c_kp1 = 2.0 * mu * c_k - c_km1;
-            const double omega = omegaprod * c_k / c_kp1;
-            k1 = 1.0 - omega;
-            k2 = omega;
-            k3 = scale * omega;
-            c_km1 = c_k;
-            c_k = c_kp1;
-        }
+        const TileCoef &k = cheb.step(step);
         const bool last = step == its;
         for (size_t q = 0; q < m; ++q) {
             const double *pk = target(step - 1, q);
             const double *pkm1 = step >= 3 ? target(step - 2, q) : nullptr;
             ops[q] = Cheb{sv[q].vals, sv[q].dinv, sv[q].b, pk, pkm1, target(step, q),
-                          k1, k2, k3,
+                          k.c1, k.c2, k.c3,
                           last ? sv[q].post1 : 1.0, last ? sv[q].post2 : 1.0};
         }
-        if (coef_out) coef_out->push_back(TileCoef{k1, k2, k3});
+        if (coef_out) coef_out->push_back(k);
         emit_cheb(ops);
     }
     if (record_solo) {
@@ -2430,7 +2256,6 @@ void SchurPC::emit_comm(const double *send, int dst, double *recv, int src) {
 
 void SchurPC::replay(size_t first, size_t last) {
     const bool xcd = S_.opts.pc_xcd;
-    Bases B{{nullptr, nullptr, nullptr, nullptr}};
     if (n_events_ > 0 && !side_) side_ = Stream::create();
     while ((int)events_.size() < n_events_) events_.push_back(Event::create(false));
     for (size_t k = first; k < last; ++k) {
@@ -2444,12 +2269,7 @@ void SchurPC::replay(size_t first, size_t last) {
                 HIPCHK(hipStreamWaitEvent(st, events_[s.ev], 0));
                 break;
             case PcStep::ROWS:
-                if (s.rows.shared_matrix &&
-                    launch_rowops_shared(st, s.rows.d_ops, s.rows.nops, s.rows.max_slices,
-                                         s.rows.R, s.rows.uniform_w, xcd))
-                    break;
-                launch_rowops(st, s.rows.d_ops, s.rows.nops, s.rows.max_slices, s.rows.R, B, 1,
-                              s.rows.uniform_w, s.rows.single ? &s.rows.h_op : nullptr);
+                run_row_launch(st, s.rows, xcd);
                 break;
             case PcStep::ROWS_IL:
                 launch_rowops_il(st, s.d_il, s.il_groups, s.il_slices, s.il_w, xcd);

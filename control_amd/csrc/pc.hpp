@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "comm.hpp"
+#include "rowlaunch.hpp"
 #include "system.hpp"
 #include "tiles.hpp"
 
@@ -176,7 +177,6 @@ class SchurPC : public PcBase {
     int m_pat_ = -1;
     double *m_vals_ = nullptr;           // bc-assembled M (cols masked)
     double *m_dinv_ = nullptr;
-    int32_t *zero_off_ = nullptr;
     double *in_ = nullptr, *out_ = nullptr;
     double *B_ = nullptr, *T_ = nullptr;             // n_ blocks each
     double *P_[3] = {nullptr, nullptr, nullptr};     // Chebyshev rotation, n_ blocks each
@@ -275,26 +275,10 @@ class SchurPC : public PcBase {
     bool prepare_tiles();
     bool fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out);
 
-    struct Term {
-        const double *vals;
-        const double *x;
-    };
-    struct Lin {   // y = mask(ca * sum_t A_t x_t + cy * yin + cz * z)
-        std::vector<Term> terms;
-        double *y;
-        double ca = 1.0, cy = 0.0, cz = 0.0;
-        const double *yin = nullptr, *z = nullptr;
-        // optional fused first Chebyshev step of the solve that follows: y2 = c3 * dinv * y
-        double *y2 = nullptr;
-        const double *dinv = nullptr;
-        double c3 = 0.0;
-    };
-    struct Cheb {
-        const double *vals;   // nullptr: no matrix term (first step)
-        const double *dinv, *b, *pk, *pkm1;
-        double *y;
-        double c1, c2, c3, post1 = 1.0, post2 = 1.0;
-    };
+    // the arguments of the op builders (rowlaunch.hpp)
+    using Term = RowTerm;
+    using Lin = LinStep;
+    using Cheb = ChebStep;
     void build();
     void clear_program();
     const double *block_vals(int q, int i, int j) const;

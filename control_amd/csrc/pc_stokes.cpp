@@ -6,42 +6,6 @@
 
 namespace kkt {
 
-static VRef vabs(const double *p) {
-    return p ? VRef{(int64_t)(uintptr_t)p, 0, 0} : VRef{0, -1, 0};
-}
-
-static RowOp base_op(const Pattern &P) {
-    RowOp op{};
-    op.col = P.d_col;
-    op.perm = P.d_perm;
-    op.slice_off = P.d_slice_off;
-    op.uniform_w = P.uniform_w;
-    op.nrows = (int32_t)P.nrows;
-    op.nslices = P.nslices;
-    op.y = op.y2 = op.yin = op.z = op.mx = op.b = op.pk = op.pkm1 = vabs(nullptr);
-    op.rowmask = nullptr;
-    op.ca = 1.0;
-    op.post1 = op.post2 = 1.0;
-    return op;
-}
-
-static RowLaunch upload_launch(DevPool &mem, const Pattern &P, std::vector<RowOp> &ops,
-                               bool shared_rows) {
-    RowLaunch L;
-    L.nops = (int)ops.size();
-    L.max_slices = P.nslices;
-    L.R = P.R;
-    L.uniform_w = P.uniform_w;
-    // every op applies one and the same matrix: the four-blocks-per-thread form applies
-    // (unless option "shared_rows" = "0")
-    L.shared_matrix = shared_rows && !ops.empty();
-    for (const RowOp &op : ops)
-        L.shared_matrix = L.shared_matrix && op.nterms == 1 && op.t[0].vals == ops[0].t[0].vals &&
-                          op.col == ops[0].col && op.rowmask == ops[0].rowmask;
-    L.d_ops = mem.upload(ops.data(), ops.size());
-    return L;
-}
-
 StokesPC::DevMat StokesPC::upload(int64_t nrows, int64_t ncols, const int32_t *ip, const int32_t *ix,
                                   const double *v, bool want_dinv) {
     if (!ip || !ix || !v) fail(KKT_ERR_ARG, "kkt_set_pc_stokes: matrix missing");
@@ -71,44 +35,24 @@ void StokesPC::emit_cheb(std::vector<ChainStep> &dst, const DevMat &A, int its, 
                                          : P_[(step - 1) % 3] + (int64_t)k * np_;
     };
     std::vector<RowOp> ops(nb);
-    const double scale = its > 0 ? 2.0 / (emax + emin) : 1.0;
-    for (int k = 0; k < nb; ++k) {   // step 1: p_1 = scale D^-1 b (its == 0: D^-1 b)
-        RowOp op = base_op(P);
-        op.mode = EPI_CHEB;
-        op.nterms = 0;
-        op.uniform_w = 0;
-        op.y = vabs(target(1, k));
-        op.b = vabs(blk(b, k));
-        op.dinv = A.dinv;
-        op.c3 = scale;
-        ops[k] = op;
-    }
-    dst.push_back(ChainStep{upload_launch(mem_, P, ops, S_.opts.shared_rows)});
-    if (its <= 1) return;
-    const double alpha = 1.0 - scale * emin, mu = 1.0 / alpha, omegaprod = 2.0 / alpha;
-    double c_km1 = 1.0, c_k = mu;
+    auto push = [&]() {
+        dst.push_back(ChainStep{make_row_launch(mem_, P, ops, false, S_.opts.shared_rows)});
+    };
+    const ChebCoefficients cheb =
+        its > 0 ? cheb_coefficients(its, emin, emax) : ChebCoefficients{1.0, {}};
+    for (int k = 0; k < nb; ++k)   // step 1: p_1 = scale D^-1 b (its == 0: D^-1 b)
+        ops[k] = cheb_op(P, P.nrows, nullptr,
+                         ChebStep{nullptr, A.dinv, blk(b, k), nullptr, nullptr, target(1, k), 0.0, 0.0,
+                                  cheb.scale});
+    push();
     for (int step = 2; step <= its; ++step) {
-        const double c_kp1 = 2.0 * mu * c_k - c_km1;
-        const double omega = omegaprod * c_k / c_kp1;
-        for (int k = 0; k < nb; ++k) {
-            RowOp op = base_op(P);
-            op.mode = EPI_CHEB;
-            op.nterms = 1;
-            op.t[0].vals = A.vals;
-            op.t[0].x = vabs(target(step - 1, k));
-            op.y = vabs(target(step, k));
-            op.b = vabs(blk(b, k));
-            op.pk = vabs(target(step - 1, k));
-            op.pkm1 = vabs(step >= 3 ? target(step - 2, k) : nullptr);
-            op.dinv = A.dinv;
-            op.c1 = 1.0 - omega;
-            op.c2 = omega;
-            op.c3 = scale * omega;
-            ops[k] = op;
-        }
-        dst.push_back(ChainStep{upload_launch(mem_, P, ops, S_.opts.shared_rows)});
-        c_km1 = c_k;
-        c_k = c_kp1;
+        const TileCoef &c = cheb.step(step);
+        for (int k = 0; k < nb; ++k)
+            ops[k] = cheb_op(P, P.nrows, nullptr,
+                             ChebStep{A.vals, A.dinv, blk(b, k), target(step - 1, k),
+                                      step >= 3 ? target(step - 2, k) : nullptr, target(step, k),
+                                      c.c1, c.c2, c.c3});
+        push();
     }
 }
 
@@ -182,41 +126,22 @@ void StokesPC::emit_kp_two_grid(int its, double emin, double emax, const double 
     const Pattern &P = S_.patterns[Kp_.pat];
     const int nb = 2 * n_;
     auto blk = [&](const double *base, int k) { return base + (int64_t)k * np_; };
-    const double scale = 2.0 / (emax + emin);
-    // coefficients of the sweeps 2 .. its (the recurrence of emit_cheb)
-    std::vector<double> c1(its + 1, 0.0), c2(its + 1, 1.0), c3(its + 1, scale);
-    {
-        const double alpha = 1.0 - scale * emin, mu = 1.0 / alpha, omegaprod = 2.0 / alpha;
-        double c_km1 = 1.0, c_k = mu;
-        for (int step = 2; step <= its; ++step) {
-            const double c_kp1 = 2.0 * mu * c_k - c_km1;
-            const double omega = omegaprod * c_k / c_kp1;
-            c1[step] = 1.0 - omega;
-            c2[step] = omega;
-            c3[step] = scale * omega;
-            c_km1 = c_k;
-            c_k = c_kp1;
-        }
-    }
+    auto wblk = [&](double *base, int k) { return base + (int64_t)k * np_; };
+    auto push = [&](const std::vector<RowOp> &ops) {
+        kp_steps_.push_back(ChainStep{make_row_launch(mem_, P, ops, false, S_.opts.shared_rows)});
+    };
+    const ChebCoefficients cheb = cheb_coefficients(its, emin, emax);
     const double *xcur = nullptr;
     for (int cyc = 0; cyc < kp_cycles_; ++cyc) {
         const bool last_cycle = cyc + 1 == kp_cycles_;
         const double *r = b;
         if (cyc > 0) {          // r = b - K_p x
             std::vector<RowOp> ops(nb);
-            for (int k = 0; k < nb; ++k) {
-                RowOp op = base_op(P);
-                op.mode = EPI_LIN;
-                op.nterms = 1;
-                op.t[0].vals = Kp_.vals;
-                op.t[0].x = vabs(blk(xcur, k));
-                op.y = vabs(blk(kp_r_, k));
-                op.ca = -1.0;
-                op.cz = 1.0;
-                op.z = vabs(blk(b, k));
-                ops[k] = op;
-            }
-            kp_steps_.push_back(ChainStep{upload_launch(mem_, P, ops, S_.opts.shared_rows)});
+            for (int k = 0; k < nb; ++k)
+                ops[k] = lin_op(P, P.nrows, nullptr,
+                                LinStep{{RowTerm{Kp_.vals, blk(xcur, k)}}, wblk(kp_r_, k), -1.0, 0.0, 1.0,
+                                        nullptr, blk(b, k)});
+            push(ops);
             r = kp_r_;
         }
         ChainStep cs;
@@ -231,24 +156,14 @@ void StokesPC::emit_kp_two_grid(int its, double emin, double emax, const double 
         for (int step = 1; step <= its; ++step) {
             const double *pk = step == 1 ? kp_x0_ : target(step - 1);
             const double *pkm1 = step == 1 ? nullptr : (step == 2 ? kp_x0_ : target(step - 2));
+            const TileCoef c = step == 1 ? TileCoef{0.0, 1.0, cheb.scale} : cheb.step(step);
             std::vector<RowOp> ops(nb);
-            for (int k = 0; k < nb; ++k) {
-                RowOp op = base_op(P);
-                op.mode = EPI_CHEB;
-                op.nterms = 1;
-                op.t[0].vals = Kp_.vals;
-                op.t[0].x = vabs(blk(pk, k));
-                op.y = vabs(blk(target(step), k));
-                op.b = vabs(blk(b, k));
-                op.pk = vabs(blk(pk, k));
-                op.pkm1 = vabs(pkm1 ? blk(pkm1, k) : nullptr);
-                op.dinv = Kp_.dinv;
-                op.c1 = step == 1 ? 0.0 : c1[step];
-                op.c2 = step == 1 ? 1.0 : c2[step];
-                op.c3 = step == 1 ? scale : c3[step];
-                ops[k] = op;
-            }
-            kp_steps_.push_back(ChainStep{upload_launch(mem_, P, ops, S_.opts.shared_rows)});
+            for (int k = 0; k < nb; ++k)
+                ops[k] = cheb_op(P, P.nrows, nullptr,
+                                 ChebStep{Kp_.vals, Kp_.dinv, blk(b, k), blk(pk, k),
+                                          pkm1 ? blk(pkm1, k) : nullptr, wblk(target(step), k), c.c1,
+                                          c.c2, c.c3});
+            push(ops);
         }
         xcur = target(its);
     }
@@ -320,22 +235,18 @@ StokesPC::StokesPC(System &outer, System &inner, System &commutator, const kkt_p
         const Pattern &P = S_.patterns[B_.pat];
         std::vector<RowOp> ops;
         for (int k = 0; k < 2 * n_; ++k) {
-            RowOp op = base_op(P);
-            op.mode = EPI_LIN;
-            op.nterms = 1;
-            op.t[0].vals = B_.vals;
-            op.t[0].x = vabs(out_ + (int64_t)k * nv_);
-            op.y = vabs(h_ + (int64_t)k * np_);
+            LinStep l{{RowTerm{B_.vals, out_ + (int64_t)k * nv_}}, h_ + (int64_t)k * np_};
             if (cn_) {   // the time transforms come between the product and the subtraction
-                op.ca = sB_;
+                l.ca = sB_;
             } else {
-                op.ca = s2_ * sB_;
-                op.cz = -s2_;
-                op.z = vabs(in_ + n0 + (int64_t)k * np_);
+                l.ca = s2_ * sB_;
+                l.cz = -s2_;
+                l.z = in_ + n0 + (int64_t)k * np_;
             }
-            ops.push_back(op);
+            ops.push_back(lin_op(P, P.nrows, nullptr, l));
         }
-        lin_.push_back(upload_launch(mem_, P, ops, S_.opts.shared_rows));
+        // B is rectangular: a plain launch, whatever "shared_rows" says
+        lin_.push_back(make_row_launch(mem_, P, ops, false, false));
     }
     int kp_its = d.kp_its;
     double kp_emin = d.kp_emin, kp_emax = d.kp_emax;
@@ -402,7 +313,6 @@ void StokesPC::solve_records(std::vector<double> &out) const {
 void StokesPC::run() {
     hipStream_t st = S_.stream;
     const int64_t n0 = 2 * (int64_t)n_ * nv_;
-    const Bases B{{nullptr, nullptr, nullptr, nullptr}};
     // nested solve on the velocity KKT system from a zero guess (control.py:1012-1027); the
     // inner system works on its own stream: order the two streams by synchronising
     HIPCHK(hipStreamSynchronize(st));
@@ -410,8 +320,7 @@ void StokesPC::run() {
     int its = 0, reason = 0;
     inner_.solve(in_, out_, &its, &reason, nullptr, nullptr, 0, nullptr);
     HIPCHK(hipStreamSynchronize(inner_.stream));
-    for (const RowLaunch &L : lin_)
-        launch_rowops(st, L.d_ops, L.nops, L.max_slices, L.R, B, 1, L.uniform_w);
+    for (const RowLaunch &L : lin_) run_row_launch(st, L, S_.opts.pc_xcd);
     if (cn_) {   // control.py:4407-4428
         const int64_t half = (int64_t)n_ * np_;
         // Time shards: T_2 / T_1 read the neighbour ranks' old blocks (one exchange each way);
@@ -452,7 +361,6 @@ void StokesPC::run() {
 // work each: the launch gaps were two thirds of their 16 us) unless "no_graph" is set.
 void StokesPC::run_chain(Chain &c, const std::vector<ChainStep> &steps) {
     hipStream_t st = S_.stream;
-    const Bases B{{nullptr, nullptr, nullptr, nullptr}};
     auto launches = [&]() {
         for (const ChainStep &cs : steps) {
             if (cs.coarse) {      // all pressure blocks: one launch per stage
@@ -460,11 +368,7 @@ void StokesPC::run_chain(Chain &c, const std::vector<ChainStep> &steps) {
                                                  np_, 2 * n_, np_);
                 continue;
             }
-            const RowLaunch &L = cs.L;
-            if (!L.shared_matrix ||
-                !launch_rowops_shared(st, L.d_ops, L.nops, L.max_slices, L.R, L.uniform_w,
-                                      S_.opts.pc_xcd))
-                launch_rowops(st, L.d_ops, L.nops, L.max_slices, L.R, B, 1, L.uniform_w);
+            run_row_launch(st, cs.L, S_.opts.pc_xcd);
         }
     };
     if (S_.opts.no_graph || !c.usable || steps.size() < 8)

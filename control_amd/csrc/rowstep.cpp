@@ -1,14 +1,16 @@
 // kkt_debug_row_step: one launch of the preconditioner's row steps on host data (include/kkt.h
 // documents the arguments).  As blockops.cpp, nothing here computes and there is no second path:
-// the vectors go up, the launcher of kernels.hpp that SchurPC::replay calls runs once on the
-// handle's stream, the vectors come back.  Every vector sits between guards; what the launch only
-// reads is downloaded again and compared with what went up.  The epilogue chain the launches run is
-// the one epilogue.hpp writes (candidate "ff" of tests/rowstep_ref.py), which the test asserts.
+// the vectors go up, the ops are filled and the launch is built and run by the functions of
+// rowlaunch.hpp that SchurPC and StokesPC use, once on the handle's stream, the vectors come back;
+// `family` and `width` are the launcher's own choice (rows_kernel / shared_kernel / il_kernel).
+// Every vector sits between guards; what the launch only reads is downloaded again and compared
+// with what went up.  The epilogue chain the launches run is the one epilogue.hpp writes (candidate
+// "ff" of tests/rowstep_ref.py), which the test asserts.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
-#include "system.hpp"
+#include "rowlaunch.hpp"
 
 namespace kkt {
 
@@ -16,12 +18,15 @@ namespace {
 
 constexpr size_t G = KKT_BLOCK_GUARD;
 static_assert(KKT_ROWSTEP_MAX_TERMS == MAX_TERMS, "kkt.h restates MAX_TERMS");
+static_assert(KKT_ROWSTEP_PC_ROWS == (int)ROW_PC_ROWS && KKT_ROWSTEP_PC_ROW_STEP == (int)ROW_PC_ROW_STEP &&
+                  KKT_ROWSTEP_PC_ROWS_SHARED == (int)ROW_PC_ROWS_SHARED &&
+                  KKT_ROWSTEP_PC_ROWS_SHARED_G == (int)ROW_PC_ROWS_SHARED_G &&
+                  KKT_ROWSTEP_PC_ROWS_IL == (int)ROW_PC_ROWS_IL,
+              "kkt.h restates RowFamily");
 
 [[noreturn]] void bad(const char *what) {
     fail(KKT_ERR_ARG, std::string("kkt_debug_row_step: ") + what);
 }
-
-VRef vabs(const double *p) { return VRef{(int64_t) reinterpret_cast<intptr_t>(p), p ? 0 : -1, 0}; }
 
 struct Watch {   // an array the launch must leave as it is
     const void *dev;
@@ -36,13 +41,6 @@ const double *block_values(const System &S, int q, int i, int j, int pat) {
     const ValueArray &va = S.values[it->second.va];
     if (va.pattern != pat) bad("a term block has another pattern than the call's");
     return va.d_vals;
-}
-
-// The instantiation the launchers of kernels.hip pick.  The launchers report nothing, so `family`
-// and `width` below RESTATE their switch statements (launch_rowops, launch_rowops_shared,
-// launch_rowops_il): a change of that dispatch has to be repeated here.  pc_rows / pc_row_step: WFIX.
-int rows_width(int R, int uniform_w) {
-    return R == 2 && uniform_w >= 1 && uniform_w <= 16 ? uniform_w : 0;
 }
 
 }  // namespace
@@ -109,15 +107,6 @@ void debug_row_step(System &S, kkt_row_step *pa) {
         if (a.il_pkm1 && !a.il_x) bad("p_{k-1} without p_k");
         if (a.ops[0].nterms != 1) bad("ops[0] of an interleaved step names the matrix (one term)");
     }
-    if (a.form == KKT_ROWSTEP_SHARED) {
-        // what SchurPC::push_rows requires of a launch before it sets shared_matrix
-        for (int k = 0; k < a.nops; ++k) {
-            const kkt_row_step_op &o = a.ops[k], &o0 = a.ops[0];
-            if (o.nterms != 1 || o.term_q[0] != o0.term_q[0] || o.term_i[0] != o0.term_i[0] ||
-                o.term_j[0] != o0.term_j[0])
-                bad("SHARED ops have one term each, all the same block");
-        }
-    }
 
     // ---- upload
     hipStream_t st = S.stream;
@@ -137,8 +126,6 @@ void debug_row_step(System &S, kkt_row_step *pa) {
     auto vec = [&](int v) -> double * { return v < 0 ? nullptr : d_vecs + (size_t)v * slot + G; };
     const uint8_t *d_mask = input(a.rowmask, n);
     const double *d_dinv = input(a.dinv, n);
-    const std::vector<int32_t> zeros((size_t)P.nslices + 1, 0);
-    const int32_t *d_zero_off = pool.upload(zeros.data(), zeros.size());
 
     a.R = P.R;
     a.uniform_w = P.uniform_w;
@@ -160,97 +147,56 @@ void debug_row_step(System &S, kkt_row_step *pa) {
                                           a.ops[0].term_j[0], pat);
         const int ng = (a.nops + 3) / 4;
         std::vector<IlOp> ops((size_t)ng);
-        for (int g = 0; g < ng; ++g) {   // as SchurPC::emit_solves_interleaved fills them
-            IlOp op{};
-            op.col = P.d_col;
-            op.slice_off = P.d_slice_off;
-            op.perm = P.d_perm;
-            op.vals = vals;
-            op.dinv = d_dinv;
-            op.rowmask = d_mask;
-            op.nrows = (int32_t)n;
-            op.nslices = P.nslices;
-            op.uniform_w = P.uniform_w;
-            op.nlev = std::min(4, a.nops - 4 * g);
-            for (int l = 0; l < op.nlev; ++l) {
-                op.b[l] = vec(a.ops[4 * g + l].b);
-                op.out[l] = a.il_y ? nullptr : vec(a.ops[4 * g + l].y);
+        const TileCoef coef{a.ops[0].c1, a.ops[0].c2, a.ops[0].c3};
+        for (int g = 0; g < ng; ++g) {
+            const int nlev = std::min(4, a.nops - 4 * g);
+            IlLevel lev[4];
+            for (int l = 0; l < nlev; ++l) {
+                const kkt_row_step_op &o = a.ops[4 * g + l];
+                lev[l] = IlLevel{vec(o.b), a.il_y ? nullptr : vec(o.y), o.post1, o.post2};
             }
-            op.x = d_x ? d_x + (size_t)g * 4 * n : nullptr;
-            op.pkm1 = d_pkm1 ? d_pkm1 + (size_t)g * 4 * n : nullptr;
-            op.y = d_il_y ? d_il_y + (size_t)g * 4 * n : nullptr;
-            op.c1 = a.ops[0].c1;
-            op.c2 = a.ops[0].c2;
-            op.c3 = a.ops[0].c3;
-            for (int l = 0; l < 4; ++l) {
-                op.post1[l] = l < op.nlev ? a.ops[4 * g + l].post1 : 1.0;
-                op.post2[l] = l < op.nlev ? a.ops[4 * g + l].post2 : 1.0;
-            }
-            ops[(size_t)g] = op;
+            ops[(size_t)g] = il_op(P, P.nrows, d_mask, vals, d_dinv, lev, nlev,
+                                   d_x ? d_x + (size_t)g * 4 * n : nullptr,
+                                   d_pkm1 ? d_pkm1 + (size_t)g * 4 * n : nullptr,
+                                   d_il_y ? d_il_y + (size_t)g * 4 * n : nullptr, coef);
         }
         const IlOp *d_ops = pool.upload(ops.data(), ops.size());
-        a.family = KKT_ROWSTEP_PC_ROWS_IL;
-        a.width = P.uniform_w > 0 && P.uniform_w <= 8 ? 8 : 4;
+        const RowKernel k = il_kernel(P.uniform_w);
+        a.family = k.family;
+        a.width = k.width;
         launch_rowops_il(st, d_ops, ng, P.nslices, P.uniform_w, a.pc_xcd != 0);
     } else {
+        const bool shared = a.form == KKT_ROWSTEP_SHARED;
         std::vector<RowOp> ops((size_t)a.nops);
-        for (int k = 0; k < a.nops; ++k) {   // as SchurPC::emit_lin / emit_cheb fill them
+        for (int k = 0; k < a.nops; ++k) {
             const kkt_row_step_op &o = a.ops[k];
-            const bool lin = o.mode == KKT_ROWSTEP_LIN;
-            RowOp op{};
-            op.col = P.d_col;
-            op.perm = P.d_perm;
-            op.slice_off = o.nterms ? P.d_slice_off : d_zero_off;
-            op.uniform_w = o.nterms ? P.uniform_w : 0;
-            op.nrows = (int32_t)n;
-            op.nslices = P.nslices;
-            op.nterms = o.nterms;
-            op.mode = lin ? EPI_LIN : EPI_CHEB;
-            for (int t = 0; t < o.nterms; ++t) {
-                op.t[t].vals = block_values(S, o.term_q[t], o.term_i[t], o.term_j[t], pat);
-                op.t[t].x = vabs(vec(o.term_x[t]));
+            std::vector<RowTerm> terms((size_t)o.nterms);
+            for (int t = 0; t < o.nterms; ++t)
+                terms[(size_t)t] = RowTerm{block_values(S, o.term_q[t], o.term_i[t], o.term_j[t], pat),
+                                           vec(o.term_x[t])};
+            if (o.mode == KKT_ROWSTEP_LIN) {
+                ops[(size_t)k] = lin_op(P, P.nrows, d_mask,
+                                        LinStep{terms, vec(o.y), o.ca, o.cy, o.cz, vec(o.yin), vec(o.z),
+                                                vec(o.y2), d_dinv, o.c3, vec(o.mx), o.malpha});
+            } else {
+                ops[(size_t)k] = cheb_op(P, P.nrows, d_mask,
+                                         ChebStep{nullptr, d_dinv, vec(o.b), vec(o.pk), vec(o.pkm1),
+                                                  vec(o.y), o.c1, o.c2, o.c3, o.post1, o.post2});
+                set_terms(ops[(size_t)k], P, terms.data(), terms.size());   // any number, any vector
             }
-            op.y = vabs(vec(o.y));
-            op.y2 = vabs(lin ? vec(o.y2) : nullptr);
-            op.yin = vabs(lin ? vec(o.yin) : nullptr);
-            op.z = vabs(lin ? vec(o.z) : nullptr);
-            op.mx = vabs(lin ? vec(o.mx) : nullptr);
-            op.b = vabs(lin ? nullptr : vec(o.b));
-            op.pk = vabs(lin ? nullptr : vec(o.pk));
-            op.pkm1 = vabs(lin ? nullptr : vec(o.pkm1));
-            op.rowmask = d_mask;
-            op.dinv = d_dinv;
-            op.ca = o.ca;
-            op.cy = o.cy;
-            op.cz = o.cz;
-            op.malpha = o.malpha;
-            op.c1 = o.c1;
-            op.c2 = o.c2;
-            op.c3 = o.c3;
-            op.post1 = o.post1;
-            op.post2 = o.post2;
-            ops[(size_t)k] = op;
         }
-        const RowOp *d_ops = pool.upload(ops.data(), ops.size());
-        if (a.form == KKT_ROWSTEP_SHARED) {
-            const bool fixed = P.uniform_w >= 1 && P.uniform_w <= 8;
-            // (pc_rows_shared<W> takes position == row; find_or_add_pattern gives row-sorted
-            // storage no uniform width)
-            if (fixed && P.d_perm) bad("row-sorted storage with a fixed width");
-            a.family = fixed ? KKT_ROWSTEP_PC_ROWS_SHARED : KKT_ROWSTEP_PC_ROWS_SHARED_G;
-            a.width = fixed ? P.uniform_w : 4;
-            a.launched = launch_rowops_shared(st, d_ops, a.nops, P.nslices, P.R, P.uniform_w,
-                                              a.pc_xcd != 0)
-                             ? 1
-                             : 0;
-        } else {
-            const Bases B{{nullptr, nullptr, nullptr, nullptr}};
-            const bool single = a.form == KKT_ROWSTEP_SINGLE;
-            a.family = single ? KKT_ROWSTEP_PC_ROW_STEP : KKT_ROWSTEP_PC_ROWS;
-            a.width = rows_width(P.R, P.uniform_w);
-            launch_rowops(st, d_ops, a.nops, P.nslices, P.R, B, 1, P.uniform_w,
-                          single ? &ops[0] : nullptr);
-        }
+        // SHARED: the launch SchurPC::push_rows flags -- the ops must qualify, and where the
+        // launcher declines (fewer than four ops) nothing runs: no fall-back to the plain launch
+        const RowLaunch L = make_row_launch(pool, P, ops, a.form == KKT_ROWSTEP_SINGLE, shared);
+        const RowKernel k = shared ? shared_kernel(L.R, L.uniform_w, L.nops) : row_launch_kernel(L);
+        if (shared && !one_shared_matrix(ops)) bad("SHARED ops have one term each, all the same block");
+        // (pc_rows_shared<W> takes position == row; find_or_add_pattern gives row-sorted
+        // storage no uniform width)
+        if (k.family == ROW_PC_ROWS_SHARED && P.d_perm) bad("row-sorted storage with a fixed width");
+        a.family = k.family;
+        a.width = k.width;
+        a.launched = k.declined ? 0 : 1;
+        if (!k.declined) run_row_launch(st, L, a.pc_xcd != 0);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));

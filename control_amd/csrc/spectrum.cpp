@@ -106,36 +106,10 @@ Spectrum jacobi_spectrum(System &S, int pattern, const double *vals, const doubl
         }
         HIPCHK(hipMemcpy(r, h.data(), n * sizeof(double), hipMemcpyHostToDevice));
     }
-    auto vabs = [](const double *q) { return q ? VRef{(int64_t)(uintptr_t)q, 0, 0} : VRef{0, -1, 0}; };
     // w = A p (boundary rows 0) and z = D^-1 r as single RowOps through the kernel arguments
-    RowOp opA{}, opZ{};
-    opA.col = P.d_col;
-    opA.perm = P.d_perm;
-    opA.slice_off = P.d_slice_off;
-    opA.uniform_w = P.uniform_w;
-    opA.nrows = (int32_t)n;
-    opA.nslices = P.nslices;
-    opA.nterms = 1;
-    opA.mode = EPI_LIN;
-    opA.t[0].vals = vals;
-    opA.t[0].x = vabs(p);
-    opA.y = vabs(w);
-    opA.y2 = opA.yin = opA.z = opA.mx = opA.b = opA.pk = opA.pkm1 = vabs(nullptr);
-    opA.ca = 1.0;
-    opA.rowmask = rowmask;
-    opZ = opA;
-    opZ.nterms = 0;
-    opZ.uniform_w = 0;
-    std::vector<int32_t> zoff(P.nslices + 1, 0);
-    int32_t *d_zoff = tmp.upload(zoff.data(), zoff.size());
-    opZ.slice_off = d_zoff;
-    opZ.mode = EPI_CHEB;
-    opZ.y = vabs(z);
-    opZ.b = vabs(r);
-    opZ.dinv = dinv;
-    opZ.c1 = opZ.c2 = 0.0;
-    opZ.c3 = 1.0;
-    opZ.post1 = opZ.post2 = 1.0;
+    const RowOp opA = lin_op(P, n, rowmask, LinStep{{RowTerm{vals, p}}, w});
+    const RowOp opZ = cheb_op(P, n, rowmask,
+                              ChebStep{nullptr, dinv, r, nullptr, nullptr, z, 0.0, 0.0, 1.0});
     RowOp *d_ops = nullptr;
     {
         RowOp both[2] = {opA, opZ};
@@ -233,29 +207,12 @@ double jacobi_skew_radius(System &S, int pattern, const double *skew_vals, const
         }
         HIPCHK(hipMemcpy(v, h.data(), n * sizeof(double), hipMemcpyHostToDevice));
     }
-    auto vabs = [](const double *q) { return q ? VRef{(int64_t)(uintptr_t)q, 0, 0} : VRef{0, -1, 0}; };
     // y = -D^-1 (0 - S x): the Chebyshev epilogue with c3 = -1 and no right-hand side
-    RowOp op{};
-    op.col = P.d_col;
-    op.perm = P.d_perm;
-    op.slice_off = P.d_slice_off;
-    op.uniform_w = P.uniform_w;
-    op.nrows = (int32_t)n;
-    op.nslices = P.nslices;
-    op.nterms = 1;
-    op.mode = EPI_CHEB;
-    op.t[0].vals = skew_vals;
-    op.y2 = op.yin = op.z = op.mx = op.b = op.pk = op.pkm1 = vabs(nullptr);
-    op.dinv = dinv;
-    op.c1 = op.c2 = 0.0;
-    op.c3 = -1.0;
-    op.post1 = op.post2 = 1.0;
-    op.rowmask = rowmask;
-    RowOp both[2] = {op, op};
-    both[0].t[0].x = vabs(v);
-    both[0].y = vabs(z);
-    both[1].t[0].x = vabs(z);
-    both[1].y = vabs(v);
+    auto op = [&](const double *x, double *y) {
+        return cheb_op(P, n, rowmask,
+                       ChebStep{skew_vals, dinv, nullptr, nullptr, nullptr, y, 0.0, 0.0, -1.0, 1.0, 1.0, x});
+    };
+    const RowOp both[2] = {op(v, z), op(z, v)};
     RowOp *d_ops = tmp.upload(both, 2);
     const Bases B{{nullptr, nullptr, nullptr, nullptr}};
     double host[2];

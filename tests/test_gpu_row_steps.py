@@ -2,7 +2,10 @@
 ``kkt_debug_row_step``: the two epilogues of ``RowOp`` (``EPI_LIN``, ``EPI_CHEB``) as ``pc_rows``,
 ``pc_row_step``, ``pc_rows_shared<W>``, ``pc_rows_shared_g``, ``pc_rows_il<8>`` and ``pc_rows_il<4>``
 run them.  Reference: ``tests/rowstep_ref.py``; the launches and their data: ``tests/rowstep_cases.py``
-(both checked on the host by ``tests/test_rowstep_ref.py``).
+(both checked on the host by ``tests/test_rowstep_ref.py``).  The hook fills the ops, builds the launch
+and runs it with the functions of ``csrc/rowlaunch.hpp`` that ``SchurPC`` and ``StokesPC`` use, and the
+family and width it reports are the answer the launcher itself dispatches on (``rows_kernel``,
+``shared_kernel``, ``il_kernel`` of ``csrc/kernels.hpp``), which ``run_case`` holds against its own table.
 
 Sizes -- each the smallest that reaches its regime (256 threads = 4 waves = 4 slices per workgroup):
 1, 63, 64, 65, 127, 128, 129 rows (positions past ``nrows`` inside a slice, R = 1 and R = 2); 511, 512,
