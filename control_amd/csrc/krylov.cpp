@@ -304,7 +304,8 @@ struct Conv {   // KSPConvergedDefault
             rnorm0 = rn;
             ttol = std::max(rtol * rn, atol);
         }
-        if (!std::isfinite(rn)) return KKT_DIVERGED_NANORINF;
+        // (a right-hand side whose preconditioned norm is not finite: no threshold could fire)
+        if (!std::isfinite(rn) || !std::isfinite(rnorm0)) return KKT_DIVERGED_NANORINF;
         if (rn <= ttol) return rn < atol ? KKT_CONVERGED_ATOL : KKT_CONVERGED_RTOL;
         if (rn >= divtol * rnorm0) return KKT_DIVERGED_DTOL;
         return 0;
@@ -352,7 +353,9 @@ void System::solve_minres(const double *d_b, double *d_u, int *its_out, int *rea
 
     pc_apply(b, Z);
     Conv conv(ksp.rtol, ksp.atol, ksp.divtol, std::sqrt(dot(Z, Z)));
-    for (double *p : {UOLD, VOLD, W, WOLD, WOOLD}) launch_fill(stream, p, 0.0, n_local);
+    // (U and V too: their first values come from y = a x + 0 y, and the arena may hold the
+    // NaNs of an earlier solve that ended non-finite)
+    for (double *p : {U, V, UOLD, VOLD, W, WOLD, WOOLD}) launch_fill(stream, p, 0.0, n_local);
     apply(d_u, R);
     launch_axpby(stream, R, 1.0, b, -1.0, n_local);   // r = b - A x
     pc_apply(R, Z);
@@ -390,6 +393,17 @@ void System::solve_minres(const double *d_b, double *d_u, int *its_out, int *rea
             const double rho1 = std::sqrt(rho0 * rho0 + beta * beta);
             const double rho2 = sold * alpha + coold * cold * betaold;
             const double rho3 = soold * betaold;
+            if (rho1 == 0.0) {
+                // the Lanczos vector vanished and the operator is singular on the Krylov
+                // space: there is no direction left to step along, x stays; true residual
+                apply(d_u, VOLD);
+                axpy(VOLD, -1.0, b);
+                np = std::sqrt(dot(VOLD, VOLD));
+                log(np);
+                reason = conv(np);
+                if (!reason) reason = KKT_DIVERGED_INDEFINITE_MAT;
+                break;
+            }
             c = rho0 / rho1;
             s = beta / rho1;
             {   // w_oold <- w_old, w_old <- w; the new w goes into the buffer w_oold leaves

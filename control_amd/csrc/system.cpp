@@ -422,7 +422,10 @@ void System::finalize() {
                     const Pattern &P = patterns[va.pattern];
                     ValueArray c = va;
                     c.d_vals = mem.alloc<double>(P.npadded);
-                    HIPCHK(hipMemcpy(c.d_vals, va.d_vals, P.npadded * 8, hipMemcpyDeviceToDevice));
+                    // on the handle's stream, which is non-blocking: the masks below are launched on
+                    // it and must find the copy done (and the copy the original still unmasked)
+                    HIPCHK(hipMemcpyAsync(c.d_vals, va.d_vals, P.npadded * 8,
+                                          hipMemcpyDeviceToDevice, stream));
                     c.colmask_set = want;
                     values.push_back(c);
                     info.bytes_device_values += P.npadded * 8;

@@ -190,7 +190,8 @@ class _ConvergedDefault:
         self.ttol = max(rtol * rnorm0, atol)
 
     def __call__(self, rnorm):
-        if not np.isfinite(rnorm):
+        # (a right-hand side whose preconditioned norm is not finite: no threshold could fire)
+        if not np.isfinite(rnorm) or not np.isfinite(self.rnorm0):
             return DIVERGED_NANORINF
         if self.rnorm0 == 0.0:
             # KSPConvergedDefault, "special case of zero RHS and nonzero guess": snorm = rnorm
@@ -407,6 +408,16 @@ def minres(A, B, b, x, *, rtol, atol, divtol, max_it, monitor=None, restart=None
         rho1 = np.sqrt(rho0 * rho0 + beta * beta)
         rho2 = sold * alpha + coold * cold * betaold
         rho3 = soold * betaold
+        if rho1 == 0.0:
+            # the Lanczos vector vanished and the operator is singular on the Krylov space:
+            # there is no direction left to step along, x stays; true residual
+            nrm = np.sqrt(dot(A(x) - b, A(x) - b))
+            res.rnorm = nrm
+            res.history.append(nrm)
+            if monitor is not None:
+                monitor(i + 1, nrm)
+            res.reason = conv(nrm) or DIVERGED_INDEFINITE_MAT
+            break
         c, s = rho0 / rho1, beta / rho1
         woold, wold = wold, w
         w = u - rho2 * wold
