@@ -252,8 +252,10 @@ struct TileArgs {
     int32_t debug_drop;                       // test hook: tile 0 skips publishing hand-off number
                                               // debug_drop (> 0), so its neighbours time out
     uint32_t epoch0;                          // hand-offs of this launch carry tags epoch0 + 1, ...
-    int32_t clear;                            // zero the granule buffers before the launch (the
-                                              // first tile launch of a replayed sequence)
+    int32_t clear;                            // host side, before the launch: 1 zero the hand-off
+                                              // granule buffers (the first tile launch of a replayed
+                                              // sequence), 2 those of the coarse exchanges (its first
+                                              // launch with coarse levels)
     int32_t fused_update;                     // 0: kernel variant without the level update
     int32_t hslots;                           // ring-entry slots per thread the plan needs
 };

@@ -594,6 +594,10 @@ bool SchurPC::fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out) {
         s.epoch0 = tile_epoch_cursor_;
         s.clear = !tile_cleared_;
         tile_cleared_ = true;
+        // the coarse exchanges' buffers with the first launch that uses them: on a one-level time
+        // shard the first tile launch of an application is the mass solve, without coarse levels
+        s.clear_coarse = coarse && !tile_coarse_cleared_;
+        tile_coarse_cleared_ = tile_coarse_cleared_ || coarse;
         tile_epoch_cursor_ += (uint32_t)(n * per_launch);
         out.push_back(s);
     };
@@ -826,6 +830,7 @@ void SchurPC::fuse_programs() {
     tile_epoch_cursor_ = 0;
     tile_cepoch_cursor_ = 0;
     tile_cleared_ = false;
+    tile_coarse_cleared_ = false;
     if (!legacy_tried_) {
         legacy_tried_ = true;
         legacy_ok_ = setup_row_programs();
@@ -891,35 +896,22 @@ void SchurPC::fuse_programs() {
         s.gmode = prog_mode_;
         out.push_back(s);
     };
-    size_t k = 0;
-    while (k < steps_.size()) {
-        size_t e = k;
+    // single-block steps [a, b) outside the tile form: two-grid levels stay plain launches, the
+    // rest becomes row programs
+    auto emit_rest = [&](size_t a, size_t b) {
+        if (a >= b) return;
         bool has_coarse = false;
-        // (the coarse corrections of two-grid levels sit between the single-block steps)
-        while (e < steps_.size() && ((steps_[e].kind == PcStep::ROWS && steps_[e].rows.nops == 1) ||
-                                     steps_[e].kind == PcStep::COARSE)) {
-            has_coarse = has_coarse || steps_[e].kind == PcStep::COARSE;
-            ++e;
+        for (size_t i = a; i < b; ++i) has_coarse = has_coarse || steps_[i].kind == PcStep::COARSE;
+        if (has_coarse) {
+            for (size_t i = a; i < b; ++i) out.push_back(steps_[i]);
+            return;
         }
-        if (e == k) {
-            out.push_back(steps_[k++]);
-            continue;
-        }
-        if (e - k >= 4 && use_tiles && fuse_tile_run(k, e, out)) {
-            k = e;
-            continue;
-        }
-        if (has_coarse) {      // two-grid levels outside the tile form stay plain launches
-            for (size_t i = k; i < e; ++i) out.push_back(steps_[i]);
-            k = e;
-            continue;
-        }
-        // row programs; the data-flow form needs phase ph >= 1 to gather exactly what phase
-        // ph - 1 produced, so a run is cut where that chain breaks
-        size_t q = k;
-        while (q < e) {
+        // the data-flow form needs phase ph >= 1 to gather exactly what phase ph - 1 produced,
+        // so a run is cut where that chain breaks
+        size_t q = a;
+        while (q < b) {
             size_t q1 = q + 1;
-            while (q1 < e) {
+            while (q1 < b) {
                 if (prog_granule_ && legacy_ok_) {
                     const RowOp &op = steps_[q1].rows.h_op, &prev = steps_[q1 - 1].rows.h_op;
                     bool chain = op.nterms > 0;
@@ -934,6 +926,51 @@ void SchurPC::fuse_programs() {
             else
                 for (size_t i = q; i < q1; ++i) out.push_back(steps_[i]);
             q = q1;
+        }
+    };
+    // the recorded sweep level that starts at step c and ends inside the run, if the tile form takes it
+    auto level_at = [&](size_t c, size_t e) -> const SweepLevel * {
+        for (const SweepLevel &lv : sweep_levels_)
+            if (lv.first == c && lv.eligible && lv.last > c && lv.last <= e) return &lv;
+        return nullptr;
+    };
+    size_t k = 0;
+    while (k < steps_.size()) {
+        size_t e = k;
+        // (the coarse corrections of two-grid levels sit between the single-block steps)
+        while (e < steps_.size() && ((steps_[e].kind == PcStep::ROWS && steps_[e].rows.nops == 1) ||
+                                     steps_[e].kind == PcStep::COARSE))
+            ++e;
+        if (e == k) {
+            out.push_back(steps_[k++]);
+            continue;
+        }
+        if (e - k >= 4 && use_tiles && fuse_tile_run(k, e, out)) {
+            k = e;
+            continue;
+        }
+        if (use_tiles && S_.sharded) {
+            // A rank with ONE level: the products between the sweeps have one op, so they are
+            // single-block steps of the same run as a sweep level wherever no hand-off separates
+            // them (rank 0 in front of the forward level, the last rank between the sweeps).  Every
+            // stretch of levels inside the run still becomes a tile launch, the steps between them
+            // stay what they were.
+            size_t pend = k, c = k;
+            while (c < e) {
+                size_t c2 = c;
+                while (const SweepLevel *lv = level_at(c2, e)) c2 = lv->last;
+                std::vector<PcStep> tiles;
+                if (c2 - c >= 4 && fuse_tile_run(c, c2, tiles)) {
+                    emit_rest(pend, c);
+                    out.insert(out.end(), tiles.begin(), tiles.end());
+                    pend = c = c2;
+                } else {
+                    c = std::max(c2, c + 1);
+                }
+            }
+            emit_rest(pend, e);
+        } else {
+            emit_rest(k, e);
         }
         k = e;
     }
@@ -2327,7 +2364,7 @@ void SchurPC::replay(size_t first, size_t last) {
                 a.granule_bytes = (unsigned)(words * sizeof(unsigned long long));
                 a.err = d_err_;
                 a.epoch0 = s.epoch0;
-                a.clear = s.clear ? 1 : 0;
+                a.clear = (s.clear ? 1 : 0) | (s.clear_coarse ? 2 : 0);
                 a.fused_update = s.fused ? 1 : 0;
                 a.hslots = tp.hslots;
                 a.stamps = S_.opts.stamps;

@@ -53,6 +53,7 @@ struct PcStep {
     uint32_t epoch0 = 0;            // TILE: first hand-off tag of this launch minus one
     bool fused = true;              // TILE: kernel variant with the level update
     bool clear = false;             // TILE: zero the granule buffers first
+    bool clear_coarse = false;      // TILE, coarse: zero the coarse exchanges' granule buffers first
     bool coarse = false;            // TILE: two-grid levels
     const double **d_einv = nullptr;   // TILE, coarse: per level (P^T A P)^-1
     uint32_t cepoch0 = 0;           // TILE, coarse: first coarse-exchange tag of this launch minus one
@@ -272,6 +273,7 @@ class SchurPC : public PcBase {
     unsigned long long *d_tg_[4] = {nullptr, nullptr, nullptr, nullptr};
     uint32_t tile_epoch_cursor_ = 0;    // hand-off tags handed out to the launches of one application
     bool tile_cleared_ = false;
+    bool tile_coarse_cleared_ = false;  // (the first tile launch of an application may have no coarse levels)
     bool prepare_tiles();
     bool fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out);
 

@@ -1429,11 +1429,12 @@ void launch_tile_sweep(hipStream_t s, const TileArgs &a, const TileLevel *d_leve
     };
     (void)hipGetLastError();
     if (a.clear) {
-        for (int i = 0; i < 2; ++i) {
-            launch_zero_bytes(s, a.gnew[i], granule_words * sizeof(unsigned long long));
-            launch_zero_bytes(s, a.gold[i], granule_words * sizeof(unsigned long long));
-        }
-        if (h_coarse)
+        if (a.clear & 1)
+            for (int i = 0; i < 2; ++i) {
+                launch_zero_bytes(s, a.gnew[i], granule_words * sizeof(unsigned long long));
+                launch_zero_bytes(s, a.gold[i], granule_words * sizeof(unsigned long long));
+            }
+        if (h_coarse && (a.clear & 2))
             for (int i = 0; i < 2; ++i) {
                 launch_zero_bytes(s, h_coarse->cg[i], h_coarse->cg_bytes);
                 launch_zero_bytes(s, h_coarse->eg[i], h_coarse->eg_bytes);

@@ -25,7 +25,10 @@ def launch(world, CN, ksp, target="run_rank"):
     q = ctx.Queue()
     sys.path.insert(0, HERE)
     import sharded_worker
-    if target == "run_rank":
+    if callable(target):
+        # a worker of another module (picklable: a module-level function or a partial of one)
+        procs = [ctx.Process(target=target, args=(r, world, conns[r], q)) for r in range(world)]
+    elif target == "run_rank":
         procs = [ctx.Process(target=sharded_worker.run_rank, args=(r, world, conns[r], CN, ksp, q))
                  for r in range(world)]
     else:
