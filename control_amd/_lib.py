@@ -68,7 +68,8 @@ class Info(C.Structure):
 class InfoRings(Info):
     """``kkt_info`` as the library fills it today: the fields of ``Info`` (whose list is pinned
     where it stood when ``blocks_unset`` was appended) followed by what was appended since."""
-    _fields_ = [("sweep_coarse_rings", C.c_int64)]
+    _fields_ = [("sweep_coarse_rings", C.c_int64), ("sweep_coarse_cache", C.c_int64),
+                ("sweep_coarse_ew", C.c_int64)]
 
 
 class StageTimes(C.Structure):
@@ -183,6 +184,21 @@ class RowStep(C.Structure):
                                             "uniform_w", "sorted", "nslices")])
 
 
+# kkt_debug_tile_levels: one level and the whole launch
+class TileLevel(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("q", "i", "j", "n_upd", "uq", "ui", "uj", "pad_")]
+                + [(n, C.c_double) for n in ("ca", "cy", "p1_scale", "post1", "post2")]
+                + [(n, c_f64p) for n in ("dinv", "coef", "einv", "bin", "out", "bout")])
+
+
+class TileLevels(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("nlevels", "its", "cycles", "own_cap")]
+                + [("levels", C.POINTER(TileLevel)), ("own_ptr", c_i32p), ("own_rows", c_i32p)]
+                + [(n, C.c_int32) for n in ("inputs_changed", "tiles", "threads", "row_slots",
+                                            "depth", "W", "nk_pad", "cache", "rings", "ew",
+                                            "n_coarse", "nrows")])
+
+
 PC_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, c_f64p, c_f64p, c_f64p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int, C.c_int)
 SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int64, C.c_int,
@@ -270,6 +286,7 @@ SIGNATURES = {
                                       c_f64p, C.c_double, C.c_double, c_f64p, c_f64p, c_f64p]),
     "kkt_debug_block_op": (C.c_int, [C.c_void_p, C.POINTER(BlockOp)]),
     "kkt_debug_row_step": (C.c_int, [C.c_void_p, C.POINTER(RowStep)]),
+    "kkt_debug_tile_levels": (C.c_int, [C.c_void_p, C.POINTER(TileLevels)]),
     "kkt_debug_set_steplock": (C.c_int, [C.c_void_p, C.POINTER(StepLock)]),
     "kkt_debug_apply_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "kkt_debug_pc_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),

@@ -67,6 +67,18 @@ static bool set_coarse_setup(Options &o, const char *v) {
     return o.coarse_columns || std::strcmp(v, "batched") == 0;
 }
 
+static bool set_tile_coarse_cache(Options &o, const char *v) {
+    if (std::strcmp(v, "auto") == 0) {
+        o.tile_coarse_cache = -1;
+        return true;
+    }
+    return set_int<&Options::tile_coarse_cache, 0, 2>(o, v);
+}
+static bool set_tile_coarse_rows(Options &o, const char *v) {
+    o.tile_coarse_full = std::strcmp(v, "full") == 0;
+    return o.tile_coarse_full || std::strcmp(v, "block") == 0;
+}
+
 static bool set_mass_tile_waves(Options &o, const char *v) {
     if (std::strcmp(v, "0") != 0 && std::strcmp(v, "4") != 0 && std::strcmp(v, "8") != 0) return false;
     o.mass_tile_waves = v[0] - '0';
@@ -103,6 +115,8 @@ static const OptionKey option_keys[] = {
     {"coarse_keep", "0 | 1", set_switch<&Options::coarse_keep>},
     {"coarse_blocks", "0 | 1", set_switch<&Options::coarse_blocks>},
     {"coarse_rings", "0 | 1", set_switch<&Options::coarse_rings>},
+    {"tile_coarse_cache", "auto | 0 | 1 | 2", set_tile_coarse_cache},
+    {"tile_coarse_rows", "block | full", set_tile_coarse_rows},
     {"mass_tiles", "0 | 1", set_switch<&Options::mass_tiles>},
     {"mass_tile_depth", "0..8", set_int<&Options::mass_tile_depth, 0, MASS_TILE_MAX_DEPTH>},
     {"mass_tile_rows", "0..65536", set_int<&Options::mass_tile_rows, 0, 65536>},
@@ -549,6 +563,14 @@ int kkt_debug_block_op(kkt_handle h, kkt_block_op *op) {
 
 int kkt_debug_row_step(kkt_handle h, kkt_row_step *step) {
     KKT_TRY(h, kkt::debug_row_step(S, step));
+}
+
+int kkt_debug_tile_levels(kkt_handle h, kkt_tile_levels *run) {
+    KKT_TRY(h, {
+        if (!run) fail(KKT_ERR_ARG, "null argument");
+        if (!S.pc) fail(KKT_ERR_STATE, "kkt_debug_tile_levels: no preconditioner built on this handle");
+        S.pc->debug_tile_levels(run);
+    });
 }
 
 int kkt_debug_set_steplock(kkt_handle h, const kkt_steplock *lock) {

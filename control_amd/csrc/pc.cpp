@@ -116,6 +116,7 @@ void SchurPC::values_changed() {
                      "%zu matrices\n", schur_its_, (long long)spectrum_steps_, mats_.size());
     S_.info.sweep_form = 0;
     S_.info.sweep_coarse_rings = 0;
+    S_.info.sweep_coarse_cache = S_.info.sweep_coarse_ew = 0;
     S_.info.sweep_tiles = S_.info.sweep_threads = S_.info.sweep_depth = S_.info.sweep_row_slots = 0;
     S_.info.sweep_its = schur_its_;
     fuse_programs();
@@ -355,6 +356,8 @@ bool SchurPC::prepare_tiles() {
             const int cache = pick < 2 ? 2 : pick < 4 ? 1 : 0;
             const bool rings = pick == 0 || pick == 2;
             if (rings && !tile_coarse_rings_built_) continue;
+            // (option "tile_coarse_cache": that level or none)
+            if (S_.opts.tile_coarse_cache >= 0 && cache != S_.opts.tile_coarse_cache) continue;
             const size_t lds_c = tile_sweep_lds_bytes(tp.nk_pad, max_its, h_tile_coarse_, cache, rings);
             if (lds_c <= 150 * 1024 &&
                 tp.ntiles <= tile_sweep_max_tiles(tp.W, tp.rpt, threads, lds_c, tp.hslots, true)) {
@@ -471,9 +474,32 @@ bool SchurPC::build_tile_coarse() {
         D.e_lo = up(e_lo);
         D.e_hi = up(e_hi);
         D.ew = ew;
-        if (ew < nc) {
-            // belt and braces: every inverse formed so far must be zero outside these ranges
-            // (exact zeros: elimination never touches an entry outside a block); else full rows
+        // (narrower than the whole row for some j -- also where ew, which starts at 64, is not
+        // below a small nc)
+        bool narrow = false;
+        for (int j = 0; j < nc; ++j) narrow = narrow || e_lo[j] > 0 || e_hi[j] < nc;
+        auto full_rows = [&] {
+            std::fill(e_lo.begin(), e_lo.end(), 0);
+            std::fill(e_hi.begin(), e_hi.end(), nc);
+            D.e_lo = up(e_lo);
+            D.e_hi = up(e_hi);
+            D.ew = nc;
+        };
+        if (S_.opts.tile_coarse_full) {
+            full_rows();      // option "tile_coarse_rows" = "full"
+        } else if (narrow) {
+            // The ranges are structure (the graph of P and the level pattern), made once per handle
+            // (prepare_tiles); the inverses are formed again with every values_changed().  What
+            // the block rows rely on for those later inverses is the structural argument, not a
+            // check: every set-up eliminates with partial pivoting inside a matrix that is block
+            // diagonal over these components -- a pivot column holds exact zeros outside its block,
+            // so no row outside the block is swapped in or updated (its multiplier is an exact
+            // zero, and a singular or non-finite block is refused by the set-up) -- and the
+            // component-block path writes exact zeros outside each block by construction
+            // (launch_coarse_block_scatter).  tests/test_gpu_tile_levels.py holds rebuilt block
+            // rows to full rows and to a fresh handle bit for bit.
+            // Belt and braces for the first build: every inverse formed so far is looked at, and
+            // the program applies full rows if one has an entry outside its ranges.
             auto d_flag = DevBuf<unsigned>::alloc(1);
             HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(unsigned), S_.stream));
             for (const double *inv : einvs_)
@@ -484,16 +510,14 @@ bool SchurPC::build_tile_coarse() {
             if (bad) {
                 std::fprintf(stderr, "[kkt] coarse inverse: entries outside the diagonal blocks of its "
                              "structure -- the tile program applies full rows\n");
-                std::fill(e_lo.begin(), e_lo.end(), 0);
-                std::fill(e_hi.begin(), e_hi.end(), nc);
-                D.e_lo = up(e_lo);
-                D.e_hi = up(e_hi);
-                D.ew = nc;
+                full_rows();
             }
         }
+        tile_e_lo_ = e_lo;
+        tile_e_hi_ = e_hi;
         if (S_.opts.verbose)
             std::fprintf(stderr, "[kkt] coarse inverse: rows of at most %d of %d columns (diagonal "
-                         "blocks of P^T A P)\n", ew, nc);
+                         "blocks of P^T A P)\n", D.ew, nc);
     }
     for (int i = 0; i < 2; ++i) {
         D.cg[i] = handle_mem_.alloc<unsigned long long>((size_t)nslots * 2);
@@ -986,10 +1010,16 @@ void SchurPC::fuse_programs() {
     S_.info.sweep_threads = form == 3 ? tile_plan_.threads : 0;
     S_.info.sweep_depth = form == 3 ? tile_plan_.depth : 0;
     S_.info.sweep_row_slots = form == 3 ? tile_plan_.rpt : 0;
-    bool rings = false;
+    bool rings = false, two_grid = false;
     for (const PcStep &s : steps_)
-        if (s.kind == PcStep::TILE && s.coarse) rings = h_tile_coarse_.ring_prolong != 0;
+        if (s.kind == PcStep::TILE && s.coarse) {
+            two_grid = true;
+            rings = h_tile_coarse_.ring_prolong != 0;
+        }
     S_.info.sweep_coarse_rings = rings ? 1 : 0;
+    S_.info.sweep_coarse_cache =
+        !two_grid ? 0 : h_tile_coarse_.cache_einv ? 2 : h_tile_coarse_.cache_lists ? 1 : 0;
+    S_.info.sweep_coarse_ew = two_grid ? h_tile_coarse_.ew : 0;
 }
 
 // The form replay() gives each row step, sweep program and tile launch (kkt_debug_pc_forms)

@@ -118,6 +118,10 @@ class PcBase {
     // kkt_debug_coarse_correction: the coarse space of the two-grid sub-solves, the Galerkin
     // launch constants of its set-up and the rows of P (false: built without a coarse space)
     virtual bool coarse_space(CoarseDev *, GalerkinDev *, int64_t *) const { return false; }
+    // kkt_debug_tile_levels: one launch of the tile program's two-grid levels on host data
+    virtual void debug_tile_levels(kkt_tile_levels *) {
+        fail(KKT_ERR_STATE, "kkt_debug_tile_levels: no two-grid tile program on this handle");
+    }
     // measurement: time the persistent programs of the next run() with events
     virtual void time_programs(float *ms, int *launches, int64_t *phases) {
         *ms = 0.f;
@@ -143,6 +147,7 @@ class SchurPC : public PcBase {
     void plain_forms(std::vector<int32_t> &out) const override;
     void solve_records(std::vector<double> &out) const override;
     bool coarse_space(CoarseDev *c, GalerkinDev *g, int64_t *n) const override;
+    void debug_tile_levels(kkt_tile_levels *run) override;
     void matrix_records(std::vector<double> &out) const override;
     void time_programs(float *ms, int *launches, int64_t *phases) override;
     int bc_set() const { return bc_set_; }
@@ -268,6 +273,7 @@ class SchurPC : public PcBase {
     TileCoarseDev *d_tile_coarse_ = nullptr;
     bool tile_coarse_ok_ = false;
     bool tile_coarse_rings_built_ = false;   // the lists hold the ring rows' entries
+    std::vector<int32_t> tile_e_lo_, tile_e_hi_;   // host copies of TileCoarseDev::e_lo / e_hi
     uint32_t tile_cepoch_cursor_ = 0;
     bool build_tile_coarse();
     unsigned long long *d_tg_[4] = {nullptr, nullptr, nullptr, nullptr};

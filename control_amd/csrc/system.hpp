@@ -38,6 +38,8 @@ struct Options {
     bool coarse_columns = false;                                  // "coarse_setup" = "columns"
     bool coarse_keep = false, coarse_blocks = true;
     bool coarse_rings = true;     // two-grid tile sweeps: tiles prolong onto their rings themselves
+    int tile_coarse_cache = -1;   // ... their coarse tables in LDS: 2 lists and inverse rows, 1 lists, 0 none; -1: what fits
+    bool tile_coarse_full = false;   // ... whole rows of the coarse inverse ("tile_coarse_rows" = "full")
     // batched mass solves, several Chebyshev steps per launch out of LDS (0: chosen)
     bool mass_tiles = true;
     int mass_tile_depth = 0, mass_tile_rows = 0, mass_tile_levels = 0, mass_tile_waves = 0;

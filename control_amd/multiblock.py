@@ -537,6 +537,67 @@ class MultiBlockSystem:
             ec.ctypes.data_as(_lib.c_f64p), out.ctypes.data_as(_lib.c_f64p), None))
         return rc, ec, out
 
+    _TILE_LEVELS_OUT = ("inputs_changed", "tiles", "threads", "row_slots", "depth", "W", "nk_pad",
+                        "cache", "rings", "ew", "n_coarse", "nrows")
+
+    def debug_tile_levels(self, levels=(), its=1, cycles=1):
+        """``kkt_debug_tile_levels``: one launch of the tile program's two-grid levels on the plan
+        and coarse tables of the preconditioner last built on this handle.  ``levels``: dicts with
+        ``block`` = (q, i, j), ``dinv``, ``b``, ``coef`` (its x 3), ``einv`` (n_coarse x n_coarse;
+        the same array object in several levels is one device copy), optionally ``p1_scale``,
+        ``post1``, ``post2``, and for a chained level ``update`` = (q, i, j), ``ca``, ``cy`` and
+        ``bout`` (True: wanted).  Returns the launch constants, ``own`` (per tile the global rows it
+        owns, in local order) and per level ``out`` and ``bout`` (None unless wanted), each whole:
+        ``BLOCK_GUARD`` guard elements on either side.  No levels: the constants and ``own`` only."""
+        G = _lib.BLOCK_GUARD
+        a = _lib.TileLevels()
+        self._ck(self._lib.kkt_debug_tile_levels(self._h, C.byref(a)))        # the sizes
+        n, nc = a.nrows, a.n_coarse
+        own_ptr = np.empty(a.tiles + 1, dtype=np.int32)
+        own_rows = np.empty(n, dtype=np.int32)
+        a.own_cap, a.own_ptr, a.own_rows = len(own_ptr), _lib.i32(own_ptr)[1], _lib.i32(own_rows)[1]
+        recs = (_lib.TileLevel * max(1, len(levels)))()
+        keep = []
+
+        def arr(v, shape, what):
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.shape != shape:
+                raise ValueError(f"{what} must have shape {shape}")
+            keep.append(v)
+            return v.ctypes.data_as(_lib.c_f64p)
+
+        def slot(v=None):
+            w = np.zeros(n + 2 * G)
+            if v is not None:
+                w[G:G + n] = np.asarray(v, dtype=np.float64).reshape(n)
+            keep.append(w)
+            return w
+        einvs, outs, bouts = {}, [], []
+        for r, L in zip(recs, levels):
+            r.q, r.i, r.j = L["block"]
+            if "update" in L:
+                r.n_upd = 1
+                r.uq, r.ui, r.uj = L["update"]
+            r.ca, r.cy = L.get("ca", 1.0), L.get("cy", 1.0)
+            r.p1_scale, r.post1, r.post2 = L.get("p1_scale", 1.0), L.get("post1", 1.0), L.get("post2", 1.0)
+            r.dinv = arr(L["dinv"], (n,), "dinv")
+            r.coef = arr(L["coef"], (its, 3), "coef")
+            if id(L["einv"]) not in einvs:
+                einvs[id(L["einv"])] = arr(L["einv"], (nc, nc), "einv")
+            r.einv = einvs[id(L["einv"])]
+            r.bin = slot(L["b"]).ctypes.data_as(_lib.c_f64p)
+            outs.append(slot())
+            r.out = outs[-1].ctypes.data_as(_lib.c_f64p)
+            bouts.append(slot() if L.get("bout") else None)
+            if bouts[-1] is not None:
+                r.bout = bouts[-1].ctypes.data_as(_lib.c_f64p)
+        a.nlevels, a.its, a.cycles, a.levels = len(levels), int(its), int(cycles), recs
+        self._ck(self._lib.kkt_debug_tile_levels(self._h, C.byref(a)))
+        res = {k: int(getattr(a, k)) for k in self._TILE_LEVELS_OUT}
+        res["own"] = [own_rows[own_ptr[t]:own_ptr[t + 1]].copy() for t in range(a.tiles)]
+        res["out"], res["bout"] = outs, bouts
+        return res
+
     def update_block_values(self, quadrant, i, j, A):
         """New values on a stored block's structure (Picard re-linearisation)."""
         _, indices, data = _as_csr(A)

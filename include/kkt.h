@@ -118,6 +118,19 @@ const char *kkt_last_error(kkt_handle h);
  *                                  coarse correction onto its ring rows itself instead of fetching
  *                                  them in a hand-off after every correction (same results; "0":
  *                                  the hand-off; see kkt_info.sweep_coarse_rings)
+ *   "tile_coarse_cache"  "auto" | "2" | "1" | "0"   two-grid sub-solves in the tile form: where the
+ *                                  tables of the coarse corrections live.  "2": a tile's lists and
+ *                                  the rows of the coarse inverse it owns in LDS, "1": the lists
+ *                                  only, "0": nothing (all read from memory); "auto": the first of
+ *                                  these that fits.  A forced level that does not fit leaves the
+ *                                  two-grid levels to another form, as any plan that does not fit
+ *                                  (same results; see kkt_info.sweep_coarse_cache).  The ring form
+ *                                  stays with "coarse_rings" and needs the lists in LDS.
+ *   "tile_coarse_rows"   "block" | "full"   ... a row of the coarse inverse is applied over the
+ *                                  columns of its diagonal block of P^T A P, or ("full") over all
+ *                                  n_coarse columns -- what the library does by itself when an
+ *                                  inverse has entries outside the blocks (same results; see
+ *                                  kkt_info.sweep_coarse_ew)
  *   "mass_tiles"    "1" | "0"      batched one-matrix solves (the mass solves) as several Chebyshev
  *                                  steps per launch out of LDS on a tile plan of their own, where
  *                                  the sweeps are programs ("persistent"), "lanes" is off, the
@@ -770,6 +783,58 @@ typedef struct kkt_row_step {
 } kkt_row_step;
 int kkt_debug_row_step(kkt_handle h, kkt_row_step *step);
 
+/* Test hook of the tile program's two-grid levels: ONE call of launch_tile_sweep (csrc/kernels.hpp,
+ * the variant with coarse corrections) on host data, on the handle's stream, with the tile plan,
+ * the coarse tables, the row mask and the error words of the two-grid block Schur preconditioner
+ * last built on this handle (kkt_set_pc_schur with a coarse space, after its first application) --
+ * so with what the options "tile_coarse_cache", "tile_coarse_rows", "coarse_rings", "tile_depth"
+ * and "tile_waves" made of them.  The launch runs `nlevels` levels of `cycles` x [coarse correction
+ * of the iterate, `its` sweeps] from a zero guess each.  Per level:
+ *   (q, i, j)   a stored block on the preconditioner's level pattern: the level's matrix
+ *   dinv        nrows doubles; coef: `its` triples c1, c2, c3 (sweep s: p+ = c1 p- + c2 p + c3 dinv
+ *               (b - A p), without the p- term in the first sweep after a correction); post1,
+ *               post2: the factors of the last sweep of the last cycle; p1_scale: the first step
+ *               p_1 = p1_scale dinv b, which a two-grid level computes and then overwrites
+ *   einv        n_coarse x n_coarse doubles, row-major, applied as (P^T A P)^-1: any matrix (with
+ *               "block" rows: zero outside the column range the tables give its rows).  Levels
+ *               that name the same array share one device copy, as levels with one matrix do.
+ *   n_upd = 0   a solo level: the right-hand side is bin
+ *   n_upd = 1   a chained level (not the first): b = ca U x_prev + cy bin with U the stored block
+ *               (uq, ui, uj) and x_prev the previous level's result, handed over inside the launch;
+ *               bout (may be NULL) receives b on the rows some tile owns
+ *   bin, out, bout   KKT_BLOCK_GUARD + nrows + KKT_BLOCK_GUARD doubles each.  The hook sets the
+ *               guards to KKT_KRYLOV_PAD and the nrows elements of out to +0.0 (the rows of the
+ *               mask belong to no tile and are never written); out and bout come back whole.
+ * What the launch only reads (bin, dinv) is downloaded again and compared: inputs_changed is the
+ * number of arrays that differ.  own_ptr (own_cap >= tiles + 1 entries) and own_rows (nrows
+ * entries) receive, tile by tile, the global rows a tile owns in its local order: tile t owns
+ * own_rows[own_ptr[t] .. own_ptr[t + 1]); unused entries are -1.  Further out: tiles, threads,
+ * row_slots, depth, W and nk_pad of the plan; cache (2 | 1 | 0), rings and ew of the coarse tables;
+ * n_coarse; nrows.  nlevels = 0 fills these and launches nothing (own_ptr, own_rows may be NULL).
+ * The workgroups of the program wait for one another: the hook launches only after the residency
+ * check of the production path for the LDS bytes of this `its`, zeroes the granule buffers as the
+ * first launch of an application does, and launches once.  A bounded-spin time-out comes back as
+ * KKT_ERR_STATE with the diagnostic record in kkt_last_error.  KKT_ERR_STATE also without a
+ * two-grid tile program on the handle.  KKT_ERR_ARG, nothing launched: nlevels < 0 or > 64, its or
+ * cycles < 1, a plan that is not resident with this `its`, a null operand, a block that is not
+ * stored or has another pattern, n_upd other than 0 | 1 or 1 on the first level, bout on a solo
+ * level, own_cap too small, "block" rows with a matrix that is non-zero outside its ranges. */
+typedef struct kkt_tile_level {
+    int32_t q, i, j, n_upd, uq, ui, uj, pad_;
+    double ca, cy, p1_scale, post1, post2;
+    const double *dinv, *coef, *einv;
+    double *bin, *out, *bout;
+} kkt_tile_level;
+typedef struct kkt_tile_levels {
+    int32_t nlevels, its, cycles, own_cap;
+    kkt_tile_level *levels;
+    int32_t *own_ptr, *own_rows;
+    /* out */
+    int32_t inputs_changed, tiles, threads, row_slots, depth, W, nk_pad, cache, rings, ew,
+        n_coarse, nrows;
+} kkt_tile_levels;
+int kkt_debug_tile_levels(kkt_handle h, kkt_tile_levels *run);
+
 /* Step-locked parity hook (tests): while set, kkt_solve / kkt_solve_device with gmres or
  * fgmres replace their Krylov basis v_0 .. v_it by the caller's vectors before inner step `it`
  * of global step s (s < n_steps), and record what the step produced from them: the classical
@@ -877,6 +942,13 @@ typedef struct kkt_info {
                                    onto the tiles' rings (option "coarse_rings", where the lists
                                    fit on chip); 0: it fetches them in a hand-off, or no two-grid
                                    tile program was built */
+    int64_t sweep_coarse_cache; /* where sweep_form == 3 and a two-grid tile program was built: 2 a
+                                   tile's coarse lists and its rows of the coarse inverse are in
+                                   LDS, 1 the lists only, 0 neither (option "tile_coarse_cache");
+                                   otherwise 0 */
+    int64_t sweep_coarse_ew;    /* ... and the row length of the coarse inverse in use: the widest
+                                   diagonal block of P^T A P (from a multiple of 64), or n_coarse
+                                   for full rows (option "tile_coarse_rows"); otherwise 0 */
 } kkt_info;
 int kkt_get_info(kkt_handle h, kkt_info *info);
 

@@ -6,7 +6,16 @@
 // each other and with the global recurrence; every local entry carries the generation of the
 // iterate it holds, and a read of an entry of another generation counts as stale.  Test
 // infrastructure: checks the plan, the lists and the scheme, not the GPU kernel.
-//   usage: tile_coarse_emu <nx> <ny> <nz> <ntiles> <depth> <its> <cycles> <components>
+//   usage: tile_coarse_emu <nx> <ny> <nz> <ntiles> <depth> <its> <cycles> <components> [--dump <file>]
+// --dump writes the run's data for tests/tile_level_ref.py, little-endian: the magic "TCEMU01\0", ten
+// int32 (n, nc, nnz of the level structure, nnz of P, tiles, levels, its, cycles, depth, W), then
+//   int32  indptr[n + 1], indices[nnz] of the level structure; uint8 mask[n]
+//   per level, doubles: F[nnz], U[nnz] (CSR order), dinv[n], B[n], E[nc * nc]
+//   doubles c1[its], c2[its], c3[its] (sweeps 1 .. its), then ca, cy, post1, post2
+//   int32  indptr[n + 1], indices[nnzP] of P, doubles values[nnzP]
+//   int32  own_ptr[tiles + 1], own_rows[own_ptr[tiles]]: the rows a tile owns, in local order
+//   per level, doubles: out[n], the result of the ring-form run (lists without rings: of the
+//   hand-off form -- the runs are equal bit for bit or the program fails)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -459,6 +468,53 @@ int main(int argc, char **argv) {
         // residual is today's where `depth` divides `its`, else it is new
         const long saved = cycles - (its % depth != 0 ? cycles - 1 : 0);
         if (LR.rings && h_plain[l] - h_ring[l] != saved) ++bad_counts;
+    }
+    if (argc >= 11 && std::strcmp(argv[9], "--dump") == 0) {
+        std::FILE *f = std::fopen(argv[10], "wb");
+        if (!f) return 5;
+        auto put = [&](const void *p, size_t bytes) {
+            if (bytes && std::fwrite(p, 1, bytes, f) != bytes) std::exit(5);
+        };
+        auto put_i = [&](const std::vector<int32_t> &v) { put(v.data(), v.size() * sizeof(int32_t)); };
+        auto put_d = [&](const std::vector<double> &v) { put(v.data(), v.size() * sizeof(double)); };
+        auto csr_vals = [&](const std::vector<double> &vals) {
+            std::vector<double> c;
+            for (int r = 0; r < n; ++r)
+                for (int k = 0; k < P.h_indptr[r + 1] - P.h_indptr[r]; ++k)
+                    c.push_back(vals[P.sell_index(r, k)]);
+            return c;
+        };
+        put("TCEMU01", 8);
+        const std::vector<int32_t> head = {n, nc, (int32_t)P.nnz, (int32_t)pj.size(), NT, nlev, its,
+                                           cycles, depth, W};
+        put_i(head);
+        put_i(P.h_indptr);
+        put_i(P.h_indices);
+        put(mask.data(), mask.size());
+        for (int l = 0; l < nlev; ++l) {
+            put_d(csr_vals(F[l]));
+            put_d(csr_vals(Um[l]));
+            put_d(dinv[l]);
+            put_d(B[l]);
+            put_d(E[l]);
+        }
+        put(c1.data() + 1, its * sizeof(double));
+        put(c2.data() + 1, its * sizeof(double));
+        put(c3.data() + 1, its * sizeof(double));
+        const std::vector<double> scal = {ca, cy, post1, post2};
+        put_d(scal);
+        put_i(pi);
+        put_i(pj);
+        put_d(pv);
+        std::vector<int32_t> own_ptr(1, 0), own_rows;
+        for (int t = 0; t < NT; ++t) {
+            for (int r = 0; r < nt(t, 0); ++r) own_rows.push_back(grow(t, r));
+            own_ptr.push_back((int32_t)own_rows.size());
+        }
+        put_i(own_ptr);
+        put_i(own_rows);
+        for (int l = 0; l < nlev; ++l) put_d(LR.rings ? o_ring[l] : o_long[l]);
+        if (std::fclose(f) != 0) return 5;
     }
     std::printf("hand-offs per level: %ld, ring form %ld (its %d depth %d cycles %d)\n", h_plain[0],
                 LR.rings ? h_ring[0] : -1, its, depth, cycles);

@@ -52,6 +52,8 @@ def test_ring_form_equals_the_handoff_form_and_the_oracle(CN, cycles, depth):
         assert info["1"]["sweep_form"] == 3 and info["0"]["sweep_form"] == 3, (its, info)
         assert info["1"]["sweep_depth"] == depth
         assert info["1"]["sweep_coarse_rings"] == 1 and info["0"]["sweep_coarse_rings"] == 0
+        # (41^2 in 52 tiles: the lists and the owned rows of the coarse inverse fit on chip)
+        assert info["1"]["sweep_coarse_cache"] == 2 and info["0"]["sweep_coarse_cache"] == 2
         assert info["1"]["program_fallbacks"] == 0 and info["0"]["program_fallbacks"] == 0
         assert np.array_equal(y["1"], y["0"]), (its, common.rel_err(y["1"], y["0"]))
         assert common.rel_err(y["1"], _oracle(CN, its, cycles)) < 1e-10, its
@@ -73,6 +75,7 @@ def test_stokes_velocity_sub_solves_in_ring_form(CN):
         inf = gpc.inner.info()
         rings[r], forms[r] = inf["sweep_coarse_rings"], inf["sweep_form"]
         assert inf["program_fallbacks"] == 0
+        assert inf["sweep_coarse_cache"] == (2 if inf["sweep_form"] == 3 else 0), inf
     assert rings["0"] == 0
     assert forms["1"] == forms["0"]
     # the velocity block's rows of P have at most 4 entries and its lists fit on chip: wherever
@@ -90,6 +93,7 @@ def test_ring_form_repeats_itself():
     pc = common.gpu_pc(p, MASS, (6, 0.07, 2.1), coarse=(P, 2))
     y0 = g.pc_apply(x, pc)
     assert g.info()["sweep_form"] == 3 and g.info()["sweep_coarse_rings"] == 1
+    assert g.info()["sweep_coarse_cache"] == 2
     for _ in range(19):
         assert np.array_equal(g.pc_apply(x, pc), y0)
     assert g.info()["program_fallbacks"] == 0

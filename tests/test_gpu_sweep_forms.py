@@ -216,6 +216,7 @@ TILE_FAMILIES = [("fd5", 160, 0, False), ("fd5", 160, 6, False),
 TILE_WAVES = (8, 12, 16)
 TILE_DEPTHS = (1, 2, 3, 4, 6, 8, 10, 12, 14, 16)
 _TILE_RUNS = {}
+caches = {}      # (space, cells) -> the placements of the coarse tables its plans took
 
 
 def tile_variant(forms):
@@ -247,15 +248,25 @@ def tile_family(space, n, cells, unfused):
             assert len(v) >= 1 and info["sweep_depth"] == depth
             assert all((t[2], t[1]) == (info["sweep_threads"], info["sweep_row_slots"]) and
                        t[4] == (co is not None) for t in v), (v, info)
+            # where the coarse tables of the plan live (auto: the first placement that fits)
+            cache, ew = info["sweep_coarse_cache"], info["sweep_coarse_ew"]
             if co is None:
+                assert (cache, ew, info["sweep_coarse_rings"]) == (0, 0, 0)
                 assert np.array_equal(y, plain), (space, opts, np.flatnonzero(y != plain)[:8])
             else:
+                nc = co[0].shape[1]
+                assert cache in (0, 1, 2) and ew >= min(nc, 64), info
+                assert info["sweep_coarse_rings"] <= (cache >= 1), info   # rings need the lists on chip
+                caches.setdefault((space, cells), set()).add(cache)
                 # by design not bit for bit: the tile program sums the coarse residual from the
                 # tiles' partial sums in tile order, the plain launches row by row (DESIGN.md
                 # section 6); the bar of test_gpu_coarse.py::
                 # test_coarse_tile_program_soak_and_sharded_equivalents
                 assert per_block_err(p, y, plain) < 1e-12, (space, opts, per_block_err(p, y, plain))
             reached |= v
+    if co is not None:
+        print(f"{space} cells {cells}: sweep_coarse_cache of the plans {sorted(caches[(space, cells)])}")
+        assert 2 in caches[(space, cells)]       # the shallow plans fit everything on chip
     _TILE_RUNS[key] = reached
     return reached
 
