@@ -25,16 +25,18 @@ class DeviceBackend:
     name = "device"
 
     def handle(self, s, diagonal=False):
-        g, _ = pair(s.nx, s.nx, s.diag_blocks() if diagonal else s.blocks(), 1, 1,
+        g, _ = pair(s.nx, s.nx, s.diag_blocks() if diagonal else s.blocks(), s.m, s.m,
                     None, None, None, None)
         return g
+
+    def pointer(self):
+        return DevicePointerBackend()
 
     def solve(self, h, s, spec, pc="id", x0=None, b=None):
         x = np.array(s.guesses["zero"] if x0 is None else x0, dtype=np.float64)
         b = s.b if b is None else b
-        u0, u1 = x[:s.nx].reshape(1, -1), x[s.nx:].reshape(1, -1)
-        r = h.solve(u0, u1, b[:s.nx].reshape(1, -1), b[s.nx:].reshape(1, -1),
-                    solver_parameters=spec.parameters(), pc_fn=kc.make_pc(s, pc))
+        r = h.solve(*s.split(x), *s.split(b), solver_parameters=spec.parameters(),
+                    pc_fn=kc.make_pc(s, pc))
         return kc.Result(int(r.reason), int(r.its), np.array(r.history, dtype=np.float64), x,
                          int(r.info["last_op_applies"]))
 

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def launch(world, CN, ksp, target="run_rank"):
+def launch(world, CN, ksp, target="run_rank", timeout=240):
     ctx = mp.get_context("spawn")
     # conns[r][q]: rank r's end of the duplex pipe to rank q
     conns = [[None] * world for _ in range(world)]
@@ -39,7 +39,7 @@ def launch(world, CN, ksp, target="run_rank"):
     res = {}
     try:
         for _ in range(world):
-            rank, status, payload = q.get(timeout=240)
+            rank, status, payload = q.get(timeout=timeout)
             assert status == "ok", f"rank {rank}: {payload}"
             res[rank] = payload
     finally:

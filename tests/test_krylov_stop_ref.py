@@ -2,7 +2,9 @@
 ``krylov_stop_ref.py`` checked against plain facts, the conditions the case table
 (``krylov_stop_cases.py``) needs of its instances asserted from the reference alone, and the whole
 table run through ``oracle.kkt_oracle`` (``gmres`` / ``fgmres`` / ``minres`` under
-``OracleSystem.solve``).  The device runs the same table in ``test_gpu_krylov_stopping.py``.
+``OracleSystem.solve``).  The device runs the same table in ``test_gpu_krylov_stopping.py``, and
+the table on the layered systems, proven here on one rank of the oracle, rank by rank on time
+shards in ``test_gpu_krylov_stopping_sharded.py``.
 
 Worst deviation of the oracle from the reference over every compared entry (bar
 ``10 N u kappa r_0 / r_k``, at most 1e-8): history 1.6e-13, iterate 2.7e-15.
@@ -121,9 +123,77 @@ def test_case_systems_have_the_stated_shape():
     assert np.array_equal(s.A, s.A.T) and np.linalg.eigvalsh(s.A).min() > 0.5
 
 
-@pytest.mark.parametrize("name,form,pc,guess", kc.B_COMBOS)
+def test_layered_systems_have_the_stated_shape():
+    assert kc.LAYER_NX == 5 and {kc.LAYERS[n][0] for n in ("L5", "L7")} == {5, 7}
+    for name, (m, _) in kc.LAYERS.items():
+        s = kc.system(name)
+        mask = kc.layer_mask(m, s.nx)
+        assert (s.m, s.nx, s.N) == (m, 5, 10 * m) and not s.A[~mask].any()
+        # every rank of 2, 3 and 5 owns whole levels, and no local length is a multiple of 32
+        for world in (2, 3, 5):
+            owned = [m // world + (r < m % world) for r in range(world)]
+            assert sum(owned) == m and min(owned) >= 1
+            assert all(10 <= 2 * n * s.nx <= 40 and (2 * n * s.nx) % 32 for n in owned)
+    for name in ("L5", "L7", "LS5"):
+        s = kc.system(name)
+        m, nx = s.m, s.nx
+        quads = s.blocks()
+        assert all(len(q) == m * m for q in quads)
+        dense = [[np.block([[np.zeros((nx, nx)) if q[(i, j)] is None else q[(i, j)].toarray()
+                             for j in range(m)] for i in range(m)]) for q in quads[:2]],
+                 [np.block([[np.zeros((nx, nx)) if q[(i, j)] is None else q[(i, j)].toarray()
+                             for j in range(m)] for i in range(m)]) for q in quads[2:]]]
+        assert np.array_equal(np.block(dense), s.A)
+        for q, quad in enumerate(quads):
+            for (i, j), blk in quad.items():
+                want = j in ((i - 1, i) if q in (0, 2) else (i, i + 1))
+                assert (blk is not None) == want and (blk is None or blk.nnz == nx * nx)
+    for name in ("L5", "L7"):
+        s = kc.system(name)
+        # every block of the structure is used, and the condition number is about 10
+        assert (s.A != 0)[kc.layer_mask(s.m, s.nx)].all()
+        assert 4 < np.linalg.cond(s.op_dense("left", "diag")) < 20
+        r_far = s.b - s.A @ s.guesses["far"]
+        assert np.linalg.norm(r_far) > 3 * np.linalg.norm(s.b)
+        for level in (0, s.m // 2, s.m - 1):
+            g0, g1 = s.split(s.guesses[f"far@{level}"])
+            assert g0[level].all() and g1[level].all()
+            assert not np.delete(g0, level, 0).any() and not np.delete(g1, level, 0).any()
+    s = kc.system("LS5")
+    k = s.m * s.nx
+    assert np.array_equal(s.A, s.A.T) and np.linalg.eigvalsh(s.A).min() > 0.5
+    blockdiag = np.kron(np.eye(s.m), np.ones((s.nx, s.nx))).astype(bool)
+    assert not s.A[:k, :k][~blockdiag].any() and not s.A[k:, k:][~blockdiag].any()
+    assert s.A[:k, k:][np.kron(np.eye(s.m, k=1), np.ones((s.nx, s.nx))).astype(bool)].all()
+    s = kc.system("Ltwo")
+    assert np.flatnonzero(s.b).tolist() == [0]            # on the first rank of every world
+
+
+@pytest.mark.parametrize("name,form,pc,guess", kc.B_COMBOS + kc.B_LAYER_COMBOS)
 def test_threshold_gaps_from_the_reference_alone(name, form, pc, guess):
     kc.check_b_conditions(name, form, pc, guess)
+
+
+@pytest.mark.parametrize("name,form,pc,m", kc.A_LAYER_COMBOS)
+def test_layered_histories_stay_under_the_cap_from_the_reference_alone(name, form, pc, m):
+    """At least 80 % of every history of cases A and B lies under the cap of the value bar."""
+    s = kc.system(name)
+    runs = [(kc.trajectory(name, form, pc, m).history, kc.a_max_its(m))]
+    if (name, form, pc, "zero") in kc.B_LAYER_COMBOS and m == kc.B_RESTART:
+        runs += [(kc.trajectory(name, form, pc, m, g).history, kc.b_steps(m)) for g in ("zero", "far")]
+    for hist, lengths in runs:
+        bar = 10 * s.N * kc.U_ROUND * kc.kappa(name, form, pc) * hist[0] / hist
+        for its in lengths:
+            assert (bar[:its + 1] < kc.BAR_CAP).mean() >= 0.8, (its, bar[:its + 1])
+
+
+@pytest.mark.parametrize("form", kc.GMRES_FORMS)
+@pytest.mark.parametrize("part", ["guess", "rhs"])
+@pytest.mark.parametrize("level", kc.LAYER_LEVELS)
+def test_one_level_cases_have_a_threshold_step_from_the_reference_alone(form, part, level):
+    traj, scale, k = kc.d_one_level_step("L5", form, "diag", part, level)
+    assert 2 <= k <= 6 and traj.history[k - 1] / traj.history[k] >= 1.5
+    assert (traj.rnorm0 == 0.0) == (part == "guess") and scale > 0.0
 
 
 # --------------------------------------------------------------------- the table on the oracle
@@ -205,6 +275,12 @@ def test_j_one_handle_many_solvers():
 @pytest.mark.parametrize("reason", sorted(kc.l_cases()))
 def test_l_python_layer_raises_or_returns(reason):
     kc.check_l(ORACLE, reason)
+
+
+@pytest.mark.parametrize("case", kc.layer_cases(), ids=lambda c: c[0])
+def test_layered_table_on_one_rank_of_the_oracle(case):
+    """Every case the time shards run (``test_gpu_krylov_stopping_sharded.py``), on one rank."""
+    assert kc.run_case(ORACLE, case)
 
 
 def test_report_worst_oracle_deviation():
