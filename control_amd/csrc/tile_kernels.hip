@@ -87,6 +87,24 @@ __device__ __forceinline__ unsigned opaque(unsigned x) {
     return x;
 }
 
+// A value every lane holds alike, moved into scalar registers.  The compiler keeps a pointer it
+// cannot prove uniform in a vector register pair: a buffer descriptor made from it is applied
+// lane by lane (a v_readfirstlane loop around every load, each with a wait of its own), and a
+// key compared once per level is spilled to scratch and waited for with everything in flight.
+__device__ __forceinline__ unsigned uniform(unsigned x) { return __builtin_amdgcn_readfirstlane(x); }
+template <typename P>
+__device__ __forceinline__ P uniform_ptr(P p) {
+    const unsigned long long u = (unsigned long long)p;
+    return (P)(((unsigned long long)uniform((unsigned)(u >> 32)) << 32) | uniform((unsigned)u));
+}
+// An offset no granule buffer reaches (they hold 16 bytes per row or slot, far below 2 GB): the
+// range check of the descriptor answers such a load with zeros -- by the documented behaviour of
+// raw buffers without a request to memory; that is reasoned, not measured, and nothing depends on
+// it but speed.  A poll slot that is dead or whose granule has arrived "loads" from here, so that
+// all polls of a round are one straight run of loads in front of one wait.  The price: such a
+// slot still issues an instruction per round where a branch issued none.
+constexpr int TILE_NO_POLL = 0x7ffffff0;
+
 // HPT_: ring-entry slots per thread of a hand-off (RPT + 1 unless the variant is short of registers)
 // COARSE: levels are cycles of [Galerkin coarse correction, `its` smoothing sweeps] (two-grid form
 // of the sub-solves); the plain variants compile none of it.
@@ -201,6 +219,17 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     // (the 1 024-thread variants -- 128 registers -- read the packed columns opaquely, see
     // opaque(); where the decoded offsets fit into registers, hoisting them is 2 % faster)
     constexpr bool OPQ = PACK && TMAX > 512;
+    // The two-grid variants at 128 (168) registers read the indices of their per-level requests
+    // opaquely too.  Hoisted out of the level loop, the sign-extended indices and the addresses
+    // made of them are a register pair per matrix entry, row and table -- 27 registers in scratch
+    // (W = 7), reloaded one by one with a wait each in front of the requests of the next level.
+    // Made where they are used they cost three instructions per request and level.
+    constexpr bool TIGHT = COARSE && TMAX > 512;
+    auto idx = [](const int i) { return TIGHT ? (int)opaque((unsigned)i) : i; };
+    // p[i] where there is an entry, the 0.0 it stands for where there is none
+    auto at = [&](const gcd_p p, const int i, const bool live) -> double {
+        return live ? p[idx(i)] : 0.0;
+    };
 #define KKT_CPK(sl, j) (OPQ ? opaque(cpk[sl][j]) : cpk[sl][j])
 #define KKT_COL(sl, k)                                                                       \
     (int)(PACK ? (((k) & 1) ? (KKT_CPK(sl, PACK ? (k) / 2 : 0) >> 16)                         \
@@ -229,8 +258,18 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     bool c_rings = false;
     int c_njp = 0, c_jx = 0;
     unsigned cepoch = A.cepoch0;
+    // the granule buffers of the exchanges as scalars (uniform_ptr), read once: both of each pair,
+    // the exchange number picks one
+    void *cg0 = nullptr, *cg1 = nullptr, *eg0 = nullptr, *eg1 = nullptr;
+    int cg_bytes = 0, eg_bytes = 0;
     if constexpr (COARSE) {
         const TileCoarseDev *cd = A.coarse;
+        cg0 = uniform_ptr((void *)cd->cg[0]);
+        cg1 = uniform_ptr((void *)cd->cg[1]);
+        eg0 = uniform_ptr((void *)cd->eg[0]);
+        eg1 = uniform_ptr((void *)cd->eg[1]);
+        cg_bytes = (int)uniform(cd->cg_bytes);
+        eg_bytes = (int)uniform(cd->eg_bytes);
         c_nc = cd->nc;
         c_jmax = cd->jmax;
         c_pstride = cd->pstride;
@@ -250,7 +289,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     int *CSLc = nullptr, *CIPc = nullptr, *RIPc = nullptr, *JGc = nullptr;
     int *PIPc = nullptr;     // ring form: entry offsets of all nk local rows (nk + 1 of them)
     uint16_t *RROWc = nullptr, *PKc = nullptr;
-    int pe0[RPT], pe1[RPT];
+    gci_p c_pip = nullptr;   // other forms: entry offsets of the own rows, read per correction
     bool c_cached = true;    // the tile's P entries are in LDS (3-D: 8 per row, they stay in memory)
     int c_re0 = 0, c_pq0 = 0;
     // Rows of (P^T A P)^-1: coarse function j belongs to tile j mod ntiles, which forms
@@ -294,7 +333,10 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         const gci_p rip = (gci_p)cd->r_ip + (size_t)tile * c_jmax;
         const gci_p pip = (gci_p)cd->p_ip + (size_t)tile * c_pstride;
         // (ring form: the ring rows' entries lie behind the own rows')
-        const int re0 = rip[0], re1 = rip[c_nj], pq0 = pip[0], pq1 = pip[c_rings ? nk : nt[0]];
+        // (uniform: first entries of the tile)
+        const int re0 = (int)uniform((unsigned)rip[0]), re1 = (int)uniform((unsigned)rip[c_nj]);
+        const int pq0 = (int)uniform((unsigned)pip[0]);
+        const int pq1 = (int)uniform((unsigned)pip[c_rings ? nk : nt[0]]);
         c_re0 = re0;
         c_pq0 = pq0;
         const gcu16_p rrow = (gcu16_p)cd->r_row, pk = (gcu16_p)cd->p_k;
@@ -317,18 +359,15 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         for (int i = tid; i < c_njp; i += T) JGc[i] = jg[i];
         if (c_rings)
             for (int i = tid; i <= nk; i += T) PIPc[i] = pip[i] - pq0;
-#pragma unroll
-        for (int sl = 0; sl < RPT; ++sl) {
-            const int r = sl * T + tid;
-            pe0[sl] = r < nt[0] ? pip[r] - pq0 : 0;
-            pe1[sl] = r < nt[0] ? pip[r + 1] - pq0 : 0;
-        }
+        c_pip = pip;
         __syncthreads();
     }
     const void *coef_key = nullptr;
     int cur = 0;             // X + cur * nkp: the newest iterate; the other half: the one before
     unsigned epoch = A.epoch0;   // tags never repeat between the launches of one application
     bool dead = false;       // a spin timed out: stop waiting, run to the end, results invalid
+    // (the keys -- vals_key, coef_key, einv_key -- are compared once per level or exchange: scalars,
+    // see uniform_ptr())
     const void *vals_key = nullptr;
     double v[RPT][W];
 
@@ -378,9 +417,9 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         ++epoch;
         double *Xc = X + cur * nkp, *Xo = X + (cur ^ 1) * nkp;
         const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)A.gnew[epoch & 1], 0, (int)A.granule_bytes, 0x00020000);
+            uniform_ptr((void *)A.gnew[epoch & 1]), 0, (int)A.granule_bytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)A.gold[epoch & 1], 0, (int)A.granule_bytes, 0x00020000);
+            uniform_ptr((void *)A.gold[epoch & 1]), 0, (int)A.granule_bytes, 0x00020000);
 #pragma unroll
         for (int sl = 0; sl < RPT; ++sl) {
             const int r = sl * T + tid;
@@ -392,14 +431,18 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         }
         // a granule {lo, tag, hi, tag} is read back by ONE 16-byte sc1 load (half the requests of
         // two 8-byte loads; a torn read shows as unequal tags and is simply read again)
-        u32x4 gn4[HPT], go4[HPT];
-        bool want_o[HPT];
+        // Per ring entry only "still wanted": a granule that arrives goes to LDS at once (nobody reads
+        // a ring row before the barrier below), so a poll needs registers only while it is in flight.
+        bool want_o[HPT], need_n[HPT], need_o[HPT];
 #pragma unroll
         for (int h = 0; h < HPT; ++h) {
             want_o[h] = both && hl[h] >= 0 && hl[h] < nk1;
-            gn4[h] = u32x4{0u, 0u, 0u, 0u};         // tag 0 never matches a hand-off number
-            go4[h] = u32x4{0u, 0u, 0u, 0u};
+            need_n[h] = hl[h] >= 0;
+            need_o[h] = want_o[h];
         }
+        auto value = [](const u32x4 g) {
+            return __longlong_as_double((long long)((unsigned long long)g.x | ((unsigned long long)g.z << 32)));
+        };
         // a poll samples memory about half a round trip after it is issued; the neighbours'
         // granules, stored at about the same time as this tile's, take about one: polling at
         // once mostly fails and costs a second round trip
@@ -408,18 +451,34 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         while (true) {
             asm volatile("" ::: "memory");   // the loads below are re-issued every round
             bool ok = true;
-            // only what has not arrived yet is requested again
+            // Every poll of the round is issued before the round's one wait.  Only what has not
+            // arrived yet is requested again: the other slots take TILE_NO_POLL, no branch around
+            // a load (a branch gives each load a wait of its own -- a round trip per slot).
+            u32x4 tn[HPT], to[HPT];
 #pragma unroll
             for (int h = 0; h < HPT; ++h) {
-                if (hl[h] >= 0 && (gn4[h].y != epoch || gn4[h].w != epoch))
-                    gn4[h] = __builtin_amdgcn_raw_buffer_load_b128(rn, hg[h] * 16, 0, 16 /* sc1 */);
-                if (want_o[h] && (go4[h].y != epoch || go4[h].w != epoch))
-                    go4[h] = __builtin_amdgcn_raw_buffer_load_b128(ro, hg[h] * 16, 0, 16 /* sc1 */);
+                tn[h] = __builtin_amdgcn_raw_buffer_load_b128(
+                    rn, need_n[h] ? hg[h] * 16 : TILE_NO_POLL, 0, 16 /* sc1 */);
+                to[h] = __builtin_amdgcn_raw_buffer_load_b128(
+                    ro, need_o[h] ? hg[h] * 16 : TILE_NO_POLL, 0, 16 /* sc1 */);
             }
+            __builtin_amdgcn_sched_barrier(0);
+            // the tags seen, for the time-out record (arrived before this round: the number itself)
+            unsigned seen[HPT][4];
 #pragma unroll
             for (int h = 0; h < HPT; ++h) {
-                if (hl[h] >= 0) ok &= gn4[h].y == epoch && gn4[h].w == epoch;
-                if (want_o[h]) ok &= go4[h].y == epoch && go4[h].w == epoch;
+                seen[h][0] = need_n[h] ? tn[h].y : (hl[h] >= 0 ? epoch : 0u);
+                seen[h][1] = need_n[h] ? tn[h].w : (hl[h] >= 0 ? epoch : 0u);
+                seen[h][2] = need_o[h] ? to[h].y : (want_o[h] ? epoch : 0u);
+                seen[h][3] = need_o[h] ? to[h].w : (want_o[h] ? epoch : 0u);
+                // (a torn read shows as unequal tags and is simply read again)
+                const bool hit_n = need_n[h] && tn[h].y == epoch && tn[h].w == epoch;
+                const bool hit_o = need_o[h] && to[h].y == epoch && to[h].w == epoch;
+                if (hit_n) Xc[hl[h]] = value(tn[h]);
+                if (hit_o) Xo[hl[h]] = value(to[h]);
+                need_n[h] = need_n[h] && !hit_n;
+                need_o[h] = need_o[h] && !hit_o;
+                ok &= !need_n[h] && !need_o[h];
             }
             if (ok || dead) break;
             if (++spins >= TILE_SPIN_LIMIT) {
@@ -430,31 +489,21 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                 if (atomicCAS(A.err + 1, 0u, 1u) == 0u) {
 #pragma unroll
                     for (int h = 0; h < HPT; ++h)
-                        if (hl[h] >= 0 && (gn4[h].y != epoch || gn4[h].w != epoch ||
-                                           (want_o[h] && (go4[h].y != epoch || go4[h].w != epoch)))) {
+                        if (need_n[h] || need_o[h]) {
                             A.err[8] = (unsigned)tile;
                             A.err[9] = epoch;
                             A.err[10] = (unsigned)hl[h];
                             A.err[11] = (unsigned)hg[h];
-                            A.err[12] = gn4[h].y;
-                            A.err[13] = gn4[h].w;
-                            A.err[14] = go4[h].y;
-                            A.err[15] = go4[h].w;
+                            A.err[12] = seen[h][0];
+                            A.err[13] = seen[h][1];
+                            A.err[14] = seen[h][2];
+                            A.err[15] = seen[h][3];
                             A.err[16] = both ? 1u : 0u;
                         }
                 }
                 break;
             }
             __builtin_amdgcn_s_sleep(1);
-        }
-#pragma unroll
-        for (int h = 0; h < HPT; ++h) {
-            if (hl[h] >= 0)
-                Xc[hl[h]] = __longlong_as_double(
-                    (long long)((unsigned long long)gn4[h].x | ((unsigned long long)gn4[h].z << 32)));
-            if (want_o[h])
-                Xo[hl[h]] = __longlong_as_double(
-                    (long long)((unsigned long long)go4[h].x | ((unsigned long long)go4[h].z << 32)));
         }
         // a wave that leaves this barrier knows every wave of the workgroup has finished reading
         // the granules of this epoch; only then may anyone publish the next one
@@ -471,11 +520,14 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     // right-hand side.  Called for level 0 up front and for level l + 1 BEFORE the hand-off that
     // ends level l, so that the HBM fetch (every tile asks for its slice of the next matrix at
     // the same moment) runs under the hand-off's wait instead of after it.
+    // (In the 1 024- and 768-thread two-grid variants that was not so while indices came back from
+    // scratch with a wait each between these requests; see TIGHT.  Emitted code of W = 7: result
+    // store, then all nine requests, no wait before the hand-off's polls.)
     double dinv[RPT], b[RPT];
     // (wide rows: the positions of all slots first, then the values -- two dependent round trips
     // instead of two per chunk of five entries)
     auto load_vals = [&](const double *ptr, const bool update_matrix) {
-        vals_key = (const void *)ptr;
+        vals_key = uniform_ptr((const void *)ptr);
         const gcd_p vp = (gcd_p)ptr;
         if constexpr (PACK) {
             // (the addresses of the positions must not be hoisted out of the level loop: they
@@ -495,8 +547,8 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                 for (int q = 0; q < G; ++q)
 #pragma unroll
                     for (int k = 0; k < W; ++k)
-                        v[s0 + q][k] = (gp[q][k] >= 0 && (!update_matrix || gr[s0 + q] >= 0))
-                                           ? vp[gp[q][k]] : 0.0;
+                        v[s0 + q][k] = at(vp, gp[q][k],
+                                          gp[q][k] >= 0 && (!update_matrix || gr[s0 + q] >= 0));
                 __builtin_amdgcn_sched_barrier(0);
             }
         } else {
@@ -505,7 +557,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
 #pragma unroll
                 for (int k = 0; k < W; ++k) {
                     const int gp = KKT_GP(sl, k);
-                    v[sl][k] = (gp >= 0 && (!update_matrix || gr[sl] >= 0)) ? vp[gp] : 0.0;
+                    v[sl][k] = at(vp, gp, gp >= 0 && (!update_matrix || gr[sl] >= 0));
                 }
         }
     };
@@ -513,12 +565,12 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         const gcd_p dp = (gcd_p)L.dinv, bp = (gcd_p)L.bin;
 #pragma unroll
         for (int sl = 0; sl < RPT; ++sl) {
-            dinv[sl] = gr[sl] >= 0 ? dp[gr[sl]] : 0.0;
-            b[sl] = gr[sl] >= 0 ? bp[gr[sl]] : 0.0;
+            dinv[sl] = at(dp, gr[sl], gr[sl] >= 0);
+            b[sl] = at(bp, gr[sl], gr[sl] >= 0);
         }
     };
     auto load_level = [&](const LevEarly &L) {
-        if ((const void *)L.vals != vals_key) load_vals(L.vals, false);
+        if (uniform_ptr((const void *)L.vals) != vals_key) load_vals(L.vals, false);
         load_db(L);
     };
     // Wide rows with the level update in the kernel (SEQ): there are no registers for a second
@@ -575,7 +627,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     auto prefetch_level = [&](const LevEarly &N) {
         if constexpr (PRE) {
             pre_issued = true;
-            pre_v = (const void *)N.vals != vals_key;
+            pre_v = uniform_ptr((const void *)N.vals) != vals_key;
             if (pre_v) {
                 const gcd_p vp = (gcd_p)N.vals;
 #pragma unroll
@@ -598,7 +650,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     auto adopt_level = [&](const LevEarly &N) {
         if constexpr (PRE) {
             if (pre_v) {
-                vals_key = (const void *)N.vals;
+                vals_key = uniform_ptr((const void *)N.vals);
 #pragma unroll
                 for (int sl = 0; sl < RPT; ++sl)
 #pragma unroll
@@ -621,11 +673,11 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         pre_issued = false;
         un_loaded = false;
         v_is_u = false;
-        if ((const void *)L.coef != coef_key) {
-            coef_key = (const void *)L.coef;
+        if (uniform_ptr((const void *)L.coef) != coef_key) {
+            coef_key = uniform_ptr((const void *)L.coef);
             const gcd_p cp = (gcd_p)(const double *)L.coef;
             __syncthreads();   // nobody still reads the old table
-            for (int i = tid; i < 3 * (COARSE ? its : its - 1); i += T) scoef[i] = cp[i];
+            for (int i = idx(tid); i < 3 * (COARSE ? its : its - 1); i += T) scoef[i] = cp[i];
             // (the barrier after the first step of the level orders these writes before their use)
         }
         // Everything loaded for the level is pinned in registers here: a value whose load is
@@ -647,7 +699,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                 if (!L.prev_in_lds) {
                     // produced before this launch (or by another rank): plain memory
                     const gcd_p xp = (gcd_p)L.x_prev;
-                    for (int l = tid; l < nk; l += T) Xc[l] = xp[grow[l]];
+                    for (int l = idx(tid); l < nk; l += T) Xc[l] = xp[grow[l]];
                     lds_barrier();
                 }
                 // b = ca * (sum_t U_t x_prev) + cy * b_in, 0 on boundary rows; p_1 = scale D^-1 b
@@ -709,7 +761,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
 #pragma unroll
                             for (int k = 0; k < CH; ++k)
                                 if (k0 + k < W)
-                                    vu[k] = (gr[sl] >= 0 && gp[k] >= 0) ? up[gp[k]] : 0.0;
+                                    vu[k] = at(up, gp[k], gr[sl] >= 0 && gp[k] >= 0);
 #pragma unroll
                             for (int k = 0; k < CH; ++k)
                                 if (k0 + k < W)
@@ -727,11 +779,11 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                     const double out2 = epi_first(L.p1_scale, dinv[sl], out);
                     b[sl] = out;
                     if (r < nk1) Xo[r] = out2;
-                    if (r < n0 && bo != nullptr) bo[gr[sl]] = out;
+                    if (r < n0 && bo != nullptr) bo[idx(gr[sl])] = out;
                 }
                 if constexpr (SEQ) {
                     // the level's own matrix, now that the update's has been used
-                    if ((const void *)L.vals != vals_key) load_vals(L.vals, false);
+                    if (uniform_ptr((const void *)L.vals) != vals_key) load_vals(L.vals, false);
                 }
             } else {
                 // first step of a solve on a right-hand side that is already final
@@ -797,6 +849,11 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                         double out = 0.0;
                         if (!msk[sl]) {
                             if (mode == 0) {
+                                // (the row's own entries are read here, behind the chain.  Read
+                                // with the gathers, one wait in front of the chain as in the plain
+                                // steps, they are four registers more across it: the 1 024-thread
+                                // variants spilled again and a step took 0.2 us longer --
+                                // profiles/coarse_polls.md)
                                 out = epi_cheb(has_old, cf1, Xo[r], true, cf2, Xc[r], cf3, dinv[sl],
                                                b[sl], acc, q1, q2);
                             } else {
@@ -846,9 +903,25 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                 // touch, a wave per function, lanes stride its list, fixed butterfly
                 ++cepoch;
                 {
+                    // (without the ring form: the entry ranges of the own rows in P, wanted at the
+                    // prolongation.  Carried through the whole launch they were two registers per
+                    // row slot that the ring form never reads, and the 128-register variants kept
+                    // them in scratch.  Requested here they have the exchange, 8 us of polls and
+                    // barriers, to land under; that is not measured on its own -- the flagship
+                    // runs the ring form -- and costs two loads from L2 per row slot and
+                    // correction where the parent read them once per launch.)
+                    int pe0[RPT], pe1[RPT];
+                    if (!c_rings) {
+#pragma unroll
+                        for (int sl = 0; sl < RPT; ++sl) {
+                            const int r = sl * T + tid;
+                            pe0[sl] = r < n0 ? c_pip[r] - c_pq0 : 0;
+                            pe1[sl] = r < n0 ? c_pip[r + 1] - c_pq0 : 0;
+                        }
+                    }
                     const double *Rb = X + (cur ^ 1) * nkp;
                     const __amdgpu_buffer_rsrc_t rc_ = __builtin_amdgcn_make_buffer_rsrc(
-                        (void *)cd->cg[cepoch & 1], 0, (int)cd->cg_bytes, 0x00020000);
+                        (cepoch & 1) ? cg1 : cg0, 0, cg_bytes, 0x00020000);
                     for (int k = wave; k < c_nj; k += nwaves) {
                         const int e0 = RIPc[k], e1 = RIPc[k + 1];
                         double a = 0.0;
@@ -867,30 +940,42 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                     }
                     // ---- every tile's partial sums ("the data is the flag"), then the coarse
                     // residual: contributions of a function summed in slot (= tile) order
-                    // (4 slots per thread in flight; more slots than 4 T: further rounds, whose
-                    // granules have mostly landed by then.  8 in flight made the compiler spill
-                    // ~200 registers in the 512-thread variants.)
+                    // (4 slots per thread, all of them in flight at once; more slots than 4 T:
+                    // further rounds, whose granules have mostly landed by then.  8 in flight made
+                    // the compiler spill ~200 registers in the 512-thread variants.)
                     constexpr int CSL = 4;
                     KKT_XS(0);      // restriction + publish
                     for (int i = 0; i < A.poll_delay; ++i) __builtin_amdgcn_s_sleep(1);
                     for (int base = 0; base < c_nslots; base += CSL * T) {
-                        u32x4 g[CSL];
+                        // (a partial sum that arrives goes to LDS at once -- nobody reads SL before
+                        // the barrier below -- so only "still wanted" is kept per slot)
+                        bool need[CSL];
 #pragma unroll
-                        for (int q = 0; q < CSL; ++q) g[q] = u32x4{0u, 0u, 0u, 0u};
+                        for (int q = 0; q < CSL; ++q) need[q] = base + q * T + tid < c_nslots;
+                        const bool live0 = need[0];
                         unsigned spins = 0;
                         while (true) {
                             asm volatile("" ::: "memory");
                             bool ok = true;
+                            // all polls of the round in front of its one wait; a slot that has
+                            // arrived is not requested again (TILE_NO_POLL)
+                            u32x4 t[CSL];
+#pragma unroll
+                            for (int q = 0; q < CSL; ++q)
+                                t[q] = __builtin_amdgcn_raw_buffer_load_b128(
+                                    rc_, need[q] ? (base + q * T + tid) * 16 : TILE_NO_POLL, 0, 16);
+                            __builtin_amdgcn_sched_barrier(0);
+                            // the tags seen in slot 0, for the time-out record
+                            const unsigned seen_y = need[0] ? t[0].y : (live0 ? cepoch : 0u);
+                            const unsigned seen_w = need[0] ? t[0].w : (live0 ? cepoch : 0u);
 #pragma unroll
                             for (int q = 0; q < CSL; ++q) {
-                                const int sidx = base + q * T + tid;
-                                if (sidx < c_nslots && (g[q].y != cepoch || g[q].w != cepoch))
-                                    g[q] = __builtin_amdgcn_raw_buffer_load_b128(rc_, sidx * 16, 0, 16);
-                            }
-#pragma unroll
-                            for (int q = 0; q < CSL; ++q) {
-                                const int sidx = base + q * T + tid;
-                                if (sidx < c_nslots) ok &= g[q].y == cepoch && g[q].w == cepoch;
+                                const bool hit = need[q] && t[q].y == cepoch && t[q].w == cepoch;
+                                if (hit)
+                                    SL[base + q * T + tid] = __longlong_as_double((long long)(
+                                        (unsigned long long)t[q].x | ((unsigned long long)t[q].z << 32)));
+                                need[q] = need[q] && !hit;
+                                ok &= !need[q];
                             }
                             if (ok || dead) break;
                             if (++spins >= TILE_SPIN_LIMIT) {
@@ -902,20 +987,13 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                                     A.err[9] = cepoch;
                                     A.err[10] = 0xffffu;            // a coarse exchange
                                     A.err[11] = (unsigned)(base + tid);
-                                    A.err[12] = g[0].y;
-                                    A.err[13] = g[0].w;
+                                    A.err[12] = seen_y;
+                                    A.err[13] = seen_w;
                                     A.err[16] = 2u;
                                 }
                                 break;
                             }
                             __builtin_amdgcn_s_sleep(1);
-                        }
-#pragma unroll
-                        for (int q = 0; q < CSL; ++q) {
-                            const int sidx = base + q * T + tid;
-                            if (sidx < c_nslots)
-                                SL[sidx] = __longlong_as_double((long long)(
-                                    (unsigned long long)g[q].x | ((unsigned long long)g[q].z << 32)));
                         }
                     }
                     KKT_XS(1);      // polls of this thread
@@ -932,13 +1010,13 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                     // ---- the coarse functions this tile owns (j = tile, tile + ntiles, ...): a wave
                     // per function, the product published as a granule of the same exchange number
                     const __amdgpu_buffer_rsrc_t re_ = __builtin_amdgcn_make_buffer_rsrc(
-                        (void *)cd->eg[cepoch & 1], 0, (int)cd->eg_bytes, 0x00020000);
+                        (cepoch & 1) ? eg1 : eg0, 0, eg_bytes, 0x00020000);
                     const int ntl = (int)gridDim.x;
                     // (row j only over the columns of its diagonal block, [e_lo[j], e_hi[j]) with
                     // e_lo a multiple of 64: a lane keeps the columns it had, the terms left out
                     // are exact zeros -- kernels.hpp, TileCoarseDev)
                     const gci_p elo = (gci_p)cd->e_lo, ehi = (gci_p)cd->e_hi;
-                    if (c_einv_cache && (const void *)einv != einv_key) {
+                    if (c_einv_cache && uniform_ptr((const void *)einv) != einv_key) {
                         // (the iterates' barrier above ordered every earlier read of EINVc)
                         for (int i = wave; i < c_nown; i += nwaves) {
                             const int j = tile + i * ntl;
@@ -947,7 +1025,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                             for (int q = lo + lane; q < hi; q += 64)
                                 EINVc[(size_t)i * c_ew + (q - lo)] = row[q];
                         }
-                        einv_key = (const void *)einv;
+                        einv_key = uniform_ptr((const void *)einv);
                         // (a wave reads back only the row it wrote: no barrier needed)
                     }
                     for (int i = wave; i < c_nown; i += nwaves) {
@@ -1054,6 +1132,11 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                     }
                     }
                 }
+                // the first sweep's row count (a full round follows) and coefficients, read in
+                // front of the barrier; the table was written at the start of the level, behind
+                // barriers long past
+                int nv_next = sn[depth - 1];
+                double cn1 = scoef[0], cn2 = scoef[1], cn3 = scoef[2];
                 // (the barrier inside the hand-off orders these stores before anyone's gathers)
                 lds_barrier();
                 if (stamps) {      // the coarse exchange, restriction to prolongation: slot 7
@@ -1065,14 +1148,21 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                 if (!c_rings) handoff(false);
                 cr = depth;
                 // ---- smoothing sweeps from the corrected iterate
+                // (row count and coefficients of a step are read from LDS one step ahead, as in the
+                // plain steps below: they land with the barrier's own wait)
                 for (int s = 1; s <= its; ++s) {
                     if (cr == 0) {
                         handoff(s >= 2);
                         cr = depth;
                     }
                     const bool last = cyc + 1 == A.cycles && s == its;
-                    cstep(0, sn[cr - 1], scoef[3 * (s - 1)], scoef[3 * (s - 1) + 1],
-                          scoef[3 * (s - 1) + 2], s >= 2, last ? post1 : 1.0, last ? post2 : 1.0);
+                    cstep(0, nv_next, cn1, cn2, cn3, s >= 2, last ? post1 : 1.0, last ? post2 : 1.0);
+                    if (s < its) {
+                        nv_next = sn[(cr - 1 == 0 ? depth : cr - 1) - 1];
+                        cn1 = scoef[3 * s];
+                        cn2 = scoef[3 * s + 1];
+                        cn3 = scoef[3 * s + 2];
+                    }
                     lds_barrier();
                     cur ^= 1;
                     --cr;
@@ -1225,7 +1315,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
 #pragma unroll
             for (int sl = 0; sl < RPT; ++sl) {
                 const int r = sl * T + tid;
-                if (r < n0) op[gr[sl]] = Xc[r];
+                if (r < n0) op[idx(gr[sl])] = Xc[r];
             }
             if (lev + 1 < A.nlevels) {
                 if (!nf_valid) Nf = read_early(&levels[lev + 1]);
