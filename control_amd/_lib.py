@@ -98,6 +98,15 @@ class CoarseStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class SpectrumStats(C.Structure):
+    _fields_ = ([(n, C.c_int64) for n in ("matrices", "batches", "lanczos_steps", "power_steps", "launches",
+                                          "syncs", "twin_syncs", "lanczos_syncs_max", "fallbacks",
+                                          "batch_bytes")] + [("ms", C.c_double)])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class StepLock(C.Structure):
     _fields_ = [("n_steps", C.c_int), ("restart", C.c_int), ("V", c_f64p), ("h", c_f64p),
                 ("v_next", c_f64p)]
@@ -277,6 +286,7 @@ SIGNATURES = {
     "kkt_time_pc_stages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(PcStageTimes)]),
     "kkt_coarse_setup_stats": (C.c_int, [C.c_void_p, C.POINTER(CoarseStats)]),
+    "kkt_spectrum_stats_get": (C.c_int, [C.c_void_p, C.POINTER(SpectrumStats)]),
     "kkt_debug_coarse_matrices": (C.c_int, [C.c_void_p, c_f64p, C.c_int64]),
     "kkt_debug_coarse_inverses": (C.c_int, [C.c_void_p, c_f64p, C.c_int64]),
     "kkt_debug_dense_inverse": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f64p, c_f64p, c_i32p]),

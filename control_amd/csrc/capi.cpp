@@ -114,6 +114,7 @@ static const OptionKey option_keys[] = {
     {"coarse_setup", "batched | columns", set_coarse_setup},
     {"coarse_keep", "0 | 1", set_switch<&Options::coarse_keep>},
     {"coarse_blocks", "0 | 1", set_switch<&Options::coarse_blocks>},
+    {"spectrum_batch", "0..4096", set_int<&Options::spectrum_batch, 0, 4096>},
     {"coarse_rings", "0 | 1", set_switch<&Options::coarse_rings>},
     {"tile_coarse_cache", "auto | 0 | 1 | 2", set_tile_coarse_cache},
     {"tile_coarse_rows", "block | full", set_tile_coarse_rows},
@@ -518,6 +519,13 @@ int kkt_coarse_setup_stats(kkt_handle h, kkt_coarse_stats *out) {
     KKT_TRY(h, {
         if (!out) fail(KKT_ERR_ARG, "null argument");
         *out = S.coarse_stats;
+    });
+}
+
+int kkt_spectrum_stats_get(kkt_handle h, kkt_spectrum_stats *out) {
+    KKT_TRY(h, {
+        if (!out) fail(KKT_ERR_ARG, "null argument");
+        *out = S.spectrum_stats;
     });
 }
 

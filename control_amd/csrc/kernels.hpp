@@ -3,6 +3,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include <string>
 
 #include "chebyshev.hpp"
@@ -380,6 +382,54 @@ void launch_mdot(hipStream_t s, const double *w, VecList V, int nv, int64_t n,
 void launch_norm2_finish(hipStream_t s, const double *dot, double *out);
 void launch_zero_bytes(hipStream_t s, void *p, size_t nbytes);   // kernel node, not a memset node
 void launch_add_constant(hipStream_t s, double *y, double v, int64_t n);   // y[i] += v
+
+// ---- batched spectrum estimates (spectrum_kernels.hip): B matrices of one pattern in lock-step.
+// Vector b of a family starts at base + b * stride (stride even, >= n); alpha / beta are
+// step-major (entry s of matrix b at [s * B + b]); everything per matrix lives on the device.
+struct SpecBatch {
+    int32_t B, max_steps;
+    int64_t n, stride;
+    double *r, *z, *p, *w;      // Lanczos: the PCG vectors; power iteration: v = r and z
+    double *part;               // B * REDUCE_BLOCKS partial sums
+    double *alpha, *beta;       // max_steps * B each
+    int32_t *na, *nb;           // entries recorded (power iteration: na = steps taken)
+    double *rz, *coef;          // <r, z>; the coefficient of the next vector update
+    double *mu2, *last;         // power iteration: the estimate and the one before
+    uint32_t *active;           // 0: the matrix is done, its workgroups leave at once
+};
+// what the second stage of a batched dot does with the sum (spectrum_host.hpp has the scalars)
+enum { SPEC_DOT_START, SPEC_DOT_PAP, SPEC_DOT_RZ, SPEC_DOT_NORM0, SPEC_DOT_NORM };
+// <x_b, y_b> for every active matrix with mdot_stage1 / mdot_stage2's chunks and trees, then:
+// START rz = dot, stop unless positive and finite; PAP a = rz / dot appended to alpha, stop before
+// that unless dot is positive and finite; RZ b = dot / rz appended to beta and rz = dot, stop
+// before that unless dot > 1e-28 rz and finite; NORM0 / NORM (after power step k) nv = sqrt(dot),
+// the 0.5 % rule from step 8 on, coef = 1 / nv.  A stop clears the matrix's `active` word.
+void launch_spec_dot(hipStream_t s, const SpecBatch &S, const double *x, const double *y, int mode,
+                     int k = 0);
+// R: r = -coef w + r; P: p = z + coef p; SCALE: r = coef r; COPY: p = z -- with the roundings of
+// launch_axpby(r, -a, w, 1), launch_axpby(p, 1, z, b), launch_axpby(v, 0, z, c)
+enum { SPEC_UPD_R, SPEC_UPD_P, SPEC_UPD_SCALE, SPEC_UPD_COPY };
+void launch_spec_update(hipStream_t s, const SpecBatch &S, int kind);
+// launch_vals_sym_skew over nmat matrices (d_m on the device), one flag word each
+struct SpecSplit { const double *a; double *h, *sk; };
+void launch_spec_sym_skew(hipStream_t s, const SpecSplit *d_m, int nmat, const int32_t *tpos, int64_t n,
+                          unsigned *nonsym);
+// 64-bit fingerprints of the bits of nmat value arrays: spec_fingerprint_blocks(n) words per array
+// (fixed order, no atomics), folded by the host with spec_fingerprint_fold
+inline int spec_fingerprint_blocks(int64_t n) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(64, (n + 2047) / 2048));
+}
+inline uint64_t spec_fingerprint_fold(const unsigned long long *w, int nwords) {
+    uint64_t h = 0x9e3779b97f4a7c15ull;
+    for (int k = 0; k < nwords; ++k) h = (h ^ (uint64_t)w[k]) * 0xff51afd7ed558ccdull + (h >> 29);
+    return h;
+}
+void launch_spec_fingerprint(hipStream_t s, const double *const *d_vals, int nmat, int64_t n,
+                             unsigned long long *out);
+// launch_vals_differ per pair: flag[q] |= 1 when pair q's arrays differ in any bit
+struct SpecPair { const double *a, *b; };
+void launch_spec_pairs_differ(hipStream_t s, const SpecPair *d_pairs, int npairs, int64_t n,
+                              unsigned *flag);
 
 // ---- coarse space of the two-grid sub-solves on the device: P by rows (prolongation) and by
 // columns (restriction), scratch for one correction

@@ -104,16 +104,26 @@ void SchurPC::values_changed() {
     solve_recs_.clear();
     einvs_.clear();
     pending_coarse_.clear();
+    S_.spectrum_stats = kkt_spectrum_stats{};
+    collect_matrices();
     if (d_.kind == KKT_PC_STATIONARY)
         build_stationary();
     else if (d_.kind == KKT_PC_INSTATIONARY_BE)
         build_BE();
     else
         build_CN();
+    pre_.clear();
+    pre_cls_.clear();
     flush_coarse();
-    if (S_.opts.verbose && d_.schur_emin <= 0)
+    if (S_.opts.verbose && d_.schur_emin <= 0) {
         std::fprintf(stderr, "[kkt] Chebyshev sub-solves: degree %d; %lld Lanczos steps spent on "
                      "%zu matrices\n", schur_its_, (long long)spectrum_steps_, mats_.size());
+        const kkt_spectrum_stats &t = S_.spectrum_stats;
+        std::fprintf(stderr, "[kkt] spectrum estimates: %lld matrices in %lld batches (at most %lld "
+                     "bytes each), %lld launches, %lld synchronisations, %lld fall-backs, %.1f ms\n",
+                     (long long)t.matrices, (long long)t.batches, (long long)t.batch_bytes,
+                     (long long)t.launches, (long long)t.syncs, (long long)t.fallbacks, t.ms);
+    }
     S_.info.sweep_form = 0;
     S_.info.sweep_coarse_rings = 0;
     S_.info.sweep_coarse_cache = S_.info.sweep_coarse_ew = 0;
@@ -1705,6 +1715,208 @@ void SchurPC::emit_coarse_solve(const Lin *upd, const Solve &sv, const Mat &F) {
     sweep_levels_.push_back(lv);
 }
 
+// the values of base + c * M~ and the Jacobi diagonal, into arrays of the current values' lifetime
+void SchurPC::form_matrix(const double *base_vals, double c, double *vals, double *dinv) {
+    const Pattern &P = S_.patterns[m_pat_];
+    hipStream_t st = S_.stream;
+    launch_vals_axpy(st, vals, base_vals, c, m_vals_, P.npadded);
+    if (mask_) launch_mask_columns(st, vals, P.d_col, mask_, P.npadded);
+    launch_extract_dinv(st, P.d_col, P.d_slice_off, vals, mask_, dinv, (int)nx_, P.nslices, P.R,
+                        P.d_perm);
+}
+
+// (base, shift) of every matrix the build of this kind solves with on this rank, in the order of
+// build_*'s schur_matrix(..., solved = true) calls.  What this list misses, schur_matrix handles
+// alone; what it has too much only costs an estimate.
+std::vector<std::pair<const double *, double>> SchurPC::solved_matrices() const {
+    std::vector<std::pair<const double *, double>> out;
+    const int n = n_, lo = lo_, hi = hi_;
+    if (d_.kind == KKT_PC_STATIONARY) {
+        const double c = 1.0 / std::sqrt(d_.beta);
+        out.emplace_back(block_vals(KKT_Q10, 0, 0), c);
+        out.emplace_back(block_vals(KKT_Q01, 0, 0), c);
+        return out;
+    }
+    const bool be = d_.kind == KKT_PC_INSTATIONARY_BE;
+    const double shift = d_.tau / std::sqrt(d_.beta);
+    auto coef = [&](int i) {
+        if (!be) return 0.5 * d_.tau / std::sqrt(d_.beta);
+        return i == 0 ? 0.0 : (i == n - 1 ? std::sqrt(d_.epsilon) * shift : shift);
+    };
+    const int imid = (lo + hi) / 2;
+    out.emplace_back(block_vals(KKT_Q10, imid, imid), coef(imid));
+    for (int i = lo; i < hi; ++i) out.emplace_back(block_vals(KKT_Q10, i, i), coef(i));
+    for (int i = hi - 1; i >= lo; --i) out.emplace_back(block_vals(KKT_Q01, i, i), coef(i));
+    return out;
+}
+
+void SchurPC::collect_matrices() {
+    pre_.clear();
+    pre_cls_.clear();
+    const int nbatch = S_.opts.spectrum_batch;
+    const bool estimates = d_.schur_emin <= 0;
+    if (nbatch <= 0 || !(estimates || coarse_cycles_ > 0)) return;
+    const Pattern &P = S_.patterns[m_pat_];
+    hipStream_t st = S_.stream;
+    kkt_spectrum_stats &stats = S_.spectrum_stats;
+    SpectrumCounters cnt;
+    HIPCHK(hipStreamSynchronize(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    // the candidates in creation order, each formed once
+    std::vector<MatKey> keys;
+    for (const auto &bc : solved_matrices()) {
+        uint64_t bits;
+        std::memcpy(&bits, &bc.second, sizeof bits);
+        const MatKey key(bc.first, bits);
+        if (pre_.count(key)) continue;
+        Pre pr;
+        pr.vals = values_mem_.alloc<double>(P.npadded);
+        pr.dinv = values_mem_.alloc<double>(nx_);
+        form_matrix(bc.first, bc.second, pr.vals, pr.dinv);
+        cnt.launches += mask_ ? 3 : 2;
+        pre_[key] = pr;
+        keys.push_back(key);
+    }
+    const int C = (int)keys.size();
+    if (C == 0) return;
+    // twins: a fingerprint per candidate, then the candidates of a (shift, fingerprint) group bit
+    // for bit against the group's first
+    std::vector<int> first_of(C);
+    for (int i = 0; i < C; ++i) first_of[i] = i;
+    DevPool tmp;
+    if (C > 1) {
+        std::vector<const double *> h_vals(C);
+        for (int i = 0; i < C; ++i) h_vals[i] = pre_[keys[i]].vals;
+        const double *const *d_vals = tmp.upload(h_vals.data(), h_vals.size());
+        const int nw = spec_fingerprint_blocks(P.npadded);
+        unsigned long long *d_fp = tmp.alloc<unsigned long long>((size_t)C * nw);
+        std::vector<unsigned long long> h_fp((size_t)C * nw);
+        launch_spec_fingerprint(st, d_vals, C, P.npadded, d_fp);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_fp.data(), d_fp, h_fp.size() * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        cnt.launches++;
+        cnt.syncs++;
+        stats.twin_syncs++;
+        std::map<std::pair<uint64_t, uint64_t>, int> groups;
+        std::vector<SpecPair> pairs;
+        std::vector<int> pair_of(C, -1);
+        for (int i = 0; i < C; ++i) {
+            const auto g = std::make_pair(keys[i].second, spec_fingerprint_fold(&h_fp[(size_t)i * nw], nw));
+            const auto it = groups.find(g);
+            if (it == groups.end()) {
+                groups[g] = i;
+                continue;
+            }
+            first_of[i] = it->second;
+            pair_of[i] = (int)pairs.size();
+            pairs.push_back(SpecPair{h_vals[it->second], h_vals[i]});
+        }
+        if (!pairs.empty()) {
+            const SpecPair *d_pairs = tmp.upload(pairs.data(), pairs.size());
+            unsigned *d_flag = tmp.alloc<unsigned>(pairs.size());
+            std::vector<unsigned> h_flag(pairs.size(), 1u);
+            HIPCHK(hipMemsetAsync(d_flag, 0, pairs.size() * sizeof(unsigned), st));
+            launch_spec_pairs_differ(st, d_pairs, (int)pairs.size(), P.npadded, d_flag);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(h_flag.data(), d_flag, h_flag.size() * sizeof(unsigned),
+                                  hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            cnt.launches++;
+            cnt.syncs++;
+            stats.twin_syncs++;
+            // equal fingerprints, different bits: left to schur_matrix's own comparison
+            for (int i = 0; i < C; ++i)
+                if (pair_of[i] >= 0 && h_flag[pair_of[i]]) first_of[i] = -1;
+        }
+    }
+    std::vector<int> reps;      // the first candidate of every class
+    for (int i = 0; i < C; ++i) {
+        Pre &pr = pre_[keys[i]];
+        if (first_of[i] == i) {
+            pr.cls = (int)pre_cls_.size();
+            pre_cls_.push_back(PreCls{});
+            reps.push_back(i);
+        } else if (first_of[i] >= 0) {
+            pr.cls = pre_[keys[first_of[i]]].cls;
+        }
+    }
+    // the distinct matrices' intervals, nbatch at a time: symmetric / skew split, Lanczos on the
+    // symmetric parts, power iteration on the skew parts of those that have one
+    const int32_t *tpos = estimates ? transpose_positions() : nullptr;
+    for (size_t r0 = 0; estimates && r0 < reps.size(); r0 += (size_t)nbatch) {
+        const int B = (int)std::min<size_t>((size_t)nbatch, reps.size() - r0);
+        DevPool bmem;      // the batch's split values: gone before the next batch
+        std::vector<const double *> lv(B), dv(B);
+        std::vector<SpecSplit> split(B);
+        std::vector<unsigned> nonsym(B, 0u);
+        for (int b = 0; b < B; ++b) {
+            const Pre &pr = pre_[keys[reps[r0 + b]]];
+            lv[b] = pr.vals;
+            dv[b] = pr.dinv;
+        }
+        size_t split_bytes = 0;
+        if (tpos) {
+            for (int b = 0; b < B; ++b)
+                split[b] = SpecSplit{lv[b], bmem.alloc<double>(P.npadded), bmem.alloc<double>(P.npadded)};
+            split_bytes = 2 * (size_t)B * P.npadded * sizeof(double);
+            const SpecSplit *d_split = bmem.upload(split.data(), split.size());
+            unsigned *d_flag = bmem.alloc<unsigned>(B);
+            HIPCHK(hipMemsetAsync(d_flag, 0, (size_t)B * sizeof(unsigned), st));
+            launch_spec_sym_skew(st, d_split, B, tpos, P.npadded, d_flag);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(nonsym.data(), d_flag, (size_t)B * sizeof(unsigned),
+                                  hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            cnt.launches++;
+            cnt.syncs++;
+            for (int b = 0; b < B; ++b)
+                if (nonsym[b]) lv[b] = split[b].h;
+        }
+        SpectrumCounters bc;
+        const std::vector<Spectrum> sp = jacobi_spectrum_batch(S_, m_pat_, lv, dv, mask_, 400, &bc);
+        // (a matrix without an interval fails the build in schur_matrix: no radius for it, as there)
+        std::vector<const double *> sk, sd;
+        std::vector<int> who;
+        for (int b = 0; b < B; ++b)
+            if (nonsym[b] && sp[b].emin > 0.0 && sp[b].emax > sp[b].emin) {
+                sk.push_back(split[b].sk);
+                sd.push_back(dv[b]);
+                who.push_back(b);
+            }
+        std::vector<int> psteps;
+        const std::vector<double> radius =
+            jacobi_skew_radius_batch(S_, m_pat_, sk, sd, mask_, 40, &psteps, &bc);
+        HIPCHK(hipGetLastError());
+        for (int b = 0; b < B; ++b) {
+            PreCls &pc = pre_cls_[pre_[keys[reps[r0 + b]]].cls];
+            pc.estimated = true;
+            pc.sp = sp[b];
+            pc.nonsym = nonsym[b] != 0;
+        }
+        for (size_t q = 0; q < who.size(); ++q) {
+            PreCls &pc = pre_cls_[pre_[keys[reps[r0 + who[q]]]].cls];
+            pc.radius = radius[q];
+            pc.power = psteps[q];
+        }
+        cnt.launches += bc.launches;
+        cnt.syncs += bc.syncs;
+        cnt.lanczos_syncs_max = std::max(cnt.lanczos_syncs_max, bc.lanczos_syncs_max);
+        cnt.bytes = std::max<int64_t>(cnt.bytes, bc.bytes + (int64_t)split_bytes);
+        stats.batches++;
+        stats.matrices += B;
+        if (S_.opts.verbose)
+            std::fprintf(stderr, "[kkt] spectrum batch of %d matrices holds %lld bytes\n", B,
+                         (long long)(bc.bytes + (int64_t)split_bytes));
+    }
+    stats.launches += cnt.launches;
+    stats.syncs += cnt.syncs;
+    stats.lanczos_syncs_max = cnt.lanczos_syncs_max;
+    stats.batch_bytes = cnt.bytes;
+    stats.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 // base + c * M with bc rows/cols of `assemble(form, bcs=...)`, and its Jacobi diagonal
 SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solved) {
     uint64_t bits;
@@ -1718,12 +1930,15 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
     if (it != mats_.end()) {
         m = it->second;      // formed for products only, now solved with: interval and inverse below
     } else {
-        m.vals = values_mem_.alloc<double>(P.npadded);
-        m.dinv = values_mem_.alloc<double>(nx_);
-        launch_vals_axpy(st, m.vals, base_vals, c, m_vals_, P.npadded);
-        if (mask_) launch_mask_columns(st, m.vals, P.d_col, mask_, P.npadded);
-        launch_extract_dinv(st, P.d_col, P.d_slice_off, m.vals, mask_, m.dinv, (int)nx_, P.nslices,
-                            P.R, P.d_perm);
+        const auto pre = pre_.find(key);
+        if (pre != pre_.end()) {
+            m.vals = pre->second.vals;      // formed by the collection pass
+            m.dinv = pre->second.dinv;
+        } else {
+            m.vals = values_mem_.alloc<double>(P.npadded);
+            m.dinv = values_mem_.alloc<double>(nx_);
+            form_matrix(base_vals, c, m.vals, m.dinv);
+        }
         m.index = (int)mat_recs_.size();
         MatRec r;
         r.c = c;
@@ -1738,9 +1953,29 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
     // level of a time-invariant operator) shares its spectrum estimate and its coarse inverse
     // (matrices only multiplied with carry neither: emax == 0)
     const Mat *twin = nullptr;
+    kkt_spectrum_stats &stats = S_.spectrum_stats;
+    const bool batched = S_.opts.spectrum_batch > 0;
+    auto cls_of = [&](const MatKey &k) {
+        const auto pre = pre_.find(k);
+        return pre == pre_.end() ? -1 : pre->second.cls;
+    };
+    const int cls = cls_of(key);
+    bool fell_back = false;
+    const auto t0 = std::chrono::steady_clock::now();
     if (d_.schur_emin <= 0 || coarse_cycles_ > 0) {
         for (auto &kv : mats_) {
             if (kv.first.second != bits || kv.second.emax <= 0.0) continue;
+            // both compared by the collection pass: equal values have one class
+            const int other = cls_of(kv.first);
+            if (cls >= 0 && other >= 0) {
+                if (cls != other) continue;
+                twin = &kv.second;
+                break;
+            }
+            fell_back = batched;
+            stats.launches++;
+            stats.syncs++;
+            stats.twin_syncs++;
             auto d_flag = DevBuf<unsigned>::alloc(1);
             HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(unsigned), st));
             launch_vals_differ(st, m.vals, kv.second.vals, P.npadded, d_flag.get());
@@ -1772,17 +2007,35 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
         // the skew part (|Im lambda| <= rho(D^-1/2 (A - A^T) / 2 D^-1/2)).
         DevBuf<double> hv, sv2;
         unsigned nonsym = 0;
-        const int32_t *tpos = transpose_positions();
-        if (tpos) {
-            hv = DevBuf<double>::alloc(P.npadded);
-            sv2 = DevBuf<double>::alloc(P.npadded);
-            auto d_flag = DevBuf<unsigned>::alloc(1);
-            HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(unsigned), st));
-            launch_vals_sym_skew(st, m.vals, tpos, hv.get(), sv2.get(), P.npadded, d_flag.get());
-            HIPCHK(hipMemcpyAsync(&nonsym, d_flag.get(), sizeof nonsym, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
+        Spectrum sp{0.0, 0.0, 0};
+        double radius = 0.0;
+        int power = 0;
+        const bool have = cls >= 0 && pre_cls_[cls].estimated;
+        if (have) {
+            const PreCls &pc = pre_cls_[cls];      // estimated in a batch, on equal values
+            sp = pc.sp;
+            nonsym = pc.nonsym;
+            radius = pc.radius;
+            power = pc.power;
+        } else {
+            fell_back = batched;
+            stats.matrices++;
+            const int32_t *tpos = transpose_positions();
+            if (tpos) {
+                hv = DevBuf<double>::alloc(P.npadded);
+                sv2 = DevBuf<double>::alloc(P.npadded);
+                auto d_flag = DevBuf<unsigned>::alloc(1);
+                HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(unsigned), st));
+                launch_vals_sym_skew(st, m.vals, tpos, hv.get(), sv2.get(), P.npadded, d_flag.get());
+                HIPCHK(hipMemcpyAsync(&nonsym, d_flag.get(), sizeof nonsym, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+            }
+            sp = jacobi_spectrum(S_, m_pat_, nonsym ? hv.get() : m.vals, m.dinv, mask_, 400);
+            if (nonsym && sp.emin > 0.0 && sp.emax > sp.emin)
+                radius = jacobi_skew_radius(S_, m_pat_, sv2.get(), m.dinv, mask_, 40, &power);
+            hv.reset(), sv2.reset();   // before the coarse inverse below is allocated
         }
-        const Spectrum sp = jacobi_spectrum(S_, m_pat_, nonsym ? hv.get() : m.vals, m.dinv, mask_, 400);
+        stats.lanczos_steps += sp.steps;
         spectrum_steps_ += sp.steps;
         rec.lanczos = sp.steps;
         if (!(sp.emin > 0.0) || !(sp.emax > sp.emin))
@@ -1790,18 +2043,20 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
         m.emin = 0.85 * sp.emin;      // Ritz values lie inside the spectrum
         m.emax = 1.05 * sp.emax;
         if (nonsym) {
-            int steps = 0;
-            m.eimag = 1.1 * jacobi_skew_radius(S_, m_pat_, sv2.get(), m.dinv, mask_, 40, &steps);
-            spectrum_steps_ += 2 * steps;
-            rec.power = steps;
+            m.eimag = 1.1 * radius;
+            spectrum_steps_ += 2 * power;
+            stats.power_steps += power;
+            rec.power = power;
         }
-        hv.reset(), sv2.reset();   // before the coarse inverse below is allocated
         // two-grid form: the sweeps smooth -- they cover the upper part of the spectrum, the
         // coarse space the rest (emax / 30: measured optimum for 8 sweeps at coarse cells of 8
         // to 16 mesh widths, scripts/proto_subsolve.py)
         if (coarse_cycles_ > 0) m.emin = std::max(m.emin, m.emax / 30.0);
         m.est = KKT_PC_EST_LANCZOS;
     }
+    if (fell_back) stats.fallbacks++;
+    if (!batched || fell_back)      // (the host's clock: every branch taken here ends in a synchronisation)
+        stats.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (coarse_cycles_ > 0) m.einv = twin && twin->einv ? twin->einv : coarse_inverse(m.vals);
     rec.est = m.est;
     rec.coarse = m.einv != nullptr;

@@ -8,18 +8,13 @@
 
 #include "comm.hpp"
 #include "rowlaunch.hpp"
+#include "spectrum_host.hpp"
 #include "system.hpp"
 #include "tiles.hpp"
 
 namespace kkt {
 
-// [emin, emax] of the Jacobi-scaled matrix D^-1 A by `steps` Lanczos steps on the device
-// (spectrum.cpp); Ritz values: emin is an upper estimate of the smallest eigenvalue, emax a
-// lower estimate of the largest.
-struct Spectrum {
-    double emin, emax;
-    int steps;
-};
+// (Spectrum: spectrum_host.hpp)
 Spectrum jacobi_spectrum(System &S, int pattern, const double *vals, const double *dinv,
                          const uint8_t *rowmask, int max_steps,
                          bool zero_mean = false);
@@ -27,6 +22,21 @@ Spectrum jacobi_spectrum(System &S, int pattern, const double *vals, const doubl
 // (power iteration on -(D^-1 S)^2; an estimate from below)
 double jacobi_skew_radius(System &S, int pattern, const double *skew_vals, const double *dinv,
                           const uint8_t *rowmask, int max_steps, int *steps_out);
+
+// The same for a batch of matrices on one pattern in lock-step (spectrum.cpp): results equal the
+// one-matrix functions' bit for bit.  Counters add up over calls; bytes and lanczos_syncs_max keep
+// the largest.
+struct SpectrumCounters {
+    int64_t launches = 0, syncs = 0, lanczos_syncs_max = 0, bytes = 0;
+};
+std::vector<Spectrum> jacobi_spectrum_batch(System &S, int pattern, const std::vector<const double *> &vals,
+                                            const std::vector<const double *> &dinv, const uint8_t *rowmask,
+                                            int max_steps, SpectrumCounters *cnt);
+std::vector<double> jacobi_skew_radius_batch(System &S, int pattern,
+                                             const std::vector<const double *> &skew_vals,
+                                             const std::vector<const double *> &dinv,
+                                             const uint8_t *rowmask, int max_steps,
+                                             std::vector<int> *steps_out, SpectrumCounters *cnt);
 
 struct PcStep {
     enum Kind { ROWS, TIME, COPY, COMM, PROG, TILE, EV_RECORD, EV_WAIT, COARSE, ROWS_IL, TILE_CHEB } kind;
@@ -293,6 +303,28 @@ class SchurPC : public PcBase {
     // `solved`: false for matrices only multiplied with (CN: c M~ and the upper blocks): no
     // interval, no coarse inverse (formed later if the same matrix is solved with after all)
     Mat schur_matrix(const double *base_vals, double c, bool solved = true);
+    // Collection pass of a build (option "spectrum_batch" >= 1): the matrices the build will
+    // solve with, in the order of its schur_matrix calls, formed at once; their twins found with
+    // one fingerprint launch and one comparison launch; the distinct ones estimated in lock-step
+    // batches.  schur_matrix then takes values, twin and interval from here -- and still forms,
+    // compares and estimates by itself whatever the pass did not cover (counted as a fall-back).
+    using MatKey = std::pair<const double *, uint64_t>;
+    struct Pre {
+        double *vals = nullptr, *dinv = nullptr;
+        int cls = -1;                    // index into pre_cls_: equal values, equal shift (-1: not compared)
+    };
+    struct PreCls {
+        bool estimated = false;
+        Spectrum sp{0.0, 0.0, 0};
+        bool nonsym = false;
+        double radius = 0.0;
+        int power = 0;
+    };
+    std::map<MatKey, Pre> pre_;
+    std::vector<PreCls> pre_cls_;
+    void form_matrix(const double *base_vals, double c, double *vals, double *dinv);
+    std::vector<std::pair<const double *, double>> solved_matrices() const;
+    void collect_matrices();
     void emit_lin(const std::vector<Lin> &ops);
     void emit_cheb(const std::vector<Cheb> &ops);
     double *il_P_[3] = {nullptr, nullptr, nullptr};

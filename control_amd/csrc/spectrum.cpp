@@ -18,51 +18,44 @@ namespace kkt {
 
 namespace {
 
-// eigenvalues of the symmetric tridiagonal matrix (d, e) by implicit QL (EISPACK tql1)
-std::vector<double> tridiag_eigenvalues(std::vector<double> d, std::vector<double> e) {
-    const int n = (int)d.size();
-    e.resize(n, 0.0);
-    for (int l = 0; l < n; ++l) {
-        int iter = 0, m;
-        do {
-            for (m = l; m < n - 1; ++m) {
-                const double dd = std::fabs(d[m]) + std::fabs(d[m + 1]);
-                if (std::fabs(e[m]) <= 1e-16 * dd) break;
-            }
-            if (m != l) {
-                if (++iter > 200) break;
-                double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
-                double r = std::hypot(g, 1.0);
-                g = d[m] - d[l] + e[l] / (g + (g >= 0 ? std::fabs(r) : -std::fabs(r)));
-                double s = 1.0, c = 1.0, p = 0.0;
-                int i;
-                for (i = m - 1; i >= l; --i) {
-                    double f = s * e[i];
-                    const double b = c * e[i];
-                    r = std::hypot(f, g);
-                    e[i + 1] = r;
-                    if (r == 0.0) {
-                        d[i + 1] -= p;
-                        e[m] = 0.0;
-                        break;
-                    }
-                    s = f / r;
-                    c = g / r;
-                    g = d[i + 1] - p;
-                    r = (d[i] - g) * s + 2.0 * c * b;
-                    p = s * r;
-                    d[i + 1] = g + p;
-                    g = c * r - b;
-                }
-                if (r == 0.0 && i >= l) continue;
-                d[l] -= p;
-                e[l] = g;
-                e[m] = 0.0;
-            }
-        } while (m != l);
+// deterministic start vector with all frequencies, zero on the boundary rows (one blocking copy of
+// the mask); zero_mean: see jacobi_spectrum
+std::vector<double> start_vector(int64_t n, uint64_t seed, const uint8_t *rowmask, bool zero_mean) {
+    std::vector<double> h(n);
+    uint64_t sd = seed;
+    for (int64_t i = 0; i < n; ++i) {
+        sd = sd * 6364136223846793005ull + 1442695040888963407ull;
+        h[i] = (double)(sd >> 11) / (double)(1ull << 53) - 0.5;
     }
-    std::sort(d.begin(), d.end());
-    return d;
+    if (rowmask) {
+        std::vector<uint8_t> m(n);
+        HIPCHK(hipMemcpy(m.data(), rowmask, n, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < n; ++i)
+            if (m[i]) h[i] = 0.0;
+    }
+    if (zero_mean) {
+        long double sum = 0.0L;
+        for (int64_t i = 0; i < n; ++i) sum += h[i];
+        const double mean = (double)(sum / (long double)n);
+        for (int64_t i = 0; i < n; ++i) h[i] -= mean;
+    }
+    return h;
+}
+constexpr uint64_t LANCZOS_SEED = 0x9e3779b97f4a7c15ull, POWER_SEED = 0x2545f4914f6cdd1dull;
+
+// the ops of the matrices still running, in batch order, as one launch list
+struct OpList {
+    RowOp *d = nullptr;
+    int n = 0;
+};
+OpList live_ops(DevPool &mem, const std::vector<RowOp> &all, const std::vector<uint32_t> &active) {
+    std::vector<RowOp> live;
+    for (size_t b = 0; b < all.size(); ++b)
+        if (active[b]) live.push_back(all[b]);
+    OpList L;
+    L.n = (int)live.size();
+    if (L.n) L.d = mem.upload(live.data(), live.size());
+    return L;
 }
 
 }  // namespace
@@ -84,26 +77,8 @@ Spectrum jacobi_spectrum(System &S, int pattern, const double *vals, const doubl
     double *r = vec(), *z = vec(), *p = vec(), *w = vec();
     double *scratch = tmp.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX);
     double *d_out = tmp.alloc<double>(4);
-    // deterministic start vector with all frequencies, zero on the boundary rows
     {
-        std::vector<double> h(n);
-        uint64_t sd = 0x9e3779b97f4a7c15ull;
-        for (int64_t i = 0; i < n; ++i) {
-            sd = sd * 6364136223846793005ull + 1442695040888963407ull;
-            h[i] = (double)(sd >> 11) / (double)(1ull << 53) - 0.5;
-        }
-        if (rowmask) {
-            std::vector<uint8_t> m(n);
-            HIPCHK(hipMemcpy(m.data(), rowmask, n, hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < n; ++i)
-                if (m[i]) h[i] = 0.0;
-        }
-        if (zero_mean) {
-            long double sum = 0.0L;
-            for (int64_t i = 0; i < n; ++i) sum += h[i];
-            const double mean = (double)(sum / (long double)n);
-            for (int64_t i = 0; i < n; ++i) h[i] -= mean;
-        }
+        const std::vector<double> h = start_vector(n, LANCZOS_SEED, rowmask, zero_mean);
         HIPCHK(hipMemcpy(r, h.data(), n * sizeof(double), hipMemcpyHostToDevice));
     }
     // w = A p (boundary rows 0) and z = D^-1 r as single RowOps through the kernel arguments
@@ -132,17 +107,7 @@ Spectrum jacobi_spectrum(System &S, int pattern, const double *vals, const doubl
     launch_copy(st, p, z, n);
     double rz = dot(r, z);
     std::vector<double> alpha, beta;
-    auto ritz = [&](double *lo_, double *hi_) {
-        const int m = (int)alpha.size();
-        std::vector<double> d(m), e(m > 1 ? m - 1 : 0);
-        for (int k = 0; k < m; ++k) {
-            d[k] = 1.0 / alpha[k] + (k > 0 ? beta[k - 1] / alpha[k - 1] : 0.0);
-            if (k + 1 < m) e[k] = std::sqrt(beta[k]) / alpha[k];
-        }
-        const std::vector<double> ev = tridiag_eigenvalues(d, e);
-        *lo_ = ev.front();
-        *hi_ = ev.back();
-    };
+    auto ritz = [&](double *lo_, double *hi_) { spec::ritz(alpha, beta, lo_, hi_); };
     double last_lo = 0.0;
     for (int k = 0; k < max_steps && rz > 0.0 && std::isfinite(rz); ++k) {
         // the smallest Ritz value is the slow one: stop when it moved by less than 1 % over the
@@ -193,18 +158,7 @@ double jacobi_skew_radius(System &S, int pattern, const double *skew_vals, const
     double *scratch = tmp.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX);
     double *d_out = tmp.alloc<double>(4);
     {
-        std::vector<double> h(n);
-        uint64_t sd = 0x2545f4914f6cdd1dull;
-        for (int64_t i = 0; i < n; ++i) {
-            sd = sd * 6364136223846793005ull + 1442695040888963407ull;
-            h[i] = (double)(sd >> 11) / (double)(1ull << 53) - 0.5;
-        }
-        if (rowmask) {
-            std::vector<uint8_t> m(n);
-            HIPCHK(hipMemcpy(m.data(), rowmask, n, hipMemcpyDeviceToHost));
-            for (int64_t i = 0; i < n; ++i)
-                if (m[i]) h[i] = 0.0;
-        }
+        const std::vector<double> h = start_vector(n, POWER_SEED, rowmask, false);
         HIPCHK(hipMemcpy(v, h.data(), n * sizeof(double), hipMemcpyHostToDevice));
     }
     // y = -D^-1 (0 - S x): the Chebyshev epilogue with c3 = -1 and no right-hand side
@@ -240,6 +194,236 @@ double jacobi_skew_radius(System &S, int pattern, const double *skew_vals, const
     }
     if (steps_out) *steps_out = k;
     return (mu2 > 0.0 && std::isfinite(mu2)) ? std::sqrt(mu2) : 0.0;
+}
+
+// ---- the same estimates for a batch of matrices on one pattern, in lock-step: one launch per
+// stage for the whole batch, the scalars of the recurrences on the device (spectrum_kernels.hip),
+// the host back in only where its stopping rule reads the coefficients.  Per matrix the arithmetic
+// and its order are jacobi_spectrum's / jacobi_skew_radius's, so the results are theirs bit for bit.
+
+namespace {
+
+// the vectors of a batch (zeroed), its partial sums and its per-matrix scalars
+struct BatchMem {
+    SpecBatch S{};
+    int32_t *ints = nullptr;      // na | nb | active: one copy back
+    size_t bytes = 0;
+    BatchMem(DevPool &tmp, hipStream_t st, int B, int64_t n, int nvec, int max_steps) {
+        S.B = B;
+        S.max_steps = max_steps;
+        S.n = n;
+        S.stride = (n + 32 + 1) & ~(int64_t)1;
+        const size_t nv = (size_t)nvec * B * S.stride;
+        double *v = tmp.alloc<double>(nv);
+        HIPCHK(hipMemsetAsync(v, 0, nv * sizeof(double), st));
+        S.r = v;
+        S.z = v + (size_t)B * S.stride;
+        if (nvec == 4) {
+            S.p = v + 2 * (size_t)B * S.stride;
+            S.w = v + 3 * (size_t)B * S.stride;
+        }
+        S.part = tmp.alloc<double>((size_t)B * REDUCE_BLOCKS);
+        const size_t nab = 2 * (size_t)max_steps * B, nsc = 4 * (size_t)B;
+        S.alpha = tmp.alloc<double>(nab);
+        S.beta = S.alpha + (size_t)max_steps * B;
+        double *sc = tmp.alloc<double>(nsc);
+        HIPCHK(hipMemsetAsync(sc, 0, nsc * sizeof(double), st));
+        S.rz = sc;
+        S.coef = sc + B;
+        S.mu2 = sc + 2 * (size_t)B;
+        S.last = sc + 3 * (size_t)B;
+        std::vector<int32_t> h(3 * (size_t)B, 0);
+        for (int b = 0; b < B; ++b) h[2 * (size_t)B + b] = 1;
+        ints = tmp.upload(h.data(), h.size());
+        S.na = ints;
+        S.nb = ints + B;
+        S.active = reinterpret_cast<uint32_t *>(ints + 2 * (size_t)B);
+        bytes = (nv + (size_t)B * REDUCE_BLOCKS + nab + nsc) * sizeof(double) + h.size() * sizeof(int32_t);
+    }
+    double *vec(double *family, int b) const { return family + (size_t)b * S.stride; }
+};
+
+// the start vector into vector b of `family`, for every b
+void spread_start(hipStream_t st, const BatchMem &M, double *family, const std::vector<double> &h) {
+    // (on the stream: behind the memset that zeroed the vectors)
+    HIPCHK(hipMemcpyAsync(family, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int b = 1; b < M.S.B; ++b)
+        HIPCHK(hipMemcpyAsync(M.vec(family, b), family, h.size() * sizeof(double),
+                              hipMemcpyDeviceToDevice, st));
+}
+
+}  // namespace
+
+std::vector<Spectrum> jacobi_spectrum_batch(System &S, int pattern, const std::vector<const double *> &vals,
+                                            const std::vector<const double *> &dinv, const uint8_t *rowmask,
+                                            int max_steps, SpectrumCounters *cnt) {
+    const int B = (int)vals.size();
+    std::vector<Spectrum> out(B, Spectrum{0.0, 0.0, 0});
+    if (B == 0) return out;
+    const Pattern &P = S.patterns[pattern];
+    const int64_t n = P.nrows;
+    hipStream_t st = S.stream;
+    DevPool tmp;   // released on every way out
+    BatchMem M(tmp, st, B, n, 4, max_steps);
+    const SpecBatch &Sb = M.S;
+    int64_t launches = 0, syncs = 0;
+    spread_start(st, M, Sb.r, start_vector(n, LANCZOS_SEED, rowmask, false));
+    syncs += rowmask ? 2 : 1;   // the mask's copy, the blocking upload
+    // w = A p (boundary rows 0) and z = D^-1 r: jacobi_spectrum's RowOps, one per matrix and launch
+    std::vector<RowOp> opsA(B), opsZ(B);
+    for (int b = 0; b < B; ++b) {
+        opsA[b] = lin_op(P, n, rowmask, LinStep{{RowTerm{vals[b], M.vec(Sb.p, b)}}, M.vec(Sb.w, b)});
+        opsZ[b] = cheb_op(P, n, rowmask, ChebStep{nullptr, dinv[b], M.vec(Sb.r, b), nullptr, nullptr,
+                                                  M.vec(Sb.z, b), 0.0, 0.0, 1.0});
+    }
+    spec::LockStep L(B);
+    OpList A = live_ops(tmp, opsA, L.active), Z = live_ops(tmp, opsZ, L.active);
+    const Bases bases{{nullptr, nullptr, nullptr, nullptr}};
+    auto run = [&](const OpList &o, int w) {
+        launch_rowops(st, o.d, o.n, P.nslices, P.R, bases, 1, w);
+        ++launches;
+    };
+    auto dot = [&](const double *x, const double *y, int mode) {
+        launch_spec_dot(st, Sb, x, y, mode);
+        launches += 2;
+    };
+    auto update = [&](int kind) {
+        launch_spec_update(st, Sb, kind);
+        ++launches;
+    };
+    std::vector<int32_t> h_ints(3 * (size_t)B);
+    std::vector<double> h_alpha, h_beta;
+    // steps [absorbed, k) of the device's coefficients, the counts and the words: one round trip
+    auto absorb = [&](int k) {
+        const int s0 = L.absorbed;
+        const size_t rows = k > s0 ? (size_t)(k - s0) : 0;
+        h_alpha.resize(rows * B + 1);
+        h_beta.resize(rows * B + 1);
+        if (rows) {
+            HIPCHK(hipMemcpyAsync(h_alpha.data(), Sb.alpha + (size_t)s0 * B, rows * B * sizeof(double),
+                                  hipMemcpyDeviceToHost, st));
+            HIPCHK(hipMemcpyAsync(h_beta.data(), Sb.beta + (size_t)s0 * B, rows * B * sizeof(double),
+                                  hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipMemcpyAsync(h_ints.data(), M.ints, h_ints.size() * sizeof(int32_t),
+                              hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        ++syncs;
+        L.absorb(k, h_alpha.data(), h_beta.data(), h_ints.data(), h_ints.data() + B,
+                 reinterpret_cast<const uint32_t *>(h_ints.data() + 2 * (size_t)B));
+    };
+    run(Z, 0);                                // z = D^-1 r
+    update(SPEC_UPD_COPY);                    // p = z
+    dot(Sb.r, Sb.z, SPEC_DOT_START);          // rz
+    int k = 0;
+    for (; k < max_steps; ++k) {
+        if (spec::ritz_due(k)) {
+            const std::vector<uint32_t> before = L.active;
+            absorb(k);
+            if (L.check(k))
+                HIPCHK(hipMemcpyAsync(Sb.active, L.active.data(), (size_t)B * sizeof(uint32_t),
+                                      hipMemcpyHostToDevice, st));
+            if (!L.any_active()) break;
+            if (L.active != before) {
+                A = live_ops(tmp, opsA, L.active);
+                Z = live_ops(tmp, opsZ, L.active);
+            }
+        }
+        run(A, P.uniform_w);                  // w = A p
+        dot(Sb.p, Sb.w, SPEC_DOT_PAP);        // alpha, or stop
+        update(SPEC_UPD_R);                   // r -= a w
+        run(Z, 0);                            // z = D^-1 r
+        dot(Sb.r, Sb.z, SPEC_DOT_RZ);         // beta, or stop
+        update(SPEC_UPD_P);                   // p = z + b p
+    }
+    if (L.absorbed < k) absorb(k);
+    for (int b = 0; b < B; ++b) out[b] = L.result(b);
+    if (cnt) {
+        cnt->launches += launches;
+        cnt->syncs += syncs;
+        cnt->lanczos_syncs_max = std::max(cnt->lanczos_syncs_max, syncs);
+        cnt->bytes = std::max<int64_t>(cnt->bytes, (int64_t)M.bytes);
+    }
+    return out;
+}
+
+std::vector<double> jacobi_skew_radius_batch(System &S, int pattern,
+                                             const std::vector<const double *> &skew_vals,
+                                             const std::vector<const double *> &dinv,
+                                             const uint8_t *rowmask, int max_steps,
+                                             std::vector<int> *steps_out, SpectrumCounters *cnt) {
+    const int B = (int)skew_vals.size();
+    std::vector<double> out(B, 0.0);
+    if (steps_out) steps_out->assign(B, 0);
+    if (B == 0) return out;
+    const Pattern &P = S.patterns[pattern];
+    const int64_t n = P.nrows;
+    hipStream_t st = S.stream;
+    DevPool tmp;   // released on every way out
+    BatchMem M(tmp, st, B, n, 2, 1);
+    const SpecBatch &Sb = M.S;      // v = r, z = z
+    int64_t launches = 0, syncs = 0;
+    spread_start(st, M, Sb.r, start_vector(n, POWER_SEED, rowmask, false));
+    syncs += rowmask ? 2 : 1;
+    const std::vector<double> last(B, -1.0);
+    HIPCHK(hipMemcpyAsync(Sb.last, last.data(), (size_t)B * sizeof(double), hipMemcpyHostToDevice, st));
+    // y = -D^-1 (0 - S x): the Chebyshev epilogue with c3 = -1 and no right-hand side
+    std::vector<RowOp> ops1(B), ops2(B);
+    for (int b = 0; b < B; ++b) {
+        auto op = [&](const double *x, double *y) {
+            return cheb_op(P, n, rowmask, ChebStep{skew_vals[b], dinv[b], nullptr, nullptr, nullptr, y,
+                                                   0.0, 0.0, -1.0, 1.0, 1.0, x});
+        };
+        ops1[b] = op(M.vec(Sb.r, b), M.vec(Sb.z, b));
+        ops2[b] = op(M.vec(Sb.z, b), M.vec(Sb.r, b));
+    }
+    std::vector<uint32_t> active(B, 1u);
+    OpList O1 = live_ops(tmp, ops1, active), O2 = live_ops(tmp, ops2, active);
+    const Bases bases{{nullptr, nullptr, nullptr, nullptr}};
+    std::vector<int32_t> h_ints(3 * (size_t)B);
+    auto read_back = [&]() {
+        HIPCHK(hipMemcpyAsync(h_ints.data(), M.ints, h_ints.size() * sizeof(int32_t),
+                              hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        ++syncs;
+        for (int b = 0; b < B; ++b) active[b] = (uint32_t)h_ints[2 * (size_t)B + b];
+    };
+    launch_spec_dot(st, Sb, Sb.r, Sb.r, SPEC_DOT_NORM0);
+    launches += 2;
+    for (int k = 0; k < max_steps; ++k) {
+        // the rule itself runs on the device every step; the host looks every 10 steps whether
+        // anything is left to launch for
+        if (k > 0 && k % 10 == 0) {
+            const std::vector<uint32_t> before = active;
+            read_back();
+            bool any = false;
+            for (uint32_t a : active) any = any || a;
+            if (!any) break;
+            if (active != before) {
+                O1 = live_ops(tmp, ops1, active);
+                O2 = live_ops(tmp, ops2, active);
+            }
+        }
+        launch_spec_update(st, Sb, SPEC_UPD_SCALE);                                     // v /= ||v||
+        launch_rowops(st, O1.d, O1.n, P.nslices, P.R, bases, 1, P.uniform_w);           // z = D^-1 S v
+        launch_rowops(st, O2.d, O2.n, P.nslices, P.R, bases, 1, P.uniform_w);           // v = D^-1 S z
+        launch_spec_dot(st, Sb, Sb.r, Sb.r, SPEC_DOT_NORM, k);
+        launches += 5;
+    }
+    std::vector<double> mu2(B);
+    HIPCHK(hipMemcpyAsync(mu2.data(), Sb.mu2, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, st));
+    read_back();
+    for (int b = 0; b < B; ++b) {
+        if (steps_out) (*steps_out)[b] = h_ints[b];
+        out[b] = (mu2[b] > 0.0 && std::isfinite(mu2[b])) ? std::sqrt(mu2[b]) : 0.0;
+    }
+    if (cnt) {
+        cnt->launches += launches;
+        cnt->syncs += syncs;
+        cnt->bytes = std::max<int64_t>(cnt->bytes, (int64_t)M.bytes);
+    }
+    return out;
 }
 
 }  // namespace kkt

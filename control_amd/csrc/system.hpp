@@ -37,6 +37,7 @@ struct Options {
     int prog_waves = 0, tile_depth = 0, tile_waves = 0;          // 0: chosen by shape / modelled
     bool coarse_columns = false;                                  // "coarse_setup" = "columns"
     bool coarse_keep = false, coarse_blocks = true;
+    int spectrum_batch = 32;   // "spectrum_batch": matrices per lock-step batch of estimates; 0: one at a time
     bool coarse_rings = true;     // two-grid tile sweeps: tiles prolong onto their rings themselves
     int tile_coarse_cache = -1;   // ... their coarse tables in LDS: 2 lists and inverse rows, 1 lists, 0 none; -1: what fits
     bool tile_coarse_full = false;   // ... whole rows of the coarse inverse ("tile_coarse_rows" = "full")
@@ -233,6 +234,7 @@ struct System {
     // byte accounting
     kkt_info info{};
     kkt_coarse_stats coarse_stats{};   // last two-grid coarse set-up (kkt_coarse_setup_stats)
+    kkt_spectrum_stats spectrum_stats{};   // spectrum estimates of the last build (kkt_spectrum_stats_get)
     std::vector<double> coarse_E;      // its Galerkin matrices (option "coarse_keep" = "1")
     std::vector<double> coarse_Einv;   // ... and their inverses
 

@@ -213,7 +213,7 @@ _ENV_OPTION_KEYS = ("sell_r", "sell_sort", "no_graph", "persistent", "prog_mode"
                     "kernarg_ops", "shared_rows", "verbose", "stamps", "tile_poll_delay",
                     "tile_unfused", "stage_timers", "sell_sigma", "interleave", "coarse_rings",
                     "mass_tiles", "mass_tile_depth", "mass_tile_rows", "mass_tile_levels",
-                    "mass_tile_waves")
+                    "mass_tile_waves", "spectrum_batch")
 
 
 # ------------------------------------------------------------------ the block system
@@ -377,6 +377,16 @@ class MultiBlockSystem:
         ``n_coarse``: the whole matrix)."""
         st = _lib.CoarseStats()
         self._ck(self._lib.kkt_coarse_setup_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def spectrum_stats(self):
+        """``kkt_spectrum_stats_get``: the spectrum estimates of the last preconditioner build on
+        this handle -- matrices estimated, lock-step batches (option ``spectrum_batch``), Lanczos
+        and power steps, launches, host synchronisations (``twin_syncs`` of the twin search,
+        ``lanczos_syncs_max`` of one batched Lanczos run), fall-backs to the one-matrix path, the
+        bytes a batch held and the milliseconds spent."""
+        st = _lib.SpectrumStats()
+        self._ck(self._lib.kkt_spectrum_stats_get(self._h, C.byref(st)))
         return st.as_dict()
 
     def _forms(self, fn, fields):

@@ -114,6 +114,11 @@ const char *kkt_last_error(kkt_handle h);
  *   "coarse_blocks" "1" | "0"      batched set-up: one inverse per component block of a
  *                                  vector-valued space (the rows keep their full layout, exact
  *                                  zeros outside the block); "0": invert P^T A P as one matrix
+ *   "spectrum_batch"  "0".."4096"  sub-solve matrices of a preconditioner build whose spectrum
+ *                                  estimates run in lock-step (default 32; further matrices in
+ *                                  further batches).  "0": one matrix at a time with a host round
+ *                                  trip per reduction (the previous path).  Same intervals, step
+ *                                  counts and preconditioner bit for bit; see kkt_spectrum_stats
  *   "coarse_rings"  "1" | "0"      two-grid sub-solves in the tile form: a tile prolongs the
  *                                  coarse correction onto its ring rows itself instead of fetching
  *                                  them in a hand-off after every correction (same results; "0":
@@ -603,6 +608,23 @@ typedef struct kkt_coarse_stats {
     int64_t blocks, block_n;
 } kkt_coarse_stats;
 int kkt_coarse_setup_stats(kkt_handle h, kkt_coarse_stats *out);
+
+/* The spectrum estimates of the last preconditioner build on this handle (kkt_set_pc_schur, every
+ * rebuild after kkt_update_block_values; kkt_set_pc_stokes: the velocity sub-solves report on the
+ * inner handle).  matrices: distinct value sets estimated (twins share); batches: lock-step
+ * batches (0 with option "spectrum_batch" = "0"); lanczos_steps / power_steps: summed over the
+ * matrices; launches: kernel launches of the estimates and of the twin search; syncs: blocking
+ * host round trips of all of it, of which twin_syncs belong to the twin search and lanczos_syncs_max
+ * is the largest count one batched Lanczos run took; fallbacks: matrices a batched build estimated
+ * or compared one at a time because its collection pass had not covered them (0 expected); ms:
+ * wall time of the estimates and the twin search between two synchronisations of the stream;
+ * batch_bytes: device memory the largest batch held. */
+typedef struct kkt_spectrum_stats {
+    int64_t matrices, batches, lanczos_steps, power_steps, launches, syncs, twin_syncs,
+        lanczos_syncs_max, fallbacks, batch_bytes;
+    double ms;
+} kkt_spectrum_stats;
+int kkt_spectrum_stats_get(kkt_handle h, kkt_spectrum_stats *out);
 /* Test hooks of the coarse set-up.  With option "coarse_keep" = "1" every set-up keeps its Galerkin
  * matrices P^T A P (before any deflation) on the host: kkt_debug_coarse_matrices copies them,
  * matrices x n_coarse^2 doubles row-major in set-up order (cap: doubles available at out).

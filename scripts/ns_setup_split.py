@@ -103,6 +103,9 @@ def one(pb, build):
     out["setup_s"] = round(t3 - t0, 4)
     out["first_pc_apply"] = round(t4 - t3, 4)
     out["other"] = round(t3 - t0 - sum(v for k, v in acc.items() if k != "bytes_uploaded"), 4)
+    st = ls.inner.spectrum_stats()      # the velocity sub-solves' estimates (KKT_SPECTRUM_BATCH)
+    out["spectrum_ms"], out["spectrum_batch_bytes"] = round(st["ms"], 1), st["batch_bytes"]
+    out["coarse_ms"] = round(ls.inner.coarse_setup_stats()["ms"], 1)
     out["device_value_bytes"] = sum(s.info()["bytes_device_values"]
                                     for s in (ls.outer, ls.inner, ls.comm))
     del ls

@@ -4,7 +4,9 @@ one GPU: wall time of a Picard iteration outside the linearised solve, the host 
 iteration each.  One JSON line per loop.
 
 "Outside the solve" is what lies between the end of one linearised solve and the start of the
-next, by a host clock around work that ends in a synchronise: update, assembly, residual, blocks
+next (``pc_setup_s``; of it ``spectrum_ms`` for the sub-solve spectrum estimates and ``coarse_ms``
+for the coarse set-up, as the library reports them -- KKT_SPECTRUM_BATCH=0 measures the
+one-matrix estimates), by a host clock around work that ends in a synchronise: update, assembly, residual, blocks
 and system construction (host) or composition (device), and the preconditioner's set-up or
 rebuild -- which both paths would otherwise do inside the solve call and which is therefore forced
 here, in front of the solve, by one preconditioner application."""
@@ -49,8 +51,9 @@ def _timed(method):
         x = np.zeros(self.local_size)
         self.pc_apply(x, kw.get("pc_fn"))        # set-up or rebuild happens here, then a sync
         t0 = time.perf_counter()
+        split = (self.spectrum_stats()["ms"], self.coarse_setup_stats()["ms"])
         out = method(self, *args, **kw)          # returns after the host has read the result
-        marks.append((t0, time.perf_counter(), t0 - tp))
+        marks.append((t0, time.perf_counter(), t0 - tp) + split)
         return out
     return solve
 
@@ -74,6 +77,8 @@ def loop(device, its):
                 outside_solve_median_s=round(statistics.median(outside), 4) if outside else None,
                 after_last_solve_s=round(t1 - marks[-1][1], 4),
                 pc_setup_s=[round(m[2], 4) for m in marks],
+                spectrum_ms=[round(m[3], 1) for m in marks],
+                coarse_ms=[round(m[4], 1) for m in marks],
                 solve_s=[round(m[1] - m[0], 3) for m in marks],
                 norms=norms)
 
