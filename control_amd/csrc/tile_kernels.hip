@@ -224,7 +224,11 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     // made of them are a register pair per matrix entry, row and table -- 27 registers in scratch
     // (W = 7), reloaded one by one with a wait each in front of the requests of the next level.
     // Made where they are used they cost three instructions per request and level.
-    constexpr bool TIGHT = COARSE && TMAX > 512;
+    // The 512-thread two-grid variants do the same although they have the registers: with the
+    // update's first term passing through `v` (SEQ) a level has two runs of requests, and hoisted
+    // addresses for both cost 2 W registers more than before (W = 9: 152 -> 170, a wave per SIMD
+    // less); made in place they cost 13-29 fewer than before.
+    constexpr bool TIGHT = COARSE;
     auto idx = [](const int i) { return TIGHT ? (int)opaque((unsigned)i) : i; };
     // p[i] where there is an entry, the 0.0 it stands for where there is none
     auto at = [&](const gcd_p p, const int i, const bool live) -> double {
@@ -556,8 +560,12 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
             for (int sl = 0; sl < RPT; ++sl)
 #pragma unroll
                 for (int k = 0; k < W; ++k) {
-                    const int gp = KKT_GP(sl, k);
-                    v[sl][k] = at(vp, gp, gp >= 0 && (!update_matrix || gr[sl] >= 0));
+                    // (TIGHT: the masks are made here from the opaque indices, level by level;
+                    // hoisted out of the level loop they are a pair of scalar registers per
+                    // entry, and scalar registers that run out are kept in lanes of vector
+                    // registers -- a whole register for every 64 of them)
+                    const int gp = idx(KKT_GP(sl, k));
+                    v[sl][k] = at(vp, gp, gp >= 0 && (!update_matrix || idx(gr[sl]) >= 0));
                 }
         }
     };
@@ -565,21 +573,32 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         const gcd_p dp = (gcd_p)L.dinv, bp = (gcd_p)L.bin;
 #pragma unroll
         for (int sl = 0; sl < RPT; ++sl) {
-            dinv[sl] = at(dp, gr[sl], gr[sl] >= 0);
-            b[sl] = at(bp, gr[sl], gr[sl] >= 0);
+            dinv[sl] = at(dp, gr[sl], idx(gr[sl]) >= 0);
+            b[sl] = at(bp, gr[sl], idx(gr[sl]) >= 0);
         }
     };
     auto load_level = [&](const LevEarly &L) {
         if (uniform_ptr((const void *)L.vals) != vals_key) load_vals(L.vals, false);
         load_db(L);
     };
-    // Wide rows with the level update in the kernel (SEQ): there are no registers for a second
-    // matrix, so the update's matrix passes through the registers of the level matrix -- it is
-    // requested in front of the hand-off that ends a level (the old matrix is dead by then),
-    // multiplied after it, and only then is the new level's own matrix requested (one exposed
-    // fetch per level instead of a kernel boundary, a plain update launch and the per-launch
-    // structure loads).
-    constexpr bool SEQ = PACK && UPD;
+    // Wide rows and two-grid levels with the level update in the kernel (SEQ): there are no
+    // registers for a second matrix, so the first term of the update passes through the registers
+    // of the level matrix -- its values are requested in front of the hand-off that ends a level
+    // (the old matrix is dead by then) and land under it, they are multiplied after it, and only
+    // then is the new level's own matrix requested.
+    // Plain wide levels wait for that request at once: their first sweep multiplies by it (one
+    // exposed fetch per level instead of a kernel boundary, a plain update launch and the
+    // per-launch structure loads).  A two-grid level multiplies by its matrix only after its first
+    // exchange -- cycle 0 restricts r = b, all-gathers, forms the owned products and prolongs --
+    // so there the request stays in flight under the exchange and `v` is waited for once, behind
+    // cycle 0's prolongation.  Between the update and that point `v` must not be read.
+    // `vals_key` names the array whose values `v` holds (or will hold once the requests land),
+    // `v_is_u` says that they were requested as an update's term, i.e. zero on rows without a
+    // global row -- rows no step computes, so where the update's array is the level's own array
+    // the values serve as the level matrix without a second request.
+    // Wide rows carry one update term only (tile_sweep_fuses_update()); on narrow rows further
+    // terms are read from memory after the first.
+    constexpr bool SEQ = (PACK || COARSE) && UPD;
     bool v_is_u = false;
     if (A.nlevels > 0) {
         const LevEarly L0 = read_early(&levels[0]);
@@ -601,7 +620,9 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
     // update's matrix out of the level's first step: they are requested together with the next
     // matrix in front of the hand-off that ends the level (PRE_U).
     // (two-grid levels are short -- a correction and a handful of sweeps -- and their exchanges
-    // need the registers: no operands of the next level are held across them)
+    // need the registers: no operands of the next level are held across them in registers of
+    // their own.  The values of the next update's matrix travel under the hand-off that ends the
+    // level all the same, in the registers of the level matrix: SEQ above.)
     constexpr bool PRE = UPD && !COARSE && W * RPT <= 14 && TMAX <= 512;
     constexpr bool PRE_U = UPD && !COARSE && !PRE && W * RPT <= 7;
     constexpr int PR = PRE ? RPT : 1, PW = PRE ? W : 1;
@@ -673,6 +694,17 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         pre_issued = false;
         un_loaded = false;
         v_is_u = false;
+        // (two-grid levels: the pointer to the level's coarse inverse, read here.  Read where the
+        // exchange first needs it, it was a load behind the request of the level matrix, and the
+        // wait for it -- loads return in order -- a wait for the matrix.  The table of these
+        // pointers is written before the launch and read through the constant address space: a
+        // scalar load, counted with the level's fields and not with the requests.)
+        const double *einv_lev = nullptr;
+        if constexpr (COARSE) {
+            typedef const double *einv_entry;
+            typedef __attribute__((address_space(4))) const einv_entry *einv_table_p;
+            einv_lev = ((einv_table_p)(uintptr_t)A.einv)[lev];
+        }
         if (uniform_ptr((const void *)L.coef) != coef_key) {
             coef_key = uniform_ptr((const void *)L.coef);
             const gcd_p cp = (gcd_p)(const double *)L.coef;
@@ -683,10 +715,13 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         // Everything loaded for the level is pinned in registers here: a value whose load is
         // conditional would otherwise be waited for at its first use INSIDE the step loop
         // (s_waitcnt vmcnt(0) there would also drain whatever the loop keeps in flight).
+        // (two-grid levels: `v` is pinned behind cycle 0's prolongation instead, see SEQ)
 #pragma unroll
         for (int sl = 0; sl < RPT; ++sl) {
+            if constexpr (!(SEQ && COARSE)) {
 #pragma unroll
-            for (int k = 0; k < W; ++k) asm volatile("" : "+v"(v[sl][k]));
+                for (int k = 0; k < W; ++k) asm volatile("" : "+v"(v[sl][k]));
+            }
             asm volatile("" : "+v"(dinv[sl]));
             asm volatile("" : "+v"(b[sl]));
         }
@@ -743,10 +778,10 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                         }
                     }
                 }
-                // (SEQ: one update term, the host's condition for this variant -- with this
-                // loop compiled in, the two-slot variant spills 88 registers)
-                if constexpr (!SEQ)
-                for (int t = have_u ? 1 : 0; t < L.n_upd; ++t) {
+                // (wide rows with the update: one term, the host's condition for these variants
+                // -- with this loop compiled in, the two-slot variant spills 88 registers)
+                if constexpr (!(PACK && SEQ))
+                for (int t = (have_u || use_v) ? 1 : 0; t < L.n_upd; ++t) {
                     const gcd_p up = (gcd_p)L.upd_vals[t];
 #pragma unroll
                     for (int sl = 0; sl < RPT; ++sl) {
@@ -757,11 +792,11 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                             double vu[CH];
 #pragma unroll
                             for (int k = 0; k < CH; ++k)
-                                if (k0 + k < W) gp[k] = KKT_GP(sl, k0 + k);
+                                if (k0 + k < W) gp[k] = idx(KKT_GP(sl, k0 + k));
 #pragma unroll
                             for (int k = 0; k < CH; ++k)
                                 if (k0 + k < W)
-                                    vu[k] = at(up, gp[k], gr[sl] >= 0 && gp[k] >= 0);
+                                    vu[k] = at(up, gp[k], idx(gr[sl]) >= 0 && gp[k] >= 0);
 #pragma unroll
                             for (int k = 0; k < CH; ++k)
                                 if (k0 + k < W)
@@ -769,6 +804,13 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                             if constexpr (PACK) __builtin_amdgcn_sched_barrier(0);
                         }
                     }
+                }
+                if constexpr (SEQ && COARSE) {
+                    // the level's own matrix, now that the update's has been used: requested in
+                    // front of the stores below (a wait the compiler puts in front of a request
+                    // must not find them in flight) and not waited for before the first exchange
+                    // is over
+                    if (uniform_ptr((const void *)L.vals) != vals_key) load_vals(L.vals, false);
                 }
                 const gd_p bo = (gd_p)L.bout;
 #pragma unroll
@@ -781,7 +823,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                     if (r < nk1) Xo[r] = out2;
                     if (r < n0 && bo != nullptr) bo[idx(gr[sl])] = out;
                 }
-                if constexpr (SEQ) {
+                if constexpr (SEQ && !COARSE) {
                     // the level's own matrix, now that the update's has been used
                     if (uniform_ptr((const void *)L.vals) != vals_key) load_vals(L.vals, false);
                 }
@@ -812,7 +854,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         }
 #pragma unroll
         for (int sl = 0; sl < RPT; ++sl) {
-            if constexpr (SEQ) {
+            if constexpr (SEQ && !COARSE) {
 #pragma unroll
                 for (int k = 0; k < W; ++k) asm volatile("" : "+v"(v[sl][k]));
             }
@@ -865,7 +907,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                 }
             };
             const TileCoarseDev *cd = A.coarse;
-            const gcd_p einv = (gcd_p)A.einv[lev];
+            const gcd_p einv = (gcd_p)einv_lev;
             const int wave = tid >> 6, lane = tid & 63, nwaves = T >> 6;
             for (int cyc = 0; cyc < A.cycles; ++cyc) {
                 // ---- residual of the current iterate on the own rows, into the older buffer
@@ -1137,6 +1179,15 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                 // barriers long past
                 int nv_next = sn[depth - 1];
                 double cn1 = scoef[0], cn2 = scoef[1], cn3 = scoef[2];
+                // The level matrix, requested at the level's start behind the update (or in front
+                // of the hand-off that ended the level before), is pinned in registers here: the
+                // one place where a level waits for it, with the exchange between the request and
+                // this point.  No step of the sweep loop below then waits for memory on its own.
+                // (later cycles: nothing is in flight, the pin costs nothing)
+#pragma unroll
+                for (int sl = 0; sl < RPT; ++sl)
+#pragma unroll
+                    for (int k = 0; k < W; ++k) asm volatile("" : "+v"(v[sl][k]));
                 // (the barrier inside the hand-off orders these stores before anyone's gathers)
                 lds_barrier();
                 if (stamps) {      // the coarse exchange, restriction to prolongation: slot 7
@@ -1308,6 +1359,15 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
             }
         }
         lap(1, (unsigned long long)(its - 1));
+        if constexpr (SEQ && COARSE) {
+            // (`v` landed long ago, but the compiler cannot know that the cycle loop with its pin
+            // ran at all: without this one it waits -- vmcnt(0) -- before the requests below
+            // overwrite `v`, and what that wait then drains is the result store in front of them)
+#pragma unroll
+            for (int sl = 0; sl < RPT; ++sl)
+#pragma unroll
+                for (int k = 0; k < W; ++k) asm volatile("" : "+v"(v[sl][k]));
+        }
         // ---- result of the level: own rows to memory; the next level's update multiplies it
         {
             double *Xc = X + cur * nkp;
@@ -1321,7 +1381,23 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                 if (!nf_valid) Nf = read_early(&levels[lev + 1]);
                 nf_want = nullptr;
                 const LevEarly &N = Nf;
-                if (!(PRE && pre_issued)) {
+                if constexpr (SEQ && COARSE) {
+                    // one run of requests for either kind of next level -- the first term of its
+                    // update or, without one, its matrix: two branches that both write `v` make
+                    // the compiler wait in front of the second for loads the first may have
+                    // issued, and that wait drains the result store above
+                    // (narrow rows, next level on the matrix `v` holds -- operators that do not
+                    // change in time, stored once: `v` stays and the update reads its matrix from
+                    // memory, out of L2, as all further terms do.  Passing it through `v` there
+                    // means requesting the level matrix again at every level, and on the flagship
+                    // stored that way it measured 1.2 % slower: profiles/level_fetch.md)
+                    const bool upd = N.n_upd > 0 &&
+                                     (PACK || uniform_ptr((const void *)N.vals) != vals_key);
+                    const double *src = upd ? N.upd0 : N.vals;
+                    if (upd || uniform_ptr((const void *)src) != vals_key) load_vals(src, upd);
+                    load_db(N);
+                    v_is_u = upd;
+                } else if (!(PRE && pre_issued)) {
                     if (SEQ && N.n_upd > 0) {
                         load_vals(N.upd0, true);
                         load_db(N);

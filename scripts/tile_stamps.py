@@ -10,7 +10,7 @@ import bench
 class A: pass
 a = A(); a.workload = os.environ.get("WORKLOAD", "heat2d"); a.n = int(os.environ.get("N", 256))
 a.n_t = int(os.environ.get("N_T", 64)); a.beta = 1e-4
-a.T = 2.0; a.scheme = "BE"; a.mode = "G"
+a.T = 2.0; a.scheme = "BE"; a.mode = os.environ.get("MODE", "G")
 a.schur_its = int(os.environ.get("ITS", 80)); a.schur_emin = float(os.environ.get("EMIN", 7e-4)); a.schur_emax = 2.1
 a.coarse_cycles = int(os.environ.get("COARSE_CYCLES", 0)); a.coarse_cell = int(os.environ.get("COARSE_CELL", 8))
 p = bench.build_problem(a)
@@ -18,7 +18,7 @@ opts = {"stamps": "1", "no_graph": "1"}
 for k in ("tile_depth", "tile_waves", "tile_poll_delay"):
     if os.environ.get(k.upper()):
         opts[k] = os.environ[k.upper()]
-g = common.gpu_system(p, share_values=False, options=opts)
+g = common.gpu_system(p, share_values=(a.mode == "S"), options=opts)
 pc = common.gpu_pc(p, p["mass"], p["schur"], coarse=p.get("coarse"))
 lib, h = g._lib, g.handle
 x = common.rng_vector(g.info()["n_local"])
