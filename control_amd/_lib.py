@@ -169,6 +169,27 @@ class BlockOp(C.Structure):
                 + [("y", c_f64p), ("y2", c_f64p), ("flag", c_u32p), ("inputs_changed", C.c_int32)])
 
 
+# kkt_debug_spectrum_op: the operations (KKT_SPECTRUM_*), the modes of DOT, the kinds of UPDATE and
+# the argument record; guards as for kkt_debug_block_op
+SPECTRUM_OPS = {name: k for k, name in enumerate(
+    ("dot", "update", "sym_skew", "fingerprint", "pairs_differ"))}
+SPECTRUM_DOT_MODES = {name: k for k, name in enumerate(("start", "pap", "rz", "norm0", "norm"))}
+SPECTRUM_UPDATES = {name: k for k, name in enumerate(("r", "p", "scale", "copy"))}
+c_u64p = C.POINTER(C.c_uint64)
+
+
+class SpectrumOp(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ("op", "mode", "k", "nmat", "max_steps", "npairs")]
+                + [("n", C.c_int64), ("stride", C.c_int64)]
+                + [("x", c_f64p), ("y", c_f64p), ("v", c_f64p), ("active", c_u32p),
+                   ("na", c_i32p), ("nb", c_i32p)]
+                + [(n, c_f64p) for n in ("rz", "coef", "last", "mu2", "alpha", "beta", "part")]
+                + [("a", c_f64p), ("tpos", c_i32p), ("h", c_f64p), ("sk", c_f64p),
+                   ("pair_a", c_i32p), ("pair_b", c_i32p), ("flag", c_u32p),
+                   ("words", c_u64p), ("fold", c_u64p),
+                   ("batch_stride", C.c_int64), ("inputs_changed", C.c_int32)])
+
+
 # kkt_debug_row_step: the forms (KKT_ROWSTEP_*), modes, kernel families it reports and its records
 ROWSTEP_FORMS = {name: k for k, name in enumerate(("rows", "single", "shared", "interleaved"))}
 ROWSTEP_LIN, ROWSTEP_CHEB = 0, 1
@@ -295,6 +316,7 @@ SIGNATURES = {
     "kkt_debug_krylov_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, c_f64p, c_f64p,
                                       c_f64p, C.c_double, C.c_double, c_f64p, c_f64p, c_f64p]),
     "kkt_debug_block_op": (C.c_int, [C.c_void_p, C.POINTER(BlockOp)]),
+    "kkt_debug_spectrum_op": (C.c_int, [C.c_void_p, C.POINTER(SpectrumOp)]),
     "kkt_debug_row_step": (C.c_int, [C.c_void_p, C.POINTER(RowStep)]),
     "kkt_debug_tile_levels": (C.c_int, [C.c_void_p, C.POINTER(TileLevels)]),
     "kkt_debug_set_steplock": (C.c_int, [C.c_void_p, C.POINTER(StepLock)]),

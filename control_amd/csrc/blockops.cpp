@@ -2,6 +2,7 @@
 // host data (include/kkt.h documents the arguments).  Nothing here computes: the arrays go up, the
 // launcher of kernels.hpp the drivers call runs once on the handle's stream, the arrays come back.
 // Arrays the launch writes sit between guards; arrays it only reads are compared with what went up.
+// kkt_debug_spectrum_op, below, does the same for the launchers of spectrum_kernels.hip.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -270,6 +271,219 @@ void debug_block_op(System &S, kkt_block_op *pa) {
         back.resize(w.bytes);
         HIPCHK(hipMemcpy(back.data(), w.dev, w.bytes, hipMemcpyDeviceToHost));
         changed += std::memcmp(back.data(), w.host, w.bytes) != 0;
+    }
+    a.inputs_changed = changed;
+}
+
+// ---- kkt_debug_spectrum_op: the same for the launchers of spectrum_kernels.hip.  The scalar state
+// of a batch is read and written by one launch, so every guarded array comes back.
+namespace {
+
+constexpr bool same(int a, int b) { return a == b; }
+static_assert(same(KKT_SPECTRUM_DOT_START, SPEC_DOT_START) && same(KKT_SPECTRUM_DOT_PAP, SPEC_DOT_PAP) &&
+              same(KKT_SPECTRUM_DOT_RZ, SPEC_DOT_RZ) && same(KKT_SPECTRUM_DOT_NORM0, SPEC_DOT_NORM0) &&
+              same(KKT_SPECTRUM_DOT_NORM, SPEC_DOT_NORM), "kkt.h names the modes of launch_spec_dot");
+static_assert(same(KKT_SPECTRUM_UPD_R, SPEC_UPD_R) && same(KKT_SPECTRUM_UPD_P, SPEC_UPD_P) &&
+              same(KKT_SPECTRUM_UPD_SCALE, SPEC_UPD_SCALE) && same(KKT_SPECTRUM_UPD_COPY, SPEC_UPD_COPY),
+              "kkt.h names the kinds of launch_spec_update");
+
+constexpr int MAX_GRID_Y = 65535;
+
+struct Back {   // a guarded allocation to download
+    void *host;
+    const void *dev;
+    size_t bytes;
+};
+
+template <class T>
+T pad_of();
+template <>
+double pad_of<double>() { return KKT_KRYLOV_PAD; }
+template <>
+uint32_t pad_of<uint32_t>() { return KKT_BLOCK_FLAG_PAD; }
+template <>
+int32_t pad_of<int32_t>() { return (int32_t)KKT_BLOCK_FLAG_PAD; }
+template <>
+uint64_t pad_of<uint64_t>() {
+    const double d = KKT_KRYLOV_PAD;
+    uint64_t u;
+    std::memcpy(&u, &d, sizeof u);
+    return u;
+}
+
+struct SpecArena : Arena {
+    std::vector<Back> back;
+
+    template <class T>
+    void set_guards(T *h, size_t n) {
+        std::fill(h, h + G, pad_of<T>());
+        std::fill(h + G + n, h + 2 * G + n, pad_of<T>());
+    }
+    // the caller's guarded allocation, read and written: comes back whole
+    template <class T>
+    T *inout(T *h, size_t n) {
+        set_guards(h, n);
+        T *d = pool.upload(h, n + 2 * G);
+        back.push_back({h, d, (n + 2 * G) * sizeof(T)});
+        return d + G;
+    }
+    // a guarded allocation the launch only reads: watched with its guards
+    template <class T>
+    T *guarded_input(T *h, size_t n) {
+        set_guards(h, n);
+        return const_cast<T *>(input(h, n + 2 * G)) + G;
+    }
+};
+
+[[noreturn]] void bad_spec(const char *what) {
+    fail(KKT_ERR_ARG, std::string("kkt_debug_spectrum_op: ") + what);
+}
+
+void check_batch(const kkt_spectrum_op &a) {
+    if (a.nmat < 1 || a.nmat > MAX_GRID_Y || a.n < 1) bad_spec("nmat and n must be at least 1");
+    if (a.stride < a.n || (a.stride & 1)) bad_spec("stride must be even and at least n");
+    if (a.stride > MAX_ELEMS / a.nmat) bad_spec("nmat * stride is too large");
+}
+
+void check_arrays(const kkt_spectrum_op &a) {
+    if (a.nmat < 1 || a.nmat > MAX_GRID_Y || a.n < 1) bad_spec("nmat and n must be at least 1");
+    if (a.n > MAX_ELEMS / a.nmat) bad_spec("nmat * n is too large");
+    if (!a.a) bad_spec("null value arrays");
+}
+
+}  // namespace
+
+void debug_spectrum_op(System &S, kkt_spectrum_op *pa) {
+    if (!pa) bad_spec("null argument");
+    kkt_spectrum_op &a = *pa;
+    hipStream_t st = S.stream;
+    SpecArena A;
+    std::vector<const double *> ptrs;   // the tables live until they are compared, below
+    std::vector<SpecSplit> splits;
+    std::vector<SpecPair> pairs;
+    const unsigned long long *d_words = nullptr;
+    int nwords = 0;
+
+    switch (a.op) {
+        case KKT_SPECTRUM_DOT: {
+            check_batch(a);
+            if (a.mode < SPEC_DOT_START || a.mode > SPEC_DOT_NORM) bad_spec("unknown mode");
+            if (a.k < 0) bad_spec("k must not be negative");
+            if (a.max_steps < 1 || a.max_steps > MAX_ELEMS / a.nmat) bad_spec("bad max_steps");
+            if (!a.x || !a.y || !a.active || !a.na || !a.nb || !a.rz || !a.coef || !a.last ||
+                !a.mu2 || !a.alpha || !a.beta || !a.part)
+                bad_spec("null array");
+            for (int b = 0; b < a.nmat; ++b)
+                if (a.na[G + b] < 0 || a.nb[G + b] < 0) bad_spec("negative na or nb");
+            const size_t nb = (size_t)a.nmat, nvec = nb * (size_t)a.stride;
+            const double *d_x = A.input(a.x, nvec);
+            const double *d_y = a.y == a.x ? d_x : A.input(a.y, nvec);
+            SpecBatch B{};
+            B.B = a.nmat;
+            B.max_steps = a.max_steps;
+            B.n = a.n;
+            B.stride = a.stride;
+            B.part = A.inout(a.part, nb * REDUCE_BLOCKS);
+            B.alpha = A.inout(a.alpha, nb * (size_t)a.max_steps);
+            B.beta = A.inout(a.beta, nb * (size_t)a.max_steps);
+            B.na = A.inout(a.na, nb);
+            B.nb = A.inout(a.nb, nb);
+            B.rz = A.inout(a.rz, nb);
+            B.coef = A.inout(a.coef, nb);
+            B.mu2 = A.inout(a.mu2, nb);
+            B.last = A.inout(a.last, nb);
+            B.active = A.inout(a.active, nb);
+            a.batch_stride = spec_batch_stride(a.n);
+            launch_spec_dot(st, B, d_x, d_y, a.mode, a.k);
+            break;
+        }
+        case KKT_SPECTRUM_UPDATE: {
+            check_batch(a);
+            if (a.mode < SPEC_UPD_R || a.mode > SPEC_UPD_COPY) bad_spec("unknown kind");
+            if (!a.x || !a.v || !a.active || !a.coef) bad_spec("null array");
+            const size_t nb = (size_t)a.nmat, nvec = nb * (size_t)a.stride;
+            double *d_x = const_cast<double *>(A.input(a.x, nvec));
+            double *d_v = A.inout(a.v, nvec);
+            SpecBatch B{};
+            B.B = a.nmat;
+            B.max_steps = 1;
+            B.n = a.n;
+            B.stride = a.stride;
+            if (a.mode == SPEC_UPD_R || a.mode == SPEC_UPD_SCALE)
+                B.r = d_v;
+            else
+                B.p = d_v;
+            if (a.mode == SPEC_UPD_R)
+                B.w = d_x;
+            else
+                B.z = d_x;
+            B.coef = A.guarded_input(a.coef, nb);
+            B.active = A.guarded_input(a.active, nb);
+            a.batch_stride = spec_batch_stride(a.n);
+            launch_spec_update(st, B, a.mode);
+            break;
+        }
+        case KKT_SPECTRUM_SYM_SKEW: {
+            check_arrays(a);
+            if (!a.tpos || !a.h || !a.sk || !a.flag) bad_spec("null array");
+            for (int64_t p = 0; p < a.n; ++p)
+                if (a.tpos[p] < -1 || a.tpos[p] >= a.n) bad_spec("transposed position outside the values");
+            const size_t nm = (size_t)a.nmat, n = (size_t)a.n;
+            const double *d_a = A.input(a.a, nm * n);
+            const int32_t *d_tpos = A.input(a.tpos, n);
+            double *d_h = A.inout(a.h, nm * n), *d_sk = A.inout(a.sk, nm * n);
+            unsigned *d_flag = A.inout(a.flag, nm);
+            for (size_t m = 0; m < nm; ++m)
+                splits.push_back(SpecSplit{d_a + m * n, d_h + m * n, d_sk + m * n});
+            const SpecSplit *d_m = A.input(splits.data(), splits.size());
+            launch_spec_sym_skew(st, d_m, a.nmat, d_tpos, a.n, d_flag);
+            break;
+        }
+        case KKT_SPECTRUM_FINGERPRINT: {
+            check_arrays(a);
+            if (!a.words || !a.fold) bad_spec("null array");
+            const size_t nm = (size_t)a.nmat, n = (size_t)a.n;
+            nwords = spec_fingerprint_blocks(a.n);
+            const double *d_a = A.input(a.a, nm * n);
+            for (size_t m = 0; m < nm; ++m) ptrs.push_back(d_a + m * n);
+            const double *const *d_vals = A.input(ptrs.data(), ptrs.size());
+            static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "64-bit words");
+            uint64_t *d_w = A.inout(a.words, nm * (size_t)nwords);
+            d_words = reinterpret_cast<unsigned long long *>(d_w);
+            launch_spec_fingerprint(st, d_vals, a.nmat, a.n, reinterpret_cast<unsigned long long *>(d_w));
+            break;
+        }
+        case KKT_SPECTRUM_PAIRS_DIFFER: {
+            check_arrays(a);
+            if (a.npairs < 1 || a.npairs > MAX_GRID_Y) bad_spec("npairs must be 1..65535");
+            if (!a.pair_a || !a.pair_b || !a.flag) bad_spec("null array");
+            for (int q = 0; q < a.npairs; ++q)
+                if (a.pair_a[q] < 0 || a.pair_a[q] >= a.nmat || a.pair_b[q] < 0 || a.pair_b[q] >= a.nmat)
+                    bad_spec("pair index outside the arrays");
+            const size_t nm = (size_t)a.nmat, n = (size_t)a.n;
+            const double *d_a = A.input(a.a, nm * n);
+            for (int q = 0; q < a.npairs; ++q)
+                pairs.push_back(SpecPair{d_a + (size_t)a.pair_a[q] * n, d_a + (size_t)a.pair_b[q] * n});
+            const SpecPair *d_pairs = A.input(pairs.data(), pairs.size());
+            unsigned *d_flag = A.inout(a.flag, (size_t)a.npairs);
+            launch_spec_pairs_differ(st, d_pairs, a.npairs, a.n, d_flag);
+            break;
+        }
+        default: bad_spec("unknown op");
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    for (const Back &b : A.back) HIPCHK(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
+    if (d_words)
+        for (int m = 0; m < a.nmat; ++m)
+            a.fold[m] = spec_fingerprint_fold(
+                reinterpret_cast<const unsigned long long *>(a.words + G + (size_t)m * nwords), nwords);
+    int32_t changed = 0;
+    std::vector<char> again;
+    for (const Watch &w : A.watched) {
+        again.resize(w.bytes);
+        HIPCHK(hipMemcpy(again.data(), w.dev, w.bytes, hipMemcpyDeviceToHost));
+        changed += std::memcmp(again.data(), w.host, w.bytes) != 0;
     }
     a.inputs_changed = changed;
 }

@@ -569,6 +569,10 @@ int kkt_debug_block_op(kkt_handle h, kkt_block_op *op) {
     KKT_TRY(h, kkt::debug_block_op(S, op));
 }
 
+int kkt_debug_spectrum_op(kkt_handle h, kkt_spectrum_op *op) {
+    KKT_TRY(h, kkt::debug_spectrum_op(S, op));
+}
+
 int kkt_debug_row_step(kkt_handle h, kkt_row_step *step) {
     KKT_TRY(h, kkt::debug_row_step(S, step));
 }

@@ -397,6 +397,8 @@ struct SpecBatch {
     double *mu2, *last;         // power iteration: the estimate and the one before
     uint32_t *active;           // 0: the matrix is done, its workgroups leave at once
 };
+// the spacing the estimates give the vectors of n rows: even (double2 accesses), 32 doubles of slack
+inline int64_t spec_batch_stride(int64_t n) { return (n + 32 + 1) & ~(int64_t)1; }
 // what the second stage of a batched dot does with the sum (spectrum_host.hpp has the scalars)
 enum { SPEC_DOT_START, SPEC_DOT_PAP, SPEC_DOT_RZ, SPEC_DOT_NORM0, SPEC_DOT_NORM };
 // <x_b, y_b> for every active matrix with mdot_stage1 / mdot_stage2's chunks and trees, then:

@@ -1781,8 +1781,11 @@ void SchurPC::collect_matrices() {
     if (C == 0) return;
     // twins: a fingerprint per candidate, then the candidates of a (shift, fingerprint) group bit
     // for bit against the group's first
-    std::vector<int> first_of(C);
-    for (int i = 0; i < C; ++i) first_of[i] = i;
+    spec::TwinGroups twins;
+    twins.first_of.resize(C);
+    for (int i = 0; i < C; ++i) twins.first_of[i] = i;
+    twins.pair_of.assign(C, -1);
+    std::vector<unsigned> h_flag;
     DevPool tmp;
     if (C > 1) {
         std::vector<const double *> h_vals(C);
@@ -1799,24 +1802,18 @@ void SchurPC::collect_matrices() {
         cnt.launches++;
         cnt.syncs++;
         stats.twin_syncs++;
-        std::map<std::pair<uint64_t, uint64_t>, int> groups;
-        std::vector<SpecPair> pairs;
-        std::vector<int> pair_of(C, -1);
+        std::vector<uint64_t> shifts(C), folded(C);
         for (int i = 0; i < C; ++i) {
-            const auto g = std::make_pair(keys[i].second, spec_fingerprint_fold(&h_fp[(size_t)i * nw], nw));
-            const auto it = groups.find(g);
-            if (it == groups.end()) {
-                groups[g] = i;
-                continue;
-            }
-            first_of[i] = it->second;
-            pair_of[i] = (int)pairs.size();
-            pairs.push_back(SpecPair{h_vals[it->second], h_vals[i]});
+            shifts[i] = keys[i].second;
+            folded[i] = spec_fingerprint_fold(&h_fp[(size_t)i * nw], nw);
         }
+        twins = spec::group_twins(shifts, folded);
+        std::vector<SpecPair> pairs;
+        for (const auto &pr : twins.pairs) pairs.push_back(SpecPair{h_vals[pr.first], h_vals[pr.second]});
         if (!pairs.empty()) {
             const SpecPair *d_pairs = tmp.upload(pairs.data(), pairs.size());
             unsigned *d_flag = tmp.alloc<unsigned>(pairs.size());
-            std::vector<unsigned> h_flag(pairs.size(), 1u);
+            h_flag.assign(pairs.size(), 1u);
             HIPCHK(hipMemsetAsync(d_flag, 0, pairs.size() * sizeof(unsigned), st));
             launch_spec_pairs_differ(st, d_pairs, (int)pairs.size(), P.npadded, d_flag);
             HIPCHK(hipGetLastError());
@@ -1826,22 +1823,13 @@ void SchurPC::collect_matrices() {
             cnt.launches++;
             cnt.syncs++;
             stats.twin_syncs++;
-            // equal fingerprints, different bits: left to schur_matrix's own comparison
-            for (int i = 0; i < C; ++i)
-                if (pair_of[i] >= 0 && h_flag[pair_of[i]]) first_of[i] = -1;
         }
     }
+    // equal fingerprints, different bits: no class, left to schur_matrix's own comparison
     std::vector<int> reps;      // the first candidate of every class
-    for (int i = 0; i < C; ++i) {
-        Pre &pr = pre_[keys[i]];
-        if (first_of[i] == i) {
-            pr.cls = (int)pre_cls_.size();
-            pre_cls_.push_back(PreCls{});
-            reps.push_back(i);
-        } else if (first_of[i] >= 0) {
-            pr.cls = pre_[keys[first_of[i]]].cls;
-        }
-    }
+    const std::vector<int> cls = spec::twin_classes(twins, h_flag, &reps);
+    for (int i = 0; i < C; ++i) pre_[keys[i]].cls = cls[i];
+    pre_cls_.assign(reps.size(), PreCls{});
     // the distinct matrices' intervals, nbatch at a time: symmetric / skew split, Lanczos on the
     // symmetric parts, power iteration on the skew parts of those that have one
     const int32_t *tpos = estimates ? transpose_positions() : nullptr;

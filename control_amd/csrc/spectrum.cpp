@@ -212,7 +212,7 @@ struct BatchMem {
         S.B = B;
         S.max_steps = max_steps;
         S.n = n;
-        S.stride = (n + 32 + 1) & ~(int64_t)1;
+        S.stride = spec_batch_stride(n);
         const size_t nv = (size_t)nvec * B * S.stride;
         double *v = tmp.alloc<double>(nv);
         HIPCHK(hipMemsetAsync(v, 0, nv * sizeof(double), st));

@@ -2,11 +2,14 @@
 // tests/native/spectrum_lockstep_emu.cpp compiles it as it is: the Lanczos tridiagonal's
 // eigenvalues, the per-step scalar work of the conjugate-gradient recurrences (what the second
 // stage of a batched dot runs on the device and the one-matrix loop runs on the host), and the
-// host's half of the lock-step loop -- the Ritz check every 10 steps.
+// host's half of the lock-step loop -- the Ritz check every 10 steps -- and the grouping of the
+// twin search (tests/native/twin_groups.cpp).
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <map>
+#include <utility>
 #include <vector>
 
 #if defined(__HIPCC__)
@@ -185,6 +188,58 @@ struct LockStep {
     }
     Spectrum result(int b) const { return ritz_result(alpha[b], beta[b]); }
 };
+
+// ---- the grouping of the twin search (SchurPC::collect_matrices).  Candidates come in creation
+// order with the bits of their shift and the folded fingerprint of their values.  A candidate whose
+// (shift, fingerprint) was seen before is compared bit for bit with the FIRST candidate that had
+// it; a fingerprint only prunes, it never makes a twin.
+struct TwinGroups {
+    std::vector<int> first_of;                  // i itself: candidate i opens its group
+    std::vector<std::pair<int, int>> pairs;     // (group's first, candidate): to compare
+    std::vector<int> pair_of;                   // the candidate's pair, -1 for a group's first
+};
+inline TwinGroups group_twins(const std::vector<uint64_t> &shift_bits,
+                              const std::vector<uint64_t> &fingerprint) {
+    const int C = (int)shift_bits.size();
+    TwinGroups T;
+    T.first_of.resize(C);
+    T.pair_of.assign(C, -1);
+    std::map<std::pair<uint64_t, uint64_t>, int> groups;
+    for (int i = 0; i < C; ++i) {
+        T.first_of[i] = i;
+        const auto g = std::make_pair(shift_bits[i], fingerprint[i]);
+        const auto it = groups.find(g);
+        if (it == groups.end()) {
+            groups[g] = i;
+            continue;
+        }
+        T.first_of[i] = it->second;
+        T.pair_of[i] = (int)T.pairs.size();
+        T.pairs.emplace_back(it->second, i);
+    }
+    return T;
+}
+// The comparison's flags (one per pair, non-zero: the arrays differ) into classes: cls[i] is the
+// class of candidate i, numbered in order of their first members (`reps`).  Equal fingerprints but
+// different bits: first_of = -1 and no class (-1) -- such a candidate is left to the caller's own
+// comparison, and nothing shares with it.
+inline std::vector<int> twin_classes(TwinGroups &T, const std::vector<unsigned> &differ,
+                                     std::vector<int> *reps) {
+    const int C = (int)T.first_of.size();
+    for (int i = 0; i < C; ++i)
+        if (T.pair_of[i] >= 0 && differ[T.pair_of[i]]) T.first_of[i] = -1;
+    std::vector<int> cls(C, -1);
+    reps->clear();
+    for (int i = 0; i < C; ++i) {
+        if (T.first_of[i] == i) {
+            cls[i] = (int)reps->size();
+            reps->push_back(i);
+        } else if (T.first_of[i] >= 0) {
+            cls[i] = cls[T.first_of[i]];
+        }
+    }
+    return cls;
+}
 
 }  // namespace spec
 }  // namespace kkt

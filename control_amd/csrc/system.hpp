@@ -340,6 +340,8 @@ struct System {
 
 // kkt_debug_block_op (include/kkt.h; csrc/blockops.cpp)
 void debug_block_op(System &S, kkt_block_op *op);
+// kkt_debug_spectrum_op (include/kkt.h; csrc/blockops.cpp)
+void debug_spectrum_op(System &S, kkt_spectrum_op *op);
 // kkt_debug_row_step (include/kkt.h; csrc/rowstep.cpp)
 void debug_row_step(System &S, kkt_row_step *step);
 

@@ -744,6 +744,63 @@ typedef struct kkt_block_op {
 } kkt_block_op;
 int kkt_debug_block_op(kkt_handle h, kkt_block_op *op);
 
+/* Test hook of the kernels of the batched spectrum estimates and the twin search
+ * (csrc/spectrum_kernels.hip): one launch_spec_* of csrc/kernels.hpp on host data, once, on the
+ * handle's stream, with the launcher's own grid.  Works on a created handle; every pointer is host
+ * memory; the hook uploads, launches, synchronises, downloads and releases.
+ *   DOT           launch_spec_dot (both stages), mode KKT_SPECTRUM_DOT_*, k (NORM: the power step),
+ *                 nmat matrices of n rows, max_steps >= 1; x, y: the two vector families, nmat
+ *                 vectors at a spacing of `stride` doubles each (even, >= n; y may be x), read only;
+ *                 the scalar state, all read and written: active, na, nb, rz, coef, last, mu2 (nmat
+ *                 each), alpha, beta (max_steps * nmat, step-major), part (1024 nmat partial sums)
+ *   UPDATE        launch_spec_update, mode KKT_SPECTRUM_UPD_*: v is the family written (R, SCALE: r;
+ *                 P, COPY: p), x the family read (R: w; P, SCALE, COPY: z), both nmat * stride;
+ *                 active and coef, read only here
+ *   SYM_SKEW      launch_spec_sym_skew over nmat arrays of n values: a (nmat * n, contiguous), tpos
+ *                 (n, -1 | < n); h, sk (nmat * n), flag (nmat words)
+ *   FINGERPRINT   launch_spec_fingerprint: a (nmat * n); words receives the nwords =
+ *                 max(1, min(64, ceil(n / 2048))) words of each array (nmat * nwords), fold (nmat,
+ *                 not guarded) the host's fold of them, the value the twin search groups by
+ *   PAIRS_DIFFER  launch_spec_pairs_differ: a (nmat * n); pair q compares arrays pair_a[q] and
+ *                 pair_b[q] (npairs entries in [0, nmat) each; an array may stand on both sides and
+ *                 in several pairs); flag (npairs words, read and written)
+ * Every array but x, y, a, tpos, pair_a, pair_b and fold is guarded as those of kkt_debug_block_op
+ * are: KKT_BLOCK_GUARD elements, the array, KKT_BLOCK_GUARD elements.  The hook sets the guards --
+ * doubles to KKT_KRYLOV_PAD, 64-bit words to its bit pattern, 32-bit words to KKT_BLOCK_FLAG_PAD --
+ * uploads the whole allocation, the array part as the caller filled it, and returns the whole
+ * allocation.  Arrays the launch only reads (active and coef of UPDATE, with their guards, among
+ * them) are downloaded again and compared with what went up: inputs_changed receives the number of
+ * arrays that differ.  batch_stride receives the spacing the estimates themselves use for n rows
+ * (DOT, UPDATE).
+ * KKT_ERR_ARG (nothing launched, no array touched) for an unknown op or mode, a null array the
+ * operation needs, nmat, n, npairs or max_steps < 1, nmat or npairs > 65535, more than 2^31
+ * elements in an array, an odd stride or one below n, k < 0, a negative na or nb, a tpos entry or
+ * pair index outside its range. */
+enum { KKT_SPECTRUM_DOT = 0, KKT_SPECTRUM_UPDATE = 1, KKT_SPECTRUM_SYM_SKEW = 2,
+       KKT_SPECTRUM_FINGERPRINT = 3, KKT_SPECTRUM_PAIRS_DIFFER = 4 };
+enum { KKT_SPECTRUM_DOT_START = 0, KKT_SPECTRUM_DOT_PAP = 1, KKT_SPECTRUM_DOT_RZ = 2,
+       KKT_SPECTRUM_DOT_NORM0 = 3, KKT_SPECTRUM_DOT_NORM = 4 };
+enum { KKT_SPECTRUM_UPD_R = 0, KKT_SPECTRUM_UPD_P = 1, KKT_SPECTRUM_UPD_SCALE = 2,
+       KKT_SPECTRUM_UPD_COPY = 3 };
+typedef struct kkt_spectrum_op {
+    int op, mode, k, nmat, max_steps, npairs;
+    int64_t n, stride;
+    const double *x, *y;
+    double *v;
+    uint32_t *active;
+    int32_t *na, *nb;
+    double *rz, *coef, *last, *mu2, *alpha, *beta, *part;
+    const double *a;
+    const int32_t *tpos;
+    double *h, *sk;
+    const int32_t *pair_a, *pair_b;
+    uint32_t *flag;
+    uint64_t *words, *fold;
+    int64_t batch_stride;
+    int32_t inputs_changed;
+} kkt_spectrum_op;
+int kkt_debug_spectrum_op(kkt_handle h, kkt_spectrum_op *op);
+
 /* Test hook of the preconditioner's row steps: ONE launch of a launcher SchurPC::replay calls
  * (csrc/kernels.hpp) on host data, on the handle's stream.  Needs a finalized handle: block
  * (q, i, j) names the SELL pattern of every op of the call, and every term matrix is a stored block

@@ -9,6 +9,13 @@ with, creation order -- and one ``pc_apply`` of the same vector are identical un
 (single-matrix batches), 3 (does not divide the counts) and 64 (larger than any count).  The
 collection pass must have covered every matrix the build solved with: ``fallbacks == 0``.
 
+Near-twins (case 2b): ``share=False`` copies of one level matrix of which one level differs in a
+single diagonal value, by one ulp or by a factor two.  Which records are estimated and which
+share, the interval each runs with, ``spectrum_stats()["matrices"]`` and, with a coarse space and
+given intervals, the number of coarse inverses are held against the value sets counted on the
+host (``spectrum_ref.value_key``): a comparison that took a near-twin for a twin would solve with
+another matrix's interval or inverse.
+
 The saving itself is asserted from ``spectrum_stats()``, without a clock: a batched Lanczos run
 takes at most ceil(400 / 10) + 4 host synchronisations and the twin search at most 2 per build,
 whatever the number of matrices.
@@ -132,6 +139,122 @@ def test_equal_copies_share_one_estimate():
         assert sum(m["estimate"] == "lanczos" for m in run["mats"]) == distinct, nb
         assert sum(m["estimate"] == "shared" for m in run["mats"]) > 0, nb
         assert run["stats"]["matrices"] == distinct, (nb, run["stats"])
+
+
+# ---- case 2b: near-twins -- level matrices equal but for one stored value of one level.  Only the
+# bit-for-bit comparison of the twin search stands between such a level and a shared interval or
+# a shared coarse inverse.
+NEAR_TWINS = ("first interior diagonal", "last interior diagonal", "dirichlet diagonal",
+              "doubled diagonal")
+NEAR_LEVEL = 2          # a level whose shift its neighbours have too (BE: 1 .. n_t - 2; CN: all)
+
+
+def near_twin_problem(CN, variant):
+    """``heat_problem(share=False)`` -- every level its own copy of the same values -- with one
+    diagonal entry of level ``NEAR_LEVEL``'s matrices moved by one ulp (``doubled``: times two): of
+    the first or last interior row, or of a Dirichlet row, which the boundary conditions remove."""
+    p = common.heat_problem(n=16, n_t=6, beta=1e-4, CN=CN, share=False)
+    nodes = np.asarray(p["nodes"])
+    interior = np.setdiff1d(np.arange(p["sd"].n_dofs), nodes)
+    row = int({NEAR_TWINS[0]: interior[0], NEAR_TWINS[1]: interior[-1], NEAR_TWINS[2]: nodes[0],
+               NEAR_TWINS[3]: interior[len(interior) // 2]}[variant])
+    for quadrant in (1, 2):
+        blk = p["blocks"][quadrant][(NEAR_LEVEL, NEAR_LEVEL)]
+        assert sp.isspmatrix_csr(blk)
+        others = [b for key, b in p["blocks"][quadrant].items() if b is not None and key != (NEAR_LEVEL,) * 2]
+        assert all(b is not blk and not np.shares_memory(b.data, blk.data) for b in others)
+        lo, hi = blk.indptr[row], blk.indptr[row + 1]
+        k = lo + int(np.flatnonzero(blk.indices[lo:hi] == row)[0])
+        blk.data[k] = 2.0 * blk.data[k] if variant == NEAR_TWINS[3] else np.nextafter(blk.data[k], np.inf)
+    return p
+
+
+def solve_keys(p):
+    """The identity of the values each sub-solve's matrix has after assembly, in emission order."""
+    kind = "CN" if p["CN"] else "BE"
+    return [spectrum_ref.value_key(spectrum_ref.assembled(blk, c, p["sd"].M, p["nodes"]), c)
+            for _, _, blk, c in spectrum_ref.schur_solve_map(kind, p["blocks"], p["m"], p["tau"], p["beta"])]
+
+
+def check_twins(name, run, keys, estimated):
+    """The records against the host's value sets: the first matrix of a set is estimated, every
+    later one shares -- with THAT matrix: all solves of a set run with one interval.  Returns
+    ``({value set: its first matrix}, {first matrix: interval bits})``."""
+    solves, mats = run["solves"], run["mats"]
+    assert len(solves) == len(keys), name
+    key_of = {}
+    for s, k in zip(solves, keys):
+        assert key_of.setdefault(s["matrix"], k) == k, (name, "one matrix record for two value sets")
+    first = {}
+    for m, rec in enumerate(mats):
+        if m not in key_of:      # multiplied with only
+            assert rec["solves"] == 0 and rec["estimate"] == "none", (name, m, rec)
+            continue
+        k = key_of[m]
+        want = ("shared" if k in first else "lanczos") if estimated else "given"
+        assert rec["estimate"] == want, (name, m, rec, want)
+        first.setdefault(k, m)
+    interval = {}
+    for s in solves:
+        iv = tuple(float(s[f]).hex() for f in ("emin", "emax", "eimag"))
+        assert interval.setdefault(first[key_of[s["matrix"]]], iv) == iv, (name, s)
+    return first, interval
+
+
+def near_twin_counts(CN, variant, keys):
+    """The number of value sets, from the host: one more than the unperturbed problem's, but for
+    the Dirichlet entry."""
+    base = spectrum_ref.distinct_solved_matrices(common.heat_problem(n=16, n_t=6, beta=1e-4, CN=CN,
+                                                                      share=False))
+    distinct = len(set(keys))
+    assert distinct == base + (0 if variant == NEAR_TWINS[2] else 1), (variant, base, distinct)
+    return distinct
+
+
+@pytest.mark.parametrize("variant", NEAR_TWINS, ids=lambda v: v.replace(" ", "-"))
+@pytest.mark.parametrize("CN", [False, True], ids=["BE", "CN"])
+def test_near_twins_are_not_twins(CN, variant):
+    name = f"near-twin {variant} {'CN' if CN else 'BE'}"
+    p = near_twin_problem(CN, variant)
+    keys = solve_keys(p)
+    distinct = near_twin_counts(CN, variant, keys)
+    runs = {nb: heat_run(p, nb) for nb in (0,) + BATCHES}
+    check_equal(name, runs)
+    for nb, run in runs.items():
+        first, interval = check_twins(f"{name} batch {nb}", run, keys, True)
+        assert len(first) == distinct
+        assert run["stats"]["matrices"] == distinct, (nb, run["stats"])
+        assert run["stats"]["fallbacks"] == 0
+        if variant == NEAR_TWINS[3]:      # a false twin would also show in the interval
+            assert interval[first[keys[NEAR_LEVEL]]] != interval[first[keys[NEAR_LEVEL - 1]]], nb
+
+
+@pytest.mark.parametrize("variant", NEAR_TWINS, ids=lambda v: v.replace(" ", "-"))
+@pytest.mark.parametrize("CN", [False, True], ids=["BE", "CN"])
+def test_near_twins_do_not_share_a_coarse_inverse(CN, variant):
+    """Two-grid sub-solves with given intervals: nothing is estimated, the twin search alone
+    decides which matrices share a coarse inverse."""
+    name = f"near-twin two-grid {variant} {'CN' if CN else 'BE'}"
+    p = near_twin_problem(CN, variant)
+    keys = solve_keys(p)
+    distinct = near_twin_counts(CN, variant, keys)
+    P = sp.csr_matrix(multilinear_coarse_space(p["sd"].coords, p["nodes"], cells=4))
+    runs = {}
+    for nb in (0,) + BATCHES:
+        g = common.gpu_system(p, options=opts(nb))
+        y = g.pc_apply(common.rng_vector(g.local_size), common.gpu_pc(p, MASS, (4, 0.3, 1.9), coarse=(P, 2)))
+        runs[nb] = dict(solves=g.pc_solves(), mats=g.pc_matrices(), stats=g.spectrum_stats(),
+                        coarse=g.coarse_setup_stats()["matrices"], y=y.tobytes())
+        g.close()
+    for nb, run in runs.items():
+        assert bits(run["mats"]) == bits(runs[0]["mats"]), (name, nb)
+        assert bits(run["solves"]) == bits(runs[0]["solves"]), (name, nb)
+        assert run["y"] == runs[0]["y"], (name, nb, "pc_apply differs")
+        first, _ = check_twins(f"{name} batch {nb}", run, keys, False)
+        assert len(first) == distinct
+        assert run["coarse"] == distinct, (name, nb, run["coarse"], distinct)
+        assert run["stats"]["fallbacks"] == 0 and run["stats"]["matrices"] == 0, (nb, run["stats"])
+        assert all(m["coarse"] for m in run["mats"] if m["solves"]), nb
 
 
 # ---- case 3: width 15, and ragged rows with perm
