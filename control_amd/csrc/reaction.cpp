@@ -19,7 +19,9 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
     if (S.relin)
         fail(KKT_ERR_STATE, "kkt_set_reaction_relinearisation: the handle carries a Navier-Stokes "
                             "plan (kkt_set_relinearisation)");
-    need(d->nq == RELIN_NQ, "nq must be 7 (Radon's rule)");
+    need(d->nq == 7 || d->nq == 15,
+         "nq must be 7 (P1 triangles, Radon's rule) or 15 (P1 tetrahedra, Stroud's T3:5-1)");
+    const int nv = d->nq == 7 ? 3 : 4, ep = nv * nv;
     need(d->n_t >= 2 && d->ne > 0 && d->n1 > 0 && d->nnz > 0, "sizes must be positive");
     need(d->degree >= 0 && d->degree <= REACTION_MAX_DEGREE, "degree must be 0 .. 4");
     const int m = d->cn ? d->n_t - 1 : d->n_t;
@@ -29,9 +31,9 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
     need(d->cells && d->W && d->lam && d->L && d->M && d->data && (d->n_bc == 0 || d->bc_idx),
          "null array");
     const int64_t n1 = d->n1, nnz = d->nnz, ne = d->ne;
-    const int64_t n_entries = ne * RELIN_EP;
+    const int64_t n_entries = ne * ep;
     const std::string api = "kkt_set_reaction_relinearisation: ";
-    check_range(api + "cells", d->cells, ne * 3, n1);
+    check_range(api + "cells", d->cells, ne * nv, n1);
     check_csr(api + "pattern", d->indptr, d->indices, n1, n1, nnz);
     check_perm(api + "tperm", d->tperm, nnz);
     check_lists(api + "contribution lists", d->cptr, d->clist, nnz, n_entries);
@@ -41,6 +43,9 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
     P->n_t = d->n_t;
     P->m = m;
     P->CN = d->cn != 0;
+    P->nv = nv;
+    P->nq = d->nq;
+    P->ep = ep;
     P->ne = ne;
     P->n1 = n1;
     P->nnz = nnz;
@@ -48,9 +53,9 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
     P->beta = d->beta;
     P->coef.degree = d->degree;
     for (int k = 0; k <= REACTION_MAX_DEGREE; ++k) P->coef.c[k] = k <= d->degree ? d->c[k] : 0.0;
-    P->d_cells = P->mem.upload(d->cells, ne * 3);
-    P->d_W = P->mem.upload(d->W, ne * RELIN_NQ);
-    P->d_lam = P->mem.upload(d->lam, (int64_t)RELIN_NQ * 3);
+    P->d_cells = P->mem.upload(d->cells, ne * nv);
+    P->d_W = P->mem.upload(d->W, ne * d->nq);
+    P->d_lam = P->mem.upload(d->lam, (int64_t)d->nq * nv);
     P->d_ip = P->mem.upload(d->indptr, n1 + 1);
     P->d_ix = P->mem.upload(d->indices, nnz);
     P->d_tperm = P->mem.upload(d->tperm, nnz);
@@ -93,7 +98,7 @@ void reaction_apply(System &T, System &PS, int assemble, int n, const kkt_relin_
     if (assemble) {
         launch_reaction_elements(PS.stream, P);
         // D = 1.0 * L[k] + acc: the product is exact, so this is L + C with one rounding
-        launch_relin_gather_one(PS.stream, P.d_cptr, P.d_clist, P.d_E, P.ne * RELIN_EP, P.d_L, 1.0,
+        launch_relin_gather_one(PS.stream, P.d_cptr, P.d_clist, P.d_E, P.ne * P.ep, P.d_L, 1.0,
                                 P.nnz, P.n_t, P.d_D);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(PS.stream));
@@ -141,7 +146,7 @@ void reaction_debug_array(System &S, int which, double *out, int64_t cap) {
     if (which < 2 && !P.assembled)
         fail(KKT_ERR_STATE, "kkt_debug_reaction_array: nothing assembled yet");
     const double *src[4] = {P.d_E, P.d_D, P.d_v, P.d_zeta};
-    const int64_t per_level[4] = {P.ne * RELIN_EP, P.nnz, P.n1, P.n1};
+    const int64_t per_level[4] = {P.ne * P.ep, P.nnz, P.n1, P.n1};
     const int64_t n = per_level[which] * P.n_t;
     if (!out || cap < n) fail(KKT_ERR_ARG, "kkt_debug_reaction_array: buffer too small");
     HIPCHK(hipStreamSynchronize(S.stream));

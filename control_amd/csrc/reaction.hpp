@@ -23,6 +23,9 @@ struct ReactionCoef {
 
 struct ReactionPlan {
     int n_t = 0, m = 0;   // time levels, unknown blocks per family
+    // the element: nodes per cell (3: triangles, 4: tetrahedra), quadrature points (7: Radon's
+    // rule, 15: Stroud's T3:5-1) and entries of one element matrix, nv * nv
+    int nv = 0, nq = 0, ep = 0;
     bool CN = false;
     int64_t ne = 0, n1 = 0, nnz = 0;
     double tau = 0.0, beta = 0.0;
@@ -35,7 +38,7 @@ struct ReactionPlan {
     double *d_L = nullptr, *d_M = nullptr;
     uint8_t *d_bc = nullptr;    // n1 bytes: Dirichlet dofs
     double *d_data = nullptr;   // 2m x n1 data rows
-    // work: element matrices (n_t x ne x 9) and D (n_t x nnz) of the last assembly
+    // work: element matrices (n_t x ne x ep) and D (n_t x nnz) of the last assembly
     double *d_E = nullptr, *d_D = nullptr;
     bool assembled = false;
     double *d_v = nullptr, *d_zeta = nullptr;   // the iterate, n_t x n1 each
@@ -43,7 +46,8 @@ struct ReactionPlan {
     Composer compose;                           // one space: the scalar pattern
 };
 
-// E[(l ne + e) 9 + 3a + b] of every (element, level) at the iterate's v
+// E[(l ne + e) ep + nv a + b] of every (element, level) at the iterate's v; the kernel is chosen
+// by the plan's element
 void launch_reaction_elements(hipStream_t s, const ReactionPlan &P);
 // rows [r0 | r1] of Instationary.non_linear_res_eval, 2m x n1
 void launch_reaction_residual(hipStream_t s, const ReactionPlan &P, double *d_r);

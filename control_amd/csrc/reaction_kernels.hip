@@ -60,10 +60,71 @@ __global__ __launch_bounds__(256) void reaction_elements_kernel(
     }
 }
 
+constexpr int TET_NV = 4;     // nodes of a tetrahedron
+constexpr int TET_NQ = 15;    // Stroud's T3:5-1
+constexpr int TET_EP = 16;    // entries of its element matrix
+
+// The same statement on P1 tetrahedra: s_q = ((lam_q0 v_0 + lam_q1 v_1) + lam_q2 v_2) + lam_q3 v_3
+// over the 15 points of Stroud's T3:5-1, W_eq = wq_q volume_e, all 16 entries on their own
+// ((wg la) lb and (wg lb) la round differently).  The 15 x 4 table is uniform over the wave: through
+// const __restrict__ it comes by scalar loads into SGPRs and costs no vector register.  One thread
+// owns the 128 contiguous bytes of its element matrix and writes them as eight 16-byte stores
+// (E is 256-byte aligned and every matrix starts at a multiple of 128 bytes).
+__global__ __launch_bounds__(256) void reaction_elements_tet_kernel(
+    const double *__restrict__ v, int64_t ne, int64_t n1, int n_t,
+    const int32_t *__restrict__ cells, const double *__restrict__ W,
+    const double *__restrict__ lam, ReactionCoef C, double *__restrict__ E) {
+    const int64_t total = ne * n_t;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
+         t += (int64_t)gridDim.x * blockDim.x) {
+#pragma clang fp contract(off)
+        const int64_t l = t / ne, e = t - l * ne;
+        const double *vl = v + l * n1;
+        const int32_t *ce = cells + e * TET_NV;
+        const double v0 = vl[ce[0]], v1 = vl[ce[1]], v2 = vl[ce[2]], v3 = vl[ce[3]];
+        double acc[TET_EP];
+#pragma unroll
+        for (int k = 0; k < TET_EP; ++k) acc[k] = 0.0;
+        // three rounds of five points: a full unroll hoists all 60 table entries out of the
+        // grid-stride loop, 120 SGPRs, and spills 74 of them into vector lanes (100 VGPRs)
+#pragma unroll 5
+        for (int q = 0; q < TET_NQ; ++q) {
+            const double la[TET_NV] = {lam[q * TET_NV], lam[q * TET_NV + 1], lam[q * TET_NV + 2],
+                                       lam[q * TET_NV + 3]};
+            const double p0 = la[0] * v0, p1 = la[1] * v1, p2 = la[2] * v2, p3 = la[3] * v3;
+            const double s01 = p0 + p1;
+            const double s012 = s01 + p2;
+            const double s = s012 + p3;
+            double g = C.c[C.degree];
+            for (int k = C.degree - 1; k >= 0; --k) {
+                const double gs = g * s;
+                g = gs + C.c[k];
+            }
+            const double wg = W[e * TET_NQ + q] * g;
+#pragma unroll
+            for (int a = 0; a < TET_NV; ++a) {
+                const double wa = wg * la[a];
+#pragma unroll
+                for (int b = 0; b < TET_NV; ++b) {
+                    const double term = wa * la[b];
+                    acc[a * TET_NV + b] = acc[a * TET_NV + b] + term;
+                }
+            }
+        }
+        double2 *o = reinterpret_cast<double2 *>(E + t * TET_EP);
+#pragma unroll
+        for (int k = 0; k < TET_EP / 2; ++k) o[k] = make_double2(acc[2 * k], acc[2 * k + 1]);
+    }
+}
+
 void launch_reaction_elements(hipStream_t s, const ReactionPlan &P) {
-    hipLaunchKernelGGL(reaction_elements_kernel,
-                       dim3(grid_of(P.ne * P.n_t, REACTION_ELEMENT_BLOCKS)), dim3(256), 0, s,
-                       P.d_v, P.ne, P.n1, P.n_t, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
+    const dim3 grid(grid_of(P.ne * P.n_t, REACTION_ELEMENT_BLOCKS));
+    if (P.nv == TET_NV)
+        hipLaunchKernelGGL(reaction_elements_tet_kernel, grid, dim3(256), 0, s, P.d_v, P.ne, P.n1,
+                           P.n_t, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
+    else
+        hipLaunchKernelGGL(reaction_elements_kernel, grid, dim3(256), 0, s, P.d_v, P.ne, P.n1,
+                           P.n_t, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
 }
 
 // sum_k A[k] x[col[k]] over CSR row r from 0.0 in stored order (tperm: the transposed matrix on

@@ -25,6 +25,7 @@ __all__ = [
     "unit_cube_p1",
     "unit_square_q2",
     "rectangle_p1",
+    "box_p1",
     "ReactionTerm",
 ]
 
@@ -38,7 +39,7 @@ class SpatialDiscretisation:
     coords: np.ndarray        # (N_x, dim) dof coordinates
     boundary: np.ndarray      # int32 sorted dof indices on the whole boundary
     name: str = ""
-    cells: np.ndarray = None  # (n_cells, 3) vertex indices (P1 triangles only)
+    cells: np.ndarray = None  # (n_cells, 3 | 4) vertex indices (P1 triangles / tetrahedra only)
 
     @property
     def n_dofs(self) -> int:
@@ -49,7 +50,7 @@ class SpatialDiscretisation:
         quadrature points: ``w(lam)`` receives the barycentric coordinates ``(nq, 3)`` of
         Radon's 7-point rule and the cell connectivity and returns ``(n_cells, nq)`` values.
         P1 triangles; same structure as ``M``."""
-        if self.cells is None:
+        if self.cells is None or np.shape(self.cells)[1] != 3:
             raise NotImplementedError("weighted_mass needs a P1 triangle discretisation")
         s15 = np.sqrt(15.0)
         a1, a2 = (6.0 - s15) / 21.0, (6.0 + s15) / 21.0
@@ -69,7 +70,7 @@ class SpatialDiscretisation:
 def _p1_convection(self, wind) -> sp.csr_matrix:
     """``inner(dot(grad(trial), wind), test) * dx`` for P1 triangles: ``wind(X) -> (n, 2)`` is
     evaluated at the points of Radon's 7-point rule (degree 5); same structure as ``M``."""
-    if self.cells is None:
+    if self.cells is None or np.shape(self.cells)[1] != 3:
         raise NotImplementedError("convection needs a P1 triangle discretisation")
     s15 = np.sqrt(15.0)
     a1, a2 = (6.0 - s15) / 21.0, (6.0 + s15) / 21.0
@@ -105,11 +106,34 @@ def _radon_rule():
     return lam, wq
 
 
+def _stroud_rule():
+    """``(lam, wq)`` of Stroud's T3:5-1: 15 points, degree 5 on the tetrahedron, all weights
+    positive (the sibling of Radon's rule, with the same root of 15).  Barycentric points,
+    weights as fractions of the volume: the centroid; two orbits of four points ``(1 - 3a, a, a,
+    a)`` with the odd coordinate at position 0, 1, 2, 3; the six points with ``b`` at the positions
+    ``(i, j)``, ``i < j`` in lexicographic order, and ``c`` at the other two."""
+    s15 = np.sqrt(15.0)
+    lam = [[0.25, 0.25, 0.25, 0.25]]
+    wq = [16.0 / 135.0]
+    for a, w in (((7.0 - s15) / 34.0, (2665.0 + 14.0 * s15) / 37800.0),
+                 ((7.0 + s15) / 34.0, (2665.0 - 14.0 * s15) / 37800.0)):
+        for k in range(4):
+            lam.append([1.0 - 3.0 * a if c == k else a for c in range(4)])
+            wq.append(w)
+    b, c = (10.0 - 2.0 * s15) / 40.0, (10.0 + 2.0 * s15) / 40.0
+    for i in range(4):
+        for j in range(i + 1, 4):
+            lam.append([b if k in (i, j) else c for k in range(4)])
+            wq.append(10.0 / 189.0)
+    return np.array(lam), np.array(wq)
+
+
 class ReactionTerm:
     """The forward form ``(L u, w) + (g(v_old) u, w)`` with a polynomial reaction coefficient
-    ``g(s) = sum_k c_k s^k`` (``coefficients = (c_0, ..., c_p)``, ``p <= 4``) on P1 triangles --
-    the reference's non-linear scalar problem is ``grad v . grad w + (2 + 0.5 v^2) v w``
-    (``test/test_control.py:715-719``): ``ReactionTerm(disc, (2, 0, 0.5))``.
+    ``g(s) = sum_k c_k s^k`` (``coefficients = (c_0, ..., c_p)``, ``p <= 4``) on P1 triangles or
+    P1 tetrahedra (``disc.cells`` with 3 or 4 columns) -- the reference's non-linear scalar problem
+    is ``grad v . grad w + (2 + 0.5 v^2) v w`` (``test/test_control.py:715-719``):
+    ``ReactionTerm(disc, (2, 0, 0.5))``.
 
     ``L`` is ``nu * disc.K``, or any CSR matrix ``linear`` inside the structure of ``disc.M``
     (``disc.K + disc.convection(wind)``: a non-symmetric linear part).  ``term(v, t)`` is the
@@ -124,16 +148,22 @@ class ReactionTerm:
         g   = c_p;  g = g s_q + c_k  for k = p - 1, ..., 0            (Horner)
         E[a][b] = sum_q ((W_eq g) lam_qa) lam_qb   from 0.0,  W_eq = wq_q area_e
 
-    every product and sum rounded separately.  The entries are summed into the structure of ``M``
-    by ``np.bincount`` (ascending element-entry order), and ``D = L + C`` with one rounding."""
+    every product and sum rounded separately.  On tetrahedra the points are the 15 of Stroud's
+    T3:5-1 (``_stroud_rule``), ``s_q = ((lam_q0 v_0 + lam_q1 v_1) + lam_q2 v_2) + lam_q3 v_3``,
+    ``W_eq = wq_q volume_e`` with ``volume = |det [1 x]| / 6``, and all 16 entries are computed
+    separately (``(wg la) lb`` and ``(wg lb) la`` round differently).  The flat element entry is
+    ``e nv^2 + nv a + b`` for ``nv`` nodes per cell.  The entries are summed into the structure
+    of ``M`` by ``np.bincount`` (ascending element-entry order), and ``D = L + C`` with one
+    rounding."""
 
     MAX_DEGREE = 4
 
     def __init__(self, disc, coefficients, *, nu=1.0, linear=None):
         from .blocks import conform_to
         cells = getattr(disc, "cells", None)
-        if cells is None or np.ndim(cells) != 2 or np.shape(cells)[1] != 3:
-            raise ValueError("ReactionTerm needs a P1 triangle discretisation (disc.cells)")
+        if cells is None or np.ndim(cells) != 2 or np.shape(cells)[1] not in (3, 4):
+            raise ValueError("ReactionTerm needs a discretisation by P1 triangles or P1 "
+                             "tetrahedra (disc.cells with 3 or 4 columns)")
         self.coefficients = tuple(float(c) for c in coefficients)
         if not 1 <= len(self.coefficients) <= self.MAX_DEGREE + 1:
             raise ValueError(f"ReactionTerm: the degree must be 0 .. {self.MAX_DEGREE}")
@@ -141,14 +171,21 @@ class ReactionTerm:
         self.M = _canonical_csr(disc.M)
         self.L = conform_to(nu * disc.K if linear is None else linear, self.M)
         self.cells = np.ascontiguousarray(cells, dtype=np.int32)
-        self.lam, self.wq = _radon_rule()
+        nv = self.nv = self.cells.shape[1]
         X = disc.coords[self.cells]
-        d1, d2 = X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]
-        self.area = 0.5 * np.abs(d1[:, 0] * d2[:, 1] - d1[:, 1] * d2[:, 0])
-        self.W = self.wq[None, :] * self.area[:, None]
-        rows = np.repeat(self.cells, 3, axis=1).ravel()
-        cols = np.tile(self.cells, (1, 3)).ravel()
-        #: position in the structure of ``M`` of every flat element entry ``e * 9 + 3 a + b``
+        if nv == 3:
+            self.lam, self.wq = _radon_rule()
+            d1, d2 = X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]
+            self.area = 0.5 * np.abs(d1[:, 0] * d2[:, 1] - d1[:, 1] * d2[:, 0])
+            self.W = self.wq[None, :] * self.area[:, None]
+        else:
+            self.lam, self.wq = _stroud_rule()
+            A = np.concatenate([np.ones((len(X), 4, 1)), X], axis=2)
+            self.volume = np.abs(np.linalg.det(A)) / 6.0
+            self.W = self.wq[None, :] * self.volume[:, None]
+        rows = np.repeat(self.cells, nv, axis=1).ravel()
+        cols = np.tile(self.cells, (1, nv)).ravel()
+        #: position in the structure of ``M`` of every flat element entry ``e nv^2 + nv a + b``
         self.scatter = self.M.indptr[rows].astype(np.int64) + _row_positions(self.M, rows, cols)
 
     @property
@@ -160,22 +197,23 @@ class ReactionTerm:
         return tuple((k + 1) * c for k, c in enumerate(self.coefficients))
 
     def element_matrices(self, v, coefficients=None):
-        """``E`` (n_cells, 3, 3) at the nodal values ``v``: the statement above, an explicit
+        """``E`` (n_cells, nv, nv) at the nodal values ``v``: the statement above, an explicit
         loop over the points, vectorised over the cells."""
         c = self.coefficients if coefficients is None else tuple(coefficients)
-        lam, W = self.lam, self.W
+        lam, W, nv = self.lam, self.W, self.nv
         vc = np.asarray(v, dtype=np.float64)[self.cells]
-        v0, v1, v2 = vc[:, 0], vc[:, 1], vc[:, 2]
-        E = np.zeros((len(self.cells), 3, 3))
+        E = np.zeros((len(self.cells), nv, nv))
         for q in range(len(self.wq)):
-            s = (lam[q, 0] * v0 + lam[q, 1] * v1) + lam[q, 2] * v2
+            s = lam[q, 0] * vc[:, 0]
+            for k in range(1, nv):                       # left to right, each product rounded
+                s = s + lam[q, k] * vc[:, k]
             g = np.full(len(s), c[-1])
             for k in range(len(c) - 2, -1, -1):
                 g = g * s + c[k]
             wg = W[:, q] * g
-            for a in range(3):
+            for a in range(nv):
                 wa = wg * lam[q, a]
-                for b in range(3):
+                for b in range(nv):
                     E[:, a, b] += wa * lam[q, b]
         return E
 
@@ -295,6 +333,43 @@ def unit_cube_p1(n: int) -> SpatialDiscretisation:
     return SpatialDiscretisation(M, K, coords,
                                  np.flatnonzero(onb).astype(np.int32),
                                  f"P1 {n}^3")
+
+
+def box_p1(nx: int, ny: int, nz: int, lx: float = 1.0, ly: float = 1.0,
+           lz: float = 1.0) -> SpatialDiscretisation:
+    """P1 on the Kuhn subdivision (six tetrahedra per cell, as ``unit_cube_p1``) of
+    ``[0,lx] x [0,ly] x [0,lz]``.  Node ``(i, j, k)`` has index ``(k (ny+1) + j)(nx+1) + i``.
+    It carries its ``cells`` (``(6 nx ny nz, 4)``), which ``ReactionTerm`` needs:
+    ``box_p1(n, n, n)`` is ``unit_cube_p1(n)``, array for array, with them -- ``unit_cube_p1``
+    itself carries none, and a ``ReactionTerm`` on it is refused as before."""
+    import itertools
+    xs = np.linspace(0.0, lx, nx + 1)
+    ys = np.linspace(0.0, ly, ny + 1)
+    zs = np.linspace(0.0, lz, nz + 1)
+    ZZ, YY, XX = np.meshgrid(zs, ys, xs, indexing="ij")
+    coords = np.stack([XX.ravel(), YY.ravel(), ZZ.ravel()], axis=1)
+
+    def nid(i, j, k):
+        return (k * (ny + 1) + j) * (nx + 1) + i
+
+    kk, jj, ii = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    ii, jj, kk = ii.ravel(), jj.ravel(), kk.ravel()
+    cells = []
+    for perm in itertools.permutations(range(3)):
+        off = [0, 0, 0]
+        verts = [nid(ii, jj, kk)]
+        for ax in perm:
+            off[ax] = 1
+            verts.append(nid(ii + off[0], jj + off[1], kk + off[2]))
+        cells.append(np.stack(verts, 1))
+    cells = np.concatenate(cells, 0)
+    M, K = _p1_simplex_assemble(coords, cells)
+    onb = np.zeros(len(coords), dtype=bool)
+    for d, ax in enumerate((xs, ys, zs)):
+        onb |= (coords[:, d] == ax[0]) | (coords[:, d] == ax[-1])
+    return SpatialDiscretisation(M, K, coords,
+                                 np.flatnonzero(onb).astype(np.int32),
+                                 f"P1 {nx}x{ny}x{nz}", cells)
 
 
 def _p2_1d(n: int, length: float):

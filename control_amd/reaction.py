@@ -1,6 +1,6 @@
 """The scalar Picard / Gauss-Newton loop on the device (``kkt_set_reaction_relinearisation``,
 DESIGN.md section 6.6a): ``Instationary.non_linear_solve(device=True)`` for a forward operator
-declared as a ``fem.ReactionTerm``.
+declared as a ``fem.ReactionTerm``, on P1 triangles or P1 tetrahedra.
 
 Host side: ``ReactionPlan`` -- the element tables of the term, the contribution lists that make
 the device assembly deterministic (``relinearise.contribution_lists``), the transpose permutation
@@ -25,7 +25,9 @@ _ARRAYS = ("E", "D", "v", "zeta")
 
 
 def _check(ctl, P=None):
-    """The ``ValueError``s of ``non_linear_solve(device=True)``: nothing here touches the GPU."""
+    """The ``ValueError``s of ``non_linear_solve(device=True)``: nothing here touches the GPU.
+    A ``fem.ReactionTerm`` is on P1 triangles or P1 tetrahedra by construction (its own
+    ``ValueError`` names both), and both run here."""
     if not isinstance(ctl._forward, ReactionTerm):
         raise ValueError("device=True needs the forward operator declared as a fem.ReactionTerm")
     if P is not None:
@@ -84,7 +86,9 @@ class ReactionPlan:
         return M.indptr.astype(np.int32), M.indices.astype(np.int32)
 
     def descriptor(self):
-        """``kkt_reaction_desc`` over this plan's arrays (valid while ``keep`` lives)."""
+        """``kkt_reaction_desc`` over this plan's arrays (valid while ``keep`` lives).  ``nq``, the
+        number of quadrature points of the term's rule, tells the library the element: 7 for P1
+        triangles, 15 for P1 tetrahedra; the tables go as the term holds them."""
         term, disc = self.term, self.ctl._disc
         i32, f64, keep = _marshal()
         c = (C.c_double * 5)(*self.coefficients)
@@ -156,10 +160,12 @@ class DeviceReaction:
         self.system._ck(self._lib.kkt_reaction_update_device(self.system.handle, d_u))
 
     def debug_array(self, which):
-        """``kkt_debug_reaction_array``: ``"E"`` (n_t, ne, 3, 3) or ``"D"`` (n_t, nnz) of the last
-        assembly, ``"v"`` / ``"zeta"`` (n_t, n) of the iterate."""
+        """``kkt_debug_reaction_array``: ``"E"`` (n_t, ne, nv, nv) or ``"D"`` (n_t, nnz) of the
+        last assembly, ``"v"`` / ``"zeta"`` (n_t, n) of the iterate (``nv``: 3 nodes per triangle,
+        4 per tetrahedron)."""
         n_t, n = self._shape()
-        shape = {"E": (n_t, len(self.plan.term.cells), 3, 3), "D": (n_t, self.plan.term.M.nnz),
+        ne, nv = self.plan.term.cells.shape
+        shape = {"E": (n_t, ne, nv, nv), "D": (n_t, self.plan.term.M.nnz),
                  "v": (n_t, n), "zeta": (n_t, n)}[which]
         out = np.empty(shape)
         self.system._ck(self._lib.kkt_debug_reaction_array(

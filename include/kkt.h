@@ -495,13 +495,20 @@ enum { KKT_RELIN_EV = 0, KKT_RELIN_EP = 1, KKT_RELIN_D2 = 2, KKT_RELIN_DP = 3, K
 int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
 /* ---- Device re-linearisation of the scalar reaction problem.
  *
- * The forward operator is (L u, w) + (g(v_old) u, w) on P1 triangles with the polynomial
- * g(s) = sum_k c[k] s^k, degree <= 4 (fem.ReactionTerm).  Per (element, level) the element matrix
- *   E[a][b] = sum_q (W_eq g(s_q)) lam_qa lam_qb,   s_q = lam_q0 v_0 + lam_q1 v_1 + lam_q2 v_2,
- * over Radon's 7 points, q ascending from 0.0, g by Horner from c[degree] down, every product and
- * sum rounded separately; the entries are gathered into the scalar pattern through the
- * contribution lists (flat entry e * 9 + 3 a + b, ascending: np.bincount's order) and
- * D = L + C with one rounding per entry.  The handle must be a scalar instationary layout
+ * The forward operator is (L u, w) + (g(v_old) u, w) on P1 triangles or P1 tetrahedra with the
+ * polynomial g(s) = sum_k c[k] s^k, degree <= 4 (fem.ReactionTerm).  nq selects the element, with
+ * nv nodes per cell:
+ *   nq = 7:  triangles (nv = 3), Radon's 7 points; cells ne x 3, lam 7 x 3, E ne x 9 per level;
+ *   nq = 15: tetrahedra (nv = 4), the 15 points of Stroud's T3:5-1 (degree 5, positive weights);
+ *            cells ne x 4, lam 15 x 4, E ne x 16 per level, W = weight times the volume;
+ * any other nq is KKT_ERR_ARG.  Per (element, level) the element matrix
+ *   E[a][b] = sum_q (W_eq g(s_q)) lam_qa lam_qb,   s_q = sum_c lam_qc v_c summed left to right,
+ * over the points q ascending from 0.0, g by Horner from c[degree] down, every product and sum
+ * rounded separately, all nv * nv entries computed on their own; the entries are gathered into the
+ * scalar pattern through the contribution lists (flat entry e * nv * nv + nv * a + b, ascending:
+ * np.bincount's order) and D = L + C with one rounding per entry.  The element matrices of all
+ * levels are kept: n_t * ne * nv * nv doubles beside D (n_t * nnz) -- on 64^3 cells x 128 levels
+ * of tetrahedra 25.8 GB and 4 GB.  The handle must be a scalar instationary layout
  * (n_blocks_00 = n_blocks_11 = m, nx0 = nx1 = n1; m = n_t, Crank-Nicolson n_t - 1), finalized,
  * on one rank.  A handle carries at most one plan, of this kind or of kkt_set_relinearisation's:
  * setting the other kind is KKT_ERR_STATE.  data: the 2m x n1 rows [adjoint | state] of
@@ -511,12 +518,13 @@ int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
  * permutations are validated as kkt_set_relinearisation validates its own (KKT_ERR_ARG naming what
  * does not fit). */
 typedef struct kkt_reaction_desc {
-    int n_t, cn, nq;              /* time levels, Crank-Nicolson (1) or backward Euler, nq = 7 */
-    int64_t ne, n1;               /* triangles, P1 nodes */
+    int n_t, cn, nq;              /* time levels, Crank-Nicolson (1) or backward Euler; nq = 7:
+                                     triangles (nv = 3), nq = 15: tetrahedra (nv = 4) */
+    int64_t ne, n1;               /* cells, P1 nodes */
     double tau, beta;
-    const int32_t *cells;         /* ne x 3 nodes per triangle */
-    const double *W;              /* ne x nq quadrature weights times the area */
-    const double *lam;            /* nq x 3 barycentric coordinates of the points */
+    const int32_t *cells;         /* ne x nv nodes per cell */
+    const double *W;              /* ne x nq quadrature weights times the area / the volume */
+    const double *lam;            /* nq x nv barycentric coordinates of the points */
     int64_t nnz;                  /* the scalar pattern (that of M) */
     const int32_t *indptr, *indices, *tperm, *cptr, *clist;
     const double *L, *M;          /* nnz values: the linear part and the mass matrix */
@@ -548,7 +556,8 @@ int kkt_reaction_residual_device(kkt_handle plan, double *d_out, int rhs, double
  * 0 .. n_t - 2); v is left untouched on the Dirichlet dofs (they hold the boundary values), zeta
  * is zero there; d_u is zeroed: the initial guess of the next solve. */
 int kkt_reaction_update_device(kkt_handle plan, double *d_u);
-/* Test hook: the element matrices E (n_t x ne x 9) or D (n_t x nnz) of the last assembly
+/* Test hook: the element matrices E (n_t x ne x nv x nv: 9 doubles per triangle, 16 per
+ * tetrahedron) or D (n_t x nnz) of the last assembly
  * (KKT_ERR_STATE before one), or v / zeta (n_t x n1) of the iterate, copied to the host; cap:
  * doubles available at out (KKT_ERR_ARG when too small). */
 enum { KKT_REACTION_E = 0, KKT_REACTION_D = 1, KKT_REACTION_V = 2, KKT_REACTION_ZETA = 3 };

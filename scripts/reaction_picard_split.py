@@ -1,5 +1,7 @@
 """Reaction-diffusion control (256^2 P1 x 64 levels, BE, g(v) = 2 + 0.5 v^2, beta = 1e-4, [0, 2]) on
-one GPU: wall time of a Picard iteration outside the linearised solve, the host loop against
+one GPU -- or, with ``--mesh cube``, the same problem on P1 tetrahedra (``box_p1(n, n, n)``; the
+record of ``profiles/reaction_picard_3d.md`` is ``--mesh cube --n 32 --n_t 32``) --: wall time of
+a Picard iteration outside the linearised solve, the host loop against
 ``non_linear_solve(device=True)``.  Both paths run in one process, alternating, after one warm-up
 iteration each.  One JSON line per loop.
 
@@ -18,6 +20,7 @@ from control_amd import fem, multiblock
 from control_amd.control import GpuBackend, Instationary
 
 ap = argparse.ArgumentParser()
+ap.add_argument("--mesh", choices=("square", "cube"), default="square")
 ap.add_argument("--n", type=int, default=256)
 ap.add_argument("--n_t", type=int, default=64)
 ap.add_argument("--beta", type=float, default=1.0e-4)
@@ -27,11 +30,15 @@ ap.add_argument("--repeats", type=int, default=1, help="measured loops per path"
 ap.add_argument("--multigrid", type=int, default=1)
 a = ap.parse_args()
 
-disc = fem.unit_square_p1(a.n)
+disc = fem.box_p1(a.n, a.n, a.n) if a.mesh == "cube" else fem.unit_square_p1(a.n)
+# the interval of the mass solves: Wathen's bounds for P1 triangles / P1 tetrahedra
+MASS = (0.5, 2.5) if a.mesh == "cube" else None
 
 
 def v_d(X, t):
-    return (1.0 + t) * np.sin(np.pi * X[:, 0]) * np.sin(np.pi * X[:, 1]) * np.exp(X[:, 0])
+    bump = np.prod(np.sin(np.pi * X), axis=1) if a.mesh == "cube" else (
+        np.sin(np.pi * X[:, 0]) * np.sin(np.pi * X[:, 1]))
+    return (1.0 + t) * bump * np.exp(X[:, 0])
 
 
 def control():
@@ -67,10 +74,12 @@ def loop(device, its):
     marks.clear()
     t0 = time.perf_counter()
     norms = ctl.non_linear_solve(max_non_linear_iter=its, relative_non_linear_tol=a.rtol,
+                                 lambda_v_bounds=MASS,
                                  backend=GpuBackend(), Multigrid=bool(a.multigrid), device=device)
     t1 = time.perf_counter()
     outside = [marks[k][0] - marks[k - 1][1] for k in range(1, len(marks))]
-    return dict(path="device" if device else "host", n=a.n, n_t=a.n_t, total_s=round(t1 - t0, 3),
+    return dict(path="device" if device else "host", mesh=a.mesh, n=a.n, n_t=a.n_t,
+                total_s=round(t1 - t0, 3),
                 picard_iterations=len(norms) - 1,
                 before_first_solve_s=round(marks[0][0] - t0, 3),
                 outside_solve_s=[round(x, 4) for x in outside],
