@@ -292,6 +292,7 @@ SIGNATURES = {
     "kkt_reaction_relinearise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                            C.POINTER(RelinRecipe)]),
     "kkt_reaction_state": (C.c_int, [C.c_void_p, C.c_int, c_f64p, c_f64p]),
+    "kkt_reaction_window": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "kkt_reaction_iterate": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 2),
     "kkt_reaction_residual_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_f64p]),
     "kkt_reaction_update_device": (C.c_int, [C.c_void_p, C.c_void_p]),

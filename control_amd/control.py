@@ -476,7 +476,8 @@ class Instationary:
     def non_linear_solve(self, *, P=None, solver_parameters=None, lambda_v_bounds=None,
                          max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                          absolute_non_linear_tol=1.0e-8, print_error_non_linear=False,
-                         backend=None, Multigrid=False, device=False):
+                         backend=None, Multigrid=False, device=False, comm=None,
+                         host_allreduce=None):
         """``control.py:3377-3560``: Picard loop around ``linear_solve``; returns the residual
         norms (initial one first).  ``Multigrid``: as in ``linear_solve``.
 
@@ -485,8 +486,17 @@ class Instationary:
         update run on the GPU, the host reads one norm per iteration and the fields once at the
         end; the linear iteration counts land in ``self.non_linear_info["linear_iterations"]``.
         Needs a ``fem.ReactionTerm`` as forward operator, no ``P=`` and a scalar discretisation
-        (``ValueError`` otherwise, before the GPU is touched).  Limits: one GPU, and the
-        time-invariant linear part ``L`` of the term only."""
+        (``ValueError`` otherwise, before the GPU is touched).  Limit: the time-invariant linear
+        part ``L`` of the term only.
+
+        ``comm`` (a transport of ``control_amd.dist``; with ``device=True`` only): the loop on
+        time shards.  Every rank makes the same call on the same global problem, keeps, assembles,
+        evaluates and updates the levels of its own block rows, and trades one level of ``v`` and
+        one of ``zeta`` with its neighbours per iteration; ``host_allreduce(array, op)`` gathers
+        the fields at the end, so ``_v`` and ``_zeta`` are whole on every rank.  The host loop is
+        not offered on shards."""
+        if comm is not None and not device:
+            raise ValueError("comm needs device=True: the host loop is not offered on time shards")
         if device:
             from .reaction import device_non_linear_solve
             return device_non_linear_solve(
@@ -495,7 +505,7 @@ class Instationary:
                 relative_non_linear_tol=relative_non_linear_tol,
                 absolute_non_linear_tol=absolute_non_linear_tol,
                 print_error_non_linear=print_error_non_linear, backend=backend,
-                Multigrid=Multigrid)
+                Multigrid=Multigrid, comm=comm, host_allreduce=host_allreduce)
         disc, n_t, CN = self._disc, self._n_t, self._CN
         v_0 = (np.zeros(disc.n_dofs) if self._initial_condition is None
                else np.asarray(self._initial_condition(disc.coords), dtype=np.float64))

@@ -434,6 +434,9 @@ int kkt_reaction_relinearise(kkt_handle h, kkt_handle plan, int assemble, int n,
 int kkt_reaction_state(kkt_handle plan, int download, double *v, double *zeta) {
     KKT_TRY(plan, reaction_state(S, download, v, zeta));
 }
+int kkt_reaction_window(kkt_handle plan, int out[8]) {
+    KKT_TRY(plan, reaction_window(S, out));
+}
 int kkt_reaction_iterate(kkt_handle plan, double **d_v, double **d_zeta) {
     KKT_TRY(plan, reaction_iterate(S, d_v, d_zeta));
 }

@@ -22,11 +22,21 @@ struct ReactionCoef {
 };
 
 struct ReactionPlan {
-    int n_t = 0, m = 0;   // time levels, unknown blocks per family
+    int n_t = 0, m = 0;   // global: time levels, unknown blocks per family
     // the element: nodes per cell (3: triangles, 4: tetrahedra), quadrature points (7: Radon's
     // rule, 15: Stroud's T3:5-1) and entries of one element matrix, nv * nv
     int nv = 0, nq = 0, ep = 0;
     bool CN = false;
+    // Level windows, by the rules of RelinPlan (relin.hpp): the rows read the same neighbours.  The
+    // rank owns the block rows [lo, lo + nl) of both families (one rank: all m) and holds the
+    // levels its rows read: v from level v_l0 (v_n of them), zeta from z_l0, D and the element
+    // matrices from D_l0; the data rows are the owned blocks'.
+    //   BE  v [lo - 1, hi)   zeta [lo, hi]   D [lo, hi)    (level -1 and level n_t do not exist)
+    //   CN  v [lo, hi]       zeta [lo, hi]   D [lo, hi]
+    // v's first level comes from the rank below and zeta's last from the rank above
+    // (reaction_exchange); CN's D_lo is assembled here from the halo v.
+    int lo = 0, nl = 0, v_l0 = 0, v_n = 0, z_l0 = 0, z_n = 0, D_l0 = 0, D_n = 0;
+    bool v_halo = false, z_halo = false;   // the first v / last zeta level belongs to a neighbour
     int64_t ne = 0, n1 = 0, nnz = 0;
     double tau = 0.0, beta = 0.0;
     ReactionCoef coef{};
@@ -37,21 +47,24 @@ struct ReactionPlan {
             *d_clist = nullptr;
     double *d_L = nullptr, *d_M = nullptr;
     uint8_t *d_bc = nullptr;    // n1 bytes: Dirichlet dofs
-    double *d_data = nullptr;   // 2m x n1 data rows
-    // work: element matrices (n_t x ne x ep) and D (n_t x nnz) of the last assembly
+    double *d_data = nullptr;   // 2 nl x n1 data rows (the owned rows)
+    // CN on a time shard: the neighbours' raw residual rows the time transforms read,
+    // [adjoint: block hi | state: block lo - 1], n1 each
+    double *d_rhalo = nullptr;
+    // work: element matrices (D_n x ne x ep) and D (D_n x nnz) of the last assembly
     double *d_E = nullptr, *d_D = nullptr;
     bool assembled = false;
-    double *d_v = nullptr, *d_zeta = nullptr;   // the iterate, n_t x n1 each
+    double *d_v = nullptr, *d_zeta = nullptr;   // the iterate: v_n x n1 and z_n x n1
     double *d_red = nullptr;                    // reduction scratch + result
     Composer compose;                           // one space: the scalar pattern
 };
 
-// E[(l ne + e) ep + nv a + b] of every (element, level) at the iterate's v; the kernel is chosen
-// by the plan's element
+// E[(s ne + e) ep + nv a + b] of every (element, level of the D window) at the iterate's v,
+// s = level - D_l0; the kernel is chosen by the plan's element
 void launch_reaction_elements(hipStream_t s, const ReactionPlan &P);
-// rows [r0 | r1] of Instationary.non_linear_res_eval, 2m x n1
+// the owned rows [r0 | r1] of Instationary.non_linear_res_eval, 2 nl x n1
 void launch_reaction_residual(hipStream_t s, const ReactionPlan &P, double *d_r);
-// Crank-Nicolson: b = [T_1 r0 | T_2 r1]
+// Crank-Nicolson: b = [T_1 r0 | T_2 r1]; across a shard boundary from P.d_rhalo
 void launch_reaction_rhs(hipStream_t s, const ReactionPlan &P, const double *d_r, double *d_b);
 void launch_reaction_update(hipStream_t s, const ReactionPlan &P, double *d_u);
 
@@ -62,6 +75,11 @@ void reaction_state(System &S, int download, double *v, double *zeta);
 void reaction_iterate(System &S, double **v, double **zeta);
 void reaction_residual(System &S, double *d_out, int rhs, double *norm);
 void reaction_update(System &S, double *d_u);
+// kkt_debug_reaction_array: E or D of the last assembly (the D window), or the v / zeta window
 void reaction_debug_array(System &S, int which, double *out, int64_t cap);
+// kkt_reaction_window: [v_l0, v_end, z_l0, z_end, D_l0, D_end, lo, hi), half-open ranges
+void reaction_window(System &S, int out[8]);
+// the iterate's halo levels from the neighbour ranks (a time shard; one rank: nothing)
+void reaction_exchange(System &S);
 
 }  // namespace kkt

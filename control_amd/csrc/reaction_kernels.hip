@@ -117,14 +117,17 @@ __global__ __launch_bounds__(256) void reaction_elements_tet_kernel(
     }
 }
 
+// The kernels' levels are those of the D window: v is passed from the slot of level D_l0 (a time
+// shard's v window may start one level below), n_t is D_n.  One rank: the base 0, every level.
 void launch_reaction_elements(hipStream_t s, const ReactionPlan &P) {
-    const dim3 grid(grid_of(P.ne * P.n_t, REACTION_ELEMENT_BLOCKS));
+    const dim3 grid(grid_of(P.ne * P.D_n, REACTION_ELEMENT_BLOCKS));
+    const double *v = P.d_v + (int64_t)(P.D_l0 - P.v_l0) * P.n1;
     if (P.nv == TET_NV)
-        hipLaunchKernelGGL(reaction_elements_tet_kernel, grid, dim3(256), 0, s, P.d_v, P.ne, P.n1,
-                           P.n_t, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
+        hipLaunchKernelGGL(reaction_elements_tet_kernel, grid, dim3(256), 0, s, v, P.ne, P.n1,
+                           P.D_n, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
     else
-        hipLaunchKernelGGL(reaction_elements_kernel, grid, dim3(256), 0, s, P.d_v, P.ne, P.n1,
-                           P.n_t, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
+        hipLaunchKernelGGL(reaction_elements_kernel, grid, dim3(256), 0, s, v, P.ne, P.n1,
+                           P.D_n, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
 }
 
 // sum_k A[k] x[col[k]] over CSR row r from 0.0 in stored order (tperm: the transposed matrix on
@@ -163,15 +166,19 @@ struct ReactionArgs {
     const double *M, *D, *data, *v, *zeta;
     const uint8_t *bc;
     int64_t n1, nnz;
-    int n_t, m, cn;
+    // Level windows of a time shard: the rank owns the block rows [lo, lo + nl) of both families
+    // (data and the residual: local row blocks f nl + i - lo); v, zeta and D start at the global
+    // levels v_l0, z_l0 and D_l0.  n_t is global, and so are the stencil's guards.
+    int n_t, cn, lo, nl, v_l0, z_l0, D_l0;
     double tau, beta;
 };
 
-// One thread per (row block, dof): row blocks 0..m-1 are the adjoint rows r0, m..2m-1 the state
-// rows r1 of Instationary.non_linear_res_eval, with its bracketing; Dirichlet rows are zero.
+// One thread per (row block, dof): local row blocks 0..nl-1 are the adjoint rows r0 of the blocks
+// lo.., nl..2nl-1 the state rows r1 of Instationary.non_linear_res_eval, with its bracketing;
+// Dirichlet rows are zero.  i: the global block row.
 __global__ __launch_bounds__(256) void reaction_residual_kernel(ReactionArgs A,
                                                                 double *__restrict__ r) {
-    const int rb = blockIdx.y, fam = rb >= A.m, i = fam ? rb - A.m : rb;
+    const int rb = blockIdx.y, fam = rb >= A.nl, i = A.lo + (fam ? rb - A.nl : rb);
     for (int64_t R = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; R < A.n1;
          R += (int64_t)gridDim.x * blockDim.x) {
 #pragma clang fp contract(off)
@@ -179,13 +186,14 @@ __global__ __launch_bounds__(256) void reaction_residual_kernel(ReactionArgs A,
         if (!A.bc[R]) {
             auto Mx = [&](const double *x) { return reaction_row(A.ip, A.ix, A.M, nullptr, R, x); };
             auto Dx = [&](int l, const double *x) {
-                return reaction_row(A.ip, A.ix, A.D + (int64_t)l * A.nnz, nullptr, R, x);
+                return reaction_row(A.ip, A.ix, A.D + (int64_t)(l - A.D_l0) * A.nnz, nullptr, R, x);
             };
             auto DTx = [&](int l, const double *x) {
-                return reaction_row(A.ip, A.ix, A.D + (int64_t)l * A.nnz, A.tperm, R, x);
+                return reaction_row(A.ip, A.ix, A.D + (int64_t)(l - A.D_l0) * A.nnz, A.tperm, R, x);
             };
-            auto v = [&](int l) { return A.v + (int64_t)l * A.n1; };
-            auto z = [&](int l) { return A.zeta + (int64_t)l * A.n1; };
+            // global level l of v and zeta: its slot in the window
+            auto v = [&](int l) { return A.v + (int64_t)(l - A.v_l0) * A.n1; };
+            auto z = [&](int l) { return A.zeta + (int64_t)(l - A.z_l0) * A.n1; };
             const double tau = A.tau, d = A.data[(int64_t)rb * A.n1 + R];
             if (!A.cn) {
                 if (!fam) {
@@ -243,49 +251,63 @@ void launch_reaction_residual(hipStream_t s, const ReactionPlan &P, double *d_r)
     ReactionArgs A;
     A.ip = P.d_ip; A.ix = P.d_ix; A.tperm = P.d_tperm;
     A.M = P.d_M; A.D = P.d_D; A.data = P.d_data; A.v = P.d_v; A.zeta = P.d_zeta; A.bc = P.d_bc;
-    A.n1 = P.n1; A.nnz = P.nnz; A.n_t = P.n_t; A.m = P.m; A.cn = P.CN;
+    A.n1 = P.n1; A.nnz = P.nnz; A.n_t = P.n_t; A.cn = P.CN;
+    A.lo = P.lo; A.nl = P.nl; A.v_l0 = P.v_l0; A.z_l0 = P.z_l0; A.D_l0 = P.D_l0;
     A.tau = P.tau; A.beta = P.beta;
     hipLaunchKernelGGL(reaction_residual_kernel,
-                       dim3(grid_of(P.n1, REACTION_ROW_BLOCKS), 2 * P.m), dim3(256), 0, s, A,
+                       dim3(grid_of(P.n1, REACTION_ROW_BLOCKS), 2 * P.nl), dim3(256), 0, s, A,
                        d_r);
 }
 
-// Crank-Nicolson: T_1 on the adjoint rows (row i + 1 into i), T_2 on the state rows (i - 1 into i)
+// Crank-Nicolson: T_1 on the adjoint rows (row i + 1 into i), T_2 on the state rows (i - 1 into i).
+// r holds the rank's 2 nl row blocks; where i + 1 or i - 1 leaves the shard the term is the
+// neighbour rank's raw row (h_up: adjoint row hi, h_dn: state row lo - 1; ReactionPlan::d_rhalo).
+// The guards are those of the global system; one rank never reads a halo.
 __global__ __launch_bounds__(256) void reaction_rhs_kernel(const double *__restrict__ r,
-                                                           double *__restrict__ b, int m,
-                                                           int64_t n1) {
-    const int64_t n = 2 * (int64_t)m * n1;
+                                                           double *__restrict__ b, int m, int lo,
+                                                           int nl, int64_t n1,
+                                                           const double *__restrict__ h_up,
+                                                           const double *__restrict__ h_dn) {
+    const int64_t n = 2 * (int64_t)nl * n1;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n;
          t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t rb = t / n1;
+        const int64_t rb = t / n1, R = t - rb * n1;
         double out = r[t];
-        if (rb < m) {
-            if (rb + 1 < m) out += r[t + n1];
-        } else if (rb > m) {
-            out += r[t - n1];
+        if (rb < nl) {
+            if (lo + rb + 1 < m) out += rb + 1 < nl ? r[t + n1] : h_up[R];
+        } else if (lo + rb - nl > 0) {
+            out += rb > nl ? r[t - n1] : h_dn[R];
         }
         b[t] = out;
     }
 }
 
 void launch_reaction_rhs(hipStream_t s, const ReactionPlan &P, const double *d_r, double *d_b) {
-    const int64_t n = 2 * (int64_t)P.m * P.n1;
+    const int64_t n = 2 * (int64_t)P.nl * P.n1;
     hipLaunchKernelGGL(reaction_rhs_kernel, dim3(grid_of(n, REACTION_VECTOR_BLOCKS)),
-                       dim3(256), 0, s, d_r, d_b, P.m, P.n1);
+                       dim3(256), 0, s, d_r, d_b, P.m, P.lo, P.nl, P.n1, P.d_rhalo,
+                       P.d_rhalo ? P.d_rhalo + P.n1 : nullptr);
 }
 
-// unknown block i: v at level i (Crank-Nicolson: i + 1), zeta at level i.  v keeps its boundary
-// values on the Dirichlet dofs, zeta is zero there.
+// Unknown block i: v at level i (Crank-Nicolson: i + 1), zeta at level i.  v keeps its boundary
+// values on the Dirichlet dofs, zeta is zero there.  The kernel's block rows are the rank's own:
+// v and zeta are passed from the slot of level lo.  z_halo: the level after the owned ones is the
+// neighbour's zeta (a time shard); it is zeroed on the Dirichlet dofs like the owned levels, and
+// refreshed by the next exchange.  (CN's fixed last level is nobody's block: it is left alone.)
 __global__ __launch_bounds__(256) void reaction_update_kernel(double *__restrict__ u,
                                                               double *__restrict__ v,
                                                               double *__restrict__ zeta,
                                                               const uint8_t *__restrict__ bc, int m,
-                                                              int64_t n1, int cn) {
-    const int64_t n0 = (int64_t)m * n1, n = 2 * n0;
-    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n;
+                                                              int64_t n1, int cn, int z_halo) {
+    const int64_t n0 = (int64_t)m * n1, n = 2 * n0, all = n + (z_halo ? n1 : 0);
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < all;
          t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t rb = t / n1, R = t - rb * n1;
         const bool fixed = bc[R] != 0;
+        if (t >= n) {
+            if (fixed) zeta[(int64_t)m * n1 + R] = 0.0;
+            continue;
+        }
         if (rb < m) {
             if (!fixed) v[(rb + cn) * n1 + R] += u[t];
         } else {
@@ -297,9 +319,11 @@ __global__ __launch_bounds__(256) void reaction_update_kernel(double *__restrict
 }
 
 void launch_reaction_update(hipStream_t s, const ReactionPlan &P, double *d_u) {
-    const int64_t n = 2 * (int64_t)P.m * P.n1;
+    const int64_t n = (2 * (int64_t)P.nl + (P.z_halo ? 1 : 0)) * P.n1;
     hipLaunchKernelGGL(reaction_update_kernel, dim3(grid_of(n, REACTION_VECTOR_BLOCKS)),
-                       dim3(256), 0, s, d_u, P.d_v, P.d_zeta, P.d_bc, P.m, P.n1, (int)P.CN);
+                       dim3(256), 0, s, d_u, P.d_v + (int64_t)(P.lo - P.v_l0) * P.n1,
+                       P.d_zeta + (int64_t)(P.lo - P.z_l0) * P.n1, P.d_bc, P.nl, P.n1, (int)P.CN,
+                       (int)P.z_halo);
 }
 
 }  // namespace kkt

@@ -1,6 +1,7 @@
 """The scalar Picard / Gauss-Newton loop on the device (``kkt_set_reaction_relinearisation``,
 DESIGN.md section 6.6a): ``Instationary.non_linear_solve(device=True)`` for a forward operator
-declared as a ``fem.ReactionTerm``, on P1 triangles or P1 tetrahedra.
+declared as a ``fem.ReactionTerm``, on P1 triangles or P1 tetrahedra, on one GPU or -- with
+``comm=`` -- on time shards.
 
 Host side: ``ReactionPlan`` -- the element tables of the term, the contribution lists that make
 the device assembly deterministic (``relinearise.contribution_lists``), the transpose permutation
@@ -24,10 +25,16 @@ __all__ = ["ReactionPlan", "DeviceReaction", "device_non_linear_solve"]
 _ARRAYS = ("E", "D", "v", "zeta")
 
 
-def _check(ctl, P=None):
+def _check(ctl, P=None, comm=None, host_allreduce=None):
     """The ``ValueError``s of ``non_linear_solve(device=True)``: nothing here touches the GPU.
     A ``fem.ReactionTerm`` is on P1 triangles or P1 tetrahedra by construction (its own
     ``ValueError`` names both), and both run here."""
+    if comm is not None and comm.world > 1:
+        if not callable(getattr(comm, "attach", None)):
+            raise ValueError("comm must be a transport of control_amd.dist (it attaches itself to "
+                             "the system)")
+        if host_allreduce is None:
+            raise ValueError("a time-sharded device loop needs host_allreduce")
     if not isinstance(ctl._forward, ReactionTerm):
         raise ValueError("device=True needs the forward operator declared as a fem.ReactionTerm")
     if P is not None:
@@ -103,27 +110,47 @@ class ReactionPlan:
         return d, keep
 
 
-class DeviceReaction:
-    """The plan on a scalar instationary ``MultiBlockSystem`` and the iterate in HBM."""
+def owned(recipes, lo, hi):
+    """The recipes of the block rows ``[lo, hi)`` (``(q, i, j, ...)``: row ``i``)."""
+    return [r for r in recipes if lo <= r[1] < hi]
 
-    def __init__(self, ctl, system, recipes=None, plan=None):
+
+class DeviceReaction:
+    """The plan on a scalar instationary ``MultiBlockSystem`` and the iterate in HBM.
+
+    On a time-sharded system every rank keeps its own levels of the iterate, of the element
+    matrices and of ``D`` (``window``), assembles, evaluates the residual of and updates those, and
+    trades one level of ``v`` and one of ``zeta`` with its neighbours before every assembly;
+    ``assemble``, ``residual`` and ``get_state`` are then collective."""
+
+    def __init__(self, ctl, system, recipes=None, plan=None, host_allreduce=None):
         """``recipes``: the blocks every re-linearisation rewrites (default: the ``"inner"`` list
-        of ``blocks.instationary_relinearisation_recipes``)."""
+        of ``blocks.instationary_relinearisation_recipes``, on a time shard those of the rank's
+        own block rows).  ``host_allreduce(array, op)`` (a time shard): what ``get_state`` gathers
+        the iterate with."""
         from .blocks import instationary_relinearisation_recipes
         self.plan = ReactionPlan(ctl) if plan is None else plan
         self.ctl, self.system, self._lib = ctl, system, system._lib
+        self.host_allreduce = host_allreduce
         d, keep = self.plan.descriptor()
         system._ck(self._lib.kkt_set_reaction_relinearisation(system.handle, C.byref(d)))
         del keep
+        w = (C.c_int * 8)()
+        system._ck(self._lib.kkt_reaction_window(system.handle, w))
+        #: half-open ranges of global levels held in HBM: v, zeta, D, and the owned block rows
+        self.window = {k: (w[2 * n], w[2 * n + 1]) for n, k in enumerate(("v", "zeta", "D", "blocks"))}
         if recipes is None:
             p = self.plan
-            recipes = instationary_relinearisation_recipes(p.tau, p.beta, p.n_t, p.CN)["inner"]
+            recipes = owned(
+                instationary_relinearisation_recipes(p.tau, p.beta, p.n_t, p.CN)["inner"],
+                *self.window["blocks"])
         self.recipes = (_recipe_array(recipes, 0), len(recipes))
 
     def _shape(self):
         return (self.plan.n_t, self.ctl._disc.n_dofs)
 
     def set_state(self, v, zeta):
+        """Global arrays; a time shard takes its windows from them, halo levels included."""
         arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (v, zeta)]
         for a in arrs:
             if a.shape != self._shape():
@@ -132,13 +159,21 @@ class DeviceReaction:
             self.system.handle, 0, *[a.ctypes.data_as(_lib.c_f64p) for a in arrs]))
 
     def get_state(self):
+        """The whole iterate on the host.  A time shard downloads the levels it owns into zeros
+        and the ranks' arrays are summed (``host_allreduce``): every rank returns the same."""
         out = [np.zeros(self._shape()), np.zeros(self._shape())]
         self.system._ck(self._lib.kkt_reaction_state(
             self.system.handle, 1, *[a.ctypes.data_as(_lib.c_f64p) for a in out]))
+        if self.window["blocks"] != (0, self.plan.m):
+            if self.host_allreduce is None:
+                raise ValueError("a time-sharded plan needs host_allreduce to gather the iterate")
+            for a in out:            # the other ranks' levels are zero here: a sum gathers
+                self.host_allreduce(a.reshape(-1), 0)
         return out
 
     def assemble(self):
-        """Element matrices and ``D`` of every level at the device iterate's ``v``."""
+        """Element matrices and ``D`` of every level of the D window at the device iterate's
+        ``v`` (a time shard first refreshes its halo levels from the neighbour ranks)."""
         self.system._ck(self._lib.kkt_reaction_relinearise(self.system.handle, self.system.handle,
                                                            1, 0, None))
 
@@ -162,21 +197,25 @@ class DeviceReaction:
     def debug_array(self, which):
         """``kkt_debug_reaction_array``: ``"E"`` (n_t, ne, nv, nv) or ``"D"`` (n_t, nnz) of the
         last assembly, ``"v"`` / ``"zeta"`` (n_t, n) of the iterate (``nv``: 3 nodes per triangle,
-        4 per tetrahedron)."""
-        n_t, n = self._shape()
+        4 per tetrahedron) -- on a time shard the levels of ``window["D"]``, ``window["v"]`` and
+        ``window["zeta"]``, halo levels included."""
+        n = self._shape()[1]
         ne, nv = self.plan.term.cells.shape
-        shape = {"E": (n_t, ne, nv, nv), "D": (n_t, self.plan.term.M.nnz),
-                 "v": (n_t, n), "zeta": (n_t, n)}[which]
+        n_D, n_v, n_z = (b - a for a, b in (self.window[k] for k in ("D", "v", "zeta")))
+        shape = {"E": (n_D, ne, nv, nv), "D": (n_D, self.plan.term.M.nnz),
+                 "v": (n_v, n), "zeta": (n_z, n)}[which]
         out = np.empty(shape)
         self.system._ck(self._lib.kkt_debug_reaction_array(
             self.system.handle, _ARRAYS.index(which), out.ctypes.data_as(_lib.c_f64p), out.size))
         return out
 
 
-def build_system(ctl, backend, plan):
+def build_system(ctl, backend, plan, comm=None):
     """The scalar block system from patterns: every block of ``blocks.instationary_blocks`` is a
     ``PatternOnly`` of the structure of ``M``, in the row-major dict order of the host path.
-    Returns ``(system, block dicts)``; the blocks are unset until the device composes them."""
+    Returns ``(system, block dicts, build recipes)``; the blocks are unset until the device
+    composes them.  ``comm``: a time shard registers the blocks of its own rows
+    (``MultiBlockSystem`` skips the others), and the build recipes are those rows'."""
     from .blocks import instationary_build_recipes
     from .multiblock import PatternOnly
     disc, m = ctl._disc, plan.m
@@ -187,22 +226,32 @@ def build_system(ctl, backend, plan):
     for (q, i, j, *_) in full:
         quads[q][(i, j)] = pat
     ns = tuple(backend.DirichletBCNullspace(disc.boundary) for _ in range(m))
+    kw = {} if comm is None or comm.world == 1 else {"comm": comm}
     system = backend.MultiBlockSystem(n, n, *quads, n_blocks_00=m, n_blocks_11=m, nullspace_0=ns,
-                                      nullspace_1=ns, CN=plan.CN)
+                                      nullspace_1=ns, CN=plan.CN, **kw)
+    if kw:
+        full = owned(full, system._lo, system._hi)
     return system, quads, full
 
 
 def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bounds=None,
                             max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                             absolute_non_linear_tol=1.0e-8, print_error_non_linear=False,
-                            backend=None, Multigrid=False):
+                            backend=None, Multigrid=False, comm=None, host_allreduce=None):
     """``Instationary.non_linear_solve`` with the iterate in HBM.  One ``MultiBlockSystem`` is
     built from patterns and composed on the device, one ``SchurPC`` is attached to it; every
     iteration then assembles, evaluates the residual (the host reads its norm), re-composes the
     blocks that carry ``D`` (the preconditioner is marked stale and rebuilt by the next solve),
-    solves and updates on the GPU.  The stopping logic is the host loop's."""
+    solves and updates on the GPU.  The stopping logic is the host loop's.
+
+    ``comm`` (``control_amd.dist``): the system is time-sharded, every rank makes this call on the
+    same global problem and runs the loop on its own levels (``DeviceReaction``); the first build
+    is still by pattern, composed on the device from the rank's rows of the build recipes, so no
+    block values ever cross from the host.  The boundary lift and the final download go through
+    the collective ``get_state`` (``host_allreduce``): ``ctl._v`` and ``ctl._zeta`` end whole on
+    every rank."""
     from .control import GpuBackend, _multigrid_kw
-    _check(ctl, P)
+    _check(ctl, P, comm, host_allreduce)
     backend = backend or GpuBackend()
     if not isinstance(backend, GpuBackend):
         raise ValueError("device=True runs on a GpuBackend")
@@ -221,8 +270,8 @@ def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bou
     lift = not np.array_equal(v_fixed, v_old)
 
     plan = ReactionPlan(ctl)
-    system, quads, full = build_system(ctl, backend, plan)
-    dev = DeviceReaction(ctl, system, plan=plan)
+    system, quads, full = build_system(ctl, backend, plan, comm)
+    dev = DeviceReaction(ctl, system, plan=plan, host_allreduce=host_allreduce)
     dev.set_state(v_old, zeta_old)
     dev.assemble()
     dev.relinearise(recipes=full)
@@ -253,5 +302,5 @@ def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bou
     finally:
         system.close()
     ctl._v, ctl._zeta = v_new, zeta_new
-    ctl.non_linear_info = {"linear_iterations": lin_its}
+    ctl.non_linear_info = {"linear_iterations": lin_its, "window": dev.window}
     return norms

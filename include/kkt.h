@@ -509,8 +509,13 @@ int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
  * np.bincount's order) and D = L + C with one rounding per entry.  The element matrices of all
  * levels are kept: n_t * ne * nv * nv doubles beside D (n_t * nnz) -- on 64^3 cells x 128 levels
  * of tetrahedra 25.8 GB and 4 GB.  The handle must be a scalar instationary layout
- * (n_blocks_00 = n_blocks_11 = m, nx0 = nx1 = n1; m = n_t, Crank-Nicolson n_t - 1), finalized,
- * on one rank.  A handle carries at most one plan, of this kind or of kkt_set_relinearisation's:
+ * (n_blocks_00 = n_blocks_11 = m, nx0 = nx1 = n1; m = n_t, Crank-Nicolson n_t - 1), finalized.
+ * A time-sharded handle (kkt_set_shard: one block family) takes its share of the same global
+ * descriptor: with [lo, hi) its block rows it keeps the levels those rows read -- backward Euler
+ * v [lo - 1, hi), zeta [lo, hi], D and E [lo, hi) (level -1 and level n_t do not exist);
+ * Crank-Nicolson [lo, hi] of all four -- and the data rows lo .. hi - 1 and m + lo .. m + hi - 1;
+ * E is then (levels of the D window) * ne * nv * nv doubles per rank.  A handle sharded in two
+ * families (kkt_set_shard_families) is KKT_ERR_ARG.  A handle carries at most one plan, of this kind or of kkt_set_relinearisation's:
  * setting the other kind is KKT_ERR_STATE.  data: the 2m x n1 rows [adjoint | state] of
  * Instationary.non_linear_res_eval at the zero iterate (desired state, forces, backward Euler's
  * initial-condition row tau D(v_0) v_0 + M v_0), Dirichlet rows zero.  c: the Gauss-Newton
@@ -535,31 +540,49 @@ typedef struct kkt_reaction_desc {
     const double *data;
 } kkt_reaction_desc;
 int kkt_set_reaction_relinearisation(kkt_handle h, const kkt_reaction_desc *desc);
-/* assemble != 0 first forms the element matrices and D of all n_t levels at the plan's iterate;
- * then the n recipes (space = 0) rewrite blocks of handle h exactly as kkt_relinearise_device
+/* assemble != 0 first forms the element matrices and D of all n_t levels at the plan's iterate
+ * (a time shard, collective: its halo levels first -- one level of v from the rank below, one of
+ * zeta from the rank above -- then the levels of its D window, Crank-Nicolson's D_lo from the
+ * halo v); then the n recipes (space = 0) rewrite blocks of handle h exactly as kkt_relinearise_device
  * does: Dirichlet columns zeroed, shared value arrays made private first, alpha = 0 recipes give
- * gamma M, a built-in preconditioner is marked stale.  n = 0 only assembles. */
+ * gamma M, a built-in preconditioner is marked stale.  n = 0 only assembles.  Time shards: h
+ * must be sharded as the plan's handle (KKT_ERR_ARG otherwise); recipes keep their global
+ * indices, and one for a block row of another rank, or whose level lies outside the rank's D
+ * window, is KKT_ERR_ARG naming the block, before anything is written. */
 int kkt_reaction_relinearise(kkt_handle h, kkt_handle plan, int assemble, int n,
                              const kkt_relin_recipe *recipes);
 /* The iterate (v, zeta: n_t x n1) in HBM: host copies in (download 0) or out (download 1), and
- * its device addresses (either out pointer may be NULL). */
+ * its device addresses (either out pointer may be NULL).  The host arrays always have the global
+ * shapes.  A time shard uploads its windows from them, halo levels included, and downloads only
+ * what it owns -- its blocks' levels, and the fixed levels (Crank-Nicolson: v_0; zeta of the last
+ * level) on the rank whose window holds them -- leaving the rest untouched; the device addresses
+ * are those of the windows' first levels.
+ * kkt_reaction_window: out = [v, zeta, D, block rows] as half-open ranges [first, end) of global
+ * levels, as kkt_picard_window (one rank: [0, n_t) three times and [0, m)). */
 int kkt_reaction_state(kkt_handle plan, int download, double *v, double *zeta);
 int kkt_reaction_iterate(kkt_handle plan, double **d_v, double **d_zeta);
+int kkt_reaction_window(kkt_handle plan, int out[8]);
 /* The rows [r0, r1] of Instationary.non_linear_res_eval at the plan's iterate with D of the last
  * assembly (backward Euler: n_t rows per family, Crank-Nicolson n_t - 1), Dirichlet rows zero, in
  * d_out (one local vector of the plan's handle); rhs = 1: the right-hand side of the linearised
  * solve (Crank-Nicolson: T_1 on the adjoint rows, T_2 on the state rows).  *norm (host): the
  * 2-norm of the untransformed rows by the deterministic reduction.  KKT_ERR_STATE before any
- * assembly. */
+ * assembly.  Time shards (collective): the rank's rows [lo, hi) of both families, each bit for
+ * bit the row of the one-rank result; Crank-Nicolson takes the transforms' terms across the shard
+ * boundary from the neighbours' raw rows; the norm is the all-reduced sum of the ranks' sums of
+ * squares, the same on every rank. */
 int kkt_reaction_residual_device(kkt_handle plan, double *d_out, int rhs, double *norm);
 /* v, zeta += the blocks of the update d_u (Crank-Nicolson: v from level 1, zeta levels
  * 0 .. n_t - 2); v is left untouched on the Dirichlet dofs (they hold the boundary values), zeta
- * is zero there; d_u is zeroed: the initial guess of the next solve. */
+ * is zero there; d_u is zeroed: the initial guess of the next solve.  Time shards: the rank's own
+ * levels (and zeta's halo level zeroed on the Dirichlet dofs); the halo levels are refreshed by
+ * the next assembly. */
 int kkt_reaction_update_device(kkt_handle plan, double *d_u);
 /* Test hook: the element matrices E (n_t x ne x nv x nv: 9 doubles per triangle, 16 per
  * tetrahedron) or D (n_t x nnz) of the last assembly
  * (KKT_ERR_STATE before one), or v / zeta (n_t x n1) of the iterate, copied to the host; cap:
- * doubles available at out (KKT_ERR_ARG when too small). */
+ * doubles available at out (KKT_ERR_ARG when too small).  On a time shard the levels of the
+ * windows, in order: E and D those of the D window, v and zeta their own, halo levels included. */
 enum { KKT_REACTION_E = 0, KKT_REACTION_D = 1, KKT_REACTION_V = 2, KKT_REACTION_ZETA = 3 };
 int kkt_debug_reaction_array(kkt_handle plan, int which, double *out, int64_t cap);
 /* The stored values of block (quadrant, i, j) in the CSR order of its pattern, read from the
