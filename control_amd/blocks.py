@@ -19,7 +19,8 @@ import scipy.sparse as sp
 
 __all__ = ["instationary_blocks", "stationary_blocks", "instationary_incompressible_blocks",
            "stationary_incompressible_blocks", "conform_to", "instationary_relinearisation_recipes",
-           "instationary_build_recipes"]
+           "instationary_build_recipes", "stationary_build_recipes",
+           "stationary_relinearisation_recipes"]
 
 
 def _csr(A):
@@ -326,3 +327,18 @@ def instationary_build_recipes(tau: float, beta: float, n_t: int, CN: bool):
     outer = sorted(((0, i + shift[q][0], j + shift[q][1], *r) for (q, i, j, *r) in inner),
                    key=lambda r: r[:3])
     return {"inner": inner, "commutator": list(inner), "outer": outer, "m": m}
+
+
+def stationary_build_recipes(beta: float):
+    """Every block of ``stationary_blocks`` as a recipe ``(quadrant, i, j, level, alpha, transpose,
+    gamma)``, block ``= alpha D(^T) + gamma M`` on the one level 0: ``M``, ``D^T``, ``D`` and
+    ``(-1 / beta) M`` with the host's one rounding (``alpha = 0``: ``gamma M`` alone; ``gamma = 0``
+    adds a zero to ``1.0 * D``).  A flat list in quadrant order: there is one system."""
+    return [(0, 0, 0, 0, 0.0, False, 1.0), (1, 0, 0, 0, 1.0, True, 0.0),
+            (2, 0, 0, 0, 1.0, False, 0.0), (3, 0, 0, 0, 0.0, False, -1.0 / beta)]
+
+
+def stationary_relinearisation_recipes(beta: float):
+    """The blocks of ``stationary_blocks`` that carry the forward operator: ``block_01 = D^T`` and
+    ``block_10 = D``.  The mass blocks do not change with the linearisation point."""
+    return [r for r in stationary_build_recipes(beta) if r[4] != 0.0]

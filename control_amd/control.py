@@ -651,7 +651,10 @@ class Stationary:
 
     ``forward_operator(v_old) -> csr`` is ``forward_form(trial, test, v_old)`` assembled;
     ``forward_jacobian(v_old) -> csr`` its Gateaux derivative in the direction of ``trial``
-    (``ufl.derivative``, ``control.py:314-318``), used after ``set_Gauss_Newton()``."""
+    (``ufl.derivative``, ``control.py:314-318``), used after ``set_Gauss_Newton()``.  A
+    ``fem.ReactionTerm`` as ``forward_operator`` declares both (the host path calls
+    ``term(v, None)`` and ``term.jacobian(v, None)``) and is what
+    ``non_linear_solve(device=True)`` needs."""
 
     def __init__(self, disc, forward_operator=None, *, desired_state=None, force_f=None,
                  beta=1.0e-3, bcs_v=None, forward_jacobian=None):
@@ -661,6 +664,8 @@ class Stationary:
         self._disc = disc
         self._forward = forward_operator or (lambda v: disc.K)
         self._jacobian = forward_jacobian
+        if forward_jacobian is None and isinstance(forward_operator, ReactionTerm):
+            self._jacobian = lambda v: forward_operator.jacobian(v, None)
         self._Gauss_Newton = False
         self._desired_state, self._force_f = desired_state, force_f
         self._beta = float(beta)
@@ -678,8 +683,13 @@ class Stationary:
 
     def construct_D_v(self, v_old):          # control.py:310-320
         # on the mass matrix's structure: the preconditioner adds multiples of M entry by entry
-        return conform_to(self._jacobian(v_old) if self._Gauss_Newton
-                          else self._forward(v_old), self._disc.M)
+        if self._Gauss_Newton:
+            D = self._jacobian(v_old)
+        elif isinstance(self._forward, ReactionTerm):     # a term takes (v, t)
+            D = self._forward(v_old, None)
+        else:
+            D = self._forward(v_old)
+        return conform_to(D, self._disc.M)
 
     def _v_inhom(self):
         v = np.zeros(self._disc.n_dofs)
@@ -754,8 +764,24 @@ class Stationary:
     def non_linear_solve(self, *, P=None, solver_parameters=None, lambda_v_bounds=None,
                          max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                          absolute_non_linear_tol=1.0e-8, print_error_non_linear=False,
-                         backend=None, Multigrid=False):
-        """``control.py:640-760``; returns the residual norms (initial one first)."""
+                         backend=None, Multigrid=False, device=False):
+        """``control.py:640-760``; returns the residual norms (initial one first).
+
+        ``device=True``: the same loop with the iterate in HBM (``control_amd.reaction``): one
+        block system and one preconditioner live through all iterations, and the forward
+        operator is re-assembled and the linearised blocks re-composed by device kernels.  The
+        forward operator must be a ``fem.ReactionTerm`` (P1 triangles or P1 tetrahedra), the
+        backend a ``GpuBackend``, and ``P`` is not taken.  Afterwards ``non_linear_info`` holds
+        the linear iteration counts."""
+        if device:
+            from .reaction import device_stationary_non_linear_solve
+            return device_stationary_non_linear_solve(
+                self, P=P, solver_parameters=solver_parameters, lambda_v_bounds=lambda_v_bounds,
+                max_non_linear_iter=max_non_linear_iter,
+                relative_non_linear_tol=relative_non_linear_tol,
+                absolute_non_linear_tol=absolute_non_linear_tol,
+                print_error_non_linear=print_error_non_linear, backend=backend,
+                Multigrid=Multigrid)
         v_old, zeta_old = self._v.copy(), self._zeta.copy()
         v_d, f = self._data()
         D_v = self.construct_D_v(v_old)

@@ -24,9 +24,20 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
     need(d->nq == 7 || d->nq == 15,
          "nq must be 7 (P1 triangles, Radon's rule) or 15 (P1 tetrahedra, Stroud's T3:5-1)");
     const int nv = d->nq == 7 ? 3 : 4, ep = nv * nv;
-    need(d->n_t >= 2 && d->ne > 0 && d->n1 > 0 && d->nnz > 0, "sizes must be positive");
+    need(d->n_t >= 1 && d->ne > 0 && d->n1 > 0 && d->nnz > 0, "sizes must be positive");
     need(d->degree >= 0 && d->degree <= REACTION_MAX_DEGREE, "degree must be 0 .. 4");
+    // n_t == 1: the stationary system [[M, D^T], [D, -(1/beta) M]] -- one level, no time step
+    const bool stationary = d->n_t == 1;
+    need(!stationary || d->cn == 0, "n_t == 1 (the stationary system) takes cn == 0");
     const int m = d->cn ? d->n_t - 1 : d->n_t;
+    if (stationary) {
+        need(S.n0 == 1 && S.n1 == 1,
+             "n_t == 1: the handle is not the stationary system (one block per family)");
+        need(S.nx0 == d->n1 && S.nx1 == d->n1,
+             "n_t == 1: the handle is not the stationary system of this space");
+        need(!S.CN, "n_t == 1: the stationary system is not a Crank-Nicolson handle");
+        need(!S.sharded, "n_t == 1: the stationary system has one block and cannot be time-sharded");
+    }
     need(S.n0 == m && S.n1 == m && S.nx0 == d->n1 && S.nx1 == d->n1 && S.CN == (d->cn != 0),
          "the handle is not the scalar instationary system of this space and these time levels");
     need(!S.sharded || (S.families == 1 && S.mf == m),
@@ -46,6 +57,7 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
     P->n_t = d->n_t;
     P->m = m;
     P->CN = d->cn != 0;
+    P->stationary = stationary;
     P->nv = nv;
     P->nq = d->nq;
     P->ep = ep;
@@ -191,9 +203,13 @@ void reaction_residual(System &S, double *d_out, int rhs, double *norm) {
     ReactionPlan &P = plan_of(S);
     if (!d_out || !norm) fail(KKT_ERR_ARG, "kkt_reaction_residual_device: null argument");
     if (!P.assembled) fail(KKT_ERR_STATE, "kkt_reaction_residual_device: D not assembled yet");
-    const bool transform = rhs && P.CN;   // backward Euler's right-hand side is the rows themselves
+    // backward Euler's right-hand side is the rows themselves, and so is the stationary system's
+    const bool transform = rhs && P.CN;
     double *r = transform ? raw_rows(S) : d_out;
-    launch_reaction_residual(S.stream, P, r);
+    if (P.stationary)
+        launch_reaction_stationary_residual(S.stream, P, r);
+    else
+        launch_reaction_residual(S.stream, P, r);
     launch_residual_norm(S, r, P.d_red);
     if (transform && S.sharded) {
         // the raw rows the time transforms read across the shard boundary: the adjoint rows (T_1)

@@ -27,6 +27,10 @@ struct ReactionPlan {
     // rule, 15: Stroud's T3:5-1) and entries of one element matrix, nv * nv
     int nv = 0, nq = 0, ep = 0;
     bool CN = false;
+    // n_t == 1: the stationary system [[M, D^T], [D, -(1/beta) M]] of Control.Stationary.  One
+    // level of everything, every window [0, 1), tau unused; the element kernels, the gather, the
+    // composition and the update run as on one level, the residual rows are their own kernel.
+    bool stationary = false;
     // Level windows, by the rules of RelinPlan (relin.hpp): the rows read the same neighbours.  The
     // rank owns the block rows [lo, lo + nl) of both families (one rank: all m) and holds the
     // levels its rows read: v from level v_l0 (v_n of them), zeta from z_l0, D and the element
@@ -64,6 +68,8 @@ struct ReactionPlan {
 void launch_reaction_elements(hipStream_t s, const ReactionPlan &P);
 // the owned rows [r0 | r1] of Instationary.non_linear_res_eval, 2 nl x n1
 void launch_reaction_residual(hipStream_t s, const ReactionPlan &P, double *d_r);
+// the rows [r0 | r1] of Stationary.non_linear_res_eval, 2 x n1 (a stationary plan)
+void launch_reaction_stationary_residual(hipStream_t s, const ReactionPlan &P, double *d_r);
 // Crank-Nicolson: b = [T_1 r0 | T_2 r1]; across a shard boundary from P.d_rhalo
 void launch_reaction_rhs(hipStream_t s, const ReactionPlan &P, const double *d_r, double *d_b);
 void launch_reaction_update(hipStream_t s, const ReactionPlan &P, double *d_u);

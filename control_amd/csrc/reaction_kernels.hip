@@ -1,8 +1,8 @@
 // Kernels of the scalar reaction re-linearisation (reaction.hpp): P1 element matrices of a
-// polynomial reaction coefficient, the Picard residual of the heat-type optimality system, its
-// Crank-Nicolson right-hand side and the update of the iterate.  gfx950, wave64; every store is a
-// plain vector store, and no floating-point atomics: every sum runs in a fixed order.  Gather and
-// composition are relin_kernels.hip's.
+// polynomial reaction coefficient, the Picard residual of the heat-type optimality system (and of
+// the stationary one, n_t == 1), its Crank-Nicolson right-hand side and the update of the iterate.
+// gfx950, wave64; every store is a plain vector store, and no floating-point atomics: every sum
+// runs in a fixed order.  Gather and composition are relin_kernels.hip's.
 #include <hip/hip_runtime.h>
 
 #include "reaction.hpp"
@@ -257,6 +257,49 @@ void launch_reaction_residual(hipStream_t s, const ReactionPlan &P, double *d_r)
     hipLaunchKernelGGL(reaction_residual_kernel,
                        dim3(grid_of(P.n1, REACTION_ROW_BLOCKS), 2 * P.nl), dim3(256), 0, s, A,
                        d_r);
+}
+
+struct StationaryArgs {
+    const int32_t *ip, *ix, *tperm;
+    const double *M, *D, *data, *v, *zeta;
+    const uint8_t *bc;
+    int64_t n1;
+    double ib;   // 1.0 / beta, rounded once on the host
+};
+
+// The stationary system (n_t == 1): one thread per (family, dof).  Family 0 is the adjoint row
+// r0 = (d0 - M v) - D^T zeta, family 1 the state row r1 = (d1 - D v) + ib (M zeta) of
+// Stationary.non_linear_res_eval, with its bracketing; Dirichlet rows are zero.
+__global__ __launch_bounds__(256) void reaction_stationary_residual_kernel(
+    StationaryArgs A, double *__restrict__ r) {
+    const int fam = blockIdx.y;
+    for (int64_t R = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; R < A.n1;
+         R += (int64_t)gridDim.x * blockDim.x) {
+#pragma clang fp contract(off)
+        double out = 0.0;
+        if (!A.bc[R]) {
+            const double d = A.data[(int64_t)fam * A.n1 + R];
+            if (!fam) {
+                const double a = d - reaction_row(A.ip, A.ix, A.M, nullptr, R, A.v);
+                out = a - reaction_row(A.ip, A.ix, A.D, A.tperm, R, A.zeta);
+            } else {
+                const double a = d - reaction_row(A.ip, A.ix, A.D, nullptr, R, A.v);
+                const double c = A.ib * reaction_row(A.ip, A.ix, A.M, nullptr, R, A.zeta);
+                out = a + c;
+            }
+        }
+        r[(int64_t)fam * A.n1 + R] = out;
+    }
+}
+
+void launch_reaction_stationary_residual(hipStream_t s, const ReactionPlan &P, double *d_r) {
+    StationaryArgs A;
+    A.ip = P.d_ip; A.ix = P.d_ix; A.tperm = P.d_tperm;
+    A.M = P.d_M; A.D = P.d_D; A.data = P.d_data; A.v = P.d_v; A.zeta = P.d_zeta; A.bc = P.d_bc;
+    A.n1 = P.n1;
+    A.ib = 1.0 / P.beta;
+    hipLaunchKernelGGL(reaction_stationary_residual_kernel,
+                       dim3(grid_of(P.n1, REACTION_ROW_BLOCKS), 2), dim3(256), 0, s, A, d_r);
 }
 
 // Crank-Nicolson: T_1 on the adjoint rows (row i + 1 into i), T_2 on the state rows (i - 1 into i).

@@ -1,13 +1,16 @@
 """The scalar Picard / Gauss-Newton loop on the device (``kkt_set_reaction_relinearisation``,
-DESIGN.md section 6.6a): ``Instationary.non_linear_solve(device=True)`` for a forward operator
-declared as a ``fem.ReactionTerm``, on P1 triangles or P1 tetrahedra, on one GPU or -- with
-``comm=`` -- on time shards.
+DESIGN.md section 6.6a): ``Instationary.non_linear_solve(device=True)`` and
+``Stationary.non_linear_solve(device=True)`` for a forward operator declared as a
+``fem.ReactionTerm``, on P1 triangles or P1 tetrahedra, on one GPU or -- the instationary loop,
+with ``comm=`` -- on time shards.
 
 Host side: ``ReactionPlan`` -- the element tables of the term, the contribution lists that make
 the device assembly deterministic (``relinearise.contribution_lists``), the transpose permutation
 and the constant data rows of the residual -- and ``DeviceReaction``, a thin binding of the device
 entry points.  ``device_non_linear_solve`` is the loop of ``Instationary.non_linear_solve`` with
-one block system and one preconditioner kept alive and the iterate in HBM.
+one block system and one preconditioner kept alive and the iterate in HBM, and
+``device_stationary_non_linear_solve`` that of ``Stationary.non_linear_solve``: the stationary
+system is the plan with one level (``n_t = 1``), so both loops share every part but the driver.
 """
 from __future__ import annotations
 
@@ -20,7 +23,8 @@ from .fem import ReactionTerm
 from .relinearise import (_marshal, _recipe_array, contribution_lists, device_picard_loop,
                           device_vectors, transpose_permutation)
 
-__all__ = ["ReactionPlan", "DeviceReaction", "device_non_linear_solve"]
+__all__ = ["ReactionPlan", "DeviceReaction", "device_non_linear_solve",
+           "device_stationary_non_linear_solve"]
 
 _ARRAYS = ("E", "D", "v", "zeta")
 
@@ -48,15 +52,21 @@ def _check(ctl, P=None, comm=None, host_allreduce=None):
 
 class ReactionPlan:
     """Everything ``kkt_set_reaction_relinearisation`` uploads, built once per problem on the
-    host from an ``Instationary`` whose forward operator is a ``fem.ReactionTerm``."""
+    host from an ``Instationary`` or a ``Stationary`` whose forward operator is a
+    ``fem.ReactionTerm``.  A ``Stationary`` gives the plan with one level: ``n_t = 1``,
+    ``stationary`` set, ``tau`` unused."""
 
     def __init__(self, ctl):
         _check(ctl)
         term, disc = ctl._forward, ctl._disc
         self.ctl, self.term = ctl, term
-        self.n_t, self.CN = ctl._n_t, ctl._CN
+        self.stationary = not hasattr(ctl, "_n_t")
+        if self.stationary:
+            self.n_t, self.CN, self.tau = 1, False, 0.0
+        else:
+            self.n_t, self.CN = ctl._n_t, ctl._CN
+            _, _, self.tau = ctl._times()
         self.m = self.n_t - 1 if self.CN else self.n_t
-        _, _, self.tau = ctl._times()
         self.beta = ctl._beta
         #: the coefficients every D of the loop is built from (``construct_D_v``)
         self.coefficients = term.jacobian_coefficients if ctl._Gauss_Newton else term.coefficients
@@ -70,6 +80,10 @@ class ReactionPlan:
         ``tau D(v_0) v_0 + M v_0``.  Boundary values live in the iterate (``v`` keeps them on the
         Dirichlet dofs), and the Dirichlet rows of the residual are zero."""
         ctl, disc, n_t, tau = self.ctl, self.ctl._disc, self.n_t, self.tau
+        if self.stationary:          # [M v_d | M f] of Stationary._data()
+            rows = np.stack(ctl._data()).astype(np.float64)
+            rows[:, disc.boundary] = 0.0
+            return np.ascontiguousarray(rows)
         v_d, f = ctl.construct_v_d(), ctl.construct_f()
         if self.CN:
             h = 0.5 * tau
@@ -116,7 +130,8 @@ def owned(recipes, lo, hi):
 
 
 class DeviceReaction:
-    """The plan on a scalar instationary ``MultiBlockSystem`` and the iterate in HBM.
+    """The plan on a scalar instationary (or, a stationary plan, stationary)
+    ``MultiBlockSystem`` and the iterate in HBM -- a stationary plan's as one level, ``(1, n)``.
 
     On a time-sharded system every rank keeps its own levels of the iterate, of the element
     matrices and of ``D`` (``window``), assembles, evaluates the residual of and updates those, and
@@ -126,9 +141,10 @@ class DeviceReaction:
     def __init__(self, ctl, system, recipes=None, plan=None, host_allreduce=None):
         """``recipes``: the blocks every re-linearisation rewrites (default: the ``"inner"`` list
         of ``blocks.instationary_relinearisation_recipes``, on a time shard those of the rank's
-        own block rows).  ``host_allreduce(array, op)`` (a time shard): what ``get_state`` gathers
+        own block rows; a stationary plan: ``blocks.stationary_relinearisation_recipes``).  ``host_allreduce(array, op)`` (a time shard): what ``get_state`` gathers
         the iterate with."""
-        from .blocks import instationary_relinearisation_recipes
+        from .blocks import (instationary_relinearisation_recipes,
+                             stationary_relinearisation_recipes)
         self.plan = ReactionPlan(ctl) if plan is None else plan
         self.ctl, self.system, self._lib = ctl, system, system._lib
         self.host_allreduce = host_allreduce
@@ -142,6 +158,7 @@ class DeviceReaction:
         if recipes is None:
             p = self.plan
             recipes = owned(
+                stationary_relinearisation_recipes(p.beta) if p.stationary else
                 instationary_relinearisation_recipes(p.tau, p.beta, p.n_t, p.CN)["inner"],
                 *self.window["blocks"])
         self.recipes = (_recipe_array(recipes, 0), len(recipes))
@@ -151,7 +168,7 @@ class DeviceReaction:
 
     def set_state(self, v, zeta):
         """Global arrays; a time shard takes its windows from them, halo levels included."""
-        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (v, zeta)]
+        arrs = [np.atleast_2d(np.ascontiguousarray(a, dtype=np.float64)) for a in (v, zeta)]
         for a in arrs:
             if a.shape != self._shape():
                 raise ValueError(f"iterate block of shape {a.shape}, expected {self._shape()}")
@@ -211,15 +228,17 @@ class DeviceReaction:
 
 
 def build_system(ctl, backend, plan, comm=None):
-    """The scalar block system from patterns: every block of ``blocks.instationary_blocks`` is a
-    ``PatternOnly`` of the structure of ``M``, in the row-major dict order of the host path.
+    """The scalar block system from patterns: every block of ``blocks.instationary_blocks`` (a
+    stationary plan: of ``blocks.stationary_blocks``) is a ``PatternOnly`` of the structure of
+    ``M``, in the row-major dict order of the host path.
     Returns ``(system, block dicts, build recipes)``; the blocks are unset until the device
     composes them.  ``comm``: a time shard registers the blocks of its own rows
     (``MultiBlockSystem`` skips the others), and the build recipes are those rows'."""
-    from .blocks import instationary_build_recipes
+    from .blocks import instationary_build_recipes, stationary_build_recipes
     from .multiblock import PatternOnly
     disc, m = ctl._disc, plan.m
-    full = instationary_build_recipes(plan.tau, plan.beta, plan.n_t, plan.CN)["inner"]
+    full = (stationary_build_recipes(plan.beta) if plan.stationary else
+            instationary_build_recipes(plan.tau, plan.beta, plan.n_t, plan.CN)["inner"])
     n = disc.n_dofs
     pat = PatternOnly(*plan.pattern(), (n, n))
     quads = [{(i, j): None for i in range(m) for j in range(m)} for _ in range(4)]
@@ -278,7 +297,21 @@ def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bou
     pc_fn = backend.construct_pc("CN" if CN else "BE", plan.term.M, quads[1], quads[2], n_t,
                                  plan.tau, plan.beta, nodes, lambda_v_bounds or (0.5, 2.0),
                                  1.0e-3, **_multigrid_kw(disc, Multigrid))
-    if solver_parameters is None:                                # control.py:3260-3266
+    norms, lin_its, v_new, zeta_new = _run_loop(
+        dev, pc_fn, solver_parameters, v_fixed if lift else None, relative_non_linear_tol,
+        absolute_non_linear_tol, max_non_linear_iter, print_error_non_linear)
+    ctl._v, ctl._zeta = v_new, zeta_new
+    ctl.non_linear_info = {"linear_iterations": lin_its, "window": dev.window}
+    return norms
+
+
+def _run_loop(dev, pc_fn, solver_parameters, v_fixed, rtol, atol, max_iter, verbose):
+    """What both drivers do with a composed system: the first residual, ``device_picard_loop``
+    and the download; the system is closed afterwards.  ``v_fixed`` (``(levels, n)``, or ``None``):
+    the starting iterate did not carry these boundary values -- they are put in once, after the
+    first update.  Returns ``(norms, linear iterations, v, zeta)``."""
+    system, nodes = dev.system, dev.ctl._disc.boundary
+    if solver_parameters is None:              # linear_solve's, control.py:3260-3266 and 556-562
         solver_parameters = {"linear_solver": "gmres", "gmres_restart": 10,
                              "maximum_iterations": 50, "relative_tolerance": 1.0e-6,
                              "absolute_tolerance": 0.0, "monitor_convergence": False}
@@ -287,7 +320,7 @@ def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bou
         ksp = system.solve_device(d_b, d_u, solver_parameters=solver_parameters, pc_fn=pc_fn)
         return ksp.getIterationNumber()
 
-    def lift_boundary():     # the starting iterate did not carry the boundary values: once
+    def lift_boundary():
         v_new, zeta_new = dev.get_state()
         v_new[:, nodes] = v_fixed[:, nodes]
         dev.set_state(v_new, zeta_new)
@@ -295,12 +328,55 @@ def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bou
         with device_vectors(system) as (d_b, d_u):
             norm_0 = dev.residual(d_b, rhs=True)
             norms, lin_its = device_picard_loop(
-                dev, d_b, d_u, norm_0, solve, dev.relinearise, True, relative_non_linear_tol,
-                absolute_non_linear_tol, max_non_linear_iter, print_error_non_linear,
-                after_first_update=lift_boundary if lift else None)
+                dev, d_b, d_u, norm_0, solve, dev.relinearise, True, rtol, atol, max_iter,
+                verbose, after_first_update=lift_boundary if v_fixed is not None else None)
             v_new, zeta_new = dev.get_state()
     finally:
         system.close()
-    ctl._v, ctl._zeta = v_new, zeta_new
+    return norms, lin_its, v_new, zeta_new
+
+
+def device_stationary_non_linear_solve(ctl, *, P=None, solver_parameters=None,
+                                       lambda_v_bounds=None, max_non_linear_iter=10,
+                                       relative_non_linear_tol=1.0e-5,
+                                       absolute_non_linear_tol=1.0e-8,
+                                       print_error_non_linear=False, backend=None,
+                                       Multigrid=False):
+    """``Stationary.non_linear_solve`` with the iterate in HBM: the loop of
+    ``device_non_linear_solve`` on the one-level plan.  One ``MultiBlockSystem`` of four
+    ``PatternOnly`` blocks is composed on the device, one ``SchurPC(kind="stationary")`` is
+    attached to it; every iteration assembles ``D`` at the device iterate, evaluates the rows of
+    ``Stationary.non_linear_res_eval`` (they are the right-hand side), re-composes ``D^T`` and
+    ``D`` (the preconditioner is marked stale and rebuilt by the next solve), solves and updates
+    on the GPU."""
+    from .control import GpuBackend, _multigrid_kw
+    _check(ctl, P)
+    backend = backend or GpuBackend()
+    if not isinstance(backend, GpuBackend):
+        raise ValueError("device=True runs on a GpuBackend")
+    disc, nodes = ctl._disc, ctl._disc.boundary
+    v_old, zeta_old = ctl._v.copy(), ctl._zeta.copy()
+    # the values the iterate keeps on the Dirichlet dofs from the first update on
+    # (Stationary.non_linear_solve: v_old[boundary] = v_inhom[boundary], only with bcs_v)
+    v_fixed = v_old.copy()
+    if ctl._bcs_v is not None:
+        v_fixed[nodes] = ctl._v_inhom()[nodes]
+    lift = not np.array_equal(v_fixed, v_old)
+
+    plan = ReactionPlan(ctl)
+    system, quads, full = build_system(ctl, backend, plan)
+    dev = DeviceReaction(ctl, system, plan=plan)
+    dev.set_state(v_old, zeta_old)
+    dev.assemble()
+    dev.relinearise(recipes=full)
+    pc_fn = backend.construct_pc("stationary", plan.term.M, quads[1], quads[2], 1, 0.0,
+                                 plan.beta, nodes, lambda_v_bounds or (0.5, 2.0), 0.0,
+                                 **_multigrid_kw(disc, Multigrid))
+    norms, lin_its, v_new, zeta_new = _run_loop(
+        dev, pc_fn, solver_parameters, v_fixed[None] if lift else None, relative_non_linear_tol,
+        absolute_non_linear_tol, max_non_linear_iter, print_error_non_linear)
+    if lin_its:              # the host loop ends every iteration in set_v / set_zeta
+        ctl.set_v(v_new[0])
+        ctl.set_zeta(zeta_new[0])
     ctl.non_linear_info = {"linear_iterations": lin_its, "window": dev.window}
     return norms

@@ -521,10 +521,20 @@ int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
  * initial-condition row tau D(v_0) v_0 + M v_0), Dirichlet rows zero.  c: the Gauss-Newton
  * coefficients (k + 1) c_k when that linearisation is on.  Arrays are copied; patterns, lists and
  * permutations are validated as kkt_set_relinearisation validates its own (KKT_ERR_ARG naming what
- * does not fit). */
+ * does not fit).
+ *
+ * n_t == 1 selects the stationary system [[M, D^T], [D, -(1/beta) M]] of Control.Stationary (no
+ * instationary system has one level): cn must be 0 and tau is ignored; the handle must be the
+ * stationary layout -- n_blocks_00 = n_blocks_11 = 1, nx0 = nx1 = n1, not Crank-Nicolson, not
+ * sharded -- each violation KKT_ERR_ARG naming it; data is 2 x n1, [M v_d | M f] with the
+ * Dirichlet rows zero; every window is [0, 1).  Every entry point below then works on that one
+ * level: the rows of kkt_reaction_residual_device are those of Stationary.non_linear_res_eval,
+ *   r0 = (d0 - M v) - D^T zeta,   r1 = (d1 - D v) + (1.0 / beta) (M zeta),
+ * and they are the right-hand side themselves (rhs = 1 gives the bits of rhs = 0). */
 typedef struct kkt_reaction_desc {
-    int n_t, cn, nq;              /* time levels, Crank-Nicolson (1) or backward Euler; nq = 7:
-                                     triangles (nv = 3), nq = 15: tetrahedra (nv = 4) */
+    int n_t, cn, nq;              /* time levels (1: the stationary system), Crank-Nicolson (1)
+                                     or backward Euler; nq = 7: triangles (nv = 3), nq = 15:
+                                     tetrahedra (nv = 4) */
     int64_t ne, n1;               /* cells, P1 nodes */
     double tau, beta;
     const int32_t *cells;         /* ne x nv nodes per cell */
