@@ -88,7 +88,26 @@ void compose_run(System &T, Composer &C, std::vector<ComposeJob> &jobs,
     T.pc_stale = true;
 }
 
-void copy_spans(hipStream_t s, bool download, std::initializer_list<CopySpan> spans) {
+void check_apply_target(const char *api, const System &T, const System &PS, int n,
+                        const kkt_relin_recipe *rec) {
+    const std::string at = std::string(api) + ": ";
+    if (n < 0 || (n > 0 && !rec)) fail(KKT_ERR_ARG, at + "bad recipe list");
+    if (T.device != PS.device) fail(KKT_ERR_ARG, at + "plan on another device");
+    if (!T.finalized) fail(KKT_ERR_ARG, at + "the target must be finalized");
+    if (T.sharded != PS.sharded || (T.sharded && (T.lo != PS.lo || T.hi != PS.hi)))
+        fail(KKT_ERR_ARG, at + "the target is not sharded as the plan's handle");
+}
+
+void exchange_iterate_halos(System &S, const LevelWindows &w, double *d_v, double *d_zeta,
+                            int64_t row_len) {
+    if (!S.sharded) return;
+    if (!S.comm) fail(KKT_ERR_STATE, "time-sharded system without a transport");
+    const int up = w.up(S.rank), dn = w.dn(S.rank);
+    S.comm->sendrecv(d_v + w.v_last_slot() * row_len, row_len, up, d_v, row_len, dn, S.stream);
+    S.comm->sendrecv(d_zeta, row_len, dn, d_zeta + (w.z_n - 1) * row_len, row_len, up, S.stream);
+}
+
+void copy_spans(hipStream_t s, bool download, const std::vector<CopySpan> &spans) {
     for (const CopySpan &c : spans) {
         if (!c.host) continue;
         if (download)
@@ -97,6 +116,42 @@ void copy_spans(hipStream_t s, bool download, std::initializer_list<CopySpan> sp
             HIPCHK(hipMemcpyAsync(c.dev, c.host, c.len * 8, hipMemcpyHostToDevice, s));
     }
     HIPCHK(hipStreamSynchronize(s));
+}
+
+std::vector<CopySpan> iterate_spans(const LevelWindows &w, bool download, double *d_v,
+                                    double *d_zeta, double *v, double *zeta, int64_t row_len) {
+    const LevelRange lv = w.v_levels(download), lz = w.z_levels(download);
+    return {{d_v + (lv.l0 - w.v_l0) * row_len, v ? v + lv.l0 * row_len : nullptr,
+             (lv.l1 - lv.l0) * row_len},
+            {d_zeta + (lz.l0 - w.z_l0) * row_len, zeta ? zeta + lz.l0 * row_len : nullptr,
+             (lz.l1 - lz.l0) * row_len}};
+}
+
+uint8_t *upload_bc_mask(DevPool &mem, const int32_t *bc_idx, int64_t n_bc, int64_t n) {
+    std::vector<uint8_t> bc(n, 0);
+    for (int64_t k = 0; k < n_bc; ++k) bc[bc_idx[k]] = 1;
+    return mem.upload(bc.data(), n);
+}
+
+double *upload_data_rows(DevPool &mem, const LevelWindows &w, const double *data, int64_t row_len) {
+    const int64_t rows = w.nl * row_len;
+    double *d = mem.alloc<double>(2 * rows);
+    for (int f = 0; f < 2; ++f)
+        HIPCHK(hipMemcpy(d + f * rows, data + ((int64_t)f * w.m + w.lo) * row_len, rows * 8,
+                         hipMemcpyHostToDevice));
+    return d;
+}
+
+void copy_debug_array(const char *api, System &S, const std::vector<DebugArray> &arrays,
+                      bool assembled, int which, double *out, int64_t cap) {
+    const std::string at = std::string(api) + ": ";
+    if (which < 0 || which >= (int)arrays.size()) fail(KKT_ERR_ARG, at + "no such array");
+    const DebugArray &a = arrays[which];
+    if (a.needs_assembly && !assembled) fail(KKT_ERR_STATE, at + "nothing assembled yet");
+    const int64_t n = a.per_level * a.levels;
+    if (!out || cap < n) fail(KKT_ERR_ARG, at + "buffer too small");
+    HIPCHK(hipStreamSynchronize(S.stream));
+    HIPCHK(hipMemcpy(out, a.src, n * 8, hipMemcpyDeviceToHost));
 }
 
 double *raw_rows(System &S) {

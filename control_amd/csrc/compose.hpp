@@ -1,11 +1,12 @@
 // What the device re-linearisation plans share (relin.hpp, reaction.hpp): the checks of a plan's
 // arrays, the composition of assembled per-level values D into block values with its
-// copy-on-write, and the tails of the state copies and residual norms.  DESIGN.md section 6.6.
+// copy-on-write, and what follows from a rank's level windows (levels.hpp) alike for both: target
+// checks, halo exchange, state copies, data uploads, debug copies, residual norms.  DESIGN.md
+// section 6.6.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
-#include <initializer_list>
 #include <set>
 #include <string>
 #include <tuple>
@@ -13,6 +14,7 @@
 
 #include "../../include/kkt.h"
 #include "devmem.hpp"
+#include "levels.hpp"
 
 namespace kkt {
 
@@ -97,12 +99,43 @@ std::vector<ComposeJob> compose_jobs(const char *api, System &T, Composer &C, in
 void compose_run(System &T, Composer &C, std::vector<ComposeJob> &jobs,
                  const kkt_relin_recipe *rec);
 
+// The head of a plan's *_apply, each a KKT_ERR_ARG that begins with `api`: the recipe list, the
+// device, a finalized target, and a target sharded like the plan's handle PS.
+void check_apply_target(const char *api, const System &T, const System &PS, int n,
+                        const kkt_relin_recipe *rec);
+
+// One level of v up and one of zeta down, after the update and before the assembly: v of my last
+// block is the first level of the window above, zeta of my first block the last of the window
+// below.  Levels (row_len doubles) are contiguous: nothing is packed.  One rank: nothing.
+void exchange_iterate_halos(System &S, const LevelWindows &w, double *d_v, double *d_zeta,
+                            int64_t row_len);
+
 // Host <-> device copies on a stream, then a wait; a null host pointer skips its span.
 struct CopySpan {
     double *dev, *host;
     int64_t len;
 };
-void copy_spans(hipStream_t s, bool download, std::initializer_list<CopySpan> spans);
+void copy_spans(hipStream_t s, bool download, const std::vector<CopySpan> &spans);
+// v and zeta between host arrays of the global shapes and a rank's windows: an upload reads the
+// windows, a download writes the owned levels (levels.hpp) and leaves the rest as it is
+std::vector<CopySpan> iterate_spans(const LevelWindows &w, bool download, double *d_v,
+                                    double *d_zeta, double *v, double *zeta, int64_t row_len);
+
+// n bytes, 1 on the n_bc Dirichlet dofs; and the data rows of the owned blocks, lo..hi-1 of the
+// adjoint rows and m+lo..m+hi-1 of the state rows of `data` (2 m rows of row_len)
+uint8_t *upload_bc_mask(DevPool &mem, const int32_t *bc_idx, int64_t n_bc, int64_t n);
+double *upload_data_rows(DevPool &mem, const LevelWindows &w, const double *data, int64_t row_len);
+
+// One array a plan's debug entry copies to the host: `levels` levels of per_level doubles;
+// needs_assembly: work of the last assembly, refused before the first
+struct DebugArray {
+    const double *src;
+    int64_t per_level;
+    int levels;
+    bool needs_assembly;
+};
+void copy_debug_array(const char *api, System &S, const std::vector<DebugArray> &arrays,
+                      bool assembled, int which, double *out, int64_t cap);
 
 // S's scratch vector for the raw residual rows a right-hand side is transformed from
 double *raw_rows(System &S);

@@ -3,7 +3,6 @@
 // Kernels: reaction_kernels.hip; checks, gather and composition: compose.hpp.
 #include "reaction.hpp"
 
-#include <algorithm>
 #include <string>
 
 #include "comm.hpp"
@@ -54,9 +53,9 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
     check_range(api + "bc_idx", d->bc_idx, d->n_bc, n1);
 
     auto P = std::make_unique<ReactionPlan>();
-    P->n_t = d->n_t;
-    P->m = m;
-    P->CN = d->cn != 0;
+    // the rank's block rows and the level windows its rows read
+    P->w = level_windows(d->n_t, d->cn != 0, S.sharded ? S.lo : 0, S.sharded ? S.hi : m);
+    const LevelWindows &w = P->w;
     P->stationary = stationary;
     P->nv = nv;
     P->nq = d->nq;
@@ -66,23 +65,6 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
     P->nnz = nnz;
     P->tau = d->tau;
     P->beta = d->beta;
-    // the rank's block rows and the level windows its rows read (reaction.hpp)
-    const int lo = S.sharded ? S.lo : 0, hi = S.sharded ? S.hi : m, nl = hi - lo;
-    P->lo = lo;
-    P->nl = nl;
-    P->v_halo = lo > 0;
-    P->z_halo = hi < m;
-    if (P->CN) {
-        P->v_l0 = P->z_l0 = P->D_l0 = lo;
-        P->v_n = P->z_n = P->D_n = nl + 1;
-    } else {
-        P->v_l0 = lo - (P->v_halo ? 1 : 0);
-        P->v_n = hi - P->v_l0;
-        P->z_l0 = lo;
-        P->z_n = nl + (P->z_halo ? 1 : 0);
-        P->D_l0 = lo;
-        P->D_n = nl;
-    }
     P->coef.degree = d->degree;
     for (int k = 0; k <= REACTION_MAX_DEGREE; ++k) P->coef.c[k] = k <= d->degree ? d->c[k] : 0.0;
     P->d_cells = P->mem.upload(d->cells, ne * nv);
@@ -95,29 +77,23 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
     P->d_clist = P->mem.upload(d->clist, n_entries);
     P->d_L = P->mem.upload(d->L, nnz);
     P->d_M = P->mem.upload(d->M, nnz);
-    std::vector<uint8_t> bc(n1, 0);
-    for (int64_t k = 0; k < d->n_bc; ++k) bc[d->bc_idx[k]] = 1;
-    P->d_bc = P->mem.upload(bc.data(), n1);
-    // the data rows of the owned blocks: lo..hi-1 of the adjoint rows, m+lo..m+hi-1 of the state rows
-    P->d_data = P->mem.alloc<double>(2 * (int64_t)nl * n1);
-    for (int f = 0; f < 2; ++f)
-        HIPCHK(hipMemcpy(P->d_data + (int64_t)f * nl * n1, d->data + ((int64_t)f * m + lo) * n1,
-                         (int64_t)nl * n1 * 8, hipMemcpyHostToDevice));
-    if (S.sharded && P->CN) {
+    P->d_bc = upload_bc_mask(P->mem, d->bc_idx, d->n_bc, n1);
+    P->d_data = upload_data_rows(P->mem, w, d->data, n1);
+    if (S.sharded && w.CN) {
         P->d_rhalo = P->mem.alloc<double>(2 * n1);
         HIPCHK(hipMemset(P->d_rhalo, 0, 2 * n1 * 8));
     }
-    P->d_E = P->mem.alloc<double>(n_entries * P->D_n);
-    P->d_D = P->mem.alloc<double>(nnz * P->D_n);
-    P->d_v = P->mem.alloc<double>(P->v_n * n1);
-    P->d_zeta = P->mem.alloc<double>(P->z_n * n1);
-    HIPCHK(hipMemset(P->d_v, 0, P->v_n * n1 * 8));
-    HIPCHK(hipMemset(P->d_zeta, 0, P->z_n * n1 * 8));
+    P->d_E = P->mem.alloc<double>(n_entries * w.D_n);
+    P->d_D = P->mem.alloc<double>(nnz * w.D_n);
+    P->d_v = P->mem.alloc<double>(w.v_n * n1);
+    P->d_zeta = P->mem.alloc<double>(w.z_n * n1);
+    HIPCHK(hipMemset(P->d_v, 0, w.v_n * n1 * 8));
+    HIPCHK(hipMemset(P->d_zeta, 0, w.z_n * n1 * 8));
     P->d_red = P->mem.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX + 2);
     P->compose.n_t = d->n_t;
     P->compose.spaces = {{"scalar", std::vector<int32_t>(d->indptr, d->indptr + n1 + 1),
                           std::vector<int32_t>(d->indices, d->indices + nnz), nnz, 1, P->d_D,
-                          P->D_l0, P->D_n, P->d_M, P->d_tperm}};
+                          w.D_l0, w.D_n, P->d_M, P->d_tperm}};
     S.reaction = std::move(P);
 }
 
@@ -127,35 +103,17 @@ static ReactionPlan &plan_of(System &S) {
     return *S.reaction;
 }
 
-// One level of v up and one of zeta down, after the update and before the assembly: v of my
-// last block (BE level hi - 1, CN level hi) is the first level of the window above, zeta of my
-// first block the last level of the window below.  Levels are contiguous: nothing is packed.
-void reaction_exchange(System &S) {
-    ReactionPlan &P = plan_of(S);
-    if (!S.sharded) return;
-    if (!S.comm) fail(KKT_ERR_STATE, "time-sharded system without a transport");
-    const int up = P.z_halo ? S.rank + 1 : -1, dn = P.v_halo ? S.rank - 1 : -1;
-    const int v_last = P.lo + P.nl - 1 + (P.CN ? 1 : 0);
-    S.comm->sendrecv(P.d_v + (int64_t)(v_last - P.v_l0) * P.n1, P.n1, up, P.d_v, P.n1, dn, S.stream);
-    S.comm->sendrecv(P.d_zeta, P.n1, dn, P.d_zeta + (int64_t)(P.z_n - 1) * P.n1, P.n1, up,
-                     S.stream);
-}
-
 void reaction_apply(System &T, System &PS, int assemble, int n, const kkt_relin_recipe *rec) {
     ReactionPlan &P = plan_of(PS);
-    if (n < 0 || (n > 0 && !rec)) fail(KKT_ERR_ARG, "kkt_reaction_relinearise: bad recipe list");
-    if (T.device != PS.device) fail(KKT_ERR_ARG, "kkt_reaction_relinearise: plan on another device");
-    if (!T.finalized) fail(KKT_ERR_ARG, "kkt_reaction_relinearise: the target must be finalized");
-    if (T.sharded != PS.sharded || (T.sharded && (T.lo != PS.lo || T.hi != PS.hi)))
-        fail(KKT_ERR_ARG, "kkt_reaction_relinearise: the target is not sharded as the plan's handle");
+    check_apply_target("kkt_reaction_relinearise", T, PS, n, rec);
     // every recipe is validated before anything is written
     std::vector<ComposeJob> jobs = compose_jobs("kkt_reaction_relinearise", T, P.compose, n, rec);
     if (assemble) {
-        reaction_exchange(PS);
+        exchange_iterate_halos(PS, P.w, P.d_v, P.d_zeta, P.n1);
         launch_reaction_elements(PS.stream, P);
         // D = 1.0 * L[k] + acc: the product is exact, so this is L + C with one rounding
         launch_relin_gather_one(PS.stream, P.d_cptr, P.d_clist, P.d_E, P.ne * P.ep, P.d_L, 1.0,
-                                P.nnz, P.D_n, P.d_D);
+                                P.nnz, P.w.D_n, P.d_D);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(PS.stream));
         P.assembled = true;
@@ -165,32 +123,17 @@ void reaction_apply(System &T, System &PS, int assemble, int n, const kkt_relin_
     compose_run(T, P.compose, jobs, rec);
 }
 
-// Host arrays of the global shapes.  Upload: the rank's windows, halo levels included.
-// Download: the levels the rank owns (BE: v, zeta of its blocks; CN: v one level up), and the
-// fixed levels -- CN's v_0, zeta of the last level -- on the rank whose window holds them; the
-// rest of the host arrays is left as it is.  (One rank: every level, both ways.)
+// Host arrays of the global shapes, by iterate_spans.
 void reaction_state(System &S, int download, double *v, double *zeta) {
     ReactionPlan &P = plan_of(S);
-    const int hi = P.lo + P.nl;
-    int v0 = P.v_l0, v1 = P.v_l0 + P.v_n, z0 = P.z_l0, z1 = P.z_l0 + P.z_n;
-    if (download) {
-        v0 = P.CN ? (P.lo == 0 ? 0 : P.lo + 1) : P.lo;
-        v1 = P.CN ? hi + 1 : hi;
-        z1 = P.CN && hi == P.m ? hi + 1 : hi;
-    }
     copy_spans(S.stream, download != 0,
-               {{P.d_v + (int64_t)(v0 - P.v_l0) * P.n1, v ? v + (int64_t)v0 * P.n1 : nullptr,
-                 (v1 - v0) * P.n1},
-                {P.d_zeta + (int64_t)(z0 - P.z_l0) * P.n1,
-                 zeta ? zeta + (int64_t)z0 * P.n1 : nullptr, (z1 - z0) * P.n1}});
+               iterate_spans(P.w, download != 0, P.d_v, P.d_zeta, v, zeta, P.n1));
 }
 
 void reaction_window(System &S, int out[8]) {
     ReactionPlan &P = plan_of(S);
     if (!out) fail(KKT_ERR_ARG, "kkt_reaction_window: null argument");
-    const int w[8] = {P.v_l0, P.v_l0 + P.v_n, P.z_l0, P.z_l0 + P.z_n, P.D_l0, P.D_l0 + P.D_n,
-                      P.lo, P.lo + P.nl};
-    std::copy(w, w + 8, out);
+    P.w.report(out);
 }
 
 void reaction_iterate(System &S, double **v, double **zeta) {
@@ -204,7 +147,7 @@ void reaction_residual(System &S, double *d_out, int rhs, double *norm) {
     if (!d_out || !norm) fail(KKT_ERR_ARG, "kkt_reaction_residual_device: null argument");
     if (!P.assembled) fail(KKT_ERR_STATE, "kkt_reaction_residual_device: D not assembled yet");
     // backward Euler's right-hand side is the rows themselves, and so is the stationary system's
-    const bool transform = rhs && P.CN;
+    const bool transform = rhs && P.w.CN;
     double *r = transform ? raw_rows(S) : d_out;
     if (P.stationary)
         launch_reaction_stationary_residual(S.stream, P, r);
@@ -214,8 +157,8 @@ void reaction_residual(System &S, double *d_out, int rhs, double *norm) {
     if (transform && S.sharded) {
         // the raw rows the time transforms read across the shard boundary: the adjoint rows (T_1)
         // send their first row down, the state rows (T_2) their last row up
-        const int up = P.z_halo ? S.rank + 1 : -1, dn = P.v_halo ? S.rank - 1 : -1;
-        const int64_t n1 = P.n1, nl = P.nl;
+        const int up = P.w.up(S.rank), dn = P.w.dn(S.rank);
+        const int64_t n1 = P.n1, nl = P.w.nl;
         S.comm->sendrecv(r, n1, dn, P.d_rhalo, n1, up, S.stream);
         S.comm->sendrecv(r + (2 * nl - 1) * n1, n1, up, P.d_rhalo + n1, n1, dn, S.stream);
     }
@@ -232,15 +175,10 @@ void reaction_update(System &S, double *d_u) {
 
 void reaction_debug_array(System &S, int which, double *out, int64_t cap) {
     ReactionPlan &P = plan_of(S);
-    if (which < 0 || which > 3) fail(KKT_ERR_ARG, "kkt_debug_reaction_array: no such array");
-    if (which < 2 && !P.assembled)
-        fail(KKT_ERR_STATE, "kkt_debug_reaction_array: nothing assembled yet");
-    const double *src[4] = {P.d_E, P.d_D, P.d_v, P.d_zeta};
-    const int64_t per_level[4] = {P.ne * P.ep, P.nnz, P.n1, P.n1};
-    const int64_t n = per_level[which] * (which < 2 ? P.D_n : which == 2 ? P.v_n : P.z_n);
-    if (!out || cap < n) fail(KKT_ERR_ARG, "kkt_debug_reaction_array: buffer too small");
-    HIPCHK(hipStreamSynchronize(S.stream));
-    HIPCHK(hipMemcpy(out, src[which], n * 8, hipMemcpyDeviceToHost));
+    const std::vector<DebugArray> arrays = {
+        {P.d_E, P.ne * P.ep, P.w.D_n, true}, {P.d_D, P.nnz, P.w.D_n, true},
+        {P.d_v, P.n1, P.w.v_n, false}, {P.d_zeta, P.n1, P.w.z_n, false}};
+    copy_debug_array("kkt_debug_reaction_array", S, arrays, P.assembled, which, out, cap);
 }
 
 }  // namespace kkt

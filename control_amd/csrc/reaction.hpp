@@ -22,25 +22,16 @@ struct ReactionCoef {
 };
 
 struct ReactionPlan {
-    int n_t = 0, m = 0;   // global: time levels, unknown blocks per family
     // the element: nodes per cell (3: triangles, 4: tetrahedra), quadrature points (7: Radon's
     // rule, 15: Stroud's T3:5-1) and entries of one element matrix, nv * nv
     int nv = 0, nq = 0, ep = 0;
-    bool CN = false;
     // n_t == 1: the stationary system [[M, D^T], [D, -(1/beta) M]] of Control.Stationary.  One
     // level of everything, every window [0, 1), tau unused; the element kernels, the gather, the
     // composition and the update run as on one level, the residual rows are their own kernel.
     bool stationary = false;
-    // Level windows, by the rules of RelinPlan (relin.hpp): the rows read the same neighbours.  The
-    // rank owns the block rows [lo, lo + nl) of both families (one rank: all m) and holds the
-    // levels its rows read: v from level v_l0 (v_n of them), zeta from z_l0, D and the element
-    // matrices from D_l0; the data rows are the owned blocks'.
-    //   BE  v [lo - 1, hi)   zeta [lo, hi]   D [lo, hi)    (level -1 and level n_t do not exist)
-    //   CN  v [lo, hi]       zeta [lo, hi]   D [lo, hi]
-    // v's first level comes from the rank below and zeta's last from the rank above
-    // (reaction_exchange); CN's D_lo is assembled here from the halo v.
-    int lo = 0, nl = 0, v_l0 = 0, v_n = 0, z_l0 = 0, z_n = 0, D_l0 = 0, D_n = 0;
-    bool v_halo = false, z_halo = false;   // the first v / last zeta level belongs to a neighbour
+    // n_t, m, CN, the rank's block rows and the levels of v, zeta and D it holds (levels.hpp): the
+    // rows read the same neighbours as RelinPlan's; the data rows are the owned blocks'
+    LevelWindows w;
     int64_t ne = 0, n1 = 0, nnz = 0;
     double tau = 0.0, beta = 0.0;
     ReactionCoef coef{};
@@ -85,7 +76,5 @@ void reaction_update(System &S, double *d_u);
 void reaction_debug_array(System &S, int which, double *out, int64_t cap);
 // kkt_reaction_window: [v_l0, v_end, z_l0, z_end, D_l0, D_end, lo, hi), half-open ranges
 void reaction_window(System &S, int out[8]);
-// the iterate's halo levels from the neighbour ranks (a time shard; one rank: nothing)
-void reaction_exchange(System &S);
 
 }  // namespace kkt

@@ -120,14 +120,14 @@ __global__ __launch_bounds__(256) void reaction_elements_tet_kernel(
 // The kernels' levels are those of the D window: v is passed from the slot of level D_l0 (a time
 // shard's v window may start one level below), n_t is D_n.  One rank: the base 0, every level.
 void launch_reaction_elements(hipStream_t s, const ReactionPlan &P) {
-    const dim3 grid(grid_of(P.ne * P.D_n, REACTION_ELEMENT_BLOCKS));
-    const double *v = P.d_v + (int64_t)(P.D_l0 - P.v_l0) * P.n1;
+    const dim3 grid(grid_of(P.ne * P.w.D_n, REACTION_ELEMENT_BLOCKS));
+    const double *v = P.d_v + (int64_t)(P.w.D_l0 - P.w.v_l0) * P.n1;
     if (P.nv == TET_NV)
         hipLaunchKernelGGL(reaction_elements_tet_kernel, grid, dim3(256), 0, s, v, P.ne, P.n1,
-                           P.D_n, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
+                           P.w.D_n, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
     else
         hipLaunchKernelGGL(reaction_elements_kernel, grid, dim3(256), 0, s, v, P.ne, P.n1,
-                           P.D_n, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
+                           P.w.D_n, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
 }
 
 // sum_k A[k] x[col[k]] over CSR row r from 0.0 in stored order (tperm: the transposed matrix on
@@ -251,11 +251,11 @@ void launch_reaction_residual(hipStream_t s, const ReactionPlan &P, double *d_r)
     ReactionArgs A;
     A.ip = P.d_ip; A.ix = P.d_ix; A.tperm = P.d_tperm;
     A.M = P.d_M; A.D = P.d_D; A.data = P.d_data; A.v = P.d_v; A.zeta = P.d_zeta; A.bc = P.d_bc;
-    A.n1 = P.n1; A.nnz = P.nnz; A.n_t = P.n_t; A.cn = P.CN;
-    A.lo = P.lo; A.nl = P.nl; A.v_l0 = P.v_l0; A.z_l0 = P.z_l0; A.D_l0 = P.D_l0;
+    A.n1 = P.n1; A.nnz = P.nnz; A.n_t = P.w.n_t; A.cn = P.w.CN;
+    A.lo = P.w.lo; A.nl = P.w.nl; A.v_l0 = P.w.v_l0; A.z_l0 = P.w.z_l0; A.D_l0 = P.w.D_l0;
     A.tau = P.tau; A.beta = P.beta;
     hipLaunchKernelGGL(reaction_residual_kernel,
-                       dim3(grid_of(P.n1, REACTION_ROW_BLOCKS), 2 * P.nl), dim3(256), 0, s, A,
+                       dim3(grid_of(P.n1, REACTION_ROW_BLOCKS), 2 * P.w.nl), dim3(256), 0, s, A,
                        d_r);
 }
 
@@ -326,9 +326,9 @@ __global__ __launch_bounds__(256) void reaction_rhs_kernel(const double *__restr
 }
 
 void launch_reaction_rhs(hipStream_t s, const ReactionPlan &P, const double *d_r, double *d_b) {
-    const int64_t n = 2 * (int64_t)P.nl * P.n1;
+    const int64_t n = 2 * (int64_t)P.w.nl * P.n1;
     hipLaunchKernelGGL(reaction_rhs_kernel, dim3(grid_of(n, REACTION_VECTOR_BLOCKS)),
-                       dim3(256), 0, s, d_r, d_b, P.m, P.lo, P.nl, P.n1, P.d_rhalo,
+                       dim3(256), 0, s, d_r, d_b, P.w.m, P.w.lo, P.w.nl, P.n1, P.d_rhalo,
                        P.d_rhalo ? P.d_rhalo + P.n1 : nullptr);
 }
 
@@ -362,11 +362,11 @@ __global__ __launch_bounds__(256) void reaction_update_kernel(double *__restrict
 }
 
 void launch_reaction_update(hipStream_t s, const ReactionPlan &P, double *d_u) {
-    const int64_t n = (2 * (int64_t)P.nl + (P.z_halo ? 1 : 0)) * P.n1;
+    const int64_t n = (2 * (int64_t)P.w.nl + (int)P.w.z_halo) * P.n1;
     hipLaunchKernelGGL(reaction_update_kernel, dim3(grid_of(n, REACTION_VECTOR_BLOCKS)),
-                       dim3(256), 0, s, d_u, P.d_v + (int64_t)(P.lo - P.v_l0) * P.n1,
-                       P.d_zeta + (int64_t)(P.lo - P.z_l0) * P.n1, P.d_bc, P.nl, P.n1, (int)P.CN,
-                       (int)P.z_halo);
+                       dim3(256), 0, s, d_u, P.d_v + (int64_t)(P.w.lo - P.w.v_l0) * P.n1,
+                       P.d_zeta + (int64_t)(P.w.lo - P.w.z_l0) * P.n1, P.d_bc, P.w.nl, P.n1,
+                       (int)P.w.CN, (int)P.w.z_halo);
 }
 
 }  // namespace kkt

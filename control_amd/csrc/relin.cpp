@@ -3,7 +3,6 @@
 // composition: compose.hpp.
 #include "relin.hpp"
 
-#include <algorithm>
 #include <string>
 
 #include "comm.hpp"
@@ -45,9 +44,9 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     check_range(api + "bc_idx", d->bc_idx, d->n_bc, nv);
 
     auto P = std::make_unique<RelinPlan>();
-    P->n_t = d->n_t;
-    P->m = m;
-    P->CN = d->cn != 0;
+    // the rank's block rows and the level windows its rows read
+    P->w = level_windows(d->n_t, d->cn != 0, S.sharded ? S.lo : 0, S.sharded ? S.hi : m);
+    const LevelWindows &w = P->w;
     P->ne = d->ne;
     P->n2 = d->n2;
     P->n1 = d->n1;
@@ -57,25 +56,6 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     P->nu = d->nu;
     P->tau = d->tau;
     P->beta = d->beta;
-    // the rank's block rows and the level windows its rows read (relin.hpp)
-    const int lo = S.sharded ? S.lo : 0, hi = S.sharded ? S.hi : m, nl = hi - lo;
-    P->lo = lo;
-    P->nl = nl;
-    if (P->CN) {
-        P->v_l0 = P->z_l0 = P->D_l0 = lo;
-        P->v_n = P->z_n = P->D_n = nl + 1;
-        P->v_halo = lo > 0;
-        P->z_halo = hi < m;
-    } else {
-        P->v_halo = lo > 0;
-        P->z_halo = hi < m;
-        P->v_l0 = lo - (P->v_halo ? 1 : 0);
-        P->v_n = hi - P->v_l0;
-        P->z_l0 = lo;
-        P->z_n = nl + (P->z_halo ? 1 : 0);
-        P->D_l0 = lo;
-        P->D_n = nl;
-    }
     const int64_t ne = d->ne, nq = RELIN_NQ;
     P->d_V = P->mem.upload(d->V, ne * 6);
     P->d_W = P->mem.upload(d->W, ne * nq);
@@ -114,39 +94,33 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     P->d_BTip = P->mem.upload(tip.data(), nv + 1);
     P->d_BTix = P->mem.upload(tix.data(), nb);
     P->d_BTv = P->mem.upload(tv.data(), nb);
-    std::vector<uint8_t> bc(nv, 0);
-    for (int64_t k = 0; k < d->n_bc; ++k) bc[d->bc_idx[k]] = 1;
-    P->d_bc = P->mem.upload(bc.data(), nv);
-    // the data rows of the owned blocks: lo..hi-1 of the adjoint rows, m+lo..m+hi-1 of the state rows
-    P->d_data = P->mem.alloc<double>(2 * (int64_t)nl * nv);
-    for (int f = 0; f < 2; ++f)
-        HIPCHK(hipMemcpy(P->d_data + (int64_t)f * nl * nv, d->data + ((int64_t)f * m + lo) * nv,
-                         (int64_t)nl * nv * 8, hipMemcpyHostToDevice));
-    if (S.sharded && P->CN) {
+    P->d_bc = upload_bc_mask(P->mem, d->bc_idx, d->n_bc, nv);
+    P->d_data = upload_data_rows(P->mem, w, d->data, nv);
+    if (S.sharded && w.CN) {
         P->d_rhalo = P->mem.alloc<double>(2 * nv + 2 * d->n1);
         HIPCHK(hipMemset(P->d_rhalo, 0, (2 * nv + 2 * d->n1) * 8));
     }
-    P->d_Ev = P->mem.alloc<double>(ne * RELIN_EV * P->D_n);
-    P->d_Ep = P->mem.alloc<double>(ne * RELIN_EP * P->D_n);
-    P->d_D2 = P->mem.alloc<double>(d->nnz2 * P->D_n);
-    P->d_Dp = P->mem.alloc<double>(d->nnz1 * P->D_n);
-    P->d_v = P->mem.alloc<double>(P->v_n * nv);
-    P->d_zeta = P->mem.alloc<double>(P->z_n * nv);
-    P->d_p = P->mem.alloc<double>((int64_t)nl * d->n1);
-    P->d_mu = P->mem.alloc<double>((int64_t)nl * d->n1);
-    HIPCHK(hipMemset(P->d_v, 0, P->v_n * nv * 8));
-    HIPCHK(hipMemset(P->d_zeta, 0, P->z_n * nv * 8));
-    HIPCHK(hipMemset(P->d_p, 0, nl * d->n1 * 8));
-    HIPCHK(hipMemset(P->d_mu, 0, nl * d->n1 * 8));
+    P->d_Ev = P->mem.alloc<double>(ne * RELIN_EV * w.D_n);
+    P->d_Ep = P->mem.alloc<double>(ne * RELIN_EP * w.D_n);
+    P->d_D2 = P->mem.alloc<double>(d->nnz2 * w.D_n);
+    P->d_Dp = P->mem.alloc<double>(d->nnz1 * w.D_n);
+    P->d_v = P->mem.alloc<double>(w.v_n * nv);
+    P->d_zeta = P->mem.alloc<double>(w.z_n * nv);
+    P->d_p = P->mem.alloc<double>(w.nl * d->n1);
+    P->d_mu = P->mem.alloc<double>(w.nl * d->n1);
+    HIPCHK(hipMemset(P->d_v, 0, w.v_n * nv * 8));
+    HIPCHK(hipMemset(P->d_zeta, 0, w.z_n * nv * 8));
+    HIPCHK(hipMemset(P->d_p, 0, w.nl * d->n1 * 8));
+    HIPCHK(hipMemset(P->d_mu, 0, w.nl * d->n1 * 8));
     P->d_red = P->mem.alloc<double>((size_t)REDUCE_BLOCKS * MDOT_MAX + 2);
     P->compose.n_t = d->n_t;
     using I32 = std::vector<int32_t>;
     P->compose.spaces = {
         {"velocity", I32(d->v_indptr, d->v_indptr + d->n2 + 1),
-         I32(d->v_indices, d->v_indices + d->nnz2), d->nnz2, 2, P->d_D2, P->D_l0, P->D_n, P->d_M2,
+         I32(d->v_indices, d->v_indices + d->nnz2), d->nnz2, 2, P->d_D2, w.D_l0, w.D_n, P->d_M2,
          P->d_t2},
         {"pressure", I32(d->p_indptr, d->p_indptr + d->n1 + 1),
-         I32(d->p_indices, d->p_indices + d->nnz1), d->nnz1, 1, P->d_Dp, P->D_l0, P->D_n, P->d_Mp,
+         I32(d->p_indices, d->p_indices + d->nnz1), d->nnz1, 1, P->d_Dp, w.D_l0, w.D_n, P->d_Mp,
          P->d_tp}};
     S.relin = std::move(P);
 }
@@ -156,34 +130,16 @@ static RelinPlan &plan_of(System &S) {
     return *S.relin;
 }
 
-// One level of v up and one of zeta down, after the update and before the assembly: v of my
-// last block (BE level hi - 1, CN level hi) is the first level of the window above, zeta of my
-// first block the last level of the window below.  Levels are contiguous: nothing is packed.
-void relin_exchange(System &S) {
-    RelinPlan &P = plan_of(S);
-    if (!S.sharded) return;
-    if (!S.comm) fail(KKT_ERR_STATE, "time-sharded system without a transport");
-    const int up = P.z_halo ? S.rank + 1 : -1, dn = P.v_halo ? S.rank - 1 : -1;
-    const int v_last = P.lo + P.nl - 1 + (P.CN ? 1 : 0);
-    S.comm->sendrecv(P.d_v + (int64_t)(v_last - P.v_l0) * P.nv, P.nv, up, P.d_v, P.nv, dn, S.stream);
-    S.comm->sendrecv(P.d_zeta, P.nv, dn, P.d_zeta + (int64_t)(P.z_n - 1) * P.nv, P.nv, up,
-                     S.stream);
-}
-
 void relin_apply(System &T, System &PS, const double *d_v, int n, const kkt_relin_recipe *rec) {
     RelinPlan &P = plan_of(PS);
-    if (n < 0 || (n > 0 && !rec)) fail(KKT_ERR_ARG, "kkt_relinearise_device: bad recipe list");
-    if (T.device != PS.device) fail(KKT_ERR_ARG, "kkt_relinearise_device: plan on another device");
-    if (!T.finalized) fail(KKT_ERR_ARG, "kkt_relinearise_device: the target must be finalized");
-    if (T.sharded != PS.sharded || (T.sharded && (T.lo != PS.lo || T.hi != PS.hi)))
-        fail(KKT_ERR_ARG, "kkt_relinearise_device: the target is not sharded as the plan's handle");
+    check_apply_target("kkt_relinearise_device", T, PS, n, rec);
     if (d_v && PS.sharded && d_v != P.d_v)
         fail(KKT_ERR_ARG, "kkt_relinearise_device: a time shard assembles at the plan's iterate "
                           "(kkt_picard_iterate)");
     // every recipe is validated before anything is written
     std::vector<ComposeJob> jobs = compose_jobs("kkt_relinearise_device", T, P.compose, n, rec);
     if (d_v) {
-        relin_exchange(PS);
+        exchange_iterate_halos(PS, P.w, P.d_v, P.d_zeta, P.nv);
         launch_relin_elements(PS.stream, P, d_v);
         launch_relin_gather(PS.stream, P);
         HIPCHK(hipGetLastError());
@@ -195,35 +151,21 @@ void relin_apply(System &T, System &PS, const double *d_v, int n, const kkt_reli
     compose_run(T, P.compose, jobs, rec);
 }
 
-// Host arrays of the global shapes.  Upload: the rank's windows, halo levels included.
-// Download: the levels the rank owns (BE: v, zeta of its blocks; CN: v one level up), and the
-// fixed levels -- CN's v_0, zeta of the last level -- on the rank whose window holds them; the
-// rest of the host arrays is left as it is.
+// Host arrays of the global shapes: v and zeta by iterate_spans, p and mu the owned blocks' both
+// ways.
 void relin_state(System &S, int download, double *v, double *zeta, double *p, double *mu) {
     RelinPlan &P = plan_of(S);
-    const int hi = P.lo + P.nl;
-    int v0 = P.v_l0, v1 = P.v_l0 + P.v_n, z0 = P.z_l0, z1 = P.z_l0 + P.z_n;
-    if (download) {
-        v0 = P.CN ? (P.lo == 0 ? 0 : P.lo + 1) : P.lo;
-        v1 = P.CN ? hi + 1 : hi;
-        z1 = P.CN && hi == P.m ? hi + 1 : hi;
-    }
-    const int64_t rows = (int64_t)P.nl * P.n1;
-    copy_spans(S.stream, download != 0,
-               {{P.d_v + (int64_t)(v0 - P.v_l0) * P.nv, v ? v + (int64_t)v0 * P.nv : nullptr,
-                 (v1 - v0) * P.nv},
-                {P.d_zeta + (int64_t)(z0 - P.z_l0) * P.nv,
-                 zeta ? zeta + (int64_t)z0 * P.nv : nullptr, (z1 - z0) * P.nv},
-                {P.d_p, p ? p + (int64_t)P.lo * P.n1 : nullptr, rows},
-                {P.d_mu, mu ? mu + (int64_t)P.lo * P.n1 : nullptr, rows}});
+    const int64_t rows = P.w.nl * P.n1, at = P.w.lo * P.n1;
+    auto spans = iterate_spans(P.w, download != 0, P.d_v, P.d_zeta, v, zeta, P.nv);
+    spans.push_back({P.d_p, p ? p + at : nullptr, rows});
+    spans.push_back({P.d_mu, mu ? mu + at : nullptr, rows});
+    copy_spans(S.stream, download != 0, spans);
 }
 
 void relin_window(System &S, int out[8]) {
     RelinPlan &P = plan_of(S);
     if (!out) fail(KKT_ERR_ARG, "kkt_picard_window: null argument");
-    const int w[8] = {P.v_l0, P.v_l0 + P.v_n, P.z_l0, P.z_l0 + P.z_n, P.D_l0, P.D_l0 + P.D_n,
-                      P.lo, P.lo + P.nl};
-    std::copy(w, w + 8, out);
+    P.w.report(out);
 }
 
 void relin_iterate(System &S, double **v, double **zeta, double **p, double **mu) {
@@ -241,11 +183,11 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
     double *r = rhs ? raw_rows(S) : d_out;
     launch_relin_residual(S.stream, P, r);
     launch_residual_norm(S, r, P.d_red);
-    if (rhs && S.sharded && P.CN) {
+    if (rhs && S.sharded && P.w.CN) {
         // the raw rows the time transforms read across the shard boundary (the pattern of
         // comm_exchange_row_halos): T_1 families send their first row down, T_2 their last up
-        const int up = P.z_halo ? S.rank + 1 : -1, dn = P.v_halo ? S.rank - 1 : -1;
-        const int64_t nv = P.nv, n1 = P.n1, nl = P.nl;
+        const int up = P.w.up(S.rank), dn = P.w.dn(S.rank);
+        const int64_t nv = P.nv, n1 = P.n1, nl = P.w.nl;
         double *rp = r + 2 * nl * nv, *h = P.d_rhalo;
         S.comm->sendrecv(r, nv, dn, h, nv, up, S.stream);
         S.comm->sendrecv(r + (2 * nl - 1) * nv, nv, up, h + nv, nv, dn, S.stream);
@@ -258,15 +200,11 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
 
 void relin_debug_array(System &S, int which, double *out, int64_t cap) {
     RelinPlan &P = plan_of(S);
-    if (which < 0 || which > 5) fail(KKT_ERR_ARG, "kkt_debug_relin_array: no such array");
-    if (which < 4 && !P.assembled)
-        fail(KKT_ERR_STATE, "kkt_debug_relin_array: nothing assembled yet");
-    const double *src[6] = {P.d_Ev, P.d_Ep, P.d_D2, P.d_Dp, P.d_v, P.d_zeta};
-    const int64_t per_level[6] = {P.ne * RELIN_EV, P.ne * RELIN_EP, P.nnz2, P.nnz1, P.nv, P.nv};
-    const int64_t n = per_level[which] * (which < 4 ? P.D_n : which == 4 ? P.v_n : P.z_n);
-    if (!out || cap < n) fail(KKT_ERR_ARG, "kkt_debug_relin_array: buffer too small");
-    HIPCHK(hipStreamSynchronize(S.stream));
-    HIPCHK(hipMemcpy(out, src[which], n * 8, hipMemcpyDeviceToHost));
+    const std::vector<DebugArray> arrays = {
+        {P.d_Ev, P.ne * RELIN_EV, P.w.D_n, true}, {P.d_Ep, P.ne * RELIN_EP, P.w.D_n, true},
+        {P.d_D2, P.nnz2, P.w.D_n, true}, {P.d_Dp, P.nnz1, P.w.D_n, true},
+        {P.d_v, P.nv, P.w.v_n, false}, {P.d_zeta, P.nv, P.w.z_n, false}};
+    copy_debug_array("kkt_debug_relin_array", S, arrays, P.assembled, which, out, cap);
 }
 
 void relin_update(System &S, double *d_u) {

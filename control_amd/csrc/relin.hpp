@@ -14,17 +14,9 @@ namespace kkt {
 struct System;
 
 struct RelinPlan {
-    int n_t = 0, m = 0;   // global: time levels, unknown blocks per family
-    bool CN = false;
-    // Level windows.  The rank owns the block rows [lo, lo + nl) of both families (one rank: all
-    // m) and holds the levels its rows read: v from level v_l0 (v_n of them), zeta from z_l0, D
-    // and the element matrices from D_l0; p, mu and the data rows are the owned blocks'.
-    //   BE  v [lo - 1, hi)   zeta [lo, hi]   D [lo, hi)    (level -1 and level n_t do not exist)
-    //   CN  v [lo, hi]       zeta [lo, hi]   D [lo, hi]
-    // The levels outside the rank's own are halos: v's first from the rank below, zeta's last
-    // from the rank above (relin_exchange), CN's D_lo assembled here from the halo v.
-    int lo = 0, nl = 0, v_l0 = 0, v_n = 0, z_l0 = 0, z_n = 0, D_l0 = 0, D_n = 0;
-    bool v_halo = false, z_halo = false;   // the first v / last zeta level belongs to a neighbour
+    // n_t, m, CN, the rank's block rows and the levels of v, zeta and D it holds (levels.hpp); p,
+    // mu and the data rows are the owned blocks'
+    LevelWindows w;
     int64_t ne = 0, n2 = 0, n1 = 0, nv = 0, nnz2 = 0, nnz1 = 0;
     double nu = 0.0, tau = 0.0, beta = 0.0;
     DevPool mem;   // everything below but the job table
@@ -77,7 +69,5 @@ void relin_update(System &S, double *d_u);
 void relin_debug_array(System &S, int which, double *out, int64_t cap);
 // kkt_picard_window: [v_l0, v_end, z_l0, z_end, D_l0, D_end, lo, hi), half-open ranges
 void relin_window(System &S, int out[8]);
-// the iterate's halo levels from the neighbour ranks (a time shard; one rank: nothing)
-void relin_exchange(System &S);
 
 }  // namespace kkt

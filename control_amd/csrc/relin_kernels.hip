@@ -88,9 +88,9 @@ __global__ __launch_bounds__(256) void relin_elements_kernel(
 
 // d_v: the v window; slot s of the D window takes its wind from level D_l0 + s of it
 void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v) {
-    hipLaunchKernelGGL(relin_elements_kernel, dim3(grid_of(P.ne * P.D_n, 256 * 64)), dim3(256),
-                       0, s, d_v + (int64_t)(P.D_l0 - P.v_l0) * P.nv, P.ne, P.n2, P.D_n, P.d_V,
-                       P.d_W, P.d_phi, P.d_gphi, P.d_lam, P.d_glam, P.d_Ev, P.d_Ep);
+    hipLaunchKernelGGL(relin_elements_kernel, dim3(grid_of(P.ne * P.w.D_n, 256 * 64)), dim3(256),
+                       0, s, d_v + (int64_t)(P.w.D_l0 - P.w.v_l0) * P.nv, P.ne, P.n2, P.w.D_n,
+                       P.d_V, P.d_W, P.d_phi, P.d_gphi, P.d_lam, P.d_glam, P.d_Ev, P.d_Ep);
 }
 
 // One thread per (stored position, level): the contributions in ascending element-entry order
@@ -115,12 +115,12 @@ __global__ __launch_bounds__(256) void relin_gather_kernel(
 }
 
 void launch_relin_gather(hipStream_t s, const RelinPlan &P) {
-    hipLaunchKernelGGL(relin_gather_kernel, dim3(grid_of(P.nnz2 * P.D_n, 256 * 64)), dim3(256),
+    hipLaunchKernelGGL(relin_gather_kernel, dim3(grid_of(P.nnz2 * P.w.D_n, 256 * 64)), dim3(256),
                        0, s, P.d_cptr2, P.d_clist2, P.d_Ev, P.ne * RELIN_EV, P.d_K2, P.nu, P.nnz2,
-                       P.D_n, P.d_D2);
-    hipLaunchKernelGGL(relin_gather_kernel, dim3(grid_of(P.nnz1 * P.D_n, 256 * 64)), dim3(256),
+                       P.w.D_n, P.d_D2);
+    hipLaunchKernelGGL(relin_gather_kernel, dim3(grid_of(P.nnz1 * P.w.D_n, 256 * 64)), dim3(256),
                        0, s, P.d_cptrp, P.d_clistp, P.d_Ep, P.ne * RELIN_EP, P.d_Kp, P.nu, P.nnz1,
-                       P.D_n, P.d_Dp);
+                       P.w.D_n, P.d_Dp);
 }
 
 // the same kernel under the same grid rule for one pattern of another plan (reaction.cpp)
@@ -260,18 +260,18 @@ static RelinArgs relin_args(const RelinPlan &P) {
     A.M2 = P.d_M2; A.D2 = P.d_D2; A.Bv = P.d_Bv; A.BTv = P.d_BTv; A.data = P.d_data;
     A.v = P.d_v; A.zeta = P.d_zeta; A.p = P.d_p; A.mu = P.d_mu; A.bc = P.d_bc;
     A.n2 = P.n2; A.nv = P.nv; A.n1 = P.n1; A.nnz2 = P.nnz2;
-    A.n_t = P.n_t; A.m = P.m; A.cn = P.CN;
-    A.lo = P.lo; A.nl = P.nl; A.v_l0 = P.v_l0; A.z_l0 = P.z_l0; A.D_l0 = P.D_l0;
+    A.n_t = P.w.n_t; A.m = P.w.m; A.cn = P.w.CN;
+    A.lo = P.w.lo; A.nl = P.w.nl; A.v_l0 = P.w.v_l0; A.z_l0 = P.w.z_l0; A.D_l0 = P.w.D_l0;
     A.tau = P.tau; A.beta = P.beta;
     return A;
 }
 
 void launch_relin_residual(hipStream_t s, const RelinPlan &P, double *d_r) {
     const RelinArgs A = relin_args(P);
-    hipLaunchKernelGGL(relin_residual_v_kernel, dim3(grid_of(P.nv, 512), 2 * P.nl), dim3(256), 0,
+    hipLaunchKernelGGL(relin_residual_v_kernel, dim3(grid_of(P.nv, 512), 2 * P.w.nl), dim3(256), 0,
                        s, A, d_r);
-    hipLaunchKernelGGL(relin_residual_p_kernel, dim3(grid_of(P.n1, 512), 2 * P.nl), dim3(256), 0,
-                       s, A, d_r + 2 * (int64_t)P.nl * P.nv);
+    hipLaunchKernelGGL(relin_residual_p_kernel, dim3(grid_of(P.n1, 512), 2 * P.w.nl), dim3(256), 0,
+                       s, A, d_r + 2 * (int64_t)P.w.nl * P.nv);
 }
 
 // b from r: velocity rows as they are, pressure rows times tau; CN: T_1 on the adjoint rows and
@@ -315,14 +315,14 @@ __global__ __launch_bounds__(256) void relin_rhs_kernel(const double *__restrict
 }
 
 void launch_relin_rhs(hipStream_t s, const RelinPlan &P, const double *d_r, double *d_b) {
-    const int64_t n = 2 * P.nl * (P.nv + P.n1);
+    const int64_t n = 2 * P.w.nl * (P.nv + P.n1);
     RhsHalo H;
     H.h[0][0] = P.d_rhalo;
     H.h[0][1] = P.d_rhalo + P.nv;
     H.h[1][0] = P.d_rhalo + 2 * P.nv;
     H.h[1][1] = P.d_rhalo + 2 * P.nv + P.n1;
-    hipLaunchKernelGGL(relin_rhs_kernel, dim3(grid_of(n, 256 * 8)), dim3(256), 0, s, d_r, d_b, P.m,
-                       P.lo, P.nl, P.nv, P.n1, (int)P.CN, P.tau, H);
+    hipLaunchKernelGGL(relin_rhs_kernel, dim3(grid_of(n, 256 * 8)), dim3(256), 0, s, d_r, d_b,
+                       P.w.m, P.w.lo, P.w.nl, P.nv, P.n1, (int)P.w.CN, P.tau, H);
 }
 
 __global__ __launch_bounds__(256) void relin_update_kernel(double *__restrict__ u,
@@ -361,13 +361,13 @@ __global__ __launch_bounds__(256) void relin_zero_bc_kernel(double *__restrict__
 
 // the kernel's block rows are the rank's own: v and zeta are passed from the slot of level lo
 void launch_relin_update(hipStream_t s, const RelinPlan &P, double *d_u) {
-    const int64_t n = 2 * P.nl * (P.nv + P.n1);
+    const int64_t n = 2 * P.w.nl * (P.nv + P.n1);
     hipLaunchKernelGGL(relin_update_kernel, dim3(grid_of(n, 256 * 8)), dim3(256), 0, s, d_u,
-                       P.d_v + (int64_t)(P.lo - P.v_l0) * P.nv,
-                       P.d_zeta + (int64_t)(P.lo - P.z_l0) * P.nv, P.d_mu, P.d_p, P.nl, P.nv, P.n1,
-                       (int)P.CN);
-    hipLaunchKernelGGL(relin_zero_bc_kernel, dim3(grid_of(P.z_n * P.nv, 256 * 8)), dim3(256), 0, s,
-                       P.d_zeta, P.d_bc, P.z_n * P.nv, P.nv);
+                       P.d_v + (int64_t)(P.w.lo - P.w.v_l0) * P.nv,
+                       P.d_zeta + (int64_t)(P.w.lo - P.w.z_l0) * P.nv, P.d_mu, P.d_p, P.w.nl, P.nv,
+                       P.n1, (int)P.w.CN);
+    hipLaunchKernelGGL(relin_zero_bc_kernel, dim3(grid_of(P.w.z_n * P.nv, 256 * 8)), dim3(256), 0,
+                       s, P.d_zeta, P.d_bc, P.w.z_n * P.nv, P.nv);
 }
 
 }  // namespace kkt

@@ -20,13 +20,11 @@ import numpy as np
 
 from . import _lib
 from .fem import ReactionTerm
-from .relinearise import (_marshal, _recipe_array, contribution_lists, device_picard_loop,
-                          device_vectors, transpose_permutation)
+from .relinearise import (DevicePlanBinding, _marshal, _recipe_array, contribution_lists,
+                          device_picard_loop, device_vectors, transpose_permutation)
 
 __all__ = ["ReactionPlan", "DeviceReaction", "device_non_linear_solve",
            "device_stationary_non_linear_solve"]
-
-_ARRAYS = ("E", "D", "v", "zeta")
 
 
 def _check(ctl, P=None, comm=None, host_allreduce=None):
@@ -129,7 +127,7 @@ def owned(recipes, lo, hi):
     return [r for r in recipes if lo <= r[1] < hi]
 
 
-class DeviceReaction:
+class DeviceReaction(DevicePlanBinding):
     """The plan on a scalar instationary (or, a stationary plan, stationary)
     ``MultiBlockSystem`` and the iterate in HBM -- a stationary plan's as one level, ``(1, n)``.
 
@@ -137,6 +135,10 @@ class DeviceReaction:
     matrices and of ``D`` (``window``), assembles, evaluates the residual of and updates those, and
     trades one level of ``v`` and one of ``zeta`` with its neighbours before every assembly;
     ``assemble``, ``residual`` and ``get_state`` are then collective."""
+
+    _SET, _WINDOW = "kkt_set_reaction_relinearisation", "kkt_reaction_window"
+    _STATE, _RESIDUAL = "kkt_reaction_state", "kkt_reaction_residual_device"
+    _UPDATE, _DEBUG = "kkt_reaction_update_device", "kkt_debug_reaction_array"
 
     def __init__(self, ctl, system, recipes=None, plan=None, host_allreduce=None):
         """``recipes``: the blocks every re-linearisation rewrites (default: the ``"inner"`` list
@@ -146,15 +148,8 @@ class DeviceReaction:
         from .blocks import (instationary_relinearisation_recipes,
                              stationary_relinearisation_recipes)
         self.plan = ReactionPlan(ctl) if plan is None else plan
-        self.ctl, self.system, self._lib = ctl, system, system._lib
-        self.host_allreduce = host_allreduce
-        d, keep = self.plan.descriptor()
-        system._ck(self._lib.kkt_set_reaction_relinearisation(system.handle, C.byref(d)))
-        del keep
-        w = (C.c_int * 8)()
-        system._ck(self._lib.kkt_reaction_window(system.handle, w))
-        #: half-open ranges of global levels held in HBM: v, zeta, D, and the owned block rows
-        self.window = {k: (w[2 * n], w[2 * n + 1]) for n, k in enumerate(("v", "zeta", "D", "blocks"))}
+        self.ctl, self.system = ctl, system
+        self._attach(system, host_allreduce)
         if recipes is None:
             p = self.plan
             recipes = owned(
@@ -163,30 +158,23 @@ class DeviceReaction:
                 *self.window["blocks"])
         self.recipes = (_recipe_array(recipes, 0), len(recipes))
 
-    def _shape(self):
-        return (self.plan.n_t, self.ctl._disc.n_dofs)
+    def _block_shapes(self):
+        """``v``, ``zeta``."""
+        return ((self.plan.n_t, self.ctl._disc.n_dofs),) * 2
+
+    def _debug_arrays(self):
+        """``kkt_debug_reaction_array``: ``"E"`` (n_t, ne, nv, nv) or ``"D"`` (n_t, nnz) of the
+        last assembly, ``"v"`` / ``"zeta"`` (n_t, n) of the iterate (``nv``: 3 nodes per triangle,
+        4 per tetrahedron) -- on a time shard the levels of ``window["D"]``, ``window["v"]`` and
+        ``window["zeta"]``, halo levels included."""
+        n, (ne, nv) = self.ctl._disc.n_dofs, self.plan.term.cells.shape
+        return {"E": ("D", (ne, nv, nv)), "D": ("D", (self.plan.term.M.nnz,)),
+                "v": ("v", (n,)), "zeta": ("zeta", (n,))}
 
     def set_state(self, v, zeta):
-        """Global arrays; a time shard takes its windows from them, halo levels included."""
-        arrs = [np.atleast_2d(np.ascontiguousarray(a, dtype=np.float64)) for a in (v, zeta)]
-        for a in arrs:
-            if a.shape != self._shape():
-                raise ValueError(f"iterate block of shape {a.shape}, expected {self._shape()}")
-        self.system._ck(self._lib.kkt_reaction_state(
-            self.system.handle, 0, *[a.ctypes.data_as(_lib.c_f64p) for a in arrs]))
-
-    def get_state(self):
-        """The whole iterate on the host.  A time shard downloads the levels it owns into zeros
-        and the ranks' arrays are summed (``host_allreduce``): every rank returns the same."""
-        out = [np.zeros(self._shape()), np.zeros(self._shape())]
-        self.system._ck(self._lib.kkt_reaction_state(
-            self.system.handle, 1, *[a.ctypes.data_as(_lib.c_f64p) for a in out]))
-        if self.window["blocks"] != (0, self.plan.m):
-            if self.host_allreduce is None:
-                raise ValueError("a time-sharded plan needs host_allreduce to gather the iterate")
-            for a in out:            # the other ranks' levels are zero here: a sum gathers
-                self.host_allreduce(a.reshape(-1), 0)
-        return out
+        """Global arrays (a stationary plan's one level may come as a vector); a time shard takes
+        its windows from them, halo levels included."""
+        super().set_state(np.atleast_2d(v), np.atleast_2d(zeta))
 
     def assemble(self):
         """Element matrices and ``D`` of every level of the D window at the device iterate's
@@ -201,30 +189,6 @@ class DeviceReaction:
         system = self.system if system is None else system
         arr, n = self.recipes if recipes is None else (_recipe_array(recipes, 0), len(recipes))
         system._ck(self._lib.kkt_reaction_relinearise(system.handle, self.system.handle, 0, n, arr))
-
-    def residual(self, d_out, rhs):
-        norm = C.c_double()
-        self.system._ck(self._lib.kkt_reaction_residual_device(self.system.handle, d_out,
-                                                               int(rhs), C.byref(norm)))
-        return norm.value
-
-    def update(self, d_u):
-        self.system._ck(self._lib.kkt_reaction_update_device(self.system.handle, d_u))
-
-    def debug_array(self, which):
-        """``kkt_debug_reaction_array``: ``"E"`` (n_t, ne, nv, nv) or ``"D"`` (n_t, nnz) of the
-        last assembly, ``"v"`` / ``"zeta"`` (n_t, n) of the iterate (``nv``: 3 nodes per triangle,
-        4 per tetrahedron) -- on a time shard the levels of ``window["D"]``, ``window["v"]`` and
-        ``window["zeta"]``, halo levels included."""
-        n = self._shape()[1]
-        ne, nv = self.plan.term.cells.shape
-        n_D, n_v, n_z = (b - a for a, b in (self.window[k] for k in ("D", "v", "zeta")))
-        shape = {"E": (n_D, ne, nv, nv), "D": (n_D, self.plan.term.M.nnz),
-                 "v": (n_v, n), "zeta": (n_z, n)}[which]
-        out = np.empty(shape)
-        self.system._ck(self._lib.kkt_debug_reaction_array(
-            self.system.handle, _ARRAYS.index(which), out.ctypes.data_as(_lib.c_f64p), out.size))
-        return out
 
 
 def build_system(ctl, backend, plan, comm=None):

@@ -19,7 +19,7 @@ from . import _lib
 from .fem import _row_positions
 
 __all__ = ["contribution_lists", "gather", "transpose_permutation", "RelinearisationPlan",
-           "DeviceRelinearisation", "device_vectors", "device_picard_loop"]
+           "DevicePlanBinding", "DeviceRelinearisation", "device_vectors", "device_picard_loop"]
 
 
 def contribution_lists(conn, pattern):
@@ -151,7 +151,68 @@ def _recipe_array(recipes, space):
     return arr
 
 
-class DeviceRelinearisation:
+class DevicePlanBinding:
+    """What the bindings of both device plans share: the plan set on its system, the ``window``
+    read-out, the iterate's way to and from the host, residual, update and the debug copies.  A
+    subclass names the library's entry points (``_SET`` ... ``_DEBUG``), gives the global shapes of
+    its iterate blocks in the state entry's order (``_block_shapes()``) and its debug arrays in the
+    library's order (``_debug_arrays()``: ``{name: (window key, shape of one level)}``), and calls
+    ``_attach`` once ``self.plan`` stands."""
+
+    def _call(self, entry, *args):
+        self._system._ck(getattr(self._lib, entry)(self._system.handle, *args))
+
+    def _attach(self, system, host_allreduce):
+        self._system, self._lib, self.host_allreduce = system, system._lib, host_allreduce
+        d, keep = self.plan.descriptor()
+        self._call(self._SET, C.byref(d))
+        del keep
+        w = (C.c_int * 8)()
+        self._call(self._WINDOW, w)
+        #: half-open ranges of global levels held in HBM: v, zeta, D, and the owned block rows
+        self.window = {k: (w[2 * n], w[2 * n + 1])
+                       for n, k in enumerate(("v", "zeta", "D", "blocks"))}
+
+    def set_state(self, *blocks):
+        """Global arrays; a time shard takes its windows from them, halo levels included."""
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in blocks]
+        for a, shape in zip(arrs, self._block_shapes()):
+            if a.shape != shape:
+                raise ValueError(f"iterate block of shape {a.shape}, expected {shape}")
+        self._call(self._STATE, 0, *[a.ctypes.data_as(_lib.c_f64p) for a in arrs])
+
+    def get_state(self):
+        """The whole iterate on the host.  A time shard downloads the levels it owns into zeros
+        and the ranks' arrays are summed (``host_allreduce``): every rank returns the same."""
+        out = [np.zeros(shape) for shape in self._block_shapes()]
+        self._call(self._STATE, 1, *[a.ctypes.data_as(_lib.c_f64p) for a in out])
+        if self.window["blocks"] != (0, self.plan.m):
+            if self.host_allreduce is None:
+                raise ValueError("a time-sharded plan needs host_allreduce to gather the iterate")
+            for a in out:            # the other ranks' levels are zero here: a sum gathers
+                self.host_allreduce(a.reshape(-1), 0)
+        return out
+
+    def residual(self, d_out, rhs):
+        norm = C.c_double()
+        self._call(self._RESIDUAL, d_out, int(rhs), C.byref(norm))
+        return norm.value
+
+    def update(self, d_u):
+        self._call(self._UPDATE, d_u)
+
+    def debug_array(self, which):
+        """The array ``which`` of ``_debug_arrays`` on the host: on a time shard the levels of its
+        window, halo levels included."""
+        table = self._debug_arrays()
+        key, per_level = table[which]
+        out = np.empty((self.window[key][1] - self.window[key][0],) + per_level)
+        self._call(self._DEBUG, list(table).index(which), out.ctypes.data_as(_lib.c_f64p),
+                   out.size)
+        return out
+
+
+class DeviceRelinearisation(DevicePlanBinding):
     """The plan on the outer system of a ``GpuLinearSolver`` and the Picard iterate in HBM.
 
     On a time-sharded outer system every rank keeps its own levels of the iterate, of the element
@@ -159,51 +220,36 @@ class DeviceRelinearisation:
     trades one level of ``v`` and one of ``zeta`` with its neighbours before every assembly;
     ``assemble``, ``residual`` and ``get_state`` are then collective."""
 
+    _SET, _WINDOW, _STATE = "kkt_set_relinearisation", "kkt_picard_window", "kkt_picard_state"
+    _RESIDUAL, _UPDATE = "kkt_picard_residual_device", "kkt_picard_update_device"
+    _DEBUG = "kkt_debug_relin_array"
+
     def __init__(self, pb, outer, recipes, plan=None, host_allreduce=None):
         """``recipes``: the blocks every re-linearisation rewrites, per system
         (``blocks.instationary_relinearisation_recipes``); on a time shard those of the rank's own
         block rows, with their global indices.  ``host_allreduce(array, op)`` (a time shard):
         what ``get_state`` gathers the iterate with."""
         self.pb, self.outer = pb, outer
-        self.host_allreduce = host_allreduce
         self.plan = RelinearisationPlan(pb) if plan is None else plan
-        self._lib = outer._lib
-        d, keep = self.plan.descriptor()
-        outer._ck(self._lib.kkt_set_relinearisation(outer.handle, C.byref(d)))
-        del keep
+        self._attach(outer, host_allreduce)
         self.recipes = {name: (_recipe_array(recipes[name], 1 if name == "commutator" else 0),
                                len(recipes[name])) for name in ("outer", "inner", "commutator")}
         ptr = [C.c_void_p() for _ in range(4)]
-        outer._ck(self._lib.kkt_picard_iterate(outer.handle, *[C.byref(p) for p in ptr]))
+        self._call("kkt_picard_iterate", *[C.byref(p) for p in ptr])
         self.d_v = ptr[0]
-        w = (C.c_int * 8)()
-        outer._ck(self._lib.kkt_picard_window(outer.handle, w))
-        #: half-open ranges of global levels held in HBM: v, zeta, D, and the owned block rows
-        self.window = {k: (w[2 * n], w[2 * n + 1]) for n, k in enumerate(("v", "zeta", "D", "blocks"))}
 
-    def set_state(self, v, zeta, p, mu):
+    def _block_shapes(self):
+        """``v``, ``zeta``, ``p``, ``mu``."""
         th, n_t, m = self.pb.disc, self.pb.n_t, self.plan.m
-        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (v, zeta, p, mu)]
-        for a, shape in zip(arrs, ((n_t, th.n_v), (n_t, th.n_v), (m, th.n_p), (m, th.n_p))):
-            if a.shape != shape:
-                raise ValueError(f"iterate block of shape {a.shape}, expected {shape}")
-        self.outer._ck(self._lib.kkt_picard_state(self.outer.handle, 0,
-                                                  *[a.ctypes.data_as(_lib.c_f64p) for a in arrs]))
+        return (n_t, th.n_v), (n_t, th.n_v), (m, th.n_p), (m, th.n_p)
 
-    def get_state(self):
-        """The whole iterate on the host.  A time shard downloads the levels it owns into zeros
-        and the ranks' arrays are summed (``host_allreduce``): every rank returns the same."""
-        th, pb, m = self.pb.disc, self.pb, self.plan.m
-        out = [np.zeros((pb.n_t, th.n_v)), np.zeros((pb.n_t, th.n_v)), np.zeros((m, th.n_p)),
-               np.zeros((m, th.n_p))]
-        self.outer._ck(self._lib.kkt_picard_state(self.outer.handle, 1,
-                                                  *[a.ctypes.data_as(_lib.c_f64p) for a in out]))
-        if self.window["blocks"] != (0, m):
-            if self.host_allreduce is None:
-                raise ValueError("a time-sharded plan needs host_allreduce to gather the iterate")
-            for a in out:            # the other ranks' levels are zero here: a sum gathers
-                self.host_allreduce(a.reshape(-1), 0)
-        return out
+    def _debug_arrays(self):
+        """``kkt_debug_relin_array``: ``"Ev"`` (n_t, ne, 6, 6), ``"Ep"`` (n_t, ne, 3, 3), ``"D2"``
+        (n_t, nnz2) or ``"Dp"`` (n_t, nnz1) of the last assembly -- on a time shard the levels of
+        ``window["D"]``; ``"v"`` / ``"zeta"``: the iterate's windows, halo levels included."""
+        ne, n_v = len(self.plan.V), self.pb.disc.n_v
+        return {"Ev": ("D", (ne, 6, 6)), "Ep": ("D", (ne, 3, 3)), "D2": ("D", (self.plan.K2.nnz,)),
+                "Dp": ("D", (self.plan.Kp.nnz,)), "v": ("v", (n_v,)), "zeta": ("zeta", (n_v,))}
 
     def assemble(self):
         """D_v, D_p of every level of the D window at the device iterate's v (a time shard first
@@ -219,29 +265,6 @@ class DeviceRelinearisation:
         if recipes is not None:
             arr, n = _recipe_array(recipes, 1 if name == "commutator" else 0), len(recipes)
         system._ck(self._lib.kkt_relinearise_device(system.handle, self.outer.handle, None, n, arr))
-
-    def residual(self, d_out, rhs):
-        norm = C.c_double()
-        self.outer._ck(self._lib.kkt_picard_residual_device(self.outer.handle, d_out, int(rhs),
-                                                            C.byref(norm)))
-        return norm.value
-
-    def update(self, d_u):
-        self.outer._ck(self._lib.kkt_picard_update_device(self.outer.handle, d_u))
-
-    def debug_array(self, which):
-        """``kkt_debug_relin_array``: ``"Ev"`` (n_t, ne, 6, 6), ``"Ep"`` (n_t, ne, 3, 3), ``"D2"``
-        (n_t, nnz2) or ``"Dp"`` (n_t, nnz1) of the last assembly -- on a time shard the levels of
-        ``window["D"]``; ``"v"`` / ``"zeta"``: the iterate's windows, halo levels included."""
-        ne, n_v = len(self.plan.V), self.pb.disc.n_v
-        n_D, n_v_lev, n_z_lev = (b - a for a, b in (self.window[k] for k in ("D", "v", "zeta")))
-        shape = {"Ev": (n_D, ne, 6, 6), "Ep": (n_D, ne, 3, 3), "D2": (n_D, self.plan.K2.nnz),
-                 "Dp": (n_D, self.plan.Kp.nnz), "v": (n_v_lev, n_v), "zeta": (n_z_lev, n_v)}[which]
-        out = np.empty(shape)
-        self.outer._ck(self._lib.kkt_debug_relin_array(
-            self.outer.handle, ("Ev", "Ep", "D2", "Dp", "v", "zeta").index(which),
-            out.ctypes.data_as(_lib.c_f64p), out.size))
-        return out
 
 
 @contextlib.contextmanager

@@ -11,6 +11,8 @@ import sys
 
 import pytest
 
+from control_amd.dist import shard_range
+
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -74,13 +76,6 @@ def results(world, CN, target="run_rank_kernels"):
     if isinstance(_cache[key], BaseException):
         raise _cache[key]
     return _cache[key]
-
-
-def shard_range(m, rank, world):
-    """kkt_shard_range: the first m % world ranks hold one block more."""
-    base, extra = divmod(m, world)
-    lo = rank * base + min(rank, extra)
-    return lo, lo + base + (1 if rank < extra else 0)
 
 
 def check(d, *keys):
