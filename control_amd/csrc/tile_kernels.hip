@@ -105,6 +105,81 @@ __device__ __forceinline__ P uniform_ptr(P p) {
 // slot still issues an instruction per round where a branch issued none.
 constexpr int TILE_NO_POLL = 0x7ffffff0;
 
+// ---- the local parts of a coarse exchange (two-grid variants only).  Each is a handful of flops
+// behind LDS reads that depend on each other -- offsets, then indices, then operands -- so what it
+// costs is round trips: the reads of one kind are issued together and the add / fma chain comes
+// last.  The chains themselves are unchanged: same operands, same order, from +0.0.  A short row
+// is predicated, never padded (+0.0 and fma(0, x, a) are no identities for -0.0, infinities and
+// NaN); its dead reads go to an index that exists -- and they are not free: where most of a
+// group's reads would be dead (restriction lists, a thread's second function or row) the plain
+// loop stayed, by the exchange stamps (profiles/exchange_chains.md).
+
+// Lane 0's value of the xor butterfly 32, 16, ..., 1 (`a += __shfl_xor(a, o)`), which is all that
+// is published: lane 0 only ever takes the partner above it, a[i] + a[i + o] on lanes i < o, and
+// the addition commutes exactly.  Register moves across lanes instead of twelve trips through the
+// LDS crossbar: half-wave and row swaps for 32 and 16, row shifts (DPP) for 8 to 1.  Other lanes
+// end with values that mean nothing.
+__device__ __forceinline__ double wave_sum_lane0(double a) {
+    auto halves = [](const double x, unsigned &lo, unsigned &hi) {
+        const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+        lo = (unsigned)b;
+        hi = (unsigned)(b >> 32);
+    };
+    auto whole = [](const unsigned lo, const unsigned hi) {
+        return __longlong_as_double((long long)((unsigned long long)lo | ((unsigned long long)hi << 32)));
+    };
+    unsigned lo, hi;
+    halves(a, lo, hi);
+    {   // lanes 32-63 of the first operand change places with lanes 0-31 of the second
+        const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        a = whole(l[0], h[0]) + whole(l[1], h[1]);
+    }
+    halves(a, lo, hi);
+    {   // odd rows of the first operand change places with even rows of the second
+        const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        a = whole(l[0], h[0]) + whole(l[1], h[1]);
+    }
+#define KKT_ROW_SHL(n)                                                                          \
+    {                                                                                           \
+        halves(a, lo, hi);                                                                      \
+        const unsigned l = (unsigned)__builtin_amdgcn_update_dpp(0, (int)lo, 0x100 + (n), 0xf, 0xf, true); \
+        const unsigned h = (unsigned)__builtin_amdgcn_update_dpp(0, (int)hi, 0x100 + (n), 0xf, 0xf, true); \
+        a += whole(l, h);                                                                       \
+    }
+    KKT_ROW_SHL(8)
+    KKT_ROW_SHL(4)
+    KKT_ROW_SHL(2)
+    KKT_ROW_SHL(1)
+#undef KKT_ROW_SHL
+    return a;
+}
+
+// A row of the prolongation: the sum over the entries [e0, e1) of a row of P, in the row's order,
+// of weight times product.  Up to U entries are read together; longer rows (3-D, vector-valued
+// spaces) go on one entry at a time.
+template <int U>
+__device__ __forceinline__ double prolong_row(const int e0, const int e1, const uint16_t *pk,
+                                              const double *pw, const double *ec) {
+    int k[U];
+    double w[U], x[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int e = e0 + u < e1 ? e0 + u : 0;
+        k[u] = pk[e];
+        w[u] = pw[e];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) x[u] = ec[k[u]];
+    double a = 0.0;
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        if (e0 + u < e1) a = __builtin_fma(w[u], x[u], a);
+    for (int e = e0 + U; e < e1; ++e) a = __builtin_fma(pw[e], ec[pk[e]], a);
+    return a;
+}
+
 // HPT_: ring-entry slots per thread of a hand-off (RPT + 1 unless the variant is short of registers)
 // COARSE: levels are cycles of [Galerkin coarse correction, `its` smoothing sweeps] (two-grid form
 // of the sub-solves); the plain variants compile none of it.
@@ -331,9 +406,11 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
         RROWc = reinterpret_cast<uint16_t *>(PIPc + (c_rings ? nkp + 1 : 0));
         PKc = RROWc + nrm;
         c_einv_cache = cd->cache_einv != 0;
-        // (8-byte aligned: behind the 2-byte lists, rounded up)
-        EINVc = reinterpret_cast<double *>(
-            (reinterpret_cast<uintptr_t>(PKc + npm) + 7) & ~(uintptr_t)7);
+        // (8-byte aligned: behind the 2-byte lists, rounded up.  As an offset from X, itself
+        // aligned: a pointer made from an integer is no longer known to point into LDS, and the
+        // rows were read and written by flat instructions)
+        EINVc = X + (static_cast<size_t>(reinterpret_cast<const char *>(PKc + npm) -
+                                         reinterpret_cast<const char *>(X)) + 7) / 8;
         const gci_p rip = (gci_p)cd->r_ip + (size_t)tile * c_jmax;
         const gci_p pip = (gci_p)cd->p_ip + (size_t)tile * c_pstride;
         // (ring form: the ring rows' entries lie behind the own rows')
@@ -391,9 +468,10 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
             sstat[slot + 3] += count;
         }
 #else
-        // -DKKT_XSTAMPS: the slots hold the parts of the coarse exchange instead
-        // (scripts/r03_exchange_stamps.py)
-        if (tid == 0 && slot == 0) sstat[3] += count;
+        // -DKKT_XSTAMPS: the slots hold the parts of the coarse exchange instead, slot 3 the
+        // prolongation (scripts/r03_exchange_stamps.py); nothing is counted
+        (void)slot;
+        (void)count;
 #endif
         t_mark = now;
     };
@@ -968,6 +1046,11 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                         const int e0 = RIPc[k], e1 = RIPc[k + 1];
                         double a = 0.0;
                         if (c_cached) {
+                            // (rows and weights of four entries of a lane read ahead of the
+                            // gathers and the chain were slower, 0.81 us against 0.66: most
+                            // lists are shorter than 64 entries, and the dead reads of the
+                            // other three cost more than the live ones gain --
+                            // profiles/exchange_chains.md)
                             for (int e = e0 + lane; e < e1; e += 64)
                                 a = __builtin_fma(RWc[e], Rb[RROWc[e]], a);
                         } else {
@@ -976,8 +1059,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                             for (int e = e0 + lane; e < e1; e += 64)
                                 a = __builtin_fma(rw[e], Rb[rrow[e]], a);
                         }
-#pragma unroll
-                        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+                        a = wave_sum_lane0(a);
                         if (lane == 0) publish(rc_, c_slot0 + k, a, cepoch);
                     }
                     // ---- every tile's partial sums ("the data is the flag"), then the coarse
@@ -1042,9 +1124,30 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                     lds_barrier();
                     KKT_XS(2);      // barrier: the slowest thread's polls
                     dead = sdead != 0;
+                    // (the offsets, then the slots of up to CU contributions, then their partial
+                    // sums, then the sum; functions with more contributions -- 3-D, vector-valued
+                    // spaces -- go on one at a time.  Two functions of a thread, j and j + T, side
+                    // by side so that a partly filled second round costs no chain of its own,
+                    // were slower, 0.83 us against 0.70: all threads then issue the reads of a
+                    // second function that 6 % of them have -- profiles/exchange_chains.md)
+                    constexpr int CU = 4;
                     for (int j = tid; j < c_nc; j += T) {
+                        const int q0 = CIPc[j], q1 = CIPc[j + 1];
+                        int cs[CU];
+                        double cp[CU];
+#pragma unroll
+                        for (int k = 0; k < CU; ++k) cs[k] = CSLc[q0 + k < q1 ? q0 + k : 0];
+#pragma unroll
+                        for (int k = 0; k < CU; ++k) cp[k] = SL[cs[k]];
+                        // (the first partial sum counts as used whatever the predicate says: the
+                        // compiler otherwise moves its two reads into a branch of their own
+                        // behind the others -- two more round trips)
+                        asm volatile("" : "+v"(cp[0]));
                         double a = 0.0;
-                        for (int q = CIPc[j]; q < CIPc[j + 1]; ++q) a += SL[CSLc[q]];
+#pragma unroll
+                        for (int k = 0; k < CU; ++k)
+                            if (q0 + k < q1) a += cp[k];
+                        for (int q = q0 + CU; q < q1; ++q) a += SL[CSLc[q]];
                         RC[j] = a;
                     }
                     lds_barrier();
@@ -1075,11 +1178,24 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                         const int j = tile + i * ntl;
                         const int lo = i == wave ? c_lo0 : elo[j], hi = i == wave ? c_hi0 : ehi[j];
                         if (c_einv_cache) {
-                            // (reading six entries ahead of the fma chain was slower: 128 its/s
-                            // against 133 -- the 1 024-thread variant has no registers to spare)
+                            // both operands of EG terms of the lane in front of their part of the
+                            // chain (a dead term reads the group's first).  (Six entries ahead
+                            // was slower while this variant kept 27 registers in scratch -- 128
+                            // its/s against 133; it has none there now, profiles/exchange_chains.md)
+                            constexpr int EG = 6;
                             const double *row = EINVc + (size_t)i * c_ew;
-                            for (int q = lo + lane; q < hi; q += 64)
-                                a = __builtin_fma(row[q - lo], RC[q], a);
+                            for (int qb = lo + lane; qb < hi; qb += 64 * EG) {
+                                double rv[EG], xc[EG];
+#pragma unroll
+                                for (int u = 0; u < EG; ++u) {
+                                    const int q = qb + 64 * u < hi ? qb + 64 * u : qb;
+                                    rv[u] = row[q - lo];
+                                    xc[u] = RC[q];
+                                }
+#pragma unroll
+                                for (int u = 0; u < EG; ++u)
+                                    if (qb + 64 * u < hi) a = __builtin_fma(rv[u], xc[u], a);
+                            }
                         } else {
                             // rows from L2: eight loads of a lane in flight before the first fma
                             const gcd_p row = einv + (size_t)j * c_nc;
@@ -1098,8 +1214,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                                 }
                             }
                         }
-#pragma unroll
-                        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+                        a = wave_sum_lane0(a);
                         if (lane == 0) publish(re_, tile + i * ntl, a, cepoch);
                     }
                     KKT_XS(5);      // owned products + publish
@@ -1148,11 +1263,13 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                         // in the order of P's row, the owners' products), so the value is the one
                         // a hand-off would fetch.  Later cycles: the hand-off in front of the
                         // residual left the current iterate on every ring.
+                        // (two rows of a thread, l and l + T, side by side were slower, as in
+                        // the coarse residual: few threads have a second row)
                         for (int l = tid; l < nk; l += T) {
-                            double a = 0.0;
-                            for (int e = PIPc[l]; e < PIPc[l + 1]; ++e)
-                                a = __builtin_fma(PWc[e], EC[PKc[e]], a);
-                            Xc[l] = cyc == 0 ? a : Xc[l] + a;
+                            const int e0 = PIPc[l], e1 = PIPc[l + 1];
+                            const double xo = Xc[l];
+                            const double a = prolong_row<4>(e0, e1, PKc, PWc, EC);
+                            Xc[l] = cyc == 0 ? a : xo + a;
                         }
                     } else {
 #pragma unroll
@@ -1161,8 +1278,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                         if (r < n0) {
                             double a = 0.0;
                             if (c_cached) {
-                                for (int e = pe0[sl]; e < pe1[sl]; ++e)
-                                    a = __builtin_fma(PWc[e], EC[PKc[e]], a);
+                                a = prolong_row<4>(pe0[sl], pe1[sl], PKc, PWc, EC);
                             } else {
                                 const gcu16_p pk = (gcu16_p)cd->p_k + c_pq0;
                                 const gcd_p pw = (gcd_p)cd->p_w + c_pq0;
@@ -1190,6 +1306,7 @@ __global__ __launch_bounds__(TMAX) void pc_tile_sweep(
                     for (int k = 0; k < W; ++k) asm volatile("" : "+v"(v[sl][k]));
                 // (the barrier inside the hand-off orders these stores before anyone's gathers)
                 lds_barrier();
+                KKT_XS(3);      // prolongation, the pin of the level matrix, barrier
                 if (stamps) {      // the coarse exchange, restriction to prolongation: slot 7
                     const unsigned long long now = wall_clock64();
                     if (tid == 0) sstat[7] += now - t_mark;

@@ -30,7 +30,12 @@ d = d[d[:, 7] > 0]
 nx = 256 * reps          # exchanges per tile
 names = {0: "restriction + publish", 1: "own polls (thread 0)", 2: "barrier after the polls",
          4: "coarse residual (sums of the partials)", 5: "owned products + publish",
-         6: "products polled + barrier", 7: "whole exchange (incl. prolongation)"}
+         6: "products polled + barrier", 3: "prolongation + matrix pin + barrier",
+         7: "whole exchange"}
+# (slot 3: builds before the prolongation had a lap of its own count hand-offs there; for them the
+# prolongation is the last line, the whole exchange less the parts in front of it)
 for c, nm in names.items():
     v = d[:, c] * 0.01 / nx
-    print(f"{nm:40s} us each: mean {v.mean():6.2f}  min {v.min():6.2f}  max {v.max():6.2f}")
+    print(f"{nm:40s} us each: mean {v.mean():6.3f}  min {v.min():6.3f}  max {v.max():6.3f}")
+v = (d[:, 7] - d[:, [0, 1, 2, 4, 5, 6]].sum(axis=1)) * 0.01 / nx
+print(f"{'whole exchange less slots 0-2, 4-6':40s} us each: mean {v.mean():6.3f}  min {v.min():6.3f}  max {v.max():6.3f}")
