@@ -326,6 +326,8 @@ SIGNATURES = {
     "kkt_debug_pc_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "kkt_debug_pc_solves": (C.c_int, [C.c_void_p, c_f64p, C.c_int]),
     "kkt_debug_pc_matrices": (C.c_int, [C.c_void_p, c_f64p, C.c_int]),
+    "kkt_debug_mass_tile_values": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                             c_f64p, c_i32p, c_f64p]),
     "kkt_get_info": (C.c_int, [C.c_void_p, C.POINTER(Info)]),
     "kkt_comm_unique_id": (C.c_int, [C.c_void_p]),
     "kkt_comm_init_rccl": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -659,6 +659,14 @@ int kkt_debug_pc_matrices(kkt_handle h, double *out, int cap) {
     });
 }
 
+int kkt_debug_mass_tile_values(kkt_handle h, int64_t *n_entries, int64_t *n_vals, double *copy,
+                               int32_t *gpos, double *vals) {
+    KKT_TRY(h, {
+        if (!S.pc) fail(KKT_ERR_STATE, "no built-in preconditioner");
+        S.pc->mass_tile_debug(n_entries, n_vals, copy, gpos, vals);
+    });
+}
+
 int kkt_get_info(kkt_handle h, kkt_info *info) {
     KKT_TRY(h, {
         if (!info) fail(KKT_ERR_ARG, "null info");

@@ -301,10 +301,11 @@ struct MassTileGroup {
 // interleaved by global row (element (row r, level l) of group g at 4 (g nx + r) + l), read from
 // the pair in_*, written to the pair out_* (another pair: other tiles read their rings from in_*).
 struct MassTileArgs {
-    const int32_t *n, *grow, *gpos;   // the plan's tables (TilePlan::d_*)
+    const int32_t *n, *grow;          // the plan's tables (TilePlan::d_*)
     const uint16_t *lcol;
     const int32_t *masked;            // the Dirichlet rows (the last launch writes their zeros)
-    const double *vals, *dinv;
+    const double *tvals;              // the matrix values in the layout of lcol (launch_mass_tile_gather)
+    const double *dinv;
     const MassTileGroup *groups;
     const double *in_new, *in_old;    // p_{s0}, p_{s0 - 1} (unused where s0 is too small)
     double *out_new, *out_old;        // p_{s0 + k}, p_{s0 + k - 1} (not the last launch)
@@ -320,6 +321,9 @@ size_t mass_tile_lds_bytes(int nk_pad);
 int mass_tile_prepare(int W, int rpt, int threads, size_t lds_bytes);
 void launch_mass_tile(hipStream_t s, const MassTileArgs &a, int ntiles, int grid_y, int rpt,
                       int threads);
+// out[i] = gpos[i] >= 0 ? vals[gpos[i]] : +0.0 for the n entries of a plan's gpos table
+void launch_mass_tile_gather(hipStream_t s, const double *vals, const int32_t *gpos, double *out,
+                             int64_t n);
 
 // ---- value-array preparation
 void launch_csr_to_sell(hipStream_t s, const double *csr_vals, const int32_t *sell2csr,

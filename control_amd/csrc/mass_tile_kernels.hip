@@ -11,7 +11,10 @@
 // launch: no spin, no co-residency requirement.
 //
 // The matrix values and local columns of the rows a thread computes stay in registers and serve
-// several level groups (the matrix is the same for every level).
+// several level groups (the matrix is the same for every level).  They come from two arrays of one
+// layout, [tile][slot][entry][T] -- the values are mass_tile_gather's copy of the value array in
+// that order -- so one round trip brings both; the tile's global rows are read once per launch
+// into LDS, and a level group's record comes by scalar loads.
 //
 // Arithmetic: per (row, level) the chain of pc_rows_il -- acc from 0 by fma over the row's entries
 // in SELL order (padding entries: value 0), then epi_cheb (epilogue.hpp) -- so results are
@@ -39,12 +42,28 @@ __device__ __forceinline__ void lds_barrier_mt() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// A level group's record, by scalar loads: the index is the same for the whole workgroup, and the
+// host wrote the records before the first launch (constant address space).
+__device__ __forceinline__ MassTileGroup mt_group(const MassTileArgs &A, const int g) {
+    typedef const __attribute__((address_space(4))) uint64_t *cu64_p;
+    constexpr int NW = sizeof(MassTileGroup) / sizeof(uint64_t);
+    static_assert(sizeof(MassTileGroup) == NW * sizeof(uint64_t), "whole words");
+    const cu64_p p = (cu64_p)(A.groups + g);
+    uint64_t w[NW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) w[i] = p[i];
+    MassTileGroup G;
+    __builtin_memcpy(&G, w, sizeof(G));
+    return G;
+}
+
 template <int W, int RPT, int T>
 __global__ __launch_bounds__(T) void pc_tile_cheb(const MassTileArgs A) {
-    extern __shared__ d4 X4[];                 // [2][nk_pad]: the two newest iterates, four levels
-    __shared__ int sn[TILE_DEPTH_MAX + 1];
+    extern __shared__ d4 X4[];                 // [2][nk_pad]: the two newest iterates, four levels;
+    __shared__ int sn[TILE_DEPTH_MAX + 1];     // behind them [nk_pad] ints: the tile's global rows
     const int tid = threadIdx.x, tile = blockIdx.x;
     const int nkp = A.nk_pad, k = A.k;
+    int *sg = (int *)(X4 + 2 * (size_t)nkp);
     const gci_p nt = (gci_p)A.n + (size_t)tile * (TILE_DEPTH_MAX + 1);
     if (tid <= TILE_DEPTH_MAX) sn[tid] = nt[tid];
     const int n0 = nt[0], nk = nt[k], nk1 = nt[k - 1];
@@ -55,6 +74,7 @@ __global__ __launch_bounds__(T) void pc_tile_cheb(const MassTileArgs A) {
         X4[2 * (size_t)nkp - 1] = zero4;
     }
     const gci_p grow = (gci_p)A.grow + (size_t)tile * nkp;
+    for (int l = tid; l < nk; l += T) sg[l] = grow[l];
     // ---- what never changes during the launch: the rows this thread computes
     double v[RPT][W], dinv[RPT];
     int col[RPT][W], gr[RPT];
@@ -62,25 +82,26 @@ __global__ __launch_bounds__(T) void pc_tile_cheb(const MassTileArgs A) {
         // (the plan's tables have its own width PW <= W: the entries behind it are padding)
         const int PW = A.W;
         const gcu16_p lcol = (gcu16_p)A.lcol + (size_t)tile * RPT * PW * T + tid;
-        const gci_p gpos = (gci_p)A.gpos + (size_t)tile * RPT * PW * T + tid;
-        const gcd_p vals = (gcd_p)A.vals, dv = (gcd_p)A.dinv;
+        const gcd_p tv = (gcd_p)A.tvals + (size_t)tile * RPT * PW * T + tid;
+        const gcd_p dv = (gcd_p)A.dinv;
 #pragma unroll
         for (int sl = 0; sl < RPT; ++sl) {
             const int r = sl * T + tid;
 #pragma unroll
             for (int e = 0; e < W; ++e) {
                 col[sl][e] = e < PW ? lcol[(size_t)(sl * PW + e) * T] : 0;
-                const int gp = e < PW ? gpos[(size_t)(sl * PW + e) * T] : -1;
-                v[sl][e] = gp >= 0 ? vals[gp] : 0.0;
+                v[sl][e] = e < PW ? tv[(size_t)(sl * PW + e) * T] : 0.0;
             }
             gr[sl] = r < nk1 ? grow[r] : -1;
-            dinv[sl] = gr[sl] >= 0 ? dv[gr[sl]] : 0.0;
         }
+#pragma unroll
+        for (int sl = 0; sl < RPT; ++sl) dinv[sl] = gr[sl] >= 0 ? dv[gr[sl]] : 0.0;
     }
+    __syncthreads();
     const int64_t nx = A.nx;
     const bool first = A.s0 == 0, last = A.last != 0;
     for (int g = blockIdx.y; g < A.ngroups; g += gridDim.y) {
-        const MassTileGroup &G = A.groups[g];
+        const MassTileGroup G = mt_group(A, g);
         const int nlev = G.nlev;
         int cur = 0;
         // ---- the two newest iterates on tile and rings; the right-hand sides on the computed rows
@@ -97,7 +118,7 @@ __global__ __launch_bounds__(T) void pc_tile_cheb(const MassTileArgs A) {
                 const gcd4_p po = (gcd4_p)A.in_old + (size_t)g * nx;
                 const bool has_old = A.s0 >= 2;
                 for (int l = tid; l < nk; l += T) {
-                    const int gl = grow[l];
+                    const int gl = sg[l];
                     Xc[l] = pn[gl];
                     Xo[l] = has_old ? po[gl] : zero4;
                 }
@@ -167,7 +188,7 @@ __global__ __launch_bounds__(T) void pc_tile_cheb(const MassTileArgs A) {
             const d4 *Xc = X4 + (size_t)cur * nkp, *Xo = X4 + (size_t)(cur ^ 1) * nkp;
             if (last) {
                 for (int l = tid; l < n0; l += T) {
-                    const int gl = grow[l];
+                    const int gl = sg[l];
                     const d4 x = Xc[l];
                     const double o[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
@@ -188,7 +209,7 @@ __global__ __launch_bounds__(T) void pc_tile_cheb(const MassTileArgs A) {
                 const gd4_p pn = (gd4_p)A.out_new + (size_t)g * nx;
                 const gd4_p po = (gd4_p)A.out_old + (size_t)g * nx;
                 for (int l = tid; l < n0; l += T) {
-                    const int gl = grow[l];
+                    const int gl = sg[l];
                     pn[gl] = Xc[l];
                     po[gl] = Xo[l];
                 }
@@ -197,6 +218,23 @@ __global__ __launch_bounds__(T) void pc_tile_cheb(const MassTileArgs A) {
         // the next group's loads overwrite what the stores above read
         __syncthreads();
     }
+}
+
+// the matrix rows of the tiles in tile order: out[i] = vals[gpos[i]], +0.0 where gpos[i] < 0
+__global__ __launch_bounds__(256) void mass_tile_gather(const double *__restrict__ vals,
+                                                        const int32_t *__restrict__ gpos,
+                                                        double *__restrict__ out, const int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int32_t gp = gpos[i];
+    out[i] = gp >= 0 ? vals[gp] : 0.0;
+}
+
+void launch_mass_tile_gather(hipStream_t s, const double *vals, const int32_t *gpos, double *out,
+                             int64_t n) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(mass_tile_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, vals, gpos,
+                       out, n);
 }
 
 typedef void (*mass_tile_fn)(const MassTileArgs);
@@ -219,7 +257,9 @@ int mass_tile_kernel_width(int W) { return W < 1 ? 0 : W <= 5 ? 5 : W <= 7 ? 7 :
 
 int mass_tile_max_rpt(int threads) { return threads == 256 ? 4 : threads == 512 ? 3 : 0; }
 
-size_t mass_tile_lds_bytes(int nk_pad) { return 2 * (size_t)nk_pad * sizeof(d4); }
+size_t mass_tile_lds_bytes(int nk_pad) {
+    return 2 * (size_t)nk_pad * sizeof(d4) + (size_t)nk_pad * sizeof(int);
+}
 
 int mass_tile_prepare(int W, int rpt, int threads, size_t lds_bytes) {
     const mass_tile_fn f = pick_mass_tile(mass_tile_kernel_width(W), rpt, threads);

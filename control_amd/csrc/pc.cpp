@@ -70,6 +70,10 @@ void SchurPC::clear_program() {
     program_mem_.release();
     il_cap_ = 0;
     mt_cap_ = 0;
+    // (the copies of arrays other than m_vals_ were the program's memory)
+    mass_vals_.erase(std::remove_if(mass_vals_.begin(), mass_vals_.end(),
+                                    [&](const MassTileValues &c) { return c.vals != m_vals_; }),
+                     mass_vals_.end());
     mass_solves_.clear();
     mass_launches_.clear();
     sweep_levels_.clear();
@@ -742,6 +746,18 @@ bool SchurPC::prepare_mass_tiles() {
     return true;
 }
 
+// The values of a matrix in the order the tile kernels read them: gathered once per value array.
+const double *SchurPC::mass_tile_values(const double *vals) {
+    for (const MassTileValues &c : mass_vals_)
+        if (c.vals == vals) return c.copy;
+    const TilePlan &tp = mass_plan_;
+    const size_t n = tp.gpos.size();
+    double *copy = (vals == m_vals_ ? handle_mem_ : program_mem_).alloc<double>(n);
+    launch_mass_tile_gather(S_.stream, vals, tp.d_gpos, copy, (int64_t)n);
+    mass_vals_.push_back(MassTileValues{vals, copy});
+    return copy;
+}
+
 // Replace every run of ROWS_IL steps of one batched solve by ceil(its / K) TILE_CHEB steps.
 void SchurPC::fuse_mass_tiles() {
     if (!S_.opts.mass_tiles || S_.opts.lanes || mass_solves_.empty()) return;
@@ -795,6 +811,7 @@ void SchurPC::fuse_mass_tiles() {
             const int gy = (int)std::max<int64_t>(1, std::min<int64_t>(ng, slots / tp.ntiles));
             gpw = (ng + gy - 1) / gy;
         }
+        const double *tvals = mass_tile_values(ms->sv[0].vals);
         const int grid_y = (ng + gpw - 1) / gpw;
         const int nl = (ms->its + K - 1) / K;
         for (int i = 0; i < ms->its; ++i) new_index[k + i] = out.size();
@@ -804,11 +821,10 @@ void SchurPC::fuse_mass_tiles() {
             a = MassTileArgs{};
             a.n = tp.d_n;
             a.grow = tp.d_grow;
-            a.gpos = tp.d_gpos;
             a.lcol = tp.d_lcol;
             a.masked = d_masked_;
             a.nmasked = (int32_t)bc_idx_.size();
-            a.vals = ms->sv[0].vals;
+            a.tvals = tvals;
             a.dinv = ms->sv[0].dinv;
             a.groups = d_groups;
             const int wr = j & 1, rd = wr ^ 1;
@@ -1055,6 +1071,22 @@ void SchurPC::plain_forms(std::vector<int32_t> &out) const {
                                    tile_plan_.threads, (s.fused ? 1 : 0) | (s.coarse ? 2 : 0)});
         }
     }
+}
+
+void SchurPC::mass_tile_debug(int64_t *n_entries, int64_t *n_vals, double *copy, int32_t *gpos,
+                              double *vals) {
+    const double *d_copy = nullptr;
+    for (const MassTileValues &c : mass_vals_)
+        if (c.vals == m_vals_) d_copy = c.copy;
+    if (!mass_ok_ || !d_copy)
+        fail(KKT_ERR_STATE, "kkt_debug_mass_tile_values: no mass solves on tiles on this handle");
+    const size_t n = mass_plan_.gpos.size(), nv = (size_t)S_.patterns[m_pat_].npadded;
+    if (n_entries) *n_entries = (int64_t)n;
+    if (n_vals) *n_vals = (int64_t)nv;
+    HIPCHK(hipStreamSynchronize(S_.stream));
+    if (copy) HIPCHK(hipMemcpy(copy, d_copy, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (gpos) HIPCHK(hipMemcpy(gpos, mass_plan_.d_gpos, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (vals) HIPCHK(hipMemcpy(vals, m_vals_, nv * sizeof(double), hipMemcpyDeviceToHost));
 }
 
 void SchurPC::debug_read(unsigned long long *out, int n) {

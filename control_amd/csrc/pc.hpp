@@ -121,6 +121,10 @@ class PcBase {
     virtual void debug_read(unsigned long long *, int) {}
     // kkt_debug_pc_forms: KKT_PC_FORM_INTS values per row step or sweep program, replay order
     virtual void plain_forms(std::vector<int32_t> &) const {}
+    // kkt_debug_mass_tile_values (include/kkt.h)
+    virtual void mass_tile_debug(int64_t *, int64_t *, double *, int32_t *, double *) {
+        fail(KKT_ERR_STATE, "kkt_debug_mass_tile_values: no mass solves on tiles on this handle");
+    }
     // kkt_debug_pc_solves / kkt_debug_pc_matrices: KKT_PC_SOLVE_VALS values per sub-solve,
     // KKT_PC_MATRIX_VALS per distinct sub-solve matrix (include/kkt.h)
     virtual void solve_records(std::vector<double> &) const {}
@@ -155,6 +159,8 @@ class SchurPC : public PcBase {
     void time_stages(kkt_pc_stage_times *out) override;
     void debug_read(unsigned long long *out, int n) override;   // diagnostic builds (KKT_STAMPS)
     void plain_forms(std::vector<int32_t> &out) const override;
+    void mass_tile_debug(int64_t *n_entries, int64_t *n_vals, double *copy, int32_t *gpos,
+                         double *vals) override;
     void solve_records(std::vector<double> &out) const override;
     bool coarse_space(CoarseDev *c, GalerkinDev *g, int64_t *n) const override;
     void debug_tile_levels(kkt_tile_levels *run) override;
@@ -361,6 +367,14 @@ class SchurPC : public PcBase {
     int32_t *d_masked_ = nullptr;
     double *mt_P_[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t mt_cap_ = 0;
+    // a value array in the layout of the plan's lcol (launch_mass_tile_gather), one copy per array:
+    // that of m_vals_ lives as long as the handle, as m_vals_ does; any other goes with the program
+    struct MassTileValues {
+        const double *vals;
+        double *copy;
+    };
+    std::vector<MassTileValues> mass_vals_;
+    const double *mass_tile_values(const double *vals);
     bool prepare_mass_tiles();
     void fuse_mass_tiles();
     void emit_solves(const std::vector<Solve> &sv, int its, double emin, double emax,

@@ -1029,6 +1029,16 @@ enum { KKT_PC_EST_GIVEN = 0, KKT_PC_EST_LANCZOS = 1, KKT_PC_EST_SHARED = 2, KKT_
 int kkt_debug_pc_solves(kkt_handle h, double *out, int cap);
 int kkt_debug_pc_matrices(kkt_handle h, double *out, int cap);
 
+/* Test hook of the batched mass solves on tiles (form KKT_PC_TILE_CHEB; read-only): the mass
+ * matrix's values as the tile kernels read them -- n_entries doubles in the layout of the plan's
+ * column table, [tile][row slot][entry][thread] -- into `copy`; the plan's position table (index
+ * into the value array, -1: padding) into `gpos`; the value array itself (n_vals doubles) into
+ * `vals`.  copy[i] is vals[gpos[i]], and +0.0 where gpos[i] < 0.  Null pointers are skipped: call
+ * once with the three arrays null for the two lengths.  KKT_ERR_STATE where no mass solve runs on
+ * tiles. */
+int kkt_debug_mass_tile_values(kkt_handle h, int64_t *n_entries, int64_t *n_vals, double *copy,
+                               int32_t *gpos, double *vals);
+
 /* Byte accounting of the stored operator ("algorithmic bytes"). */
 typedef struct kkt_info {
     int64_t n_local;            /* local KKT vector length */
