@@ -20,7 +20,8 @@ import scipy.sparse as sp
 __all__ = ["instationary_blocks", "stationary_blocks", "instationary_incompressible_blocks",
            "stationary_incompressible_blocks", "conform_to", "instationary_relinearisation_recipes",
            "instationary_build_recipes", "stationary_build_recipes",
-           "stationary_relinearisation_recipes"]
+           "stationary_relinearisation_recipes", "stationary_incompressible_build_recipes",
+           "stationary_incompressible_relinearisation_recipes"]
 
 
 def _csr(A):
@@ -342,3 +343,22 @@ def stationary_relinearisation_recipes(beta: float):
     """The blocks of ``stationary_blocks`` that carry the forward operator: ``block_01 = D^T`` and
     ``block_10 = D``.  The mass blocks do not change with the linearisation point."""
     return [r for r in stationary_build_recipes(beta) if r[4] != 0.0]
+
+
+def stationary_incompressible_build_recipes(beta: float):
+    """The three systems of the stationary Navier-Stokes loop as recipes: ``"inner"`` (velocity
+    KKT, ``stationary_blocks(M_v, D_v, beta)``) and ``"commutator"`` (``stationary_blocks(M_p, D_p,
+    beta)``) are ``stationary_build_recipes``; ``"outer"`` holds the same four blocks inside the
+    ``block_00`` of ``stationary_incompressible_blocks``, quadrant ``q`` at ``(q // 2, q % 2)``,
+    in its row-major dict order.  What is left to the host are the outer system's ``B^T`` / ``B``
+    blocks: one value set each."""
+    inner = stationary_build_recipes(beta)
+    outer = [(0, q // 2, q % 2, *r) for (q, _, _, *r) in inner]
+    return {"outer": outer, "inner": inner, "commutator": list(inner)}
+
+
+def stationary_incompressible_relinearisation_recipes(beta: float):
+    """The blocks of ``stationary_incompressible_build_recipes`` that carry the forward operator
+    (``alpha != 0``): ``D^T`` and ``D`` on each of the three systems."""
+    full = stationary_incompressible_build_recipes(beta)
+    return {name: [r for r in recipes if r[4] != 0.0] for name, recipes in full.items()}

@@ -20,7 +20,7 @@ import scipy.sparse as sp
 
 from .blocks import (conform_to, instationary_blocks, instationary_incompressible_blocks,
                      stationary_blocks, stationary_incompressible_blocks)
-from .fem import ReactionTerm
+from .fem import ConvectionTerm, ReactionTerm
 
 __all__ = ["Instationary", "Stationary", "GpuBackend", "suggest_chebyshev", "coarse_space"]
 
@@ -654,7 +654,9 @@ class Stationary:
     (``ufl.derivative``, ``control.py:314-318``), used after ``set_Gauss_Newton()``.  A
     ``fem.ReactionTerm`` as ``forward_operator`` declares both (the host path calls
     ``term(v, None)`` and ``term.jacobian(v, None)``) and is what
-    ``non_linear_solve(device=True)`` needs."""
+    ``non_linear_solve(device=True)`` needs.  On a Taylor-Hood discretisation a
+    ``fem.ConvectionTerm`` declares the Navier-Stokes form on both spaces and is what
+    ``incompressible_non_linear_solve(device=True)`` needs."""
 
     def __init__(self, disc, forward_operator=None, *, desired_state=None, force_f=None,
                  beta=1.0e-3, bcs_v=None, forward_jacobian=None):
@@ -875,12 +877,34 @@ class Stationary:
                                         relative_non_linear_tol=1.0e-5,
                                         absolute_non_linear_tol=1.0e-8,
                                         print_error_non_linear=False, backend=None,
-                                        Multigrid=False):
+                                        Multigrid=False, device=False):
         """``control.py:1112-1480``: Picard loop of stationary Navier-Stokes-type control around
-        ``incompressible_linear_solve``; returns the residual norms (initial one first)."""
+        ``incompressible_linear_solve``; returns the residual norms (initial one first).  With a
+        ``fem.ConvectionTerm`` as forward operator, ``forward_operator_p=None`` means its
+        ``pressure``.
+
+        ``device=True``: the same loop with the iterate in HBM (``control_amd.stationary_picard``):
+        the three block systems and one ``StokesPC`` live through all iterations, and the forward
+        operator is re-assembled, the residual evaluated and the linearised blocks re-composed by
+        device kernels.  The forward operator must be a ``fem.ConvectionTerm`` on a
+        discretisation with element data (``fem.rectangle_p2p1``), ``forward_operator_p`` ``None``
+        or its ``pressure``, the backend a ``GpuBackend``, and ``P`` is not taken.  Afterwards
+        ``non_linear_info`` holds the linear iteration counts."""
+        if device:
+            from .stationary_picard import device_stationary_incompressible_non_linear_solve
+            return device_stationary_incompressible_non_linear_solve(
+                self, nullspace_p, forward_operator_p=forward_operator_p, P=P,
+                solver_parameters=solver_parameters, lambda_v_bounds=lambda_v_bounds,
+                lambda_p_bounds=lambda_p_bounds, max_non_linear_iter=max_non_linear_iter,
+                relative_non_linear_tol=relative_non_linear_tol,
+                absolute_non_linear_tol=absolute_non_linear_tol,
+                print_error_non_linear=print_error_non_linear, backend=backend,
+                Multigrid=Multigrid)
         th = self._th
         if th is None:
             raise ValueError("Undefined space_p")
+        if forward_operator_p is None and isinstance(self._forward, ConvectionTerm):
+            forward_operator_p = self._forward.pressure
         disc, beta, nodes = self._disc, self._beta, self._disc.boundary
         M, B = disc.M, th.B
         BT = sp.csr_matrix(B.T)

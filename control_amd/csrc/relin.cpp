@@ -22,9 +22,23 @@ void relin_set(System &S, const kkt_relin_desc *d) {
         fail(KKT_ERR_STATE, "kkt_set_relinearisation: the handle carries a reaction plan "
                             "(kkt_set_reaction_relinearisation)");
     need(d->nq == RELIN_NQ, "nq must be 7 (Radon's rule)");
-    need(d->n_t >= 2 && d->ne > 0 && d->n2 > 0 && d->n1 > 0, "sizes must be positive");
+    need(d->n_t >= 1, "n_t must be at least 1 (1: the stationary system)");
+    need(d->ne > 0 && d->n2 > 0 && d->n1 > 0, "sizes must be positive");
+    // n_t == 1: the stationary outer system, one (v, zeta) block pair and no time step
+    const bool stationary = d->n_t == 1;
+    need(!stationary || d->cn == 0, "n_t == 1 (the stationary system) takes cn == 0");
     const int m = d->cn ? d->n_t - 1 : d->n_t;
     const int64_t nv = 2 * d->n2;
+    if (stationary) {
+        need(S.n0 == 2 && S.n1 == 2,
+             "n_t == 1: the handle is not the stationary outer system (n_blocks_00 = n_blocks_11 "
+             "= 2)");
+        need(S.nx0 == nv && S.nx1 == d->n1,
+             "n_t == 1: the handle is not the stationary outer system of these spaces");
+        need(!S.CN, "n_t == 1: the stationary system is not a Crank-Nicolson handle");
+        need(!S.sharded, "n_t == 1: the stationary system has one block per family and cannot be "
+                         "time-sharded");
+    }
     need(S.n0 == 2 * m && S.n1 == 2 * m && S.nx0 == nv && S.nx1 == d->n1 && S.CN == (d->cn != 0),
          "the handle is not the outer system of these spaces and time levels");
     need(!S.sharded || (S.families == 2 && S.mf == m),
@@ -47,6 +61,7 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     // the rank's block rows and the level windows its rows read
     P->w = level_windows(d->n_t, d->cn != 0, S.sharded ? S.lo : 0, S.sharded ? S.hi : m);
     const LevelWindows &w = P->w;
+    P->stationary = stationary;
     P->ne = d->ne;
     P->n2 = d->n2;
     P->n1 = d->n1;
@@ -180,10 +195,15 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
     RelinPlan &P = plan_of(S);
     if (!d_out || !norm) fail(KKT_ERR_ARG, "kkt_picard_residual_device: null argument");
     if (!P.assembled) fail(KKT_ERR_STATE, "kkt_picard_residual_device: D not assembled yet");
-    double *r = rhs ? raw_rows(S) : d_out;
-    launch_relin_residual(S.stream, P, r);
+    // the stationary system's right-hand side is the rows themselves: no tau, no time transform
+    const bool transform = rhs && !P.stationary;
+    double *r = transform ? raw_rows(S) : d_out;
+    if (P.stationary)
+        launch_relin_stationary_residual(S.stream, P, r);
+    else
+        launch_relin_residual(S.stream, P, r);
     launch_residual_norm(S, r, P.d_red);
-    if (rhs && S.sharded && P.w.CN) {
+    if (transform && S.sharded && P.w.CN) {
         // the raw rows the time transforms read across the shard boundary (the pattern of
         // comm_exchange_row_halos): T_1 families send their first row down, T_2 their last up
         const int up = P.w.up(S.rank), dn = P.w.dn(S.rank);
@@ -194,7 +214,7 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
         S.comm->sendrecv(rp + (nl - 1) * n1, n1, up, h + 2 * nv, n1, dn, S.stream);
         S.comm->sendrecv(rp + nl * n1, n1, dn, h + 2 * nv + n1, n1, up, S.stream);
     }
-    if (rhs) launch_relin_rhs(S.stream, P, r, d_out);
+    if (transform) launch_relin_rhs(S.stream, P, r, d_out);
     read_residual_norm(S, P.d_red, norm);
 }
 

@@ -17,6 +17,10 @@ struct RelinPlan {
     // n_t, m, CN, the rank's block rows and the levels of v, zeta and D it holds (levels.hpp); p,
     // mu and the data rows are the owned blocks'
     LevelWindows w;
+    // n_t == 1: the stationary system of Control.Stationary.incompressible_non_linear_solve,
+    // outer blocks [[M, D^T], [D, -(1/beta) M]] with B / B^T.  One level, every window [0, 1),
+    // tau unused; its velocity rows are not backward Euler's (launch_relin_stationary_residual)
+    bool stationary = false;
     int64_t ne = 0, n2 = 0, n1 = 0, nv = 0, nnz2 = 0, nnz1 = 0;
     double nu = 0.0, tau = 0.0, beta = 0.0;
     DevPool mem;   // everything below but the job table
@@ -52,6 +56,9 @@ void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v)
 void launch_relin_gather(hipStream_t s, const RelinPlan &P);
 // velocity and pressure rows of the residual in the outer system's vector layout
 void launch_relin_residual(hipStream_t s, const RelinPlan &P, double *d_r);
+// the rows [r00 | r01 | r10 | r11] of Stationary.incompressible_non_linear_solve's evaluate(), a
+// stationary plan's; they are the solve's right-hand side as they are
+void launch_relin_stationary_residual(hipStream_t s, const RelinPlan &P, double *d_r);
 // the solve's right-hand side from the residual: pressure rows times tau, CN time transforms
 void launch_relin_rhs(hipStream_t s, const RelinPlan &P, const double *d_r, double *d_b);
 // v, zeta, mu, p += the update's blocks, the update zeroed; zeta zero on the Dirichlet dofs

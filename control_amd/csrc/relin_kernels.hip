@@ -274,6 +274,44 @@ void launch_relin_residual(hipStream_t s, const RelinPlan &P, double *d_r) {
                        s, A, d_r + 2 * (int64_t)P.w.nl * P.nv);
 }
 
+// The stationary system (n_t == 1): one thread per (family, velocity dof), the velocity rows of
+// Stationary.incompressible_non_linear_solve's evaluate() with its bracketing:
+//   family 0 (adjoint)  ((d0 - M v) - D^T zeta) - B^T mu
+//   family 1 (state)    ((d1 - D v) + ib (M zeta)) - B^T p
+// ib = 1 / beta rounded once on the host; Dirichlet rows are zero.  These are not backward Euler's
+// rows at n_t = 1: its last adjoint row drops M v, and its rows carry tau.
+__global__ __launch_bounds__(256) void relin_stationary_residual_kernel(RelinArgs A, double ib,
+                                                                        double *__restrict__ r) {
+    const int fam = blockIdx.y;
+    for (int64_t R = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; R < A.nv;
+         R += (int64_t)gridDim.x * blockDim.x) {
+        double out = 0.0;
+        if (!A.bc[R]) {
+            const int64_t c = R >= A.n2, row = R - c * A.n2, off = c * A.n2;
+            const double d = A.data[fam * A.nv + R];
+            if (!fam) {
+                const double Mv = relin_row(A.ip2, A.ix2, A.M2, nullptr, row, A.v + off);
+                const double DTz = relin_row(A.ip2, A.ix2, A.D2, A.t2, row, A.zeta + off);
+                out = ((d - Mv) - DTz) - relin_row(A.BTip, A.BTix, A.BTv, nullptr, R, A.mu);
+            } else {
+                const double Dv = relin_row(A.ip2, A.ix2, A.D2, nullptr, row, A.v + off);
+                const double Mz = relin_row(A.ip2, A.ix2, A.M2, nullptr, row, A.zeta + off);
+                out = ((d - Dv) + ib * Mz) - relin_row(A.BTip, A.BTix, A.BTv, nullptr, R, A.p);
+            }
+        }
+        r[fam * A.nv + R] = out;
+    }
+}
+
+// the pressure rows -B v, -B zeta are relin_residual_p_kernel's with one block per family
+void launch_relin_stationary_residual(hipStream_t s, const RelinPlan &P, double *d_r) {
+    const RelinArgs A = relin_args(P);
+    hipLaunchKernelGGL(relin_stationary_residual_kernel, dim3(grid_of(P.nv, 512), 2), dim3(256), 0,
+                       s, A, 1.0 / P.beta, d_r);
+    hipLaunchKernelGGL(relin_residual_p_kernel, dim3(grid_of(P.n1, 512), 2), dim3(256), 0, s, A,
+                       d_r + 2 * P.nv);
+}
+
 // b from r: velocity rows as they are, pressure rows times tau; CN: T_1 on the adjoint rows and
 // on the zeta pressure rows, T_2 on the state rows and the v pressure rows (picard.py).  r holds
 // the rank's 2 nl row blocks per variable; the transforms' terms from the block rows hi and

@@ -27,6 +27,7 @@ __all__ = [
     "rectangle_p1",
     "box_p1",
     "ReactionTerm",
+    "ConvectionTerm",
 ]
 
 
@@ -515,6 +516,33 @@ class TaylorHoodDiscretisation:
     @property
     def n_p(self):
         return self.M_p.shape[0]
+
+
+class ConvectionTerm:
+    """The declared forward form ``nu (grad u, grad v) + ((w . grad) u, v)`` of Navier-Stokes
+    control on a Taylor-Hood discretisation with element data (``rectangle_p2p1``) -- a forward
+    operator the library can read: ``Stationary.incompressible_non_linear_solve(device=True)``
+    assembles it on the GPU from ``nu`` and the element tables.
+
+    ``term(w)``: ``nu K_v + C_v(w)`` on the structure of ``K_v`` (explicit zeros kept), built as
+    ``picard.NavierStokesControl.D_v`` builds it; ``term.pressure(w)``: ``nu K_p + C_p(w)`` on
+    the structure of ``K_p``, the ``forward_operator_p`` of the incompressible drivers."""
+
+    def __init__(self, disc, nu):
+        if getattr(disc, "elem", None) is None:
+            raise ValueError("ConvectionTerm needs a Taylor-Hood discretisation with element data "
+                             "(fem.rectangle_p2p1)")
+        self.disc, self.nu = disc, float(nu)
+
+    def __call__(self, w):
+        from .picard import _same_structure_sum
+        th = self.disc
+        return _same_structure_sum(th.K_v, [(self.nu, th.K_v), (1.0, th.convection_v(w))])
+
+    def pressure(self, w):
+        from .picard import _same_structure_sum
+        th = self.disc
+        return _same_structure_sum(th.K_p, [(self.nu, th.K_p), (1.0, th.convection_p(w))])
 
 
 def _row_positions(A, rows, cols):

@@ -76,7 +76,9 @@ def _marshal():
 
 
 class RelinearisationPlan:
-    """Everything ``kkt_set_relinearisation`` uploads, built once per problem on the host."""
+    """Everything ``kkt_set_relinearisation`` uploads, built once per problem on the host.
+    ``pb``: a ``picard.NavierStokesControl``, or the stationary problem
+    (``stationary_picard.StationaryNavierStokes``: ``n_t = 1``, ``m = 1``, ``tau`` unused)."""
 
     def __init__(self, pb):
         from .picard import non_linear_res_eval
@@ -108,6 +110,11 @@ class RelinearisationPlan:
         self.B.sort_indices()
         m = pb.n_t - 1 if pb.CN else pb.n_t
         self.m = m
+        #: one level (``n_t = 1``): the stationary system; ``pb.data_rows()``: [M v_d | M f]
+        self.stationary = bool(getattr(pb, "stationary", False))
+        if self.stationary:
+            self.data = np.ascontiguousarray(pb.data_rows(), dtype=np.float64)
+            return
         z = np.zeros((pb.n_t, th.n_v))
         r00, r01, _, _ = non_linear_res_eval(pb, [th.K_v] * pb.n_t, z, z.copy(),
                                              np.zeros((m, th.n_p)), np.zeros((m, th.n_p)))

@@ -380,8 +380,7 @@ int kkt_sync(kkt_handle h);
  * the device iterate (construct_D_v, control.py:1887-1896 on the velocity space, 3779-3785 on
  * the pressure space), the non-linear residual is evaluated there (control.py:2442-2620 and
  * 4976-5082) and the update is added in place.  Taylor-Hood P2-P1 triangles, Radon's 7-point
- * rule (control_amd/fem.py rectangle_p2p1: the arrays of its `elem` dict).  Not for
- * time-sharded handles.
+ * rule (control_amd/fem.py rectangle_p2p1: the arrays of its `elem` dict).
  *
  * The plan lives on the handle it is set on, which must be the outer incompressible system of
  * the loop: n_blocks_00 = n_blocks_11 = 2m (m = n_t, CN: n_t - 1), nx0 = 2 n2, nx1 = n1.
@@ -405,9 +404,21 @@ int kkt_sync(kkt_handle h);
  * p, mu and the data rows of its blocks.  The first v level and the last zeta level are halos:
  * kkt_relinearise_device refreshes them from the neighbour ranks before it assembles (one level
  * of v up, one of zeta down), and assembles CN's D_lo from the halo v.  kkt_picard_window reports
- * the windows. */
+ * the windows.
+ *
+ * n_t = 1 is the stationary system of Stationary.incompressible_non_linear_solve
+ * (control.py:1112-1480): cn must be 0, tau is ignored, and the handle must be the stationary outer
+ * system -- n_blocks_00 = n_blocks_11 = 2 (v, zeta | mu, p), nx0 = 2 n2, nx1 = n1, not
+ * Crank-Nicolson, not time-sharded; each violation is a KKT_ERR_ARG that names it.  data: the
+ * 2 x 2 n2 rows [M v_d | M f].  Every window is [0, 1), the iterate is one level of each field.
+ * The velocity rows of the residual are
+ *   ((d_0 - M v) - D^T zeta) - B^T mu   and   ((d_1 - D v) + (1 / beta) (M zeta)) - B^T p
+ * (not backward Euler's with n_t = 1: those carry tau, and the last adjoint row drops M v), the
+ * pressure rows -B v and -B zeta; with rhs = 1 kkt_picard_residual_device returns the same rows:
+ * the stationary right-hand side has no tau and no time transform.  Recipes name level 0
+ * (blocks.stationary_incompressible_build_recipes). */
 typedef struct kkt_relin_desc {
-    int n_t, cn, nq;              /* time levels, Crank-Nicolson (1) or backward Euler, nq = 7 */
+    int n_t, cn, nq;              /* time levels (1: stationary), CN (1) or backward Euler, nq = 7 */
     int64_t ne, n2, n1;           /* triangles, P2 nodes (one component), P1 nodes */
     double nu, tau, beta;
     const int32_t *V;             /* ne x 6 P2 nodes per triangle */
