@@ -46,6 +46,8 @@ struct PcStep {
     const double *einv = nullptr;   // COARSE: y = (x or 0) + P E^-1 P^T cr
     const double *cr = nullptr;     // COARSE: the residual that is restricted
     int lane = 0;                   // 0: the system's stream; 1: the side stream
+    int level = -1;                 // the sweep level this step belongs to (index into sweep_levels_)
+    int solve = -1;                 // the batched mass solve it belongs to (index into mass_solves_)
     int ev = -1;                    // EV_RECORD / EV_WAIT: event index
     RowLaunch rows;                 // ROWS
     double *y = nullptr;            // TIME / COPY
@@ -256,49 +258,6 @@ class SchurPC : public PcBase {
     int n_events_ = 0;
     int emit_record(int lane);          // returns the event index
     void emit_wait(int lane, int ev);
-    // persistent row programs (kernels.hip, pc_row_program)
-    bool use_programs_ = true;
-    int prog_wpw_ = 0, prog_nwg_ = 0;
-    int32_t *d_dep_ = nullptr;
-    unsigned *d_flags_ = nullptr, *d_err_ = nullptr;
-    bool prog_granule_ = false;
-    bool prog_lowreg_ = false;   // counter form at three waves per SIMD (> 2 048 slices)
-    int prog_mode_ = 0;   // 0 counter form, 1 pc_row_program_g, 2 pc_row_program_gw
-    unsigned long long *d_g0_ = nullptr, *d_g1_ = nullptr;
-    size_t granule_words_ = 0;
-    void fuse_programs();
-    bool setup_row_programs();
-    bool legacy_tried_ = false, legacy_ok_ = false;
-    // tile form (tile_kernels.hip): levels of the sweeps as the emit functions recorded them
-    struct SweepLevel {
-        size_t first = 0, last = 0;     // steps_[first, last) are the level's single-block steps
-        TileLevel lev{};
-        std::vector<TileCoef> coef;     // steps 2 .. its
-        int its = 0;
-        bool eligible = false;
-        const double *b_after = nullptr;   // the right-hand side after the update (B_i)
-        bool coarse = false;               // two-grid level: coef holds sweeps 1 .. its
-        const double *einv = nullptr;      // its (P^T A P)^-1
-    };
-    std::vector<SweepLevel> sweep_levels_;
-    TilePlan tile_plan_;
-    bool tile_tried_ = false, tile_ok_ = false;
-    size_t tile_lds_checked_ = 0;       // dynamic LDS bytes residency was checked for
-    // coarse corrections inside the tile program (kernels.hpp, TileCoarseDev)
-    TileCoarseDev h_tile_coarse_{};     // host copy (device pointers inside)
-    TileCoarseDev *d_tile_coarse_ = nullptr;
-    bool tile_coarse_ok_ = false;
-    bool tile_coarse_rings_built_ = false;   // the lists hold the ring rows' entries
-    std::vector<int32_t> tile_e_lo_, tile_e_hi_;   // host copies of TileCoarseDev::e_lo / e_hi
-    uint32_t tile_cepoch_cursor_ = 0;
-    bool build_tile_coarse();
-    unsigned long long *d_tg_[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t tile_epoch_cursor_ = 0;    // hand-off tags handed out to the launches of one application
-    bool tile_cleared_ = false;
-    bool tile_coarse_cleared_ = false;  // (the first tile launch of an application may have no coarse levels)
-    bool prepare_tiles();
-    bool fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out);
-
     // the arguments of the op builders (rowlaunch.hpp)
     using Term = RowTerm;
     using Lin = LinStep;
@@ -344,18 +303,98 @@ class SchurPC : public PcBase {
         double *out;
         double post1 = 1.0, post2 = 1.0;
     };
-    // batched solves on one matrix with the iterates of four levels interleaved (kernels.hpp IlOp)
-    bool emit_solves_interleaved(const std::vector<Solve> &sv, int its, double emin, double emax);
-    // ... and several of their steps per launch out of LDS (mass_tile_kernels.hip): the runs of
-    // ROWS_IL steps the function above emitted, as it recorded them, are replaced by
-    // ceil(its / K) TILE_CHEB steps on a tile plan of the form's own (depth K)
+    // The levels of the sweeps as the emit functions record them.  A level's steps carry its index
+    // (PcStep::level): they are the maximal stretch of consecutive steps with that tag.
+    struct SweepLevel {
+        TileLevel lev{};
+        std::vector<TileCoef> coef;     // steps 2 .. its
+        int its = 0;
+        bool eligible = false;
+        const double *b_after = nullptr;   // the right-hand side after the update (B_i)
+        bool coarse = false;               // two-grid level: coef holds sweeps 1 .. its
+        const double *einv = nullptr;      // its (P^T A P)^-1
+    };
+    std::vector<SweepLevel> sweep_levels_;
+    int cur_level_ = -1;                // the level being emitted: push_rows / emit_coarse stamp it
+    size_t level_first_ = 0;
+    void begin_level();
+    void end_level(SweepLevel lv);      // fails unless exactly the steps since begin_level() carry the tag
+    // what the tile form runs as the level "[update;] solve" (ok: it can express the update)
+    struct LevelForm {
+        TileLevel lev{};
+        const double *b_after = nullptr;
+        bool ok = true;
+    };
+    static LevelForm level_form(const Lin *upd, const Solve &sv, double p1_scale);
+    // batched solves on one matrix with the iterates of four levels interleaved (kernels.hpp IlOp);
+    // the ROWS_IL steps of a solve carry its index (PcStep::solve)
     struct MassSolve {
-        size_t first = 0;               // steps_[first, first + its) are the solve's ROWS_IL steps
         int its = 0;
         std::vector<Solve> sv;
         std::vector<TileCoef> coef;     // steps 1 .. its
     };
     std::vector<MassSolve> mass_solves_;
+    bool emit_solves_interleaved(const std::vector<Solve> &sv, int its, double emin, double emax);
+    void emit_solves(const std::vector<Solve> &sv, int its, double emin, double emax,
+                     double *const P[3], int64_t pstride, bool first_done = false,
+                     std::vector<TileCoef> *coef_out = nullptr, double eimag = 0.0,
+                     const Mat *mat = nullptr);
+    // the sweep step "b -= A u_prev (masked), then solve": the update and the first
+    // Chebyshev step share one launch
+    void emit_update_and_solve(Lin upd, const Solve &sv, int its, double emin, double emax,
+                               double eimag = 0.0, const Mat *mat = nullptr);
+    void emit_coarse_solve(const Lin *upd, const Solve &sv, const Mat &F);
+    // position of the transposed entry of every stored entry of the preconditioner's sparsity
+    // structure (device array, built on first use; null when the structure is not symmetric)
+    const int32_t *transpose_positions();
+    int32_t *d_tpos_ = nullptr;
+    bool tpos_tried_ = false;
+    void push_rows(std::vector<RowOp> &r);
+    void build_stationary();
+    void build_BE();
+    void build_CN();
+    void replay(size_t first, size_t last);
+
+    // ---- lowering (pc_lower.cpp): runs of steps_ become tile launches, batched mass-tile launches
+    // or row programs
+    bool use_programs_ = true;
+    void fuse_programs();
+    // the row programs' tables (kernels.hip, pc_row_program)
+    int prog_wpw_ = 0, prog_nwg_ = 0;
+    int32_t *d_dep_ = nullptr;
+    unsigned *d_flags_ = nullptr, *d_err_ = nullptr;
+    bool prog_granule_ = false;
+    bool prog_lowreg_ = false;   // counter form at three waves per SIMD (> 2 048 slices)
+    int prog_mode_ = 0;   // 0 counter form, 1 pc_row_program_g, 2 pc_row_program_gw
+    unsigned long long *d_g0_ = nullptr, *d_g1_ = nullptr;
+    size_t granule_words_ = 0;
+    bool setup_row_programs();
+    bool legacy_tried_ = false, legacy_ok_ = false;
+    // the tile plan of the sweeps (tile_kernels.hip), its coarse tables (kernels.hpp,
+    // TileCoarseDev) and the cursors of one application's hand-off tags
+    TilePlan tile_plan_;
+    bool tile_tried_ = false, tile_ok_ = false;
+    size_t tile_lds_checked_ = 0;       // dynamic LDS bytes residency was checked for
+    TileCoarseDev h_tile_coarse_{};     // host copy (device pointers inside)
+    TileCoarseDev *d_tile_coarse_ = nullptr;
+    bool tile_coarse_ok_ = false;
+    bool tile_coarse_rings_built_ = false;   // the lists hold the ring rows' entries
+    std::vector<int32_t> tile_e_lo_, tile_e_hi_;   // host copies of TileCoarseDev::e_lo / e_hi
+    unsigned long long *d_tg_[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t tile_epoch_cursor_ = 0;    // hand-off tags handed out to the launches of one application
+    uint32_t tile_cepoch_cursor_ = 0;
+    bool tile_cleared_ = false;
+    bool tile_coarse_cleared_ = false;  // (the first tile launch of an application may have no coarse levels)
+    bool prepare_tiles();
+    bool build_tile_coarse();
+    // the plan holds `need` bytes of dynamic LDS per tile on the chip at once (and notes the bytes)
+    bool tile_resident(size_t need, bool coarse);
+    bool fuse_tile_run(size_t k, size_t e, std::vector<PcStep> &out);
+    // what a TILE step launches, options as they are now (replay() and debug_tile_levels)
+    TileArgs tile_args(const PcStep &s) const;
+    // the mass-tile plan (mass_tile_kernels.hip) and its buffers: the runs of ROWS_IL steps of a
+    // batched solve are replaced by ceil(its / K) TILE_CHEB steps on a tile plan of the form's own
+    // (depth K)
     struct MassLaunch {
         MassTileArgs a;
         int grid_y = 1;
@@ -377,25 +416,6 @@ class SchurPC : public PcBase {
     const double *mass_tile_values(const double *vals);
     bool prepare_mass_tiles();
     void fuse_mass_tiles();
-    void emit_solves(const std::vector<Solve> &sv, int its, double emin, double emax,
-                     double *const P[3], int64_t pstride, bool first_done = false,
-                     std::vector<TileCoef> *coef_out = nullptr, double eimag = 0.0,
-                     const Mat *mat = nullptr);
-    // the sweep step "b -= A u_prev (masked), then solve": the update and the first
-    // Chebyshev step share one launch
-    void emit_update_and_solve(Lin upd, const Solve &sv, int its, double emin, double emax,
-                               double eimag = 0.0, const Mat *mat = nullptr);
-    void emit_coarse_solve(const Lin *upd, const Solve &sv, const Mat &F);
-    // position of the transposed entry of every stored entry of the preconditioner's sparsity
-    // structure (device array, built on first use; null when the structure is not symmetric)
-    const int32_t *transpose_positions();
-    int32_t *d_tpos_ = nullptr;
-    bool tpos_tried_ = false;
-    void push_rows(std::vector<RowOp> &r);
-    void build_stationary();
-    void build_BE();
-    void build_CN();
-    void replay(size_t first, size_t last);
 };
 
 // Preconditioner of the incompressible (Stokes / Navier-Stokes) control systems:

@@ -1,8 +1,9 @@
 // kkt_debug_tile_levels: one launch of the tile program's two-grid levels on host data
 // (include/kkt.h documents the arguments).  As rowstep.cpp, nothing here computes and there is no
 // second path: the vectors go up, the TileLevel records are filled as fuse_tile_run fills them and
-// launch_tile_sweep runs once on the handle's stream with the preconditioner's own plan, coarse
-// tables, row mask, granule buffers and error words -- what replay() passes for a TILE step.
+// launch_tile_sweep runs once on the handle's stream with the arguments replay() passes for a TILE
+// step (SchurPC::tile_args: the preconditioner's own plan, coarse tables, granule buffers and
+// error words) after the residency check fuse_tile_run makes (SchurPC::tile_resident).
 // Every vector sits between guards; what the launch only reads is downloaded again and compared
 // with what went up.
 #include <algorithm>
@@ -98,11 +99,8 @@ void SchurPC::debug_tile_levels(kkt_tile_levels *pa) {
     }
     // residency, as fuse_tile_run checks it: for the bytes of this `its`, and never below what was
     // checked before (the kernel's dynamic-LDS limit is set to the bytes of the last check)
-    const size_t need = std::max(tile_sweep_lds_bytes(tp.nk_pad, a.its, D), tile_lds_checked_);
-    if (need > 150 * 1024 ||
-        tp.ntiles > tile_sweep_max_tiles(tp.W, tp.rpt, tp.threads, need, tp.hslots, true))
+    if (!tile_resident(std::max(tile_sweep_lds_bytes(tp.nk_pad, a.its, D), tile_lds_checked_), true))
         bad("the plan is not resident with this number of sweeps");
-    tile_lds_checked_ = need;
     if (!tile_sweep_fuses_update(tp.W, 1)) bad("no kernel variant with the level update for this width");
 
     // ---- upload
@@ -169,34 +167,21 @@ void SchurPC::debug_tile_levels(kkt_tile_levels *pa) {
         T.coef = d_coef;
     }
     const TileLevel *d_levels = pool.upload(levels.data(), levels.size());
-    const double *const *d_einvs = pool.upload(einvs.data(), einvs.size());
+    const double **d_einvs = pool.upload(einvs.data(), einvs.size());
 
     // ---- the launch replay() makes for a TILE step, as the first one of an application
-    TileArgs t{};
-    t.coarse = d_tile_coarse_;
-    t.einv = d_einvs;
+    PcStep step;
+    step.kind = PcStep::TILE;
+    step.coarse = true;
+    step.d_einv = d_einvs;
+    step.nlevels = a.nlevels;
+    step.its = a.its;
+    step.clear = step.clear_coarse = true;
+    TileArgs t = tile_args(step);
     t.cycles = a.cycles;
-    t.cepoch0 = 0;
-    t.nlevels = a.nlevels;
-    t.its = a.its;
-    t.depth = tp.depth;
-    t.nk_pad = tp.nk_pad;
-    t.rpt = tp.rpt;
-    t.W = tp.W;
-    t.gnew[0] = d_tg_[0];
-    t.gnew[1] = d_tg_[1];
-    t.gold[0] = d_tg_[2];
-    t.gold[1] = d_tg_[3];
-    const size_t words = 2 * n;
-    t.granule_bytes = (unsigned)(words * sizeof(unsigned long long));
-    t.err = d_err_;
-    t.epoch0 = 0;
-    t.clear = 3;
-    t.fused_update = 1;
-    t.hslots = tp.hslots;
     t.stamps = 0;
     t.debug_drop = 0;
-    t.poll_delay = S_.opts.tile_poll_delay;
+    const size_t words = 2 * n;
     HIPCHK(hipStreamSynchronize(st));
     try {
         launch_tile_sweep(st, t, d_levels, tp.d_n, tp.d_grow, tp.d_lcol, tp.d_gpos, mask_, tp.ntiles,

@@ -41,7 +41,7 @@ REFUSED_ON_A_SHARD = {
 NEEDS_FOUR_LEVELS = {
     "interleaved": "csrc/pc.cpp:1982 (emit_solves) `if (m >= 4 && !first_done && its >= 2 && ...`",
     "shared": "csrc/kernels.hpp:88 launch_rowops_shared `serves R = 2 and at least four ops`",
-    "mass_tile": "csrc/pc.cpp:726 (fuse_mass_tiles) replaces runs of ROWS_IL steps only",
+    "mass_tile": "csrc/pc_lower.cpp (fuse_mass_tiles) replaces runs of ROWS_IL steps only",
 }
 # (world, m) -> levels per rank (kkt_shard_range)
 LEVELS = {(2, 7): [4, 3], (5, 7): [2, 2, 1, 1, 1], (5, 5): [1, 1, 1, 1, 1], (3, 4): [2, 1, 1],
@@ -136,7 +136,7 @@ def check_heat_set(label, r, d, name, rb, width):
         # one tile launch per sweep (a one-level rank: its mass solve, a single solve, as well) and
         # no row program: on a one-level rank the products between the sweeps are single-block
         # steps of the sweeps' runs (rank 0: in front of the forward level; the last rank: between
-        # the sweeps), which fuse_programs (csrc/pc.cpp) must not let take the levels with them
+        # the sweeps), which fuse_programs (csrc/pc_lower.cpp) must not let take the levels with them
         assert not progs and sum(f["n"] for f in tiles) == 2 + (nl == 1), (label, r, name, rb["forms"])
         assert all((f["count"], f["slots"]) == (info["sweep_threads"], info["sweep_row_slots"])
                    for f in tiles), (tiles, info)

@@ -1,5 +1,5 @@
 """The launch schedule of the batched mass solves on tiles (control_amd/csrc/mass_tile_kernels.hip,
-planned in csrc/pc.cpp) on a real tile plan of control_amd/csrc/tiles.cpp, emulated on the CPU by
+planned in csrc/pc_lower.cpp) on a real tile plan of control_amd/csrc/tiles.cpp, emulated on the CPU by
 tests/native/mass_tile_emu.cpp: ceil(its / K) launches of at most K steps out of a tile's local
 vectors, the older iterate overwritten in place, the iterates between launches in two pairs of
 global vectors.  Against the global three-term recurrence bit for bit; no local row read while
