@@ -20,9 +20,10 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
     if (S.relin)
         fail(KKT_ERR_STATE, "kkt_set_reaction_relinearisation: the handle carries a Navier-Stokes "
                             "plan (kkt_set_relinearisation)");
-    need(d->nq == 7 || d->nq == 15,
-         "nq must be 7 (P1 triangles, Radon's rule) or 15 (P1 tetrahedra, Stroud's T3:5-1)");
-    const int nv = d->nq == 7 ? 3 : 4, ep = nv * nv;
+    need(d->nq == 7 || d->nq == 15 || d->nq == 25,
+         "nq must be 7 (P1 triangles, Radon's rule), 15 (P1 tetrahedra, Stroud's T3:5-1) or 25 "
+         "(P2 triangles, the 5 x 5 conical rule)");
+    const int nv = d->nq == 7 ? 3 : d->nq == 15 ? 4 : 6, ep = nv * nv;
     need(d->n_t >= 1 && d->ne > 0 && d->n1 > 0 && d->nnz > 0, "sizes must be positive");
     need(d->degree >= 0 && d->degree <= REACTION_MAX_DEGREE, "degree must be 0 .. 4");
     // n_t == 1: the stationary system [[M, D^T], [D, -(1/beta) M]] -- one level, no time step
@@ -83,6 +84,9 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
         P->d_rhalo = P->mem.alloc<double>(2 * n1);
         HIPCHK(hipMemset(P->d_rhalo, 0, 2 * n1 * 8));
     }
+    // E is a hipMalloc of its own, so 256-byte aligned: the 16-byte stores of the
+    // tetrahedral and the P2 kernel rely on it (128 and 288 bytes a matrix).  n_entries fits an int32 (check_lists:
+    // cptr[nnz] == n_entries), so n_entries * D_n * 8 stays far inside int64
     P->d_E = P->mem.alloc<double>(n_entries * w.D_n);
     P->d_D = P->mem.alloc<double>(nnz * w.D_n);
     P->d_v = P->mem.alloc<double>(w.v_n * n1);

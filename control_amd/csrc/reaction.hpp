@@ -1,5 +1,5 @@
 // Device re-linearisation of the scalar reaction problem (include/kkt.h,
-// kkt_set_reaction_relinearisation): P1 element matrices of a polynomial reaction coefficient,
+// kkt_set_reaction_relinearisation): element matrices of a polynomial reaction coefficient,
 // their gather and composition into block values (compose.hpp), the Picard residual and the
 // update of the iterate.  DESIGN.md section 6.6a.
 #pragma once
@@ -22,8 +22,9 @@ struct ReactionCoef {
 };
 
 struct ReactionPlan {
-    // the element: nodes per cell (3: triangles, 4: tetrahedra), quadrature points (7: Radon's
-    // rule, 15: Stroud's T3:5-1) and entries of one element matrix, nv * nv
+    // the element: nodes per cell (3: P1 triangles, 4: P1 tetrahedra, 6: P2 triangles), quadrature
+    // points (7: Radon's rule, 15: Stroud's T3:5-1, 25: the 5 x 5 conical rule) and entries of one
+    // element matrix, nv * nv.  d_lam: the nq x nv values of the shape functions at the points
     int nv = 0, nq = 0, ep = 0;
     // n_t == 1: the stationary system [[M, D^T], [D, -(1/beta) M]] of Control.Stationary.  One
     // level of everything, every window [0, 1), tau unused; the element kernels, the gather, the

@@ -1,5 +1,5 @@
-// Kernels of the scalar reaction re-linearisation (reaction.hpp): P1 element matrices of a
-// polynomial reaction coefficient, the Picard residual of the heat-type optimality system (and of
+// Kernels of the scalar reaction re-linearisation (reaction.hpp): element matrices (P1 triangles
+// and tetrahedra, P2 triangles) of a polynomial reaction coefficient, the Picard residual of the heat-type optimality system (and of
 // the stationary one, n_t == 1), its Crank-Nicolson right-hand side and the update of the iterate.
 // gfx950, wave64; every store is a plain vector store, and no floating-point atomics: every sum
 // runs in a fixed order.  Gather and composition are relin_kernels.hip's.
@@ -117,12 +117,80 @@ __global__ __launch_bounds__(256) void reaction_elements_tet_kernel(
     }
 }
 
+constexpr int P2_NV = 6;      // nodes of a P2 triangle: three vertices, three edge midpoints
+constexpr int P2_NQ = 25;     // the 5 x 5 conical product rule, degree 9
+constexpr int P2_EP = 36;     // entries of its element matrix
+
+// The same statement on P2 triangles: `phi` holds the 25 x 6 values of the shape functions at the
+// points of the conical rule (they are no longer the barycentric coordinates),
+// s_q = ((((phi_q0 v_0 + phi_q1 v_1) + phi_q2 v_2) + phi_q3 v_3) + phi_q4 v_4) + phi_q5 v_5,
+// W_eq = wq_q area_e, all 36 entries on their own.  One thread per (element, level) keeps the 36
+// sums in registers; the table is uniform over the wave and comes by scalar loads.  One thread
+// owns the 288 contiguous bytes of its element matrix (288 = 18 x 16 and E is 256-byte aligned,
+// so every matrix starts at a multiple of 16 bytes) and writes them as eighteen 16-byte stores.
+__global__ __launch_bounds__(256) void reaction_elements_p2_kernel(
+    const double *__restrict__ v, int64_t ne, int64_t n1, int n_t,
+    const int32_t *__restrict__ cells, const double *__restrict__ W,
+    const double *__restrict__ phi, ReactionCoef C, double *__restrict__ E) {
+    const int64_t total = ne * n_t;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total;
+         t += (int64_t)gridDim.x * blockDim.x) {
+#pragma clang fp contract(off)
+        const int64_t l = t / ne, e = t - l * ne;
+        const double *vl = v + l * n1;
+        const int32_t *ce = cells + e * P2_NV;
+        double vn[P2_NV];
+#pragma unroll
+        for (int k = 0; k < P2_NV; ++k) vn[k] = vl[ce[k]];
+        double acc[P2_EP];
+#pragma unroll
+        for (int k = 0; k < P2_EP; ++k) acc[k] = 0.0;
+        // five rounds of five points, 30 table entries (60 SGPRs) a round: 104 SGPRs, 115 VGPRs,
+        // no scratch, four waves per SIMD.  A full unroll wants all 150 entries at once and
+        // spills 282 SGPRs into vector lanes (185 VGPRs, two waves); one point a round needs
+        // 56 SGPRs and 100 VGPRs, with a wait for scalar loads in each of 25 rounds (not timed)
+#pragma unroll 5
+        for (int q = 0; q < P2_NQ; ++q) {
+            double pa[P2_NV];
+#pragma unroll
+            for (int k = 0; k < P2_NV; ++k) pa[k] = phi[q * P2_NV + k];
+            double s = pa[0] * vn[0];
+#pragma unroll
+            for (int k = 1; k < P2_NV; ++k) {
+                const double p = pa[k] * vn[k];
+                s = s + p;
+            }
+            double g = C.c[C.degree];
+            for (int k = C.degree - 1; k >= 0; --k) {
+                const double gs = g * s;
+                g = gs + C.c[k];
+            }
+            const double wg = W[e * P2_NQ + q] * g;
+#pragma unroll
+            for (int a = 0; a < P2_NV; ++a) {
+                const double wa = wg * pa[a];
+#pragma unroll
+                for (int b = 0; b < P2_NV; ++b) {
+                    const double term = wa * pa[b];
+                    acc[a * P2_NV + b] = acc[a * P2_NV + b] + term;
+                }
+            }
+        }
+        double2 *o = reinterpret_cast<double2 *>(E + t * P2_EP);
+#pragma unroll
+        for (int k = 0; k < P2_EP / 2; ++k) o[k] = make_double2(acc[2 * k], acc[2 * k + 1]);
+    }
+}
+
 // The kernels' levels are those of the D window: v is passed from the slot of level D_l0 (a time
 // shard's v window may start one level below), n_t is D_n.  One rank: the base 0, every level.
 void launch_reaction_elements(hipStream_t s, const ReactionPlan &P) {
     const dim3 grid(grid_of(P.ne * P.w.D_n, REACTION_ELEMENT_BLOCKS));
     const double *v = P.d_v + (int64_t)(P.w.D_l0 - P.w.v_l0) * P.n1;
-    if (P.nv == TET_NV)
+    if (P.nv == P2_NV)
+        hipLaunchKernelGGL(reaction_elements_p2_kernel, grid, dim3(256), 0, s, v, P.ne, P.n1,
+                           P.w.D_n, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
+    else if (P.nv == TET_NV)
         hipLaunchKernelGGL(reaction_elements_tet_kernel, grid, dim3(256), 0, s, v, P.ne, P.n1,
                            P.w.D_n, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
     else

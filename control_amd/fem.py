@@ -26,6 +26,8 @@ __all__ = [
     "unit_square_q2",
     "rectangle_p1",
     "box_p1",
+    "rectangle_p2",
+    "unit_square_p2",
     "ReactionTerm",
     "ConvectionTerm",
 ]
@@ -40,7 +42,8 @@ class SpatialDiscretisation:
     coords: np.ndarray        # (N_x, dim) dof coordinates
     boundary: np.ndarray      # int32 sorted dof indices on the whole boundary
     name: str = ""
-    cells: np.ndarray = None  # (n_cells, 3 | 4) vertex indices (P1 triangles / tetrahedra only)
+    cells: np.ndarray = None  # (n_cells, 3 | 4 | 6) node indices (P1 triangles / tetrahedra, P2
+    #                           triangles: ``rectangle_p2``)
 
     @property
     def n_dofs(self) -> int:
@@ -129,12 +132,36 @@ def _stroud_rule():
     return np.array(lam), np.array(wq)
 
 
+def _conical_rule():
+    """``(lam, wq)`` of the 5 x 5 conical product rule on the triangle: 25 interior points,
+    positive weights, degree 9 (and not 10), built from ``numpy`` / ``scipy`` Gauss rules alone.
+    With ``u_i`` the Gauss-Jacobi nodes of weight ``(1 - u)`` on [0, 1] (``roots_jacobi(5, 1, 0)``
+    mapped from [-1, 1]: the weights take a factor 1/4) and ``t_j`` the Gauss-Legendre nodes on
+    [0, 1], point ``5 i + j`` has ``lam_1 = u_i``, ``lam_2 = (1 - u_i) t_j``, ``lam_0 = 1 - lam_1 -
+    lam_2``; the weights are fractions of the area.
+
+    Degree 9 is what the reference's coefficient ``2 + 0.5 v^2`` needs on P2 to be integrated
+    exactly: ``v^2`` has degree 4 and ``phi_a phi_b`` degree 4, together 8.  (The degree-4
+    coefficients ``ReactionTerm`` also takes are inexact here, as they are under Radon's and
+    Stroud's degree-5 rules on P1.)"""
+    from scipy.special import roots_jacobi
+    x, w = np.polynomial.legendre.leggauss(5)
+    t, wt = 0.5 * (x + 1.0), 0.5 * w
+    xj, wj = roots_jacobi(5, 1, 0)
+    u, wu = 0.5 * (xj + 1.0), 0.25 * wj
+    l1 = np.repeat(u, 5)
+    l2 = np.repeat(1.0 - u, 5) * np.tile(t, 5)
+    lam = np.stack([(1.0 - l1) - l2, l1, l2], axis=1)
+    wq = 2.0 * (np.repeat(wu, 5) * np.tile(wt, 5))
+    return lam, wq
+
+
 class ReactionTerm:
     """The forward form ``(L u, w) + (g(v_old) u, w)`` with a polynomial reaction coefficient
-    ``g(s) = sum_k c_k s^k`` (``coefficients = (c_0, ..., c_p)``, ``p <= 4``) on P1 triangles or
-    P1 tetrahedra (``disc.cells`` with 3 or 4 columns) -- the reference's non-linear scalar problem
-    is ``grad v . grad w + (2 + 0.5 v^2) v w`` (``test/test_control.py:715-719``):
-    ``ReactionTerm(disc, (2, 0, 0.5))``.
+    ``g(s) = sum_k c_k s^k`` (``coefficients = (c_0, ..., c_p)``, ``p <= 4``) on P1 triangles,
+    P1 tetrahedra or P2 triangles (``disc.cells`` with 3, 4 or 6 columns) -- the reference's
+    non-linear scalar problem is ``grad v . grad w + (2 + 0.5 v^2) v w``
+    (``test/test_control.py:715-719``): ``ReactionTerm(disc, (2, 0, 0.5))``.
 
     ``L`` is ``nu * disc.K``, or any CSR matrix ``linear`` inside the structure of ``disc.M``
     (``disc.K + disc.convection(wind)``: a non-symmetric linear part).  ``term(v, t)`` is the
@@ -152,19 +179,32 @@ class ReactionTerm:
     every product and sum rounded separately.  On tetrahedra the points are the 15 of Stroud's
     T3:5-1 (``_stroud_rule``), ``s_q = ((lam_q0 v_0 + lam_q1 v_1) + lam_q2 v_2) + lam_q3 v_3``,
     ``W_eq = wq_q volume_e`` with ``volume = |det [1 x]| / 6``, and all 16 entries are computed
-    separately (``(wg la) lb`` and ``(wg lb) la`` round differently).  The flat element entry is
-    ``e nv^2 + nv a + b`` for ``nv`` nodes per cell.  The entries are summed into the structure
-    of ``M`` by ``np.bincount`` (ascending element-entry order), and ``D = L + C`` with one
-    rounding."""
+    separately (``(wg la) lb`` and ``(wg lb) la`` round differently).
+
+    On P2 triangles (``rectangle_p2``: vertices 0, 1, 2, then the midpoints of edges (0,1), (1,2),
+    (0,2)) the points are the 25 of ``_conical_rule`` (degree 9) and the shape functions are no
+    longer the barycentric coordinates: ``basis`` (25, 6) holds ``phi_qa``, computed once from the
+    barycentric table ``lam`` (25, 3).  ``area`` comes from the three vertices, ``W_eq = wq_q
+    area_e``,
+
+        s_q = ((((phi_q0 v_0 + phi_q1 v_1) + phi_q2 v_2) + phi_q3 v_3) + phi_q4 v_4) + phi_q5 v_5
+        g   by Horner from c_p down, as above
+        E[a][b] = sum_q ((W_eq g) phi_qa) phi_qb   from 0.0, q ascending
+
+    and all 36 entries are computed on their own.  On P1 elements ``basis`` is ``lam``.
+
+    The flat element entry is ``e nv^2 + nv a + b`` for ``nv`` nodes per cell.  The entries are
+    summed into the structure of ``M`` by ``np.bincount`` (ascending element-entry order), and
+    ``D = L + C`` with one rounding."""
 
     MAX_DEGREE = 4
 
     def __init__(self, disc, coefficients, *, nu=1.0, linear=None):
         from .blocks import conform_to
         cells = getattr(disc, "cells", None)
-        if cells is None or np.ndim(cells) != 2 or np.shape(cells)[1] not in (3, 4):
-            raise ValueError("ReactionTerm needs a discretisation by P1 triangles or P1 "
-                             "tetrahedra (disc.cells with 3 or 4 columns)")
+        if cells is None or np.ndim(cells) != 2 or np.shape(cells)[1] not in (3, 4, 6):
+            raise ValueError("ReactionTerm needs a discretisation by P1 or P2 triangles or P1 "
+                             "tetrahedra (disc.cells with 3, 6 or 4 columns)")
         self.coefficients = tuple(float(c) for c in coefficients)
         if not 1 <= len(self.coefficients) <= self.MAX_DEGREE + 1:
             raise ValueError(f"ReactionTerm: the degree must be 0 .. {self.MAX_DEGREE}")
@@ -179,11 +219,18 @@ class ReactionTerm:
             d1, d2 = X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]
             self.area = 0.5 * np.abs(d1[:, 0] * d2[:, 1] - d1[:, 1] * d2[:, 0])
             self.W = self.wq[None, :] * self.area[:, None]
+        elif nv == 6:
+            self.lam, self.wq = _conical_rule()
+            d1, d2 = X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]
+            self.area = 0.5 * np.abs(d1[:, 0] * d2[:, 1] - d1[:, 1] * d2[:, 0])
+            self.W = self.wq[None, :] * self.area[:, None]
         else:
             self.lam, self.wq = _stroud_rule()
             A = np.concatenate([np.ones((len(X), 4, 1)), X], axis=2)
             self.volume = np.abs(np.linalg.det(A)) / 6.0
             self.W = self.wq[None, :] * self.volume[:, None]
+        #: (nq, nv) values of the shape functions at the points (P1: the barycentric coordinates)
+        self.basis = _p2_shape_functions(self.lam) if nv == 6 else self.lam
         rows = np.repeat(self.cells, nv, axis=1).ravel()
         cols = np.tile(self.cells, (1, nv)).ravel()
         #: position in the structure of ``M`` of every flat element entry ``e nv^2 + nv a + b``
@@ -201,7 +248,7 @@ class ReactionTerm:
         """``E`` (n_cells, nv, nv) at the nodal values ``v``: the statement above, an explicit
         loop over the points, vectorised over the cells."""
         c = self.coefficients if coefficients is None else tuple(coefficients)
-        lam, W, nv = self.lam, self.W, self.nv
+        lam, W, nv = self.basis, self.W, self.nv
         vc = np.asarray(v, dtype=np.float64)[self.cells]
         E = np.zeros((len(self.cells), nv, nv))
         for q in range(len(self.wq)):
@@ -600,12 +647,13 @@ def unit_square_q2q1(n: int, length: float = 1.0) -> TaylorHoodDiscretisation:
 
 # ------------------------------------------------------- Taylor-Hood (P2-P1, triangles)
 
-def rectangle_p2p1(nx: int, ny: int, lx: float = 1.0, ly: float = 1.0) -> TaylorHoodDiscretisation:
-    """P2 velocity / P1 pressure on the right-diagonal triangulation of ``[0,lx] x [0,ly]``
-    (``RectangleMesh(nx, ny, lx, ly)``, the spaces of the reference's Stokes-control tests,
-    ``test/test_control.py:3546-3560``).  P2 dofs are the points of the ``(2nx+1) x (2ny+1)``
-    grid, P1 dofs the mesh vertices, both in lexicographic (y-major) order; the velocity
-    vector is component-major."""
+def _p2_triangle_elements(nx: int, ny: int, lx: float, ly: float) -> dict:
+    """The P2 element data of the right-diagonal triangulation of ``[0,lx] x [0,ly]``, shared by
+    ``rectangle_p2p1`` (one velocity component) and ``rectangle_p2`` (the scalar space): the
+    connectivity ``V`` (ne, 6) and ``P`` (ne, 3), Radon's tables, the shape functions and their
+    gradients at the points, the element matrices ``Me`` / ``Ke``, dof coordinates and boundary
+    dofs.  P2 dofs are the points of the ``(2nx+1) x (2ny+1)`` grid in y-major order; local P2
+    order: vertices 0, 1, 2, then the midpoints of edges (0,1), (1,2), (0,2)."""
     nvx, nvy = 2 * nx + 1, 2 * ny + 1
     npx = nx + 1
 
@@ -617,8 +665,7 @@ def rectangle_p2p1(nx: int, ny: int, lx: float = 1.0, ly: float = 1.0) -> Taylor
     ii, jj = np.meshgrid(np.arange(nx), np.arange(ny), indexing="xy")
     ii, jj = ii.ravel(), jj.ravel()
     hx, hy = lx / nx, ly / ny
-    # two triangles per cell: (00, 10, 11) and (00, 11, 01); local P2 order:
-    # vertices 0,1,2 then midpoints of edges (0,1), (1,2), (0,2)
+    # two triangles per cell: (00, 10, 11) and (00, 11, 01)
     tri_v, tri_p, tri_x = [], [], []
     for (a, b, c) in (((0, 0), (1, 0), (1, 1)), ((0, 0), (1, 1), (0, 1))):
         verts = [a, b, c]
@@ -650,9 +697,7 @@ def rectangle_p2p1(nx: int, ny: int, lx: float = 1.0, ly: float = 1.0) -> Taylor
     glam = np.transpose(Ainv[:, 1:, :], (0, 2, 1))          # (ne, 3, 2)
     detJ = np.abs(np.linalg.det(A))                         # 2 * area
     l = lam                                                 # (nq, 3)
-    phi = np.stack([l[:, 0] * (2 * l[:, 0] - 1), l[:, 1] * (2 * l[:, 1] - 1),
-                    l[:, 2] * (2 * l[:, 2] - 1), 4 * l[:, 0] * l[:, 1],
-                    4 * l[:, 1] * l[:, 2], 4 * l[:, 0] * l[:, 2]], 1)     # (nq, 6)
+    phi = _p2_shape_functions(l)                            # (nq, 6)
     # d phi / d lambda_k, (nq, 6, 3)
     dphi = np.zeros((len(l), 6, 3))
     for k in range(3):
@@ -664,31 +709,72 @@ def rectangle_p2p1(nx: int, ny: int, lx: float = 1.0, ly: float = 1.0) -> Taylor
     W = wq[None, :] * detJ[:, None]                         # (ne, nq)
     Me = np.einsum("eq,qa,qb->eab", W, phi, phi)
     Ke = np.einsum("eq,eqad,eqbd->eab", W, gphi, gphi)
+    xs, ys = np.linspace(0, lx, nvx), np.linspace(0, ly, nvy)
+    XX, YY = np.meshgrid(xs, ys, indexing="xy")
+    coords_v = np.stack([XX.ravel(), YY.ravel()], 1)
+    onb = ((coords_v[:, 0] == 0) | (coords_v[:, 0] == xs[-1]) | (coords_v[:, 1] == 0)
+           | (coords_v[:, 1] == ys[-1]))
+    return dict(V=V, P=Pn, X=X, lam=l, glam=glam, detJ=detJ, phi=phi, gphi=gphi, W=W, Me=Me,
+                Ke=Ke, n2=nvx * nvy, coords=coords_v, boundary=np.flatnonzero(onb))
+
+
+def _p2_shape_functions(l: np.ndarray) -> np.ndarray:
+    """The six P2 shape functions at the barycentric points ``l`` (nq, 3), in the local order
+    of ``_p2_triangle_elements``: ``(nq, 6)``."""
+    return np.stack([l[:, 0] * (2 * l[:, 0] - 1), l[:, 1] * (2 * l[:, 1] - 1),
+                     l[:, 2] * (2 * l[:, 2] - 1), 4 * l[:, 0] * l[:, 1],
+                     4 * l[:, 1] * l[:, 2], 4 * l[:, 0] * l[:, 2]], 1)
+
+
+def rectangle_p2(nx: int, ny: int, lx: float = 1.0, ly: float = 1.0) -> SpatialDiscretisation:
+    """Scalar P2 on the right-diagonal triangulation of ``[0,lx] x [0,ly]``: one velocity
+    component of ``rectangle_p2p1(nx, ny, lx, ly)``, array for array (``M``, ``K``, ``coords``,
+    ``boundary``).  Dofs are the points of the ``(2nx+1) x (2ny+1)`` grid in y-major order;
+    ``cells`` is ``(ne, 6)`` int32 in the local order vertices 0, 1, 2, then the midpoints of
+    edges (0,1), (1,2), (0,2) -- what ``ReactionTerm`` needs.  The Jacobi-scaled mass matrix has
+    its spectrum in ``(0.3924, 2.0598)`` (the reference's interval for P2 triangles)."""
+    e = _p2_triangle_elements(nx, ny, lx, ly)
+    V, n2 = e["V"], e["n2"]
+    return SpatialDiscretisation(_assemble_like(e["Me"], V, V, (n2, n2)),
+                                 _assemble_like(e["Ke"], V, V, (n2, n2)), e["coords"],
+                                 e["boundary"].astype(np.int32), name=f"rectangle_p2({nx},{ny})",
+                                 cells=np.ascontiguousarray(V, dtype=np.int32))
+
+
+def unit_square_p2(n: int) -> SpatialDiscretisation:
+    return rectangle_p2(n, n)
+
+
+def rectangle_p2p1(nx: int, ny: int, lx: float = 1.0, ly: float = 1.0) -> TaylorHoodDiscretisation:
+    """P2 velocity / P1 pressure on the right-diagonal triangulation of ``[0,lx] x [0,ly]``
+    (``RectangleMesh(nx, ny, lx, ly)``, the spaces of the reference's Stokes-control tests,
+    ``test/test_control.py:3546-3560``).  P2 dofs are the points of the ``(2nx+1) x (2ny+1)``
+    grid, P1 dofs the mesh vertices, both in lexicographic (y-major) order; the velocity
+    vector is component-major."""
+    e = _p2_triangle_elements(nx, ny, lx, ly)
+    V, Pn, W, l, phi, gphi, glam, detJ = (e[k] for k in ("V", "P", "W", "lam", "phi", "gphi",
+                                                         "glam", "detJ"))
+    npx = nx + 1
     Bxe = -np.einsum("eq,qc,eqa->eca", W, l, gphi[..., 0])  # (ne, 3, 6)
     Bye = -np.einsum("eq,qc,eqa->eca", W, l, gphi[..., 1])
     Mpe = np.einsum("eq,qc,qd->ecd", W, l, l)
     Kpe = np.einsum("e,ecx,edx->ecd", 0.5 * detJ, glam, glam)
-    n2, n1 = nvx * nvy, npx * (ny + 1)
+    n2, n1 = e["n2"], npx * (ny + 1)
 
     asm = _assemble_like
-    M2 = asm(Me, V, V, (n2, n2))
-    K2 = asm(Ke, V, V, (n2, n2))
+    M2 = asm(e["Me"], V, V, (n2, n2))
+    K2 = asm(e["Ke"], V, V, (n2, n2))
     Bx = asm(Bxe, Pn, V, (n1, n2))
     By = asm(Bye, Pn, V, (n1, n2))
     M_p = asm(Mpe, Pn, Pn, (n1, n1))
     K_p = asm(Kpe, Pn, Pn, (n1, n1))
     I2 = sp.identity(2, format="csr")
-    xs, ys = np.linspace(0, lx, nvx), np.linspace(0, ly, nvy)
-    XX, YY = np.meshgrid(xs, ys, indexing="xy")
-    coords_v = np.stack([XX.ravel(), YY.ravel()], 1)
     xp, yp = np.linspace(0, lx, npx), np.linspace(0, ly, ny + 1)
     XP, YP = np.meshgrid(xp, yp, indexing="xy")
     coords_p = np.stack([XP.ravel(), YP.ravel()], 1)
-    onb = ((coords_v[:, 0] == 0) | (coords_v[:, 0] == xs[-1]) | (coords_v[:, 1] == 0)
-           | (coords_v[:, 1] == ys[-1]))
-    nb = np.flatnonzero(onb)
+    nb = e["boundary"]
     return TaylorHoodDiscretisation(
         _canonical_csr(sp.kron(I2, M2)), _canonical_csr(sp.kron(I2, K2)),
-        _canonical_csr(sp.hstack([Bx, By])), M_p, K_p, coords_v, coords_p,
+        _canonical_csr(sp.hstack([Bx, By])), M_p, K_p, e["coords"], coords_p,
         np.concatenate([nb, nb + n2]).astype(np.int32),
         elem=dict(V=V, P=Pn, W=W, phi=phi, gphi=gphi, lam=l, glam=glam))

@@ -1,6 +1,8 @@
 """Reaction-diffusion control (256^2 P1 x 64 levels, BE, g(v) = 2 + 0.5 v^2, beta = 1e-4, [0, 2]) on
 one GPU -- or, with ``--mesh cube``, the same problem on P1 tetrahedra (``box_p1(n, n, n)``; the
-record of ``profiles/reaction_picard_3d.md`` is ``--mesh cube --n 32 --n_t 32``) --: wall time of
+record of ``profiles/reaction_picard_3d.md`` is ``--mesh cube --n 32 --n_t 32``) or, with
+``--mesh p2``, on P2 triangles (``unit_square_p2(n)``; ``profiles/reaction_picard_p2.md`` is
+``--mesh p2 --n 128 --n_t 32``) --: wall time of
 a Picard iteration outside the linearised solve, the host loop against
 ``non_linear_solve(device=True)``.  Both paths run in one process, alternating, after one warm-up
 iteration each.  One JSON line per loop.
@@ -20,7 +22,7 @@ from control_amd import fem, multiblock
 from control_amd.control import GpuBackend, Instationary
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mesh", choices=("square", "cube"), default="square")
+ap.add_argument("--mesh", choices=("square", "cube", "p2"), default="square")
 ap.add_argument("--n", type=int, default=256)
 ap.add_argument("--n_t", type=int, default=64)
 ap.add_argument("--beta", type=float, default=1.0e-4)
@@ -30,9 +32,11 @@ ap.add_argument("--repeats", type=int, default=1, help="measured loops per path"
 ap.add_argument("--multigrid", type=int, default=1)
 a = ap.parse_args()
 
-disc = fem.box_p1(a.n, a.n, a.n) if a.mesh == "cube" else fem.unit_square_p1(a.n)
-# the interval of the mass solves: Wathen's bounds for P1 triangles / P1 tetrahedra
-MASS = (0.5, 2.5) if a.mesh == "cube" else None
+disc = {"cube": lambda: fem.box_p1(a.n, a.n, a.n), "p2": lambda: fem.unit_square_p2(a.n),
+        "square": lambda: fem.unit_square_p1(a.n)}[a.mesh]()
+# the interval of the mass solves: Wathen's bounds for P1 triangles / P1 tetrahedra, the
+# reference's interval for P2 triangles
+MASS = {"cube": (0.5, 2.5), "p2": (0.3924, 2.0598), "square": None}[a.mesh]
 
 
 def v_d(X, t):
