@@ -132,9 +132,11 @@ class RelinRecipe(C.Structure):
 
 
 class ReactionDesc(C.Structure):
-    # kkt_reaction_desc; nq selects the element: 7 P1 triangles, 15 P1 tetrahedra, 25 P2 triangles;
-    # lam: the nq x nv values of the shape functions at the points
-    _fields_ = ([("n_t", C.c_int), ("cn", C.c_int), ("nq", C.c_int), ("ne", C.c_int64),
+    # kkt_reaction_desc; nq selects the element: 7 P1 triangles, 15 P1 tetrahedra, 25 P2 triangles
+    # or, with nv = 9, Q2 quadrilaterals (nv = 0: inferred from nq; the field fills the padding
+    # before ne); lam: the nq x nv values of the shape functions at the points
+    _fields_ = ([("n_t", C.c_int), ("cn", C.c_int), ("nq", C.c_int), ("nv", C.c_int),
+                 ("ne", C.c_int64),
                  ("n1", C.c_int64), ("tau", C.c_double), ("beta", C.c_double),
                  ("cells", c_i32p), ("W", c_f64p), ("lam", c_f64p), ("nnz", C.c_int64)]
                 + [(n, c_i32p) for n in ("indptr", "indices", "tperm", "cptr", "clist")]

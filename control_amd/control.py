@@ -485,9 +485,10 @@ class Instationary:
         block system and one preconditioner live through the loop, re-linearisation, residual and
         update run on the GPU, the host reads one norm per iteration and the fields once at the
         end; the linear iteration counts land in ``self.non_linear_info["linear_iterations"]``.
-        Needs a ``fem.ReactionTerm`` as forward operator (P1 or P2 triangles, P1 tetrahedra), no
-        ``P=`` and a scalar discretisation (``ValueError`` otherwise, before the GPU is touched);
-        ``lambda_v_bounds`` stays the caller's: ``(0.3924, 2.0598)`` on P2 triangles.  Limit: the time-invariant linear
+        Needs a ``fem.ReactionTerm`` as forward operator (P1 or P2 triangles, P1 tetrahedra, Q2
+        quadrilaterals of ``fem.rectangle_q2``), no ``P=`` and a scalar discretisation
+        (``ValueError`` otherwise, before the GPU is touched); ``lambda_v_bounds`` stays the
+        caller's: ``(0.3924, 2.0598)`` on P2 triangles, ``(0.25, 1.5625)`` on Q2.  Limit: the time-invariant linear
         part ``L`` of the term only.
 
         ``comm`` (a transport of ``control_amd.dist``; with ``device=True`` only): the loop on
@@ -773,9 +774,10 @@ class Stationary:
         ``device=True``: the same loop with the iterate in HBM (``control_amd.reaction``): one
         block system and one preconditioner live through all iterations, and the forward
         operator is re-assembled and the linearised blocks re-composed by device kernels.  The
-        forward operator must be a ``fem.ReactionTerm`` (P1 or P2 triangles, P1 tetrahedra), the
-        backend a ``GpuBackend``, and ``P`` is not taken.  ``lambda_v_bounds`` stays the
-        caller's: ``(0.3924, 2.0598)`` on P2 triangles.  Afterwards ``non_linear_info`` holds
+        forward operator must be a ``fem.ReactionTerm`` (P1 or P2 triangles, P1 tetrahedra, Q2
+        quadrilaterals of ``fem.rectangle_q2``), the backend a ``GpuBackend``, and ``P`` is not
+        taken.  ``lambda_v_bounds`` stays the caller's: ``(0.3924, 2.0598)`` on P2 triangles,
+        ``(0.25, 1.5625)`` on Q2.  Afterwards ``non_linear_info`` holds
         the linear iteration counts."""
         if device:
             from .reaction import device_stationary_non_linear_solve

@@ -22,8 +22,15 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
                             "plan (kkt_set_relinearisation)");
     need(d->nq == 7 || d->nq == 15 || d->nq == 25,
          "nq must be 7 (P1 triangles, Radon's rule), 15 (P1 tetrahedra, Stroud's T3:5-1) or 25 "
-         "(P2 triangles, the 5 x 5 conical rule)");
-    const int nv = d->nq == 7 ? 3 : d->nq == 15 ? 4 : 6, ep = nv * nv;
+         "(P2 triangles, the 5 x 5 conical rule; with nv = 9 Q2 quadrilaterals, the 5 x 5 "
+         "Gauss-Legendre product rule)");
+    const int inferred = d->nq == 7 ? 3 : d->nq == 15 ? 4 : 6;
+    need(d->nv == 0 || d->nv == 3 || d->nv == 4 || d->nv == 6 || d->nv == 9,
+         "nv must be 0 (inferred from nq), 3, 4, 6 or 9 (Q2 quadrilaterals, with nq = 25)");
+    need(d->nv == 0 || d->nv == inferred || (d->nv == 9 && d->nq == 25),
+         "nv = " + std::to_string(d->nv) + " contradicts nq = " + std::to_string(d->nq) +
+             " (nq = 7: nv = 3, nq = 15: nv = 4, nq = 25: nv = 6 or 9)");
+    const int nv = d->nv ? d->nv : inferred, ep = nv * nv;
     need(d->n_t >= 1 && d->ne > 0 && d->n1 > 0 && d->nnz > 0, "sizes must be positive");
     need(d->degree >= 0 && d->degree <= REACTION_MAX_DEGREE, "degree must be 0 .. 4");
     // n_t == 1: the stationary system [[M, D^T], [D, -(1/beta) M]] -- one level, no time step
@@ -85,7 +92,8 @@ void reaction_set(System &S, const kkt_reaction_desc *d) {
         HIPCHK(hipMemset(P->d_rhalo, 0, 2 * n1 * 8));
     }
     // E is a hipMalloc of its own, so 256-byte aligned: the 16-byte stores of the
-    // tetrahedral and the P2 kernel rely on it (128 and 288 bytes a matrix).  n_entries fits an int32 (check_lists:
+    // tetrahedral and the P2 kernel rely on it (128 and 288 bytes a matrix; a Q2 matrix has
+    // 648 bytes, is only 8-byte aligned and is written in runs of 8-byte stores).  n_entries fits an int32 (check_lists:
     // cptr[nnz] == n_entries), so n_entries * D_n * 8 stays far inside int64
     P->d_E = P->mem.alloc<double>(n_entries * w.D_n);
     P->d_D = P->mem.alloc<double>(nnz * w.D_n);

@@ -22,8 +22,9 @@ struct ReactionCoef {
 };
 
 struct ReactionPlan {
-    // the element: nodes per cell (3: P1 triangles, 4: P1 tetrahedra, 6: P2 triangles), quadrature
-    // points (7: Radon's rule, 15: Stroud's T3:5-1, 25: the 5 x 5 conical rule) and entries of one
+    // the element: nodes per cell (3: P1 triangles, 4: P1 tetrahedra, 6: P2 triangles, 9: Q2
+    // quadrilaterals), quadrature points (7: Radon's rule, 15: Stroud's T3:5-1, 25: the 5 x 5
+    // conical rule, or the 5 x 5 Gauss-Legendre product rule on Q2) and entries of one
     // element matrix, nv * nv.  d_lam: the nq x nv values of the shape functions at the points
     int nv = 0, nq = 0, ep = 0;
     // n_t == 1: the stationary system [[M, D^T], [D, -(1/beta) M]] of Control.Stationary.  One

@@ -1,5 +1,5 @@
 // Kernels of the scalar reaction re-linearisation (reaction.hpp): element matrices (P1 triangles
-// and tetrahedra, P2 triangles) of a polynomial reaction coefficient, the Picard residual of the heat-type optimality system (and of
+// and tetrahedra, P2 triangles, Q2 quadrilaterals) of a polynomial reaction coefficient, the Picard residual of the heat-type optimality system (and of
 // the stationary one, n_t == 1), its Crank-Nicolson right-hand side and the update of the iterate.
 // gfx950, wave64; every store is a plain vector store, and no floating-point atomics: every sum
 // runs in a fixed order.  Gather and composition are relin_kernels.hip's.
@@ -182,12 +182,117 @@ __global__ __launch_bounds__(256) void reaction_elements_p2_kernel(
     }
 }
 
+constexpr int Q2_NV = 9;      // nodes of a Q2 quadrilateral: 3 j + i, i along x, j along y
+constexpr int Q2_NQ = 25;     // the 5 x 5 Gauss-Legendre product rule, degree 9 per variable
+constexpr int Q2_EP = 81;     // entries of its element matrix
+
+// The same statement on Q2 quadrilaterals: `phi` holds the 25 x 9 values of the tensor-product
+// shape functions at the points, s_q is summed left to right over the nine nodes, W_eq = wq_q
+// hx hy, all 81 entries on their own.  81 sums are 162 VGPRs, so three lanes share one (element,
+// level): lane t works on pair t / 3 and owns the rows part, part + 3, part + 6 with part = t % 3
+// -- 27 sums.  Every lane recomputes s_q, g and W g (about 25 operations a point against 57 of
+// its own); every entry is still ((W g) phi_qa) phi_qb summed over q ascending, so the bits do
+// not depend on the split.  The nine phi_q. of s_q and of the columns are uniform over the wave
+// and come by scalar loads, one point a round (18 SGPRs; P2's rounds of five points would be 90
+// and spill); the three phi_qa of the lane's own rows depend on the lane and are read from a copy
+// of the table in LDS (1800 bytes, three addresses a wave).
+//
+// The stores are staged through LDS: a lane's piece of E is only 8-byte aligned (648 bytes a
+// matrix), and written directly a store is 64 pieces of 8 bytes 216 bytes apart -- 42 M requests
+// for the 340 MB of 128^2 cells x 32 levels, which bound the kernel (profiles/
+// reaction_picard_q2.md).  In round r the three lanes of a pair hold the rows 3r, 3r + 1, 3r + 2:
+// 27 contiguous doubles.  Each round the wave lays its 64 x 9 values into its own 4608 bytes of
+// LDS (slot 9 lane + c) and reads them back slot j 64 + lane, j = 0 .. 8: a store then covers 64
+// consecutive slots, which are runs of 216 contiguous bytes of E (slot f belongs to lane-item
+// tt = t0 + f / 9, pair tt / 3, and sits at 81 pair + 27 r + 9 (tt % 3) + f % 9 = 9 tt + 54 pair
+// + 27 r + f % 9).  The loop bound is uniform over the block (the barriers); lanes past the end
+// work on the last lane-item and store nothing.
+__global__ __launch_bounds__(256) void reaction_elements_q2_kernel(
+    const double *__restrict__ v, int64_t ne, int64_t n1, int n_t,
+    const int32_t *__restrict__ cells, const double *__restrict__ W,
+    const double *__restrict__ phi, ReactionCoef C, double *__restrict__ E) {
+    constexpr int PARTS = 3, ROWS = 3, OWN = ROWS * Q2_NV;
+    __shared__ double table[Q2_NQ * Q2_NV];
+    __shared__ double stage[256 * Q2_NV];
+    for (int k = threadIdx.x; k < Q2_NQ * Q2_NV; k += blockDim.x) table[k] = phi[k];
+    const int lane = threadIdx.x & 63, wave0 = threadIdx.x - lane;
+    double *mine = stage + wave0 * Q2_NV;
+    const int64_t total = ne * n_t * PARTS;
+    for (int64_t base = blockIdx.x * (int64_t)blockDim.x; base < total;
+         base += (int64_t)gridDim.x * blockDim.x) {
+#pragma clang fp contract(off)
+        const int64_t t = min(base + threadIdx.x, total - 1);
+        const int64_t pair = t / PARTS;
+        const int part = (int)(t - pair * PARTS);
+        const int64_t l = pair / ne, e = pair - l * ne;
+        const double *vl = v + l * n1;
+        const int32_t *ce = cells + e * Q2_NV;
+        double vn[Q2_NV];
+#pragma unroll
+        for (int k = 0; k < Q2_NV; ++k) vn[k] = vl[ce[k]];
+        double acc[OWN];
+#pragma unroll
+        for (int k = 0; k < OWN; ++k) acc[k] = 0.0;
+        __syncthreads();          // the table stands; the last round's slots have been read
+        const double *own = table + part;
+#pragma unroll 1
+        for (int q = 0; q < Q2_NQ; ++q) {
+            double pa[Q2_NV];
+#pragma unroll
+            for (int k = 0; k < Q2_NV; ++k) pa[k] = phi[q * Q2_NV + k];
+            double s = pa[0] * vn[0];
+#pragma unroll
+            for (int k = 1; k < Q2_NV; ++k) {
+                const double p = pa[k] * vn[k];
+                s = s + p;
+            }
+            double g = C.c[C.degree];
+            for (int k = C.degree - 1; k >= 0; --k) {
+                const double gs = g * s;
+                g = gs + C.c[k];
+            }
+            const double wg = W[e * Q2_NQ + q] * g;
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const double wa = wg * own[q * Q2_NV + PARTS * r];
+#pragma unroll
+                for (int b = 0; b < Q2_NV; ++b) {
+                    const double term = wa * pa[b];
+                    acc[r * Q2_NV + b] = acc[r * Q2_NV + b] + term;
+                }
+            }
+        }
+        // the wave's first lane-item t0 = 3 p0 + m0: slot f is at o + 9 d + 54 ((m0 + d) / 3)
+        // + 27 r + f % 9 with d = f / 9 and o = E + 9 t0 + 54 p0, and is live for d < live
+        const int64_t t0 = base + wave0, p0 = t0 / PARTS;
+        const int m0 = (int)(t0 - p0 * PARTS);
+        const int live = (int)min((int64_t)64, total - t0);
+        double *o = E + 9 * t0 + 54 * p0;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            if (r) __syncthreads();
+#pragma unroll
+            for (int c = 0; c < Q2_NV; ++c) mine[lane * Q2_NV + c] = acc[r * Q2_NV + c];
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < Q2_NV; ++j) {
+                const int f = j * 64 + lane, d = f / Q2_NV;
+                if (d < live) o[9 * d + 54 * ((m0 + d) / PARTS) + 27 * r + f % Q2_NV] = mine[f];
+            }
+        }
+    }
+}
+
 // The kernels' levels are those of the D window: v is passed from the slot of level D_l0 (a time
 // shard's v window may start one level below), n_t is D_n.  One rank: the base 0, every level.
 void launch_reaction_elements(hipStream_t s, const ReactionPlan &P) {
     const dim3 grid(grid_of(P.ne * P.w.D_n, REACTION_ELEMENT_BLOCKS));
     const double *v = P.d_v + (int64_t)(P.w.D_l0 - P.w.v_l0) * P.n1;
-    if (P.nv == P2_NV)
+    if (P.nv == Q2_NV)
+        hipLaunchKernelGGL(reaction_elements_q2_kernel,
+                           dim3(grid_of(P.ne * P.w.D_n * 3, REACTION_ELEMENT_BLOCKS)), dim3(256),
+                           0, s, v, P.ne, P.n1, P.w.D_n, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
+    else if (P.nv == P2_NV)
         hipLaunchKernelGGL(reaction_elements_p2_kernel, grid, dim3(256), 0, s, v, P.ne, P.n1,
                            P.w.D_n, P.d_cells, P.d_W, P.d_lam, P.coef, P.d_E);
     else if (P.nv == TET_NV)

@@ -28,6 +28,7 @@ __all__ = [
     "box_p1",
     "rectangle_p2",
     "unit_square_p2",
+    "rectangle_q2",
     "ReactionTerm",
     "ConvectionTerm",
 ]
@@ -42,8 +43,8 @@ class SpatialDiscretisation:
     coords: np.ndarray        # (N_x, dim) dof coordinates
     boundary: np.ndarray      # int32 sorted dof indices on the whole boundary
     name: str = ""
-    cells: np.ndarray = None  # (n_cells, 3 | 4 | 6) node indices (P1 triangles / tetrahedra, P2
-    #                           triangles: ``rectangle_p2``)
+    cells: np.ndarray = None  # (n_cells, 3 | 4 | 6 | 9) node indices (P1 triangles / tetrahedra,
+    #                           P2 triangles: ``rectangle_p2``, Q2 quadrilaterals: ``rectangle_q2``)
 
     @property
     def n_dofs(self) -> int:
@@ -156,11 +157,35 @@ def _conical_rule():
     return lam, wq
 
 
+def _q2_shape_functions_1d(x: np.ndarray) -> np.ndarray:
+    """The three 1-D quadratic Lagrange functions on [0, 1] (nodes 0, 1/2, 1) at ``x``: (3, n),
+    the expressions of ``_p1p2_1d``."""
+    return np.stack([2 * (x - 0.5) * (x - 1.0), 4 * x * (1.0 - x), 2 * x * (x - 0.5)])
+
+
+def _gauss_square_rule():
+    """``(points, wq, basis)`` of the 5 x 5 Gauss-Legendre product rule on the unit square: 25
+    interior points, positive weights, degree 9 in each variable (and not 10).  With ``t`` / ``wt``
+    the Gauss-Legendre nodes and weights on [0, 1], point ``q = 5 r + s`` is ``(t_s, t_r)`` and
+    its weight ``wt_r wt_s``, a fraction of the area.  ``basis[q, 3 j + i] = l_i(t_s) l_j(t_r)``
+    are the nine Q2 shape functions at the points (``i`` along x, ``j`` along y), each entry one
+    rounded product of the 1-D values.
+
+    Degree 9 per variable is what the reference's coefficient ``2 + 0.5 v^2`` needs on Q2 to be
+    integrated exactly: ``v^2`` has degree 4 per variable and so has ``phi_a phi_b``, together 8."""
+    t, wt = _gauss(5)
+    pts = np.stack([np.tile(t, 5), np.repeat(t, 5)], axis=1)
+    wq = np.repeat(wt, 5) * np.tile(wt, 5)
+    l = _q2_shape_functions_1d(t)                               # (3, 5): l[i, s]
+    basis = (l.T[None, :, None, :] * l.T[:, None, :, None]).reshape(25, 9)   # [r, s, j, i]
+    return pts, wq, basis
+
+
 class ReactionTerm:
     """The forward form ``(L u, w) + (g(v_old) u, w)`` with a polynomial reaction coefficient
     ``g(s) = sum_k c_k s^k`` (``coefficients = (c_0, ..., c_p)``, ``p <= 4``) on P1 triangles,
-    P1 tetrahedra or P2 triangles (``disc.cells`` with 3, 4 or 6 columns) -- the reference's
-    non-linear scalar problem is ``grad v . grad w + (2 + 0.5 v^2) v w``
+    P1 tetrahedra, P2 triangles or Q2 quadrilaterals (``disc.cells`` with 3, 4, 6 or 9 columns)
+    -- the reference's non-linear scalar problem is ``grad v . grad w + (2 + 0.5 v^2) v w``
     (``test/test_control.py:715-719``): ``ReactionTerm(disc, (2, 0, 0.5))``.
 
     ``L`` is ``nu * disc.K``, or any CSR matrix ``linear`` inside the structure of ``disc.M``
@@ -193,6 +218,13 @@ class ReactionTerm:
 
     and all 36 entries are computed on their own.  On P1 elements ``basis`` is ``lam``.
 
+    On Q2 quadrilaterals (``rectangle_q2``: axis-parallel cells, local node ``3 j + i`` with ``i``
+    along x and ``j`` along y) the points are the 25 of ``_gauss_square_rule`` (degree 9 per
+    variable): ``lam`` (25, 2) holds their coordinates in the unit square, ``basis`` (25, 9) the
+    tensor-product shape functions ``l_i(x_q) l_j(y_q)``.  ``area = hx hy`` comes from the corner
+    nodes 0, 2 and 6, ``W_eq = wq_q area_e``; ``s_q`` is summed left to right over the nine nodes,
+    ``g`` and ``E[a][b]`` are as on P2 triangles, and all 81 entries are computed on their own.
+
     The flat element entry is ``e nv^2 + nv a + b`` for ``nv`` nodes per cell.  The entries are
     summed into the structure of ``M`` by ``np.bincount`` (ascending element-entry order), and
     ``D = L + C`` with one rounding."""
@@ -202,9 +234,10 @@ class ReactionTerm:
     def __init__(self, disc, coefficients, *, nu=1.0, linear=None):
         from .blocks import conform_to
         cells = getattr(disc, "cells", None)
-        if cells is None or np.ndim(cells) != 2 or np.shape(cells)[1] not in (3, 4, 6):
-            raise ValueError("ReactionTerm needs a discretisation by P1 or P2 triangles or P1 "
-                             "tetrahedra (disc.cells with 3, 6 or 4 columns)")
+        if cells is None or np.ndim(cells) != 2 or np.shape(cells)[1] not in (3, 4, 6, 9):
+            raise ValueError("ReactionTerm needs a discretisation by P1 or P2 triangles, P1 "
+                             "tetrahedra or Q2 quadrilaterals (disc.cells with 3, 6, 4 or 9 "
+                             "columns: rectangle_q2, not unit_square_q2)")
         self.coefficients = tuple(float(c) for c in coefficients)
         if not 1 <= len(self.coefficients) <= self.MAX_DEGREE + 1:
             raise ValueError(f"ReactionTerm: the degree must be 0 .. {self.MAX_DEGREE}")
@@ -224,13 +257,19 @@ class ReactionTerm:
             d1, d2 = X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]
             self.area = 0.5 * np.abs(d1[:, 0] * d2[:, 1] - d1[:, 1] * d2[:, 0])
             self.W = self.wq[None, :] * self.area[:, None]
+        elif nv == 9:
+            self.lam, self.wq, basis = _gauss_square_rule()
+            hx, hy = X[:, 2, 0] - X[:, 0, 0], X[:, 6, 1] - X[:, 0, 1]
+            self.area = np.abs(hx * hy)
+            self.W = self.wq[None, :] * self.area[:, None]
         else:
             self.lam, self.wq = _stroud_rule()
             A = np.concatenate([np.ones((len(X), 4, 1)), X], axis=2)
             self.volume = np.abs(np.linalg.det(A)) / 6.0
             self.W = self.wq[None, :] * self.volume[:, None]
         #: (nq, nv) values of the shape functions at the points (P1: the barycentric coordinates)
-        self.basis = _p2_shape_functions(self.lam) if nv == 6 else self.lam
+        self.basis = (_p2_shape_functions(self.lam) if nv == 6 else basis if nv == 9
+                      else self.lam)
         rows = np.repeat(self.cells, nv, axis=1).ravel()
         cols = np.tile(self.cells, (1, nv)).ravel()
         #: position in the structure of ``M`` of every flat element entry ``e nv^2 + nv a + b``
@@ -456,11 +495,45 @@ def unit_square_q2(n: int, length: float = 1.0) -> SpatialDiscretisation:
                                  f"Q2 {n}x{n}")
 
 
-# --------------------------------------------------------------- Taylor-Hood (Q2-Q1)
-
 def _gauss(npts=4):
     x, w = np.polynomial.legendre.leggauss(npts)
     return 0.5 * (x + 1.0), 0.5 * w          # on [0, 1]
+
+
+def rectangle_q2(nx: int, ny: int, lx: float = 1.0, ly: float = 1.0) -> SpatialDiscretisation:
+    """Q2 on the ``nx x ny`` quadrilateral mesh of ``[0,lx] x [0,ly]``, assembled from elements:
+    the space of ``unit_square_q2`` (for ``nx = ny``, ``lx = ly``: its ``coords`` and ``boundary``
+    array for array, its matrices to rounding) with the element data ``ReactionTerm`` needs.  Dofs
+    are the points of the ``(2nx+1) x (2ny+1)`` grid in y-major order; ``cells`` is ``(nx ny, 9)``
+    int32 with local node ``3 j + i`` (``i`` along x, ``j`` along y, each 0..2), cell ``(ex, ey)``
+    at index ``ey nx + ex``.  The element matrices are the tensor products of the 1-D ones of
+    ``_p2_1d``.  The Jacobi-scaled mass matrix has its spectrum in ``(0.25, 1.5625)`` (the
+    reference's interval for Q2)."""
+    nvx, nvy = 2 * nx + 1, 2 * ny + 1
+    hx, hy = lx / nx, ly / ny
+    m = np.array([[4.0, 2.0, -1.0], [2.0, 16.0, 2.0], [-1.0, 2.0, 4.0]])
+    k = np.array([[7.0, -8.0, 1.0], [-8.0, 16.0, -8.0], [1.0, -8.0, 7.0]])
+    Mx, My = hx / 30.0 * m, hy / 30.0 * m
+    Kx, Ky = 1.0 / (3.0 * hx) * k, 1.0 / (3.0 * hy) * k
+    Me = np.kron(My, Mx)                                        # [3 j + i, 3 j' + i']
+    Ke = np.kron(My, Kx) + np.kron(Ky, Mx)
+    ex, ey = np.meshgrid(np.arange(nx), np.arange(ny), indexing="xy")
+    first = (2 * ey.ravel() * nvx + 2 * ex.ravel())[:, None]
+    i, j = np.tile(np.arange(3), 3), np.repeat(np.arange(3), 3)
+    cells = np.ascontiguousarray(first + (j * nvx + i)[None, :], dtype=np.int32)
+    ne, n = nx * ny, nvx * nvy
+    xs, ys = np.linspace(0.0, lx, nvx), np.linspace(0.0, ly, nvy)
+    XX, YY = np.meshgrid(xs, ys, indexing="xy")
+    coords = np.stack([XX.ravel(), YY.ravel()], axis=1)
+    onb = ((coords[:, 0] == 0.0) | (coords[:, 0] == xs[-1])
+           | (coords[:, 1] == 0.0) | (coords[:, 1] == ys[-1]))
+    return SpatialDiscretisation(
+        _assemble_like(np.broadcast_to(Me, (ne, 9, 9)), cells, cells, (n, n)),
+        _assemble_like(np.broadcast_to(Ke, (ne, 9, 9)), cells, cells, (n, n)), coords,
+        np.flatnonzero(onb).astype(np.int32), f"rectangle_q2({nx},{ny})", cells)
+
+
+# --------------------------------------------------------------- Taylor-Hood (Q2-Q1)
 
 
 def _p1p2_1d(n: int, length: float):

@@ -1,7 +1,7 @@
 """The scalar Picard / Gauss-Newton loop on the device (``kkt_set_reaction_relinearisation``,
 DESIGN.md section 6.6a): ``Instationary.non_linear_solve(device=True)`` and
 ``Stationary.non_linear_solve(device=True)`` for a forward operator declared as a
-``fem.ReactionTerm``, on P1 or P2 triangles, P1 tetrahedra, on one GPU or -- the instationary loop,
+``fem.ReactionTerm``, on P1 or P2 triangles, P1 tetrahedra or Q2 quadrilaterals, on one GPU or -- the instationary loop,
 with ``comm=`` -- on time shards.
 
 Host side: ``ReactionPlan`` -- the element tables of the term, the contribution lists that make
@@ -29,8 +29,9 @@ __all__ = ["ReactionPlan", "DeviceReaction", "device_non_linear_solve",
 
 def _check(ctl, P=None, comm=None, host_allreduce=None):
     """The ``ValueError``s of ``non_linear_solve(device=True)``: nothing here touches the GPU.
-    A ``fem.ReactionTerm`` is on P1 or P2 triangles, P1 tetrahedra by construction (its own
-    ``ValueError`` names triangles and tetrahedra), and all three run here."""
+    A ``fem.ReactionTerm`` is on P1 or P2 triangles, P1 tetrahedra or Q2 quadrilaterals
+    (``fem.rectangle_q2``) by construction (its own ``ValueError`` names them), and all four run
+    here."""
     if comm is not None and comm.world > 1:
         if not callable(getattr(comm, "attach", None)):
             raise ValueError("comm must be a transport of control_amd.dist (it attaches itself to "
@@ -107,13 +108,14 @@ class ReactionPlan:
     def descriptor(self):
         """``kkt_reaction_desc`` over this plan's arrays (valid while ``keep`` lives).  ``nq``, the
         number of quadrature points of the term's rule, tells the library the element: 7 for P1
-        triangles, 15 for P1 tetrahedra, 25 for P2 triangles; the tables go as the term holds them
+        triangles, 15 for P1 tetrahedra, 25 for P2 triangles and for Q2 quadrilaterals, which
+        ``nv`` (the nodes per cell, 6 or 9) tells apart; the tables go as the term holds them
         (``lam``: ``term.basis``, the shape functions at the points)."""
         term, disc = self.term, self.ctl._disc
         i32, f64, keep = _marshal()
         c = (C.c_double * 5)(*self.coefficients)
         d = _lib.ReactionDesc(
-            n_t=self.n_t, cn=int(self.CN), nq=term.W.shape[1], ne=len(term.cells),
+            n_t=self.n_t, cn=int(self.CN), nq=term.W.shape[1], nv=term.nv, ne=len(term.cells),
             n1=disc.n_dofs, tau=float(self.tau), beta=float(self.beta), cells=i32(term.cells),
             W=f64(term.W), lam=f64(term.basis), nnz=term.M.nnz, indptr=i32(term.M.indptr),
             indices=i32(term.M.indices), tperm=i32(self.tperm), cptr=i32(self.lists[0]),
@@ -166,7 +168,8 @@ class DeviceReaction(DevicePlanBinding):
     def _debug_arrays(self):
         """``kkt_debug_reaction_array``: ``"E"`` (n_t, ne, nv, nv) or ``"D"`` (n_t, nnz) of the
         last assembly, ``"v"`` / ``"zeta"`` (n_t, n) of the iterate (P1 or P2 triangles, P1
-        tetrahedra: ``nv`` = 3 or 6 nodes per triangle, 4 per tetrahedron) -- on a time shard the levels of ``window["D"]``, ``window["v"]`` and
+        tetrahedra, Q2 quadrilaterals: ``nv`` = 3 or 6 nodes per triangle, 4 per tetrahedron, 9 per
+        quadrilateral) -- on a time shard the levels of ``window["D"]``, ``window["v"]`` and
         ``window["zeta"]``, halo levels included."""
         n, (ne, nv) = self.ctl._disc.n_dofs, self.plan.term.cells.shape
         return {"E": ("D", (ne, nv, nv)), "D": ("D", (self.plan.term.M.nnz,)),
@@ -227,8 +230,9 @@ def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bou
     iteration then assembles, evaluates the residual (the host reads its norm), re-composes the
     blocks that carry ``D`` (the preconditioner is marked stale and rebuilt by the next solve),
     solves and updates on the GPU.  The stopping logic is the host loop's.  The term may be on P1
-    or P2 triangles, P1 tetrahedra; ``lambda_v_bounds`` stays the caller's, as in the reference
-    (P2 triangles: ``(0.3924, 2.0598)``, ``test/test_control.py:3476``).
+    or P2 triangles, P1 tetrahedra or Q2 quadrilaterals; ``lambda_v_bounds`` stays the caller's, as
+    in the reference (P2 triangles: ``(0.3924, 2.0598)``, ``test/test_control.py:3476``; Q2:
+    ``(0.25, 1.5625)``, ``test/test_control.py:93``).
 
     ``comm`` (``control_amd.dist``): the system is time-sharded, every rank makes this call on the
     same global problem and runs the loop on its own levels (``DeviceReaction``); the first build
@@ -315,8 +319,8 @@ def device_stationary_non_linear_solve(ctl, *, P=None, solver_parameters=None,
     attached to it; every iteration assembles ``D`` at the device iterate, evaluates the rows of
     ``Stationary.non_linear_res_eval`` (they are the right-hand side), re-composes ``D^T`` and
     ``D`` (the preconditioner is marked stale and rebuilt by the next solve), solves and updates
-    on the GPU.  P1 or P2 triangles, P1 tetrahedra; ``lambda_v_bounds`` is the caller's (P2
-    triangles: ``(0.3924, 2.0598)``)."""
+    on the GPU.  P1 or P2 triangles, P1 tetrahedra, Q2 quadrilaterals; ``lambda_v_bounds`` is the
+    caller's (P2 triangles: ``(0.3924, 2.0598)``, Q2: ``(0.25, 1.5625)``)."""
     from .control import GpuBackend, _multigrid_kw
     _check(ctl, P)
     backend = backend or GpuBackend()

@@ -506,9 +506,9 @@ enum { KKT_RELIN_EV = 0, KKT_RELIN_EP = 1, KKT_RELIN_D2 = 2, KKT_RELIN_DP = 3, K
 int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
 /* ---- Device re-linearisation of the scalar reaction problem.
  *
- * The forward operator is (L u, w) + (g(v_old) u, w) on P1 or P2 triangles or P1 tetrahedra with
- * the polynomial g(s) = sum_k c[k] s^k, degree <= 4 (fem.ReactionTerm).  nq selects the element,
- * with nv nodes per cell:
+ * The forward operator is (L u, w) + (g(v_old) u, w) on P1 or P2 triangles, P1 tetrahedra or Q2
+ * quadrilaterals with the polynomial g(s) = sum_k c[k] s^k, degree <= 4 (fem.ReactionTerm).  nq
+ * and nv (nodes per cell) select the element; nv = 0 leaves it to nq (7 -> 3, 15 -> 4, 25 -> 6):
  *   nq = 7:  P1 triangles (nv = 3), Radon's 7 points; cells ne x 3, lam 7 x 3, E ne x 9 per level;
  *   nq = 15: P1 tetrahedra (nv = 4), the 15 points of Stroud's T3:5-1 (degree 5, positive
  *            weights); cells ne x 4, lam 15 x 4, E ne x 16 per level, W = weight times the volume;
@@ -516,7 +516,12 @@ int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
  *            (0,2)), the 25 points of the 5 x 5 conical product rule (degree 9, positive weights,
  *            interior points); cells ne x 6, lam 25 x 6, W ne x 25 (weight times the area of the
  *            vertex triangle), E ne x 36 per level;
- * any other nq is KKT_ERR_ARG.  lam holds the nq x nv values of the element's shape functions at
+ *   nq = 25, nv = 9: Q2 quadrilaterals (axis-parallel cells, local node 3 j + i with i along x
+ *            and j along y), the 25 points of the 5 x 5 Gauss-Legendre product rule (degree 9 per
+ *            variable, positive weights, interior points; point 5 r + s is (t_s, t_r)); cells
+ *            ne x 9, lam 25 x 9, W ne x 25 (weight times hx hy), E ne x 81 per level;
+ * any other nq, any other non-zero nv and an nv that contradicts nq (nv = 9 with nq = 7, nv = 6
+ * with nq = 15) are KKT_ERR_ARG naming the field.  lam holds the nq x nv values of the element's shape functions at
  * the points (barycentric coordinates on P1 elements).  Per (element, level) the element matrix
  *   E[a][b] = sum_q (W_eq g(s_q)) lam_qa lam_qb,   s_q = sum_c lam_qc v_c summed left to right,
  * over the points q ascending from 0.0, g by Horner from c[degree] down, every product and sum
@@ -525,7 +530,7 @@ int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
  * np.bincount's order) and D = L + C with one rounding per entry.  The element matrices of all
  * levels are kept: n_t * ne * nv * nv doubles beside D (n_t * nnz) -- on 64^3 cells x 128 levels
  * of tetrahedra 25.8 GB and 4 GB, on 256^2 cells x 64 levels of P2 triangles 2.4 GB of element
- * matrices.  The handle must be a scalar instationary layout
+ * matrices, on 256^2 cells x 64 levels of Q2 quadrilaterals (81 doubles per matrix) 2.7 GB.  The handle must be a scalar instationary layout
  * (n_blocks_00 = n_blocks_11 = m, nx0 = nx1 = n1; m = n_t, Crank-Nicolson n_t - 1), finalized.
  * A time-sharded handle (kkt_set_shard: one block family) takes its share of the same global
  * descriptor: with [lo, hi) its block rows it keeps the levels those rows read -- backward Euler
@@ -551,7 +556,11 @@ int kkt_debug_relin_array(kkt_handle plan, int which, double *out, int64_t cap);
 typedef struct kkt_reaction_desc {
     int n_t, cn, nq;              /* time levels (1: the stationary system), Crank-Nicolson (1)
                                      or backward Euler; nq = 7: P1 triangles (nv = 3), nq = 15:
-                                     P1 tetrahedra (nv = 4), nq = 25: P2 triangles (nv = 6) */
+                                     P1 tetrahedra (nv = 4), nq = 25: P2 triangles (nv = 6) or
+                                     Q2 quadrilaterals (nv = 9) */
+    int nv;                       /* nodes per cell; 0: inferred from nq (25: P2 triangles).  It
+                                     sits in what was padding before ne: a zeroed descriptor of
+                                     the earlier layout reads as nv = 0 */
     int64_t ne, n1;               /* cells, dofs of the space */
     double tau, beta;
     const int32_t *cells;         /* ne x nv nodes per cell */
@@ -607,7 +616,7 @@ int kkt_reaction_residual_device(kkt_handle plan, double *d_out, int rhs, double
  * the next assembly. */
 int kkt_reaction_update_device(kkt_handle plan, double *d_u);
 /* Test hook: the element matrices E (n_t x ne x nv x nv: 9 doubles per P1 triangle, 16 per
- * tetrahedron, 36 per P2 triangle) or D (n_t x nnz) of the last assembly
+ * tetrahedron, 36 per P2 triangle, 81 per Q2 quadrilateral) or D (n_t x nnz) of the last assembly
  * (KKT_ERR_STATE before one), or v / zeta (n_t x n1) of the iterate, copied to the host; cap:
  * doubles available at out (KKT_ERR_ARG when too small).  On a time shard the levels of the
  * windows, in order: E and D those of the D window, v and zeta their own, halo levels included. */

@@ -2,7 +2,9 @@
 one GPU -- or, with ``--mesh cube``, the same problem on P1 tetrahedra (``box_p1(n, n, n)``; the
 record of ``profiles/reaction_picard_3d.md`` is ``--mesh cube --n 32 --n_t 32``) or, with
 ``--mesh p2``, on P2 triangles (``unit_square_p2(n)``; ``profiles/reaction_picard_p2.md`` is
-``--mesh p2 --n 128 --n_t 32``) --: wall time of
+``--mesh p2 --n 128 --n_t 32``) or, with ``--mesh q2``, on Q2 quadrilaterals
+(``rectangle_q2(n, n)``; ``profiles/reaction_picard_q2.md`` is ``--mesh q2 --n 128 --n_t 32
+--multigrid 0``) --: wall time of
 a Picard iteration outside the linearised solve, the host loop against
 ``non_linear_solve(device=True)``.  Both paths run in one process, alternating, after one warm-up
 iteration each.  One JSON line per loop.
@@ -22,7 +24,7 @@ from control_amd import fem, multiblock
 from control_amd.control import GpuBackend, Instationary
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mesh", choices=("square", "cube", "p2"), default="square")
+ap.add_argument("--mesh", choices=("square", "cube", "p2", "q2"), default="square")
 ap.add_argument("--n", type=int, default=256)
 ap.add_argument("--n_t", type=int, default=64)
 ap.add_argument("--beta", type=float, default=1.0e-4)
@@ -33,10 +35,12 @@ ap.add_argument("--multigrid", type=int, default=1)
 a = ap.parse_args()
 
 disc = {"cube": lambda: fem.box_p1(a.n, a.n, a.n), "p2": lambda: fem.unit_square_p2(a.n),
+        "q2": lambda: fem.rectangle_q2(a.n, a.n),
         "square": lambda: fem.unit_square_p1(a.n)}[a.mesh]()
 # the interval of the mass solves: Wathen's bounds for P1 triangles / P1 tetrahedra, the
-# reference's interval for P2 triangles
-MASS = {"cube": (0.5, 2.5), "p2": (0.3924, 2.0598), "square": None}[a.mesh]
+# reference's intervals for P2 triangles and for Q2
+MASS = {"cube": (0.5, 2.5), "p2": (0.3924, 2.0598), "q2": (0.25, 1.5625),
+        "square": None}[a.mesh]
 
 
 def v_d(X, t):
