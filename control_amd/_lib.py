@@ -101,7 +101,8 @@ class CoarseStats(C.Structure):
 class SpectrumStats(C.Structure):
     _fields_ = ([(n, C.c_int64) for n in ("matrices", "batches", "lanczos_steps", "power_steps", "launches",
                                           "syncs", "twin_syncs", "lanczos_syncs_max", "fallbacks",
-                                          "batch_bytes")] + [("ms", C.c_double)])
+                                          "batch_bytes")] + [("ms", C.c_double)] +
+                [(n, C.c_int64) for n in ("alias_blocks", "aliased")])
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -329,6 +330,7 @@ SIGNATURES = {
     "kkt_debug_pc_forms": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "kkt_debug_pc_solves": (C.c_int, [C.c_void_p, c_f64p, C.c_int]),
     "kkt_debug_pc_matrices": (C.c_int, [C.c_void_p, c_f64p, C.c_int]),
+    "kkt_debug_pc_alias": (C.c_int, [C.c_void_p, c_i32p, C.c_int]),
     "kkt_debug_mass_tile_values": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                              c_f64p, c_i32p, c_f64p]),
     "kkt_get_info": (C.c_int, [C.c_void_p, C.POINTER(Info)]),

@@ -115,6 +115,7 @@ static const OptionKey option_keys[] = {
     {"coarse_keep", "0 | 1", set_switch<&Options::coarse_keep>},
     {"coarse_blocks", "0 | 1", set_switch<&Options::coarse_blocks>},
     {"spectrum_batch", "0..4096", set_int<&Options::spectrum_batch, 0, 4096>},
+    {"pc_alias", "0 | 1", set_switch<&Options::pc_alias>},
     {"coarse_rings", "0 | 1", set_switch<&Options::coarse_rings>},
     {"tile_coarse_cache", "auto | 0 | 1 | 2", set_tile_coarse_cache},
     {"tile_coarse_rows", "block | full", set_tile_coarse_rows},
@@ -631,6 +632,14 @@ int kkt_debug_pc_forms(kkt_handle h, int32_t *out, int cap) {
         std::vector<int32_t> rec;
         if (S.pc) S.pc->plain_forms(rec);
         return put_forms(rec, KKT_PC_FORM_INTS, out, cap);
+    });
+}
+
+int kkt_debug_pc_alias(kkt_handle h, int32_t *out, int cap) {
+    KKT_TRY(h, {
+        std::vector<int32_t> rec;
+        if (S.pc) S.pc->alias_records(rec);
+        return put_forms(rec, KKT_PC_ALIAS_INTS, out, cap);
     });
 }
 

@@ -107,6 +107,7 @@ void SchurPC::values_changed() {
     mats_.clear();
     mat_recs_.clear();
     solve_recs_.clear();
+    alias_recs_.clear();
     einvs_.clear();
     pending_coarse_.clear();
     S_.spectrum_stats = kkt_spectrum_stats{};
@@ -569,11 +570,36 @@ std::vector<std::pair<const double *, double>> SchurPC::solved_matrices() const 
     return out;
 }
 
+// The stored blocks the program multiplies with (the right-hand-side products and the updates of
+// the sweeps), in emission order.
+std::vector<const double *> SchurPC::multiplied_blocks() const {
+    std::vector<const double *> out;
+    if (d_.kind == KKT_PC_STATIONARY) {
+        out.push_back(block_vals(KKT_Q10, 0, 0));
+        return out;
+    }
+    for (int i = lo_; i < hi_; ++i) {
+        out.push_back(block_vals(KKT_Q10, i, i));
+        if (i >= 1) out.push_back(block_vals(KKT_Q10, i, i - 1));
+    }
+    for (int i = hi_ - 1; i >= lo_; --i)
+        if (i <= n_ - 2) out.push_back(block_vals(KKT_Q01, i, i + 1));
+    return out;
+}
+
+const double *SchurPC::shared_block(const double *vals) const {
+    const auto it = block_rep_.find(vals);
+    return it == block_rep_.end() ? vals : it->second;
+}
+
 void SchurPC::collect_matrices() {
     pre_.clear();
     pre_cls_.clear();
+    block_rep_.clear();
+    formed_.clear();
     const int nbatch = S_.opts.spectrum_batch;
     const bool estimates = d_.schur_emin <= 0;
+    const bool alias = S_.opts.pc_alias;
     if (nbatch <= 0 || !(estimates || coarse_cycles_ > 0)) return;
     const Pattern &P = S_.patterns[m_pat_];
     hipStream_t st = S_.stream;
@@ -581,16 +607,19 @@ void SchurPC::collect_matrices() {
     SpectrumCounters cnt;
     HIPCHK(hipStreamSynchronize(st));
     const auto t0 = std::chrono::steady_clock::now();
-    // the candidates in creation order, each formed once
+    // the candidates in creation order, each formed once (owned here until their classes are known)
     std::vector<MatKey> keys;
+    std::vector<DevBuf<double>> own_vals, own_dinv;
     for (const auto &bc : solved_matrices()) {
         uint64_t bits;
         std::memcpy(&bits, &bc.second, sizeof bits);
         const MatKey key(bc.first, bits);
         if (pre_.count(key)) continue;
+        own_vals.push_back(DevBuf<double>::alloc(P.npadded));
+        own_dinv.push_back(DevBuf<double>::alloc(nx_));
         Pre pr;
-        pr.vals = values_mem_.alloc<double>(P.npadded);
-        pr.dinv = values_mem_.alloc<double>(nx_);
+        pr.vals = own_vals.back().get();
+        pr.dinv = own_dinv.back().get();
         form_matrix(bc.first, bc.second, pr.vals, pr.dinv);
         cnt.launches += mask_ ? 3 : 2;
         pre_[key] = pr;
@@ -598,22 +627,29 @@ void SchurPC::collect_matrices() {
     }
     const int C = (int)keys.size();
     if (C == 0) return;
-    // twins: a fingerprint per candidate, then the candidates of a (shift, fingerprint) group bit
-    // for bit against the group's first
+    // "pc_alias": the stored blocks the program multiplies with ride the same search, behind the
+    // formed candidates and under a tag of their own (no shift)
+    std::vector<const double *> h_vals(C);
+    for (int i = 0; i < C; ++i) h_vals[i] = pre_[keys[i]].vals;
+    if (alias)
+        for (const double *b : multiplied_blocks())
+            if (std::find(h_vals.begin() + C, h_vals.end(), b) == h_vals.end()) h_vals.push_back(b);
+    const int N = (int)h_vals.size();
+    stats.alias_blocks += N - C;
+    // twins: a fingerprint per candidate, then the candidates of a (tag, shift, fingerprint) group
+    // bit for bit against the group's first
     spec::TwinGroups twins;
-    twins.first_of.resize(C);
-    for (int i = 0; i < C; ++i) twins.first_of[i] = i;
-    twins.pair_of.assign(C, -1);
+    twins.first_of.resize(N);
+    for (int i = 0; i < N; ++i) twins.first_of[i] = i;
+    twins.pair_of.assign(N, -1);
     std::vector<unsigned> h_flag;
     DevPool tmp;
-    if (C > 1) {
-        std::vector<const double *> h_vals(C);
-        for (int i = 0; i < C; ++i) h_vals[i] = pre_[keys[i]].vals;
+    if (N > 1) {
         const double *const *d_vals = tmp.upload(h_vals.data(), h_vals.size());
         const int nw = spec_fingerprint_blocks(P.npadded);
-        unsigned long long *d_fp = tmp.alloc<unsigned long long>((size_t)C * nw);
-        std::vector<unsigned long long> h_fp((size_t)C * nw);
-        launch_spec_fingerprint(st, d_vals, C, P.npadded, d_fp);
+        unsigned long long *d_fp = tmp.alloc<unsigned long long>((size_t)N * nw);
+        std::vector<unsigned long long> h_fp((size_t)N * nw);
+        launch_spec_fingerprint(st, d_vals, N, P.npadded, d_fp);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_fp.data(), d_fp, h_fp.size() * sizeof(unsigned long long),
                               hipMemcpyDeviceToHost, st));
@@ -621,12 +657,13 @@ void SchurPC::collect_matrices() {
         cnt.launches++;
         cnt.syncs++;
         stats.twin_syncs++;
-        std::vector<uint64_t> shifts(C), folded(C);
-        for (int i = 0; i < C; ++i) {
-            shifts[i] = keys[i].second;
+        std::vector<uint64_t> shifts(N, 0), folded(N);
+        std::vector<int> tag(N, 1);
+        for (int i = 0; i < N; ++i) {
+            if (i < C) shifts[i] = keys[i].second, tag[i] = 0;
             folded[i] = spec_fingerprint_fold(&h_fp[(size_t)i * nw], nw);
         }
-        twins = spec::group_twins(shifts, folded);
+        twins = spec::group_twins(shifts, folded, tag);
         std::vector<SpecPair> pairs;
         for (const auto &pr : twins.pairs) pairs.push_back(SpecPair{h_vals[pr.first], h_vals[pr.second]});
         if (!pairs.empty()) {
@@ -645,10 +682,33 @@ void SchurPC::collect_matrices() {
         }
     }
     // equal fingerprints, different bits: no class, left to schur_matrix's own comparison
-    std::vector<int> reps;      // the first candidate of every class
-    const std::vector<int> cls = spec::twin_classes(twins, h_flag, &reps);
+    std::vector<int> all_reps;      // the first candidate of every class
+    const std::vector<int> cls = spec::twin_classes(twins, h_flag, &all_reps);
     for (int i = 0; i < C; ++i) pre_[keys[i]].cls = cls[i];
-    pre_cls_.assign(reps.size(), PreCls{});
+    pre_cls_.assign(all_reps.size(), PreCls{});
+    // a twin reads its class's first array: the formed ones give theirs up, the stored blocks get
+    // a representative.  (Every comparison was synchronised above: nothing in flight reads them.)
+    for (int i = 0; i < N; ++i) {
+        const int first = alias && cls[i] >= 0 ? all_reps[cls[i]] : i;
+        if (first != i) stats.aliased++;
+        if (i >= C) {
+            if (first != i) block_rep_[h_vals[i]] = h_vals[first];
+            continue;
+        }
+        Pre &pr = pre_[keys[i]];
+        if (first != i) {
+            pr.vals = pre_[keys[first]].vals;
+            pr.dinv = pre_[keys[first]].dinv;
+            own_vals[i].reset();
+            own_dinv[i].reset();
+        } else {
+            values_mem_.adopt(std::move(own_vals[i]));
+            values_mem_.adopt(std::move(own_dinv[i]));
+        }
+    }
+    std::vector<int> reps;          // ... of the formed matrices: the ones to estimate
+    for (int r : all_reps)
+        if (r < C) reps.push_back(r);
     // the distinct matrices' intervals, nbatch at a time: symmetric / skew split, Lanczos on the
     // symmetric parts, power iteration on the skew parts of those that have one
     const int32_t *tpos = estimates ? transpose_positions() : nullptr;
@@ -742,9 +802,17 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
             m.vals = pre->second.vals;      // formed by the collection pass
             m.dinv = pre->second.dinv;
         } else {
-            m.vals = values_mem_.alloc<double>(P.npadded);
-            m.dinv = values_mem_.alloc<double>(nx_);
-            form_matrix(base_vals, c, m.vals, m.dinv);
+            // formed here, once per (class of the base block, shift)
+            auto &f = formed_[MatKey(shared_block(base_vals), bits)];
+            if (!f.first) {
+                f.first = values_mem_.alloc<double>(P.npadded);
+                f.second = values_mem_.alloc<double>(nx_);
+                form_matrix(base_vals, c, f.first, f.second);
+            } else {
+                S_.spectrum_stats.aliased++;
+            }
+            m.vals = f.first;
+            m.dinv = f.second;
         }
         m.index = (int)mat_recs_.size();
         MatRec r;
@@ -794,6 +862,13 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
                 break;
             }
         }
+    }
+    if (twin && S_.opts.pc_alias && m.vals != twin->vals) {
+        // found equal here and not by the collection pass: read the twin's arrays from now on
+        // (this one's stay allocated until the values change)
+        m.vals = twin->vals;
+        m.dinv = twin->dinv;
+        stats.aliased++;
     }
     if (d_.schur_emin > 0) {
         m.emin = d_.schur_emin;
@@ -871,7 +946,20 @@ SchurPC::Mat SchurPC::schur_matrix(const double *base_vals, double c, bool solve
     return m;
 }
 
-void SchurPC::note_solve(int sweep, int level, const Mat &m) {
+void SchurPC::alias_records(std::vector<int32_t> &out) const {
+    out.clear();
+    std::map<const double *, int32_t> number;      // arrays in order of first appearance
+    for (const double *p : alias_recs_) {
+        if (p && !number.count(p)) {
+            const int32_t k = (int32_t)number.size();
+            number[p] = k;
+        }
+        out.push_back(p ? number[p] : -1);
+    }
+}
+
+void SchurPC::note_solve(int sweep, int level, const Mat &m, const double *upd_vals) {
+    alias_recs_.insert(alias_recs_.end(), {m.vals, m.dinv, upd_vals});
     mat_recs_[m.index].solves++;
     solve_recs_.insert(solve_recs_.end(),
                        {(double)sweep, (double)level, (double)m.index, mat_recs_[m.index].c, m.emin,
@@ -1114,7 +1202,7 @@ void SchurPC::build_stationary() {
     double *b0 = in_, *b1 = in_ + nx_;
     double *u0 = out_, *u1 = out_ + nx_;
     emit_solves({Solve{m_vals_, m_dinv_, b0, u0}}, d_.mass_its, d_.mass_emin, d_.mass_emax, P_, nx_);
-    emit_lin({Lin{{Term{Dv, u0}}, B_, 1.0, 0.0, -1.0, nullptr, b1}});
+    emit_lin({Lin{{Term{shared_block(Dv), u0}}, B_, 1.0, 0.0, -1.0, nullptr, b1}});
     Mat S1 = schur_matrix(Dv, c), S2 = schur_matrix(Dz, c);
     schur_its_ = resolve_its(S1);
     note_solve(KKT_PC_SWEEP_FIRST, 0, S1);
@@ -1171,9 +1259,9 @@ void SchurPC::build_BE() {
             std::vector<Lin> ops;
             for (int i = c0; i < c1; ++i) {
                 Lin l;
-                l.terms.push_back(Term{block_vals(KKT_Q10, i, i), blk(u0, i)});
+                l.terms.push_back(Term{mult_vals(KKT_Q10, i, i), blk(u0, i)});
                 if (i >= 1)
-                    l.terms.push_back(Term{block_vals(KKT_Q10, i, i - 1),
+                    l.terms.push_back(Term{mult_vals(KKT_Q10, i, i - 1),
                                            i - 1 >= lo ? blk(u0, i - 1) : h_u0_});
                 l.y = blk(B_, i);
                 l.cz = -1.0;
@@ -1190,11 +1278,11 @@ void SchurPC::build_BE() {
         if (lanes) emit_wait(0, chunk_done[c]);
         for (int i = cfirst[c]; i < cfirst[c + 1]; ++i) {
             Mat F = schur_matrix(block_vals(KKT_Q10, i, i), coef(i));
-            note_solve(KKT_PC_SWEEP_FORWARD, i, F);
+            const double *upd = i >= 1 ? mult_vals(KKT_Q10, i, i - 1) : nullptr;
+            note_solve(KKT_PC_SWEEP_FORWARD, i, F, upd);
             const Solve sv{F.vals, F.dinv, blk(B_, i), blk(u1, i)};
             if (i >= 1)
-                emit_update_and_solve(Lin{{Term{block_vals(KKT_Q10, i, i - 1),
-                                                i - 1 >= lo ? blk(u1, i - 1) : h_u1_}},
+                emit_update_and_solve(Lin{{Term{upd, i - 1 >= lo ? blk(u1, i - 1) : h_u1_}},
                                           blk(B_, i), -1.0, 1.0, 0.0, blk(B_, i), nullptr},
                                       sv, schur_its_, F.emin, F.emax, F.eimag, &F);
             else
@@ -1229,11 +1317,11 @@ void SchurPC::build_BE() {
     if (up >= 0) emit_comm(nullptr, -1, h_u1_, up);
     for (int i = hi - 1; i >= lo; --i) {
         Mat G = schur_matrix(block_vals(KKT_Q01, i, i), coef(i));
-        note_solve(KKT_PC_SWEEP_BACKWARD, i, G);
+        const double *upd = i <= n - 2 ? mult_vals(KKT_Q01, i, i + 1) : nullptr;
+        note_solve(KKT_PC_SWEEP_BACKWARD, i, G, upd);
         const Solve sv{G.vals, G.dinv, blk(B_, i), blk(u1, i)};
         if (i <= n - 2)
-            emit_update_and_solve(Lin{{Term{block_vals(KKT_Q01, i, i + 1),
-                                            i + 1 < hi ? blk(u1, i + 1) : h_u1_}},
+            emit_update_and_solve(Lin{{Term{upd, i + 1 < hi ? blk(u1, i + 1) : h_u1_}},
                                       blk(B_, i), -1.0, 1.0, 0.0, blk(B_, i), nullptr},
                                   sv, schur_its_, G.emin, G.emax, G.eimag, &G);
         else
@@ -1277,9 +1365,9 @@ void SchurPC::build_CN() {
         std::vector<Lin> ops;
         for (int i = lo; i < hi; ++i) {
             Lin l;
-            l.terms.push_back(Term{block_vals(KKT_Q10, i, i), blk(u0, i)});
+            l.terms.push_back(Term{mult_vals(KKT_Q10, i, i), blk(u0, i)});
             if (i >= 1)
-                l.terms.push_back(Term{block_vals(KKT_Q10, i, i - 1),
+                l.terms.push_back(Term{mult_vals(KKT_Q10, i, i - 1),
                                        i - 1 >= lo ? blk(u0, i - 1) : h_u0_});
             l.y = blk(B_, i);
             ops.push_back(l);
@@ -1301,11 +1389,12 @@ void SchurPC::build_CN() {
     if (dn >= 0) emit_comm(nullptr, -1, h_u1_, dn);
     for (int i = lo; i < hi; ++i) {
         Mat F = schur_matrix(block_vals(KKT_Q10, i, i), c);
-        note_solve(KKT_PC_SWEEP_FORWARD, i, F);
+        const double *upd = i >= 1 ? mult_vals(KKT_Q10, i, i - 1) : nullptr;
+        note_solve(KKT_PC_SWEEP_FORWARD, i, F, upd);
         const Solve sv{F.vals, F.dinv, blk(B_, i), blk(u1, i)};
         if (i >= 1) {
             const double *prev = i - 1 >= lo ? blk(u1, i - 1) : h_u1_;
-            emit_update_and_solve(Lin{{Term{block_vals(KKT_Q10, i, i - 1), prev},
+            emit_update_and_solve(Lin{{Term{upd, prev},
                                        Term{cM.vals, prev}},
                                       blk(B_, i), -1.0, 1.0, 0.0, blk(B_, i), nullptr},
                                   sv, schur_its_, F.emin, F.emax, F.eimag, &F);
@@ -1326,11 +1415,12 @@ void SchurPC::build_CN() {
     if (up >= 0) emit_comm(nullptr, -1, h_u1_, up);
     for (int i = hi - 1; i >= lo; --i) {
         Mat G = schur_matrix(block_vals(KKT_Q01, i, i), c);
-        note_solve(KKT_PC_SWEEP_BACKWARD, i, G);
+        // the update's matrix h K^T + (c - 1) M: only multiplied with (indefinite for c < 1)
+        Mat H{};
+        if (i <= n - 2) H = schur_matrix(block_vals(KKT_Q01, i, i + 1), c, false);
+        note_solve(KKT_PC_SWEEP_BACKWARD, i, G, H.vals);
         const Solve sv{G.vals, G.dinv, blk(B_, i), blk(u1, i)};
         if (i <= n - 2) {
-            // h K^T + (c - 1) M: only multiplied with (indefinite for c < 1)
-            Mat H = schur_matrix(block_vals(KKT_Q01, i, i + 1), c, false);
             emit_update_and_solve(Lin{{Term{H.vals, i + 1 < hi ? blk(u1, i + 1) : h_u1_}},
                                       blk(B_, i), -1.0, 1.0, 0.0, blk(B_, i), nullptr},
                                   sv, schur_its_, G.emin, G.emax, G.eimag, &G);

@@ -131,6 +131,8 @@ class PcBase {
     // KKT_PC_MATRIX_VALS per distinct sub-solve matrix (include/kkt.h)
     virtual void solve_records(std::vector<double> &) const {}
     virtual void matrix_records(std::vector<double> &) const {}
+    // kkt_debug_pc_alias: KKT_PC_ALIAS_INTS values per sub-solve (include/kkt.h)
+    virtual void alias_records(std::vector<int32_t> &) const {}
     // kkt_debug_coarse_correction: the coarse space of the two-grid sub-solves, the Galerkin
     // launch constants of its set-up and the rows of P (false: built without a coarse space)
     virtual bool coarse_space(CoarseDev *, GalerkinDev *, int64_t *) const { return false; }
@@ -167,6 +169,7 @@ class SchurPC : public PcBase {
     bool coarse_space(CoarseDev *c, GalerkinDev *g, int64_t *n) const override;
     void debug_tile_levels(kkt_tile_levels *run) override;
     void matrix_records(std::vector<double> &out) const override;
+    void alias_records(std::vector<int32_t> &out) const override;
     void time_programs(float *ms, int *launches, int64_t *phases) override;
     int bc_set() const { return bc_set_; }
     // degree and interval the sub-solves of a typical time level run with (given or derived)
@@ -222,7 +225,8 @@ class SchurPC : public PcBase {
     };
     std::vector<MatRec> mat_recs_;
     std::vector<double> solve_recs_;
-    void note_solve(int sweep, int level, const Mat &m);
+    std::vector<const double *> alias_recs_;   // per sub-solve: matrix, diagonal, first update term
+    void note_solve(int sweep, int level, const Mat &m, const double *upd_vals = nullptr);
     int schur_its_ = 0;                  // degree of the sub-solves (given or derived)
     double typical_emin_ = 0.0, typical_emax_ = 0.0;
     int resolve_its(const Mat &typical);
@@ -287,6 +291,18 @@ class SchurPC : public PcBase {
     };
     std::map<MatKey, Pre> pre_;
     std::vector<PreCls> pre_cls_;
+    // Option "pc_alias": the twins the pass proves are read from one array.  A formed twin takes its
+    // class representative's vals / dinv (its own are not kept); the stored blocks the program
+    // multiplies with join the same search under a tag of their own, and shared_block() names the
+    // representative of a block's class -- an array of the system's, as the block itself.
+    // Matrices the pass does not cover (those only multiplied with) are formed once per (class of
+    // the base block, shift): form_matrix is a function of the bits of its inputs.
+    std::map<const double *, const double *> block_rep_;
+    std::map<MatKey, std::pair<double *, double *>> formed_;
+    const double *shared_block(const double *vals) const;
+    std::vector<const double *> multiplied_blocks() const;
+    // the array a product with block (i, j) of quadrant q reads
+    const double *mult_vals(int q, int i, int j) const { return shared_block(block_vals(q, i, j)); }
     void form_matrix(const double *base_vals, double c, double *vals, double *dinv);
     std::vector<std::pair<const double *, double>> solved_matrices() const;
     void collect_matrices();

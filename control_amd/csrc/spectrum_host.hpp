@@ -192,22 +192,25 @@ struct LockStep {
 // ---- the grouping of the twin search (SchurPC::collect_matrices).  Candidates come in creation
 // order with the bits of their shift and the folded fingerprint of their values.  A candidate whose
 // (shift, fingerprint) was seen before is compared bit for bit with the FIRST candidate that had
-// it; a fingerprint only prunes, it never makes a twin.
+// it; a fingerprint only prunes, it never makes a twin.  `tag` (optional, one per candidate) keeps
+// kinds of candidates apart that share a search: only candidates of one tag are ever compared.
 struct TwinGroups {
     std::vector<int> first_of;                  // i itself: candidate i opens its group
     std::vector<std::pair<int, int>> pairs;     // (group's first, candidate): to compare
     std::vector<int> pair_of;                   // the candidate's pair, -1 for a group's first
 };
 inline TwinGroups group_twins(const std::vector<uint64_t> &shift_bits,
-                              const std::vector<uint64_t> &fingerprint) {
+                              const std::vector<uint64_t> &fingerprint,
+                              const std::vector<int> &tag = {}) {
     const int C = (int)shift_bits.size();
     TwinGroups T;
     T.first_of.resize(C);
     T.pair_of.assign(C, -1);
-    std::map<std::pair<uint64_t, uint64_t>, int> groups;
+    std::map<std::pair<int, std::pair<uint64_t, uint64_t>>, int> groups;
     for (int i = 0; i < C; ++i) {
         T.first_of[i] = i;
-        const auto g = std::make_pair(shift_bits[i], fingerprint[i]);
+        const auto g = std::make_pair(tag.empty() ? 0 : tag[i],
+                                      std::make_pair(shift_bits[i], fingerprint[i]));
         const auto it = groups.find(g);
         if (it == groups.end()) {
             groups[g] = i;

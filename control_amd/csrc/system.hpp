@@ -38,6 +38,7 @@ struct Options {
     bool coarse_columns = false;                                  // "coarse_setup" = "columns"
     bool coarse_keep = false, coarse_blocks = true;
     int spectrum_batch = 32;   // "spectrum_batch": matrices per lock-step batch of estimates; 0: one at a time
+    bool pc_alias = true;      // "pc_alias": value arrays proven bit-equal by the twin search are read from one array
     bool coarse_rings = true;     // two-grid tile sweeps: tiles prolong onto their rings themselves
     int tile_coarse_cache = -1;   // ... their coarse tables in LDS: 2 lists and inverse rows, 1 lists, 0 none; -1: what fits
     bool tile_coarse_full = false;   // ... whole rows of the coarse inverse ("tile_coarse_rows" = "full")

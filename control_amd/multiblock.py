@@ -384,7 +384,9 @@ class MultiBlockSystem:
         this handle -- matrices estimated, lock-step batches (option ``spectrum_batch``), Lanczos
         and power steps, launches, host synchronisations (``twin_syncs`` of the twin search,
         ``lanczos_syncs_max`` of one batched Lanczos run), fall-backs to the one-matrix path, the
-        bytes a batch held and the milliseconds spent."""
+        bytes a batch held, the milliseconds spent and, with option ``pc_alias``, the stored
+        blocks that rode the twin search (``alias_blocks``) and the arrays read from an equal
+        earlier one (``aliased``)."""
         st = _lib.SpectrumStats()
         self._ck(self._lib.kkt_spectrum_stats_get(self._h, C.byref(st)))
         return st.as_dict()
@@ -417,6 +419,12 @@ class MultiBlockSystem:
         threads)."""
         return self._forms(self._lib.kkt_debug_pc_forms,
                            ("form", "width", "slots", "lane", "count", "variant"))
+
+    def pc_alias(self):
+        """``kkt_debug_pc_alias``: one dict per Schur sub-solve, in the order of ``pc_solves`` --
+        the device arrays the level reads as small integers (equal: the same array): ``matrix``,
+        ``dinv`` and the first term of its ``update`` (-1: a level without update)."""
+        return self._forms(self._lib.kkt_debug_pc_alias, ("matrix", "dinv", "update"))
 
     def _records(self, fn, width):
         n = fn(self._h, None, 0)

@@ -119,6 +119,15 @@ const char *kkt_last_error(kkt_handle h);
  *                                  further batches).  "0": one matrix at a time with a host round
  *                                  trip per reduction (the previous path).  Same intervals, step
  *                                  counts and preconditioner bit for bit; see kkt_spectrum_stats
+ *   "pc_alias"      "1" | "0"      Schur preconditioner: value arrays that the twin search of a
+ *                                  build proved equal bit for bit (the per-level copies mode G
+ *                                  keeps of a time-invariant operator) are read from one array --
+ *                                  the formed matrices blk + c M~ and their Jacobi diagonals, and
+ *                                  the stored blocks the updates and right-hand-side products
+ *                                  multiply with -- and the formed duplicates are not kept.  Proved
+ *                                  again by every rebuild after kkt_update_block_values.  "0":
+ *                                  every level reads its own arrays (same results bit for bit; see
+ *                                  kkt_debug_pc_alias and kkt_spectrum_stats.alias_blocks)
  *   "coarse_rings"  "1" | "0"      two-grid sub-solves in the tile form: a tile prolongs the
  *                                  coarse correction onto its ring rows itself instead of fetching
  *                                  them in a hand-off after every correction (same results; "0":
@@ -687,11 +696,15 @@ int kkt_coarse_setup_stats(kkt_handle h, kkt_coarse_stats *out);
  * is the largest count one batched Lanczos run took; fallbacks: matrices a batched build estimated
  * or compared one at a time because its collection pass had not covered them (0 expected); ms:
  * wall time of the estimates and the twin search between two synchronisations of the stream;
- * batch_bytes: device memory the largest batch held. */
+ * batch_bytes: device memory the largest batch held.  Option "pc_alias": alias_blocks: stored
+ * blocks the preconditioner multiplies with that rode the twin search (its launches and
+ * synchronisations, not counted in matrices or fallbacks); aliased: arrays, formed or stored, that
+ * the build reads from an equal earlier array instead. */
 typedef struct kkt_spectrum_stats {
     int64_t matrices, batches, lanczos_steps, power_steps, launches, syncs, twin_syncs,
         lanczos_syncs_max, fallbacks, batch_bytes;
     double ms;
+    int64_t alias_blocks, aliased;
 } kkt_spectrum_stats;
 int kkt_spectrum_stats_get(kkt_handle h, kkt_spectrum_stats *out);
 /* Test hooks of the coarse set-up.  With option "coarse_keep" = "1" every set-up keeps its Galerkin
@@ -1055,6 +1068,13 @@ enum { KKT_PC_EST_GIVEN = 0, KKT_PC_EST_LANCZOS = 1, KKT_PC_EST_SHARED = 2, KKT_
        KKT_PC_EST_ZERO_MEAN = 4, KKT_PC_EST_UPPER = 5 };
 int kkt_debug_pc_solves(kkt_handle h, double *out, int cap);
 int kkt_debug_pc_matrices(kkt_handle h, double *out, int cap);
+/* Test hook of option "pc_alias" (read-only; same calling convention as kkt_debug_pc_forms): one
+ * record of KKT_PC_ALIAS_INTS per Schur sub-solve, in the order of kkt_debug_pc_solves, naming the
+ * device arrays the level reads -- its matrix, its Jacobi diagonal, the first term of its update
+ * (-1: a level without update).  Arrays are numbered in order of first appearance; equal numbers
+ * mean the same device array. */
+enum { KKT_PC_ALIAS_INTS = 3 };
+int kkt_debug_pc_alias(kkt_handle h, int32_t *out, int cap);
 
 /* Test hook of the batched mass solves on tiles (form KKT_PC_TILE_CHEB; read-only): the mass
  * matrix's values as the tile kernels read them -- n_entries doubles in the layout of the plan's
