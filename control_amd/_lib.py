@@ -114,7 +114,10 @@ class StepLock(C.Structure):
 
 
 class RelinDesc(C.Structure):
-    _fields_ = ([("n_t", C.c_int), ("cn", C.c_int), ("nq", C.c_int),
+    # kkt_relin_desc; nv (it fills the padding before ne) selects the element: 0 P2-P1 triangles
+    # (nq = 7), 9 Q2-Q1 quadrilaterals (nq = 16: gphi / glam are the reference tables, jinv the
+    # cells' 1 / hx, 1 / hy)
+    _fields_ = ([("n_t", C.c_int), ("cn", C.c_int), ("nq", C.c_int), ("nv", C.c_int),
                  ("ne", C.c_int64), ("n2", C.c_int64), ("n1", C.c_int64),
                  ("nu", C.c_double), ("tau", C.c_double), ("beta", C.c_double),
                  ("V", c_i32p)] + [(n, c_f64p) for n in ("W", "phi", "gphi", "lam", "glam")]
@@ -124,7 +127,7 @@ class RelinDesc(C.Structure):
                 + [(n, c_i32p) for n in ("p_indptr", "p_indices", "p_tperm", "p_cptr", "p_clist")]
                 + [("Kp", c_f64p), ("Mp", c_f64p), ("nnz_b", C.c_int64),
                    ("b_indptr", c_i32p), ("b_indices", c_i32p), ("b_values", c_f64p),
-                   ("n_bc", C.c_int64), ("bc_idx", c_i32p), ("data", c_f64p)])
+                   ("n_bc", C.c_int64), ("bc_idx", c_i32p), ("data", c_f64p), ("jinv", c_f64p)])
 
 
 class RelinRecipe(C.Structure):

@@ -891,8 +891,8 @@ class Stationary:
         the three block systems and one ``StokesPC`` live through all iterations, and the forward
         operator is re-assembled, the residual evaluated and the linearised blocks re-composed by
         device kernels.  The forward operator must be a ``fem.ConvectionTerm`` on a
-        discretisation with element data (``fem.rectangle_p2p1``), ``forward_operator_p`` ``None``
-        or its ``pressure``, the backend a ``GpuBackend``, and ``P`` is not taken.  Afterwards
+        discretisation with element data (``fem.rectangle_p2p1`` or ``fem.rectangle_q2q1``),
+        ``forward_operator_p`` ``None`` or its ``pressure``, the backend a ``GpuBackend``, and ``P`` is not taken.  Afterwards
         ``non_linear_info`` holds the linear iteration counts."""
         if device:
             from .stationary_picard import device_stationary_incompressible_non_linear_solve

@@ -21,7 +21,16 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     if (S.reaction)
         fail(KKT_ERR_STATE, "kkt_set_relinearisation: the handle carries a reaction plan "
                             "(kkt_set_reaction_relinearisation)");
-    need(d->nq == RELIN_NQ, "nq must be 7 (Radon's rule)");
+    // nv == 0: the P2-P1 descriptor; nv == 9 with nq == 16: Q2-Q1 (include/kkt.h)
+    const bool q2 = d->nv == 9 && d->nq == 16;
+    if (d->nv == 0)
+        need(d->nq == RELIN_NQ, "nq must be 7 (Radon's rule)");
+    else
+        need(q2, "nv = " + std::to_string(d->nv) + " with nq = " + std::to_string(d->nq) +
+                     ": nv must be 0 (P2-P1 triangles, nq = 7) or 9 with nq = 16 (Q2-Q1 "
+                     "quadrilaterals)");
+    need(!q2 || d->jinv, "nv = 9 needs jinv (ne x 2: 1 / hx, 1 / hy per cell)");
+    const int kv = q2 ? 9 : 6, kp = q2 ? 4 : 3, ev = kv * kv, ep = kp * kp;
     need(d->n_t >= 1, "n_t must be at least 1 (1: the stationary system)");
     need(d->ne > 0 && d->n2 > 0 && d->n1 > 0, "sizes must be positive");
     // n_t == 1: the stationary outer system, one (v, zeta) block pair and no time step
@@ -47,14 +56,14 @@ void relin_set(System &S, const kkt_relin_desc *d) {
              d->Mp && d->b_values && d->data && (d->n_bc == 0 || d->bc_idx),
          "null array");
     const std::string api = "kkt_set_relinearisation: ";
-    check_range(api + "V", d->V, d->ne * 6, d->n2);
+    check_range(api + "V", d->V, d->ne * kv, d->n2);
     check_csr(api + "P2 pattern", d->v_indptr, d->v_indices, d->n2, d->n2, d->nnz2);
     check_csr(api + "P1 pattern", d->p_indptr, d->p_indices, d->n1, d->n1, d->nnz1);
     check_csr(api + "B", d->b_indptr, d->b_indices, d->n1, nv, d->nnz_b);
     check_perm(api + "P2 pattern", d->v_tperm, d->nnz2);
     check_perm(api + "P1 pattern", d->p_tperm, d->nnz1);
-    check_lists(api + "P2", d->v_cptr, d->v_clist, d->nnz2, d->ne * RELIN_EV);
-    check_lists(api + "P1", d->p_cptr, d->p_clist, d->nnz1, d->ne * RELIN_EP);
+    check_lists(api + "P2", d->v_cptr, d->v_clist, d->nnz2, d->ne * ev);
+    check_lists(api + "P1", d->p_cptr, d->p_clist, d->nnz1, d->ne * ep);
     check_range(api + "bc_idx", d->bc_idx, d->n_bc, nv);
 
     auto P = std::make_unique<RelinPlan>();
@@ -71,13 +80,24 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     P->nu = d->nu;
     P->tau = d->tau;
     P->beta = d->beta;
-    const int64_t ne = d->ne, nq = RELIN_NQ;
-    P->d_V = P->mem.upload(d->V, ne * 6);
+    P->kv = kv;
+    P->kp = kp;
+    P->nq = d->nq;
+    P->ev = ev;
+    P->ep = ep;
+    const int64_t ne = d->ne, nq = d->nq;
+    P->d_V = P->mem.upload(d->V, ne * kv);
     P->d_W = P->mem.upload(d->W, ne * nq);
-    P->d_phi = P->mem.upload(d->phi, nq * 6);
-    P->d_gphi = P->mem.upload(d->gphi, ne * nq * 12);
-    P->d_lam = P->mem.upload(d->lam, nq * 3);
-    P->d_glam = P->mem.upload(d->glam, ne * 6);
+    P->d_phi = P->mem.upload(d->phi, nq * kv);
+    P->d_lam = P->mem.upload(d->lam, nq * kp);
+    if (q2) {   // reference gradients, one table for all cells, and the cells' 1 / hx, 1 / hy
+        P->d_gphi = P->mem.upload(d->gphi, nq * kv * 2);
+        P->d_glam = P->mem.upload(d->glam, nq * kp * 2);
+        P->d_jinv = P->mem.upload(d->jinv, ne * 2);
+    } else {
+        P->d_gphi = P->mem.upload(d->gphi, ne * nq * 12);
+        P->d_glam = P->mem.upload(d->glam, ne * 6);
+    }
     P->d_ip2 = P->mem.upload(d->v_indptr, d->n2 + 1);
     P->d_ix2 = P->mem.upload(d->v_indices, d->nnz2);
     P->d_t2 = P->mem.upload(d->v_tperm, d->nnz2);
@@ -87,9 +107,9 @@ void relin_set(System &S, const kkt_relin_desc *d) {
     P->d_Kp = P->mem.upload(d->Kp, d->nnz1);
     P->d_Mp = P->mem.upload(d->Mp, d->nnz1);
     P->d_cptr2 = P->mem.upload(d->v_cptr, d->nnz2 + 1);
-    P->d_clist2 = P->mem.upload(d->v_clist, ne * RELIN_EV);
+    P->d_clist2 = P->mem.upload(d->v_clist, ne * ev);
     P->d_cptrp = P->mem.upload(d->p_cptr, d->nnz1 + 1);
-    P->d_clistp = P->mem.upload(d->p_clist, ne * RELIN_EP);
+    P->d_clistp = P->mem.upload(d->p_clist, ne * ep);
     // B and its transpose (rows of B^T in ascending column order of B: sorted)
     const int64_t nb = d->nnz_b;
     std::vector<int32_t> tip(nv + 1, 0), tix(nb);
@@ -115,8 +135,8 @@ void relin_set(System &S, const kkt_relin_desc *d) {
         P->d_rhalo = P->mem.alloc<double>(2 * nv + 2 * d->n1);
         HIPCHK(hipMemset(P->d_rhalo, 0, (2 * nv + 2 * d->n1) * 8));
     }
-    P->d_Ev = P->mem.alloc<double>(ne * RELIN_EV * w.D_n);
-    P->d_Ep = P->mem.alloc<double>(ne * RELIN_EP * w.D_n);
+    P->d_Ev = P->mem.alloc<double>(ne * ev * w.D_n);
+    P->d_Ep = P->mem.alloc<double>(ne * ep * w.D_n);
     P->d_D2 = P->mem.alloc<double>(d->nnz2 * w.D_n);
     P->d_Dp = P->mem.alloc<double>(d->nnz1 * w.D_n);
     P->d_v = P->mem.alloc<double>(w.v_n * nv);
@@ -221,7 +241,7 @@ void relin_residual(System &S, double *d_out, int rhs, double *norm) {
 void relin_debug_array(System &S, int which, double *out, int64_t cap) {
     RelinPlan &P = plan_of(S);
     const std::vector<DebugArray> arrays = {
-        {P.d_Ev, P.ne * RELIN_EV, P.w.D_n, true}, {P.d_Ep, P.ne * RELIN_EP, P.w.D_n, true},
+        {P.d_Ev, P.ne * P.ev, P.w.D_n, true}, {P.d_Ep, P.ne * P.ep, P.w.D_n, true},
         {P.d_D2, P.nnz2, P.w.D_n, true}, {P.d_Dp, P.nnz1, P.w.D_n, true},
         {P.d_v, P.nv, P.w.v_n, false}, {P.d_zeta, P.nv, P.w.z_n, false}};
     copy_debug_array("kkt_debug_relin_array", S, arrays, P.assembled, which, out, cap);

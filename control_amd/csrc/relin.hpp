@@ -23,10 +23,14 @@ struct RelinPlan {
     bool stationary = false;
     int64_t ne = 0, n2 = 0, n1 = 0, nv = 0, nnz2 = 0, nnz1 = 0;
     double nu = 0.0, tau = 0.0, beta = 0.0;
+    // the element: nodes per cell of the velocity (6: P2 triangles, 9: Q2 quadrilaterals) and of
+    // the pressure, quadrature points, and the entries of the two element matrices
+    int kv = 6, kp = 3, nq = RELIN_NQ, ev = RELIN_EV, ep = RELIN_EP;
     DevPool mem;   // everything below but the job table
     int32_t *d_V = nullptr;
     double *d_W = nullptr, *d_phi = nullptr, *d_gphi = nullptr, *d_lam = nullptr,
            *d_glam = nullptr;
+    double *d_jinv = nullptr;   // Q2-Q1: ne x 2, and gphi / glam are the reference tables
     // scalar P2 pattern (one velocity component) and P1 pattern
     int32_t *d_ip2 = nullptr, *d_ix2 = nullptr, *d_t2 = nullptr, *d_tp = nullptr;
     double *d_K2 = nullptr, *d_M2 = nullptr, *d_Kp = nullptr, *d_Mp = nullptr;
@@ -50,7 +54,8 @@ struct RelinPlan {
 };
 
 // element matrices of every (element, level of the D window): Ev[(s ne + e) 36 + 6a + b],
-// Ep[... 9 + 3c + d], s = level - D_l0; d_v: the plan's v window
+// Ep[... 9 + 3c + d] (Q2-Q1: ... 81 + 9a + b, ... 16 + 4c + d), s = level - D_l0; d_v: the plan's
+// v window.  Dispatches on the plan's element (kv).
 void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v);
 // D[l nnz + k] = nu K[k] + sum of the contributions of position k in list order
 void launch_relin_gather(hipStream_t s, const RelinPlan &P);

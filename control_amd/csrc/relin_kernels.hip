@@ -86,8 +86,197 @@ __global__ __launch_bounds__(256) void relin_elements_kernel(
     }
 }
 
+// a value that is the same in every lane of the wave, moved to scalar registers
+__device__ inline int uniform32(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ inline int64_t uniform64(int64_t x) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+constexpr int Q2_KV = 9;      // nodes of a Q2 cell: 3 j + i, i along x, j along y
+constexpr int Q2_KP = 4;      // nodes of a Q1 cell: 2 j + i
+constexpr int Q2_NQ = 16;     // the 4 x 4 Gauss-Legendre product rule, degree 7 per variable
+constexpr int Q2_EP = 16;     // entries of the pressure element matrix (the velocity one: 81)
+
+// The same two element matrices on Q2-Q1 quadrilaterals (fem.py rectangle_q2q1):
+//   Nv[a][b] = sum_q W_eq phi_qa (w_q . grad phi_eqb)   9 x 9
+//   Np[c][d] = sum_q W_eq lam_qc (w_q . grad lam_eqd)   4 x 4
+// with grad phi_eqb = gref_qb * jinv_e per component (one rounding, as the host forms its gphi),
+// w_q the Q2 interpolant of the level's wind summed left to right over the nine nodes, every sum
+// over q ascending from 0.0 and every entry ((W phi_qa) adv_b), so the bits do not depend on how
+// the entries are split over lanes.
+//
+// The shape is that of reaction_elements_q2_kernel (reaction_kernels.hip): 81 sums are 162 VGPRs,
+// so three lanes share one (element, level) pair: lane t works on pair t / 3 and owns the velocity
+// rows part, part + 3, part + 6 with part = t % 3 -- 27 sums.  Every lane recomputes the wind at
+// the point and the nine advections (72 operations a point against 30 of its own).  The pressure
+// sums run in a second loop over the points, after the velocity rows have left for LDS: next to
+// the 27 sums, the 18 nodal values of the wind and the nine advections they do not fit 168
+// registers without scratch, and forming the wind 16 times more (18 fma each) costs less than a
+// wave per SIMD.  Of the pressure matrix the lane owns row `part`, and all three lanes of a pair
+// carry row 3 (four sums more than an even split would be, and no lane-dependent register index);
+// lane 0's copy is the one stored.  The tables a point needs that are uniform over the wave
+// (phi_q., gref_q.., lam_q3, lref_q..) come by scalar loads, one point a round; the values of the
+// lane's own rows (phi_q,part+3r and lam_q,part) depend on the lane and are read from copies in
+// LDS.  144 VGPRs, three waves per SIMD.
+//
+// Stores are staged through LDS so that a pair's 648 + 128 bytes leave in contiguous runs.  Ev:
+// the rounds of reaction_elements_q2_kernel, word for word (in round r the three lanes of a pair
+// hold the rows 3r, 3r + 1, 3r + 2: 27 contiguous doubles; the wave lays 64 x 9 values into its
+// own 4608 bytes and reads them back slot j 64 + lane).  Ep: the block's lane-items cover the
+// pairs from pb = base / 3 on; every lane lays its pressure rows at 16 (pair - pb) + 4 row of the
+// same buffer (at most 86 pairs: 1376 of its 2304 slots), and slot f = 16 (pair - pb) + 4 c + d is
+// stored by thread f % 256 if the lane-item that owns row c of that pair (3 pair + c, row 3:
+// 3 pair) belongs to this block's round -- a block stores 16 consecutive doubles per pair, and the
+// rows of a pair split between two blocks each leave with their owner.  The loop bound is uniform
+// over the block (the barriers); lanes past the end work on the last lane-item and store nothing.
+__global__ __launch_bounds__(256, 3) void relin_elements_q2q1_kernel(
+    const double *__restrict__ vlev, int64_t ne, int64_t n2, int n_t,
+    const int32_t *__restrict__ V, const double *__restrict__ W, const double *__restrict__ phi,
+    const double *__restrict__ gref, const double *__restrict__ lam,
+    const double *__restrict__ lref, const double *__restrict__ jinv, double *__restrict__ Ev,
+    double *__restrict__ Ep) {
+    constexpr int PARTS = 3, ROWS = 3, OWN = ROWS * Q2_KV;
+    __shared__ double tphi[Q2_NQ * Q2_KV];
+    __shared__ double tlam[Q2_NQ * Q2_KP];
+    __shared__ double stage[256 * Q2_KV];
+    for (int k = threadIdx.x; k < Q2_NQ * Q2_KV; k += blockDim.x) tphi[k] = phi[k];
+    for (int k = threadIdx.x; k < Q2_NQ * Q2_KP; k += blockDim.x) tlam[k] = lam[k];
+    const int lane = threadIdx.x & 63, wave0 = threadIdx.x - lane;
+    double *mine = stage + wave0 * Q2_KV;
+    const int64_t total = ne * n_t * PARTS;
+    for (int64_t base = blockIdx.x * (int64_t)blockDim.x; base < total;
+         base += (int64_t)gridDim.x * blockDim.x) {
+        // the block's first lane-item is the same in every lane: what follows from it (the
+        // staging offsets, the pressure slots) stays in scalar registers
+        const int64_t ub = uniform64(base);
+        const int64_t t = min(ub + threadIdx.x, total - 1);
+        const int64_t pair = t / PARTS;
+        const int part = (int)(t - pair * PARTS);
+        const int64_t l = pair / ne, e = pair - l * ne;
+        const double *w = vlev + l * 2 * n2;
+        const int32_t *ce = V + e * Q2_KV;
+        double wx[Q2_KV], wy[Q2_KV];
+#pragma unroll
+        for (int k = 0; k < Q2_KV; ++k) {
+            const int32_t node = ce[k];
+            wx[k] = w[node];
+            wy[k] = w[n2 + node];
+        }
+        const double jx = jinv[2 * e], jy = jinv[2 * e + 1];
+        double acc[OWN];
+#pragma unroll
+        for (int k = 0; k < OWN; ++k) acc[k] = 0.0;
+        __syncthreads();          // the tables stand; the last round's slots have been read
+        const double *own = tphi + part, *ownp = tlam + part;
+#pragma unroll 1
+        for (int q = 0; q < Q2_NQ; ++q) {
+            double qx = 0.0, qy = 0.0;
+#pragma unroll
+            for (int k = 0; k < Q2_KV; ++k) {
+                const double p = phi[q * Q2_KV + k];
+                qx += wx[k] * p;
+                qy += wy[k] * p;
+            }
+            const double wq = W[e * Q2_NQ + q];
+            double adv[Q2_KV];
+#pragma unroll
+            for (int b = 0; b < Q2_KV; ++b) {
+                const double gx = gref[(q * Q2_KV + b) * 2] * jx;
+                const double gy = gref[(q * Q2_KV + b) * 2 + 1] * jy;
+                adv[b] = gx * qx + gy * qy;
+            }
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const double s = wq * own[q * Q2_KV + PARTS * r];
+#pragma unroll
+                for (int b = 0; b < Q2_KV; ++b) acc[r * Q2_KV + b] += s * adv[b];
+            }
+        }
+        // Ev.  The wave's first lane-item t0 = 3 p0 + m0: slot f is at o + 9 d + 54 ((m0 + d) / 3)
+        // + 27 r + f % 9 with d = f / 9 and o = Ev + 9 t0 + 54 p0, and is live for d < live
+        // (the lane index is taken afresh: what the store rounds derive from it -- f / 9, f % 9 per
+        // slot -- is otherwise kept in registers across the whole loop over the blocks' rounds)
+        int ln = lane, tid = threadIdx.x;
+        asm volatile("" : "+v"(ln), "+v"(tid));
+        const int64_t t0 = ub + uniform32(wave0), p0 = t0 / PARTS;
+        const int m0 = (int)(t0 - p0 * PARTS);
+        const int live = (int)min((int64_t)64, total - t0);
+        double *o = Ev + 9 * t0 + 54 * p0;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            if (r) __syncthreads();
+#pragma unroll
+            for (int c = 0; c < Q2_KV; ++c) mine[ln * Q2_KV + c] = acc[r * Q2_KV + c];
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < Q2_KV; ++j) {
+                const int f = j * 64 + ln, d = f / Q2_KV;
+                if (d < live) o[9 * d + 54 * ((m0 + d) / PARTS) + 27 * r + f % Q2_KV] = mine[f];
+            }
+        }
+        // the pressure sums in a loop of their own, once the velocity sums have left the
+        // registers: the wind at the point is formed again, in the same order
+        double accp[2 * Q2_KP];
+#pragma unroll
+        for (int k = 0; k < 2 * Q2_KP; ++k) accp[k] = 0.0;
+#pragma unroll 1
+        for (int q = 0; q < Q2_NQ; ++q) {
+            double qx = 0.0, qy = 0.0;
+#pragma unroll
+            for (int k = 0; k < Q2_KV; ++k) {
+                const double p = phi[q * Q2_KV + k];
+                qx += wx[k] * p;
+                qy += wy[k] * p;
+            }
+            const double wq = W[e * Q2_NQ + q];
+            double advp[Q2_KP];
+#pragma unroll
+            for (int d = 0; d < Q2_KP; ++d) {
+                const double gx = lref[(q * Q2_KP + d) * 2] * jx;
+                const double gy = lref[(q * Q2_KP + d) * 2 + 1] * jy;
+                advp[d] = gx * qx + gy * qy;
+            }
+            const double sp = wq * ownp[q * Q2_KP], s3 = wq * lam[q * Q2_KP + 3];
+#pragma unroll
+            for (int d = 0; d < Q2_KP; ++d) {
+                accp[d] += sp * advp[d];
+                accp[Q2_KP + d] += s3 * advp[d];
+            }
+        }
+        // Ep.  pb: the pair of the block's first lane-item; end: one past its last live one
+        __syncthreads();
+        const int64_t pb = ub / PARTS, end = min(ub + 256, total);
+        if (ub + tid < total) {
+            double *row = stage + (pair - pb) * Q2_EP;
+#pragma unroll
+            for (int d = 0; d < Q2_KP; ++d) row[part * Q2_KP + d] = accp[d];
+            if (part == 0) {
+#pragma unroll
+                for (int d = 0; d < Q2_KP; ++d) row[3 * Q2_KP + d] = accp[Q2_KP + d];
+            }
+        }
+        __syncthreads();
+        const int nslots = (int)((end - 1) / PARTS - pb + 1) * Q2_EP;
+        for (int f = tid; f < nslots; f += 256) {
+            const int64_t pr = pb + f / Q2_EP;
+            const int c = (f % Q2_EP) / Q2_KP;
+            const int64_t owner = PARTS * pr + (c == 3 ? 0 : c);
+            if (owner >= ub && owner < end) Ep[pb * Q2_EP + f] = stage[f];
+        }
+    }
+}
+
 // d_v: the v window; slot s of the D window takes its wind from level D_l0 + s of it
 void launch_relin_elements(hipStream_t s, const RelinPlan &P, const double *d_v) {
+    if (P.kv == Q2_KV) {
+        hipLaunchKernelGGL(relin_elements_q2q1_kernel,
+                           dim3(grid_of(P.ne * P.w.D_n * 3, 256 * 64)), dim3(256), 0, s,
+                           d_v + (int64_t)(P.w.D_l0 - P.w.v_l0) * P.nv, P.ne, P.n2, P.w.D_n, P.d_V,
+                           P.d_W, P.d_phi, P.d_gphi, P.d_lam, P.d_glam, P.d_jinv, P.d_Ev, P.d_Ep);
+        return;
+    }
     hipLaunchKernelGGL(relin_elements_kernel, dim3(grid_of(P.ne * P.w.D_n, 256 * 64)), dim3(256),
                        0, s, d_v + (int64_t)(P.w.D_l0 - P.w.v_l0) * P.nv, P.ne, P.n2, P.w.D_n,
                        P.d_V, P.d_W, P.d_phi, P.d_gphi, P.d_lam, P.d_glam, P.d_Ev, P.d_Ep);
@@ -116,10 +305,10 @@ __global__ __launch_bounds__(256) void relin_gather_kernel(
 
 void launch_relin_gather(hipStream_t s, const RelinPlan &P) {
     hipLaunchKernelGGL(relin_gather_kernel, dim3(grid_of(P.nnz2 * P.w.D_n, 256 * 64)), dim3(256),
-                       0, s, P.d_cptr2, P.d_clist2, P.d_Ev, P.ne * RELIN_EV, P.d_K2, P.nu, P.nnz2,
+                       0, s, P.d_cptr2, P.d_clist2, P.d_Ev, P.ne * P.ev, P.d_K2, P.nu, P.nnz2,
                        P.w.D_n, P.d_D2);
     hipLaunchKernelGGL(relin_gather_kernel, dim3(grid_of(P.nnz1 * P.w.D_n, 256 * 64)), dim3(256),
-                       0, s, P.d_cptrp, P.d_clistp, P.d_Ep, P.ne * RELIN_EP, P.d_Kp, P.nu, P.nnz1,
+                       0, s, P.d_cptrp, P.d_clistp, P.d_Ep, P.ne * P.ep, P.d_Kp, P.nu, P.nnz1,
                        P.w.D_n, P.d_Dp);
 }
 

@@ -29,6 +29,7 @@ __all__ = [
     "rectangle_p2",
     "unit_square_p2",
     "rectangle_q2",
+    "rectangle_q2q1",
     "ReactionTerm",
     "ConvectionTerm",
 ]
@@ -575,7 +576,7 @@ class TaylorHoodDiscretisation:
     coords_v: np.ndarray      # (n_v / 2, 2) node coordinates of one component
     coords_p: np.ndarray
     boundary_v: np.ndarray    # Dirichlet dofs of the vector space (both components)
-    elem: dict = None         # element data for re-assembly (P2-P1 triangles only)
+    elem: dict = None         # element data for re-assembly (rectangle_p2p1, rectangle_q2q1)
 
     @property
     def n_v(self):
@@ -624,13 +625,17 @@ class TaylorHoodDiscretisation:
         n2 = self.n_v // 2
         V, Pn = e["V"], e["P"]
         wq = np.stack([e["phi"] @ w[:n2][V].T, e["phi"] @ w[n2:][V].T], axis=2)
-        adv = np.einsum("qed,ecd->eqc", wq, e["glam"])                 # (w . grad lambda_c)
+        if e["glam"].ndim == 4:          # gradients that depend on the point (Q1)
+            adv = np.einsum("qed,eqcd->eqc", wq, e["glam"])
+        else:
+            adv = np.einsum("qed,ecd->eqc", wq, e["glam"])             # (w . grad lambda_c)
         Ne = np.einsum("eq,qa,eqc->eac", e["W"], e["lam"], adv)
         return _assemble_like(Ne, Pn, Pn, (self.n_p, self.n_p))
 
     def _need_elem(self):
         if self.elem is None:
-            raise NotImplementedError("re-assembly is implemented for rectangle_p2p1 only")
+            raise NotImplementedError("re-assembly needs element data (rectangle_p2p1 or "
+                                      "rectangle_q2q1)")
         return self.elem
 
     @property
@@ -640,7 +645,8 @@ class TaylorHoodDiscretisation:
 
 class ConvectionTerm:
     """The declared forward form ``nu (grad u, grad v) + ((w . grad) u, v)`` of Navier-Stokes
-    control on a Taylor-Hood discretisation with element data (``rectangle_p2p1``) -- a forward
+    control on a Taylor-Hood discretisation with element data (``rectangle_p2p1``,
+    ``rectangle_q2q1``) -- a forward
     operator the library can read: ``Stationary.incompressible_non_linear_solve(device=True)``
     assembles it on the GPU from ``nu`` and the element tables.
 
@@ -651,7 +657,7 @@ class ConvectionTerm:
     def __init__(self, disc, nu):
         if getattr(disc, "elem", None) is None:
             raise ValueError("ConvectionTerm needs a Taylor-Hood discretisation with element data "
-                             "(fem.rectangle_p2p1)")
+                             "(fem.rectangle_p2p1 or fem.rectangle_q2q1)")
         self.disc, self.nu = disc, float(nu)
 
     def __call__(self, w):
@@ -716,6 +722,80 @@ def unit_square_q2q1(n: int, length: float = 1.0) -> TaylorHoodDiscretisation:
     nb = sd.boundary
     boundary_v = np.concatenate([nb, nb + sd.n_dofs]).astype(np.int32)
     return TaylorHoodDiscretisation(M_v, K_v, B, M_p, K_p, sd.coords, coords_p, boundary_v)
+
+
+def rectangle_q2q1(nx: int, ny: int, lx: float = 1.0, ly: float = 1.0) -> TaylorHoodDiscretisation:
+    """Q2 velocity / Q1 pressure on the ``nx x ny`` quadrilateral mesh of ``[0,lx] x [0,ly]``,
+    assembled from elements, with the element data the convection re-assembly needs: the spaces of
+    ``unit_square_q2q1`` (for ``nx = ny``, ``lx = ly``: its ``coords_*`` and ``boundary_v`` array
+    for array, its matrices to rounding).
+
+    Velocity nodes and cells are those of ``rectangle_q2`` (y-major ``(2nx+1) x (2ny+1)`` grid,
+    ``V`` (ne, 9) with local node ``3 j + i``, cell ``(ex, ey)`` at index ``ey nx + ex``), and
+    ``M_v`` / ``K_v`` are its ``M`` / ``K`` once per component (component-major).  Pressure nodes
+    are the ``(nx+1) x (ny+1)`` vertices, y-major; ``P`` is (ne, 4) with local node ``2 j + i``.
+
+    The rule is the 4 x 4 Gauss-Legendre product rule on the unit square: point ``q = 4 r + s`` is
+    ``(t_s, t_r)`` with weight ``wt_r wt_s``, exact to degree 7 in each variable.  On axis-parallel
+    cells the velocity integrand ``phi_a (w . grad phi_b)`` with a Q2 wind has degree at most 6 per
+    variable (2 + 2 + 2; the derivative lowers one of them), the pressure integrand
+    ``lam_c (w . grad lam_d)`` at most 4 (1 + 2 + 1), and those of ``B``, ``M_p``, ``K_p`` at most
+    3: all are integrated exactly.
+
+    ``elem``: ``V``, ``P``, ``W`` (ne, 16) weight times ``hx hy``, ``phi`` (16, 9) the rounded
+    products of the 1-D values as ``_gauss_square_rule`` forms them, ``gref`` (16, 9, 2) the
+    gradients on the unit square, ``lam`` (16, 4), ``lref`` (16, 4, 2), ``jinv`` (ne, 2) =
+    ``1 / hx, 1 / hy``, and the physical gradients ``gphi`` (ne, 16, 9, 2), ``glam``
+    (ne, 16, 4, 2), each entry the one rounded product ``ref jinv`` (views of one cell's tables:
+    all cells are congruent); ``kind = "q2q1"``."""
+    sd = rectangle_q2(nx, ny, lx, ly)
+    V, n2 = sd.cells, sd.n_dofs
+    ne, npx = nx * ny, nx + 1
+    n1 = npx * (ny + 1)
+    hx, hy = lx / nx, ly / ny
+    ex, ey = np.meshgrid(np.arange(nx), np.arange(ny), indexing="xy")
+    first = (ey.ravel() * npx + ex.ravel())[:, None]
+    i, j = np.tile(np.arange(2), 2), np.repeat(np.arange(2), 2)
+    Pn = np.ascontiguousarray(first + (j * npx + i)[None, :], dtype=np.int32)
+
+    t, wt = _gauss(4)
+    wq = np.repeat(wt, 4) * np.tile(wt, 4)
+
+    def tensor(fx, fy):           # [q = 4 r + s, k j + i] = fx[i, s] fy[j, r]
+        k = len(fx)
+        return (fx.T[None, :, None, :] * fy.T[:, None, :, None]).reshape(16, k * k)
+    l = _q2_shape_functions_1d(t)                                     # (3, 4): l[i, s]
+    dl = np.stack([4 * t - 3.0, 4.0 - 8 * t, 4 * t - 1.0])
+    psi = np.stack([1.0 - t, t])
+    dpsi = np.stack([-np.ones(4), np.ones(4)])
+    phi, lam = tensor(l, l), tensor(psi, psi)
+    gref = np.stack([tensor(dl, l), tensor(l, dl)], axis=2)           # (16, 9, 2)
+    lref = np.stack([tensor(dpsi, psi), tensor(psi, dpsi)], axis=2)   # (16, 4, 2)
+    j1 = np.array([1.0 / hx, 1.0 / hy])
+    gphi1, glam1 = gref * j1, lref * j1
+    W1 = wq * (hx * hy)
+    Bxe = -np.einsum("q,qc,qa->ca", W1, lam, gphi1[..., 0])           # (4, 9)
+    Bye = -np.einsum("q,qc,qa->ca", W1, lam, gphi1[..., 1])
+    Mpe = np.einsum("q,qc,qd->cd", W1, lam, lam)
+    Kpe = np.einsum("q,qcx,qdx->cd", W1, glam1, glam1)
+
+    def asm(Ee, rows, cols, shape):
+        return _assemble_like(np.broadcast_to(Ee, (ne,) + Ee.shape), rows, cols, shape)
+    Bx, By = asm(Bxe, Pn, V, (n1, n2)), asm(Bye, Pn, V, (n1, n2))
+    I2 = sp.identity(2, format="csr")
+    xp, yp = np.linspace(0.0, lx, npx), np.linspace(0.0, ly, ny + 1)
+    XP, YP = np.meshgrid(xp, yp, indexing="xy")
+    coords_p = np.stack([XP.ravel(), YP.ravel()], axis=1)
+    nb = sd.boundary
+    elem = dict(V=V, P=Pn, W=np.broadcast_to(W1, (ne, 16)), phi=phi, gref=gref, lam=lam,
+                lref=lref, jinv=np.broadcast_to(j1, (ne, 2)),
+                gphi=np.broadcast_to(gphi1, (ne, 16, 9, 2)),
+                glam=np.broadcast_to(glam1, (ne, 16, 4, 2)), kind="q2q1")
+    return TaylorHoodDiscretisation(
+        _canonical_csr(sp.kron(I2, sd.M)), _canonical_csr(sp.kron(I2, sd.K)),
+        _canonical_csr(sp.hstack([Bx, By])), asm(Mpe, Pn, Pn, (n1, n1)),
+        asm(Kpe, Pn, Pn, (n1, n1)), sd.coords, coords_p,
+        np.concatenate([nb, nb + n2]).astype(np.int32), elem=elem)
 
 
 # ------------------------------------------------------- Taylor-Hood (P2-P1, triangles)

@@ -181,7 +181,7 @@ class GpuLinearSolver:
         Picard iterate in HBM -- the first linear solve builds the three systems (``build``),
         every later re-linearisation re-assembles the convection blocks, the
         residual and the update on the GPU (``control_amd.relinearise``).  Needs the element
-        data of ``fem.rectangle_p2p1``.  With ``comm`` every rank keeps, assembles, evaluates and
+        data of ``fem.rectangle_p2p1`` or ``fem.rectangle_q2q1``.  With ``comm`` every rank keeps, assembles, evaluates and
         updates its own time levels only and trades one level of ``v`` and one of ``zeta`` (CN:
         and the boundary residual rows) with its neighbours per iteration; ``host_allreduce``
         then only gathers the fields once at the end.
@@ -208,7 +208,7 @@ class GpuLinearSolver:
         if relinearise == "device":
             if getattr(pb.disc, "elem", None) is None:
                 raise ValueError("relinearise='device' needs a discretisation with element data "
-                                 "(fem.rectangle_p2p1)")
+                                 "(fem.rectangle_p2p1 or fem.rectangle_q2q1)")
         self.relinearise, self.build = relinearise, build
         self.setup_s = None             # wall time of setup(): the builds and the preconditioner
         self._device = None             # control_amd.relinearise.DeviceRelinearisation
@@ -470,7 +470,7 @@ def incompressible_non_linear_solve(pb: NavierStokesControl, linear_solver=None,
     first) and the linear iteration counts."""
     if device and getattr(pb.disc, "elem", None) is None:
         raise ValueError("device=True needs a discretisation with element data "
-                         "(fem.rectangle_p2p1)")
+                         "(fem.rectangle_p2p1 or fem.rectangle_q2q1)")
     if linear_solver is None:
         linear_solver = GpuLinearSolver(pb, Multigrid=Multigrid,
                                         relinearise="device" if device else "host")

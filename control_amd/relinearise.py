@@ -1,6 +1,7 @@
 """Picard re-linearisation on the device (``kkt_set_relinearisation``).
 
-Host side: the plan of a Taylor-Hood P2-P1 discretisation (``fem.rectangle_p2p1``) --
+Host side: the plan of a Taylor-Hood discretisation with element data (``fem.rectangle_p2p1``,
+``fem.rectangle_q2q1``) --
 element tables, the contribution lists that make the device assembly deterministic, transpose
 permutations, the data rows of the residual -- and a thin binding of the device entry points.
 The lists are CSR over stored positions: position ``k`` of the scalar P2 (P1) pattern sums the
@@ -84,8 +85,8 @@ class RelinearisationPlan:
         from .picard import non_linear_res_eval
         th = pb.disc
         if getattr(th, "elem", None) is None:
-            raise ValueError("device re-linearisation needs the element data of "
-                             "fem.rectangle_p2p1")
+            raise ValueError("device re-linearisation needs a discretisation with element data "
+                             "(fem.rectangle_p2p1 or fem.rectangle_q2q1)")
         e = th.elem
         n2 = th.n_v // 2
         K2 = th.K_v[:n2, :n2].tocsr()
@@ -100,8 +101,14 @@ class RelinearisationPlan:
         self.pb, self.n2, self.K2, self.M2, self.Kp, self.Mp = pb, n2, K2, M2, Kp, Mp
         self.V = np.ascontiguousarray(e["V"], dtype=np.int32)
         self.P = np.ascontiguousarray(e["P"], dtype=np.int32)
-        self.tables = {k: np.ascontiguousarray(e[k], dtype=np.float64)
-                       for k in ("W", "phi", "gphi", "lam", "glam")}
+        #: "p2p1" (triangles: per-cell physical gradients) or "q2q1" (quadrilaterals: the
+        #: descriptor carries the reference gradients and the cells' inverse Jacobians)
+        self.kind = e.get("kind", "p2p1")
+        names = {"W": "W", "phi": "phi", "gphi": "gphi", "lam": "lam", "glam": "glam"}
+        if self.kind == "q2q1":
+            names.update(gphi="gref", glam="lref", jinv="jinv")
+        self.tables = {k: np.ascontiguousarray(e[src], dtype=np.float64)
+                       for k, src in names.items()}
         self.v_lists = contribution_lists(self.V, K2)
         self.p_lists = contribution_lists(self.P, Kp)
         self.v_tperm = transpose_permutation(K2)
@@ -147,6 +154,8 @@ class RelinearisationPlan:
             Mp=f64(self.Mp.data), nnz_b=self.B.nnz, b_indptr=i32(self.B.indptr),
             b_indices=i32(self.B.indices), b_values=f64(self.B.data),
             n_bc=len(th.boundary_v), bc_idx=i32(th.boundary_v), data=f64(self.data))
+        if self.kind == "q2q1":
+            d.nv, d.jinv = self.V.shape[1], f64(t["jinv"])
         return d, keep
 
 
@@ -251,11 +260,14 @@ class DeviceRelinearisation(DevicePlanBinding):
         return (n_t, th.n_v), (n_t, th.n_v), (m, th.n_p), (m, th.n_p)
 
     def _debug_arrays(self):
-        """``kkt_debug_relin_array``: ``"Ev"`` (n_t, ne, 6, 6), ``"Ep"`` (n_t, ne, 3, 3), ``"D2"``
+        """``kkt_debug_relin_array``: ``"Ev"`` (n_t, ne, 6, 6), ``"Ep"`` (n_t, ne, 3, 3) (Q2-Q1:
+        (n_t, ne, 9, 9) and (n_t, ne, 4, 4)), ``"D2"``
         (n_t, nnz2) or ``"Dp"`` (n_t, nnz1) of the last assembly -- on a time shard the levels of
         ``window["D"]``; ``"v"`` / ``"zeta"``: the iterate's windows, halo levels included."""
         ne, n_v = len(self.plan.V), self.pb.disc.n_v
-        return {"Ev": ("D", (ne, 6, 6)), "Ep": ("D", (ne, 3, 3)), "D2": ("D", (self.plan.K2.nnz,)),
+        kv, kp = self.plan.V.shape[1], self.plan.P.shape[1]
+        return {"Ev": ("D", (ne, kv, kv)), "Ep": ("D", (ne, kp, kp)),
+                "D2": ("D", (self.plan.K2.nnz,)),
                 "Dp": ("D", (self.plan.Kp.nnz,)), "v": ("v", (n_v,)), "zeta": ("zeta", (n_v,))}
 
     def assemble(self):

@@ -39,7 +39,7 @@ def _check(ctl, forward_operator_p=None, P=None, backend=None):
                          "forward_operator_p must be None or its pressure")
     if getattr(th, "elem", None) is None:
         raise ValueError("device=True needs a discretisation with element data "
-                         "(fem.rectangle_p2p1)")
+                         "(fem.rectangle_p2p1 or fem.rectangle_q2q1)")
     if term.disc is not th:
         raise ValueError("the ConvectionTerm was declared on another discretisation")
     if backend is not None and not isinstance(backend, GpuBackend):

@@ -425,21 +425,33 @@ int kkt_sync(kkt_handle h);
  * (not backward Euler's with n_t = 1: those carry tau, and the last adjoint row drops M v), the
  * pressure rows -B v and -B zeta; with rhs = 1 kkt_picard_residual_device returns the same rows:
  * the stationary right-hand side has no tau and no time transform.  Recipes name level 0
- * (blocks.stationary_incompressible_build_recipes). */
+ * (blocks.stationary_incompressible_build_recipes).
+ *
+ * nv selects the element (the field fills what was padding after nq: every offset is unchanged).
+ * nv = 0 is the P2-P1 descriptor described above: nq must be 7 and jinv is not read.  nv = 9 with
+ * nq = 16 is Q2-Q1 on axis-parallel quadrilaterals (fem.rectangle_q2q1): local velocity node
+ * 3 j + i and pressure node 2 j + i (i along x, j along y), the 4 x 4 Gauss-Legendre product rule
+ * on the unit square (point q = 4 r + s is (t_s, t_r); degree 7 per variable, the convection
+ * integrand with a Q2 wind has degree 6).  gphi and glam then hold the gradients on the unit
+ * square, one table for all cells, and jinv the cells' 1 / hx, 1 / hy (non-NULL): the physical
+ * gradient is the one rounded product ref * jinv per component.  The contribution lists run over
+ * ne * 81 (e * 81 + 9 a + b) and ne * 16 (e * 16 + 4 c + d) entries.  Any other (nv, nq) is
+ * KKT_ERR_ARG naming nv. */
 typedef struct kkt_relin_desc {
-    int n_t, cn, nq;              /* time levels (1: stationary), CN (1) or backward Euler, nq = 7 */
-    int64_t ne, n2, n1;           /* triangles, P2 nodes (one component), P1 nodes */
+    int n_t, cn, nq;              /* time levels (1: stationary), CN (1) or backward Euler, points */
+    int nv;                       /* 0: P2-P1 triangles (nq = 7); 9: Q2-Q1 quadrilaterals (nq = 16) */
+    int64_t ne, n2, n1;           /* cells, velocity nodes (one component), pressure nodes */
     double nu, tau, beta;
-    const int32_t *V;             /* ne x 6 P2 nodes per triangle */
-    const double *W;              /* ne x nq quadrature weights times |det J| */
-    const double *phi;            /* nq x 6 P2 basis at the points */
-    const double *gphi;           /* ne x nq x 6 x 2 their gradients */
-    const double *lam;            /* nq x 3 P1 basis (barycentric coordinates) */
-    const double *glam;           /* ne x 3 x 2 their gradients */
-    int64_t nnz2;                 /* scalar P2 pattern */
+    const int32_t *V;             /* ne x 6 P2 nodes per triangle           | ne x 9 Q2 nodes */
+    const double *W;              /* ne x nq quadrature weights times |det J| (Q2-Q1: hx hy) */
+    const double *phi;            /* nq x 6 P2 basis at the points          | 16 x 9 Q2 basis */
+    const double *gphi;           /* ne x nq x 6 x 2 their gradients        | 16 x 9 x 2, reference */
+    const double *lam;            /* nq x 3 P1 basis (barycentric)          | 16 x 4 Q1 basis */
+    const double *glam;           /* ne x 3 x 2 their gradients             | 16 x 4 x 2, reference */
+    int64_t nnz2;                 /* scalar velocity pattern */
     const int32_t *v_indptr, *v_indices, *v_tperm, *v_cptr, *v_clist;
     const double *K2, *M2;        /* nnz2 values: grad-grad and mass of one component */
-    int64_t nnz1;                 /* P1 pattern */
+    int64_t nnz1;                 /* pressure pattern */
     const int32_t *p_indptr, *p_indices, *p_tperm, *p_cptr, *p_clist;
     const double *Kp, *Mp;
     int64_t nnz_b;
@@ -448,6 +460,7 @@ typedef struct kkt_relin_desc {
     int64_t n_bc;
     const int32_t *bc_idx;
     const double *data;
+    const double *jinv;           /* nv = 9: ne x 2, 1 / hx and 1 / hy per cell; nv = 0: ignored */
 } kkt_relin_desc;
 int kkt_set_relinearisation(kkt_handle h, const kkt_relin_desc *desc);
 
@@ -506,8 +519,9 @@ int kkt_picard_update_device(kkt_handle plan, double *d_u);
 
 /* Test hooks of the device re-linearisation: plain copies of what the kernels left, no launches.
  * kkt_debug_relin_array downloads one array of the plan's last assembly (cap: doubles available
- * at out): the element matrices Ev (n_t x ne x 36) and Ep (n_t x ne x 9), or the assembled
- * D2 (n_t x nnz2) and Dp (n_t x nnz1) -- on a time shard the levels of the D window, in order.
+ * at out): the element matrices Ev (n_t x ne x 36; Q2-Q1: 81) and Ep (n_t x ne x 9; Q2-Q1: 16),
+ * or the assembled D2 (n_t x nnz2) and Dp (n_t x nnz1) -- on a time shard the levels of the D
+ * window, in order.
  * KKT_ERR_STATE before any assembly, KKT_ERR_ARG when cap is too small.  KKT_RELIN_V and
  * KKT_RELIN_ZETA: the v and zeta windows of the iterate as they are, halo levels included. */
 enum { KKT_RELIN_EV = 0, KKT_RELIN_EP = 1, KKT_RELIN_D2 = 2, KKT_RELIN_DP = 3, KKT_RELIN_V = 4,

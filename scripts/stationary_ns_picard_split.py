@@ -38,10 +38,15 @@ ap.add_argument("--max_linear", type=int, default=200, help="FGMRES(10) iteratio
 ap.add_argument("--perturb_ulps", type=int, default=0,
                 help="k > 0: one more host loop with D_v and D_p scaled by 1 + k 2^-52 -- how far "
                      "a change in the last place of the operator moves the loop's iteration counts")
+ap.add_argument("--element", default="p2p1", choices=["p2p1", "q2q1"],
+                help="q2q1: fem.rectangle_q2q1 with the reference's Q2 / Q1 mass intervals "
+                     "(profiles/ns_picard_q2q1.md)")
 a = ap.parse_args()
 
 t_mesh = time.perf_counter()
-th = fem.rectangle_p2p1(a.n, a.n, 2.0, 2.0)
+th = (fem.rectangle_q2q1 if a.element == "q2q1" else fem.rectangle_p2p1)(a.n, a.n, 2.0, 2.0)
+bounds = (dict(lambda_v_bounds=(0.25, 1.5625), lambda_p_bounds=(0.25, 2.25))
+          if a.element == "q2q1" else {})
 term = fem.ConvectionTerm(th, a.nu)
 t_mesh = time.perf_counter() - t_mesh
 
@@ -126,14 +131,14 @@ def loop(device, its):
     norms = ctl.incompressible_non_linear_solve(
         solver_parameters=sp, max_non_linear_iter=its, relative_non_linear_tol=a.rtol,
         absolute_non_linear_tol=0.0, backend=GpuBackend(), Multigrid=bool(a.multigrid),
-        device=device)
+        device=device, **bounds)
     t1 = time.perf_counter()
     between = range(1, len(marks))
     outside = [marks[k][0] - marks[k - 1][1] for k in between]
     names = ("assembly", "residual", "update", "composition", "systems", "pc_setup")
     split = {n + "_s": [round(marks[k][2].get(n, 0.0), 4) for k in between] for n in names}
     split["other_s"] = [round(outside[k - 1] - sum(marks[k][2].values()), 4) for k in between]
-    return dict(path="device" if device else "host", operator_scale=scale[0], n=a.n, n_v=th.n_v, n_p=th.n_p,
+    return dict(path="device" if device else "host", element=a.element, operator_scale=scale[0], n=a.n, n_v=th.n_v, n_p=th.n_p,
                 multigrid=a.multigrid, nu=a.nu, mesh_and_term_s=round(t_mesh, 2),
                 total_s=round(t1 - t0, 3), picard_iterations=len(norms) - 1,
                 before_first_solve_s=round(marks[0][0] - t0, 3),
