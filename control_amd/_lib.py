@@ -237,6 +237,27 @@ class TileLevels(C.Structure):
                                             "n_coarse", "nrows")])
 
 
+# kkt_anderson_*: the mixer's depth limit, what a step reports, the debug operations and record
+ANDERSON_MAX_DEPTH = 8
+ANDERSON_OPS = {name: k for k, name in enumerate(("push", "gram", "mix", "read"))}
+
+
+class AndersonInfo(C.Structure):
+    _fields_ = [("columns", C.c_int32), ("dropped", C.c_int32),
+                ("gamma", C.c_double * ANDERSON_MAX_DEPTH),
+                ("G", C.c_double * (ANDERSON_MAX_DEPTH * ANDERSON_MAX_DEPTH)),
+                ("r", C.c_double * ANDERSON_MAX_DEPTH)] + \
+               [(n, C.c_double) for n in ("push_ms", "gram_ms", "mix_ms")]
+
+
+class AndersonOp(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("op", "c", "alias", "which", "slot", "inputs_changed")]
+                + [("n", C.c_int64), ("slack", C.c_int64), ("beta", C.c_double),
+                   ("gamma", C.c_double * ANDERSON_MAX_DEPTH)]
+                + [(n, c_f64p) for n in ("f", "dF", "dX", "f_prev", "out", "out2", "G", "r")]
+                + [("ring", C.c_int32 * 4)])
+
+
 PC_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, c_f64p, c_f64p, c_f64p)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int, C.c_int)
 SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_f64p, C.c_int64, C.c_int,
@@ -304,6 +325,10 @@ SIGNATURES = {
     "kkt_reaction_residual_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_f64p]),
     "kkt_reaction_update_device": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kkt_debug_reaction_array": (C.c_int, [C.c_void_p, C.c_int, c_f64p, C.c_int64]),
+    "kkt_anderson_set": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double]),
+    "kkt_anderson_step": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(AndersonInfo)]),
+    "kkt_anderson_reset": (C.c_int, [C.c_void_p]),
+    "kkt_debug_anderson_op": (C.c_int, [C.c_void_p, C.POINTER(AndersonOp)]),
     "kkt_debug_block_values": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_f64p,
                                          C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
     "kkt_time_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

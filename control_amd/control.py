@@ -477,7 +477,7 @@ class Instationary:
                          max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                          absolute_non_linear_tol=1.0e-8, print_error_non_linear=False,
                          backend=None, Multigrid=False, device=False, comm=None,
-                         host_allreduce=None):
+                         host_allreduce=None, anderson=0, anderson_beta=1.0):
         """``control.py:3377-3560``: Picard loop around ``linear_solve``; returns the residual
         norms (initial one first).  ``Multigrid``: as in ``linear_solve``.
 
@@ -496,7 +496,16 @@ class Instationary:
         evaluates and updates the levels of its own block rows, and trades one level of ``v`` and
         one of ``zeta`` with its neighbours per iteration; ``host_allreduce(array, op)`` gathers
         the fields at the end, so ``_v`` and ``_zeta`` are whole on every rank.  The host loop is
-        not offered on shards."""
+        not offered on shards.
+
+        ``anderson`` (depth 1..8; 0, the default: off), ``anderson_beta``: Anderson acceleration
+        of the loop in update space (``control_amd.anderson``): the update of every linearised
+        solve is mixed with the last ``anderson`` secant pairs before it is added -- on the GPU
+        with ``device=True``, by the NumPy mirror in the host loop.  ``ValueError`` with ``comm``
+        of more than one rank, under ``set_Gauss_Newton()`` and outside 0..8.
+        ``non_linear_info["anderson"]``: per iteration the pairs used and dropped."""
+        from .anderson import HostAnderson, check_anderson
+        check_anderson(anderson, anderson_beta, comm, self._Gauss_Newton)
         if comm is not None and not device:
             raise ValueError("comm needs device=True: the host loop is not offered on time shards")
         if device:
@@ -507,7 +516,9 @@ class Instationary:
                 relative_non_linear_tol=relative_non_linear_tol,
                 absolute_non_linear_tol=absolute_non_linear_tol,
                 print_error_non_linear=print_error_non_linear, backend=backend,
-                Multigrid=Multigrid, comm=comm, host_allreduce=host_allreduce)
+                Multigrid=Multigrid, comm=comm, host_allreduce=host_allreduce,
+                anderson=anderson, anderson_beta=anderson_beta)
+        mixer = HostAnderson(anderson, anderson_beta) if anderson else None
         disc, n_t, CN = self._disc, self._n_t, self._CN
         v_0 = (np.zeros(disc.n_dofs) if self._initial_condition is None
                else np.asarray(self._initial_condition(disc.coords), dtype=np.float64))
@@ -516,6 +527,10 @@ class Instationary:
             v_old[0] = v_0                                           # control.py:3425-3426
         zeta_old[n_t - 1] = 0.0
         f, v_d = self.construct_f(), self.construct_v_d()
+        # as the device loop: the first update puts boundary values in that the start did not carry
+        lift = mixer is not None and any(
+            not np.array_equal(v_old[i, disc.boundary], self._bc_values(i)[disc.boundary])
+            for i in range(n_t))
 
         def evaluate():
             r0, r1 = self.non_linear_res_eval(v_old, zeta_old, v_0, v_d, f)
@@ -527,12 +542,18 @@ class Instationary:
             self.linear_solve(P=P, solver_parameters=solver_parameters,
                               lambda_v_bounds=lambda_v_bounds, v_d=rhs_0, f=rhs_1,
                               backend=backend, Multigrid=Multigrid)
+            if mixer is not None:
+                if CN:
+                    self._v[0] = 0.0         # the loop keeps v_0
+                self._v, self._zeta = mixer.step_fields(disc.boundary, (self._v, self._zeta))
             v_old = v_old + self._v
             for i in range(n_t):                                     # :3490-3493
                 v_old[i, disc.boundary] = self._bc_values(i)[disc.boundary]
             if CN:
                 v_old[0] = v_0
                 v_old[0, disc.boundary] = self._bc_values(0)[disc.boundary]
+            if lift and k == 0:
+                mixer.reset()        # the boundary lift moved the iterate outside the step
             zeta_old = zeta_old + self._zeta
             zeta_old[:, disc.boundary] = 0.0
             self.set_v(v_old)
@@ -545,6 +566,8 @@ class Instationary:
                       f"{norm_k:.16e}")
             if k + 1 > max_non_linear_iter:
                 break
+        if mixer is not None:
+            self.non_linear_info = {"anderson": mixer.history}
         return norms
 
     def set_p(self, p):              # control.py:1858-1865
@@ -765,11 +788,20 @@ class Stationary:
         rhs_1[nodes] = 0.0
         return rhs_0, rhs_1
 
+    def _lifts(self, mixer, v_old):
+        """With a mixer: the first update of a host loop from ``v_old`` puts boundary values in
+        that ``v_old`` does not carry (what gives the device loops their ``after_first_update``)."""
+        nodes = self._disc.boundary
+        return (mixer is not None and self._bcs_v is not None
+                and not np.array_equal(v_old[nodes], self._v_inhom()[nodes]))
+
     def non_linear_solve(self, *, P=None, solver_parameters=None, lambda_v_bounds=None,
                          max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                          absolute_non_linear_tol=1.0e-8, print_error_non_linear=False,
-                         backend=None, Multigrid=False, device=False):
+                         backend=None, Multigrid=False, device=False, anderson=0,
+                         anderson_beta=1.0):
         """``control.py:640-760``; returns the residual norms (initial one first).
+        ``anderson``, ``anderson_beta``: as in ``Instationary.non_linear_solve``.
 
         ``device=True``: the same loop with the iterate in HBM (``control_amd.reaction``): one
         block system and one preconditioner live through all iterations, and the forward
@@ -779,6 +811,8 @@ class Stationary:
         taken.  ``lambda_v_bounds`` stays the caller's: ``(0.3924, 2.0598)`` on P2 triangles,
         ``(0.25, 1.5625)`` on Q2.  Afterwards ``non_linear_info`` holds
         the linear iteration counts."""
+        from .anderson import HostAnderson, check_anderson
+        check_anderson(anderson, anderson_beta, None, self._Gauss_Newton)
         if device:
             from .reaction import device_stationary_non_linear_solve
             return device_stationary_non_linear_solve(
@@ -787,8 +821,11 @@ class Stationary:
                 relative_non_linear_tol=relative_non_linear_tol,
                 absolute_non_linear_tol=absolute_non_linear_tol,
                 print_error_non_linear=print_error_non_linear, backend=backend,
-                Multigrid=Multigrid)
+                Multigrid=Multigrid, anderson=anderson, anderson_beta=anderson_beta)
+        mixer = HostAnderson(anderson, anderson_beta) if anderson else None
         v_old, zeta_old = self._v.copy(), self._zeta.copy()
+        nodes = self._disc.boundary
+        lift = self._lifts(mixer, v_old)
         v_d, f = self._data()
         D_v = self.construct_D_v(v_old)
         rhs_0, rhs_1 = self.non_linear_res_eval(v_d, f, v_old, zeta_old, D_v)
@@ -798,9 +835,13 @@ class Stationary:
             self.linear_solve(P=P, solver_parameters=solver_parameters,
                               lambda_v_bounds=lambda_v_bounds, v_d=rhs_0, f=rhs_1,
                               backend=backend, Multigrid=Multigrid)
+            if mixer is not None:
+                self._v, self._zeta = mixer.step_fields(nodes, (self._v, self._zeta))
             v_old = v_old + self._v
             if self._bcs_v is not None:
                 v_old[self._disc.boundary] = self._v_inhom()[self._disc.boundary]
+            if lift and k == 0:
+                mixer.reset()        # the boundary lift moved the iterate outside the step
             self.set_v(v_old)
             zeta_old = zeta_old + self._zeta
             self.set_zeta(zeta_old)
@@ -815,6 +856,8 @@ class Stationary:
                       f"{norm_k:.16e}")
             if k + 1 > max_non_linear_iter:
                 break
+        if mixer is not None:
+            self.non_linear_info = {"anderson": mixer.history}
         return norms
 
     def incompressible_linear_solve(self, nullspace_p=None, *, forward_operator_p=None, P=None,
@@ -881,7 +924,8 @@ class Stationary:
                                         relative_non_linear_tol=1.0e-5,
                                         absolute_non_linear_tol=1.0e-8,
                                         print_error_non_linear=False, backend=None,
-                                        Multigrid=False, device=False):
+                                        Multigrid=False, device=False, anderson=0,
+                                        anderson_beta=1.0):
         """``control.py:1112-1480``: Picard loop of stationary Navier-Stokes-type control around
         ``incompressible_linear_solve``; returns the residual norms (initial one first).  With a
         ``fem.ConvectionTerm`` as forward operator, ``forward_operator_p=None`` means its
@@ -893,7 +937,11 @@ class Stationary:
         device kernels.  The forward operator must be a ``fem.ConvectionTerm`` on a
         discretisation with element data (``fem.rectangle_p2p1`` or ``fem.rectangle_q2q1``),
         ``forward_operator_p`` ``None`` or its ``pressure``, the backend a ``GpuBackend``, and ``P`` is not taken.  Afterwards
-        ``non_linear_info`` holds the linear iteration counts."""
+        ``non_linear_info`` holds the linear iteration counts.
+        ``anderson``, ``anderson_beta``: as in ``Instationary.non_linear_solve``; the mixed
+        vector is the update of ``v``, ``zeta``, ``mu`` and ``p``."""
+        from .anderson import HostAnderson, check_anderson
+        check_anderson(anderson, anderson_beta, None, getattr(self, "_Gauss_Newton", False))
         if device:
             from .stationary_picard import device_stationary_incompressible_non_linear_solve
             return device_stationary_incompressible_non_linear_solve(
@@ -903,7 +951,8 @@ class Stationary:
                 relative_non_linear_tol=relative_non_linear_tol,
                 absolute_non_linear_tol=absolute_non_linear_tol,
                 print_error_non_linear=print_error_non_linear, backend=backend,
-                Multigrid=Multigrid)
+                Multigrid=Multigrid, anderson=anderson, anderson_beta=anderson_beta)
+        mixer = HostAnderson(anderson, anderson_beta) if anderson else None
         th = self._th
         if th is None:
             raise ValueError("Undefined space_p")
@@ -915,6 +964,7 @@ class Stationary:
         v_old, zeta_old = self._v.copy(), self._zeta.copy()
         p_old = getattr(self, "_p", np.zeros(th.n_p)).copy()
         mu_old = getattr(self, "_mu", np.zeros(th.n_p)).copy()
+        lift = self._lifts(mixer, v_old)
         v_d, f = self._data()
 
         def evaluate():                                              # :1272-1310
@@ -935,9 +985,14 @@ class Stationary:
                 solver_parameters=solver_parameters, lambda_v_bounds=lambda_v_bounds,
                 lambda_p_bounds=lambda_p_bounds, v_d=r00, f=r01, div_v=r10, div_zeta=r11,
                 backend=backend, Multigrid=Multigrid)
+            if mixer is not None:
+                self._v, self._zeta, self._mu, self._p = mixer.step_fields(
+                    nodes, (self._v, self._zeta), (self._mu, self._p))
             v_old = v_old + self._v
             if self._bcs_v is not None:
                 v_old[nodes] = self._v_inhom()[nodes]
+            if lift and k == 0:
+                mixer.reset()        # the boundary lift moved the iterate outside the step
             zeta_old = zeta_old + self._zeta
             zeta_old[nodes] = 0.0
             p_old = p_old + self._p
@@ -953,4 +1008,6 @@ class Stationary:
                       f"{norm_k:.16e}")
             if k + 1 > max_non_linear_iter:
                 break
+        if mixer is not None:
+            self.non_linear_info = {"anderson": mixer.history}
         return norms

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <string>
 
+#include "anderson.hpp"
 #include "comm.hpp"
 #include "pc.hpp"
 #include "reaction.hpp"
@@ -449,6 +450,16 @@ int kkt_reaction_update_device(kkt_handle plan, double *d_u) {
 }
 int kkt_debug_reaction_array(kkt_handle plan, int which, double *out, int64_t cap) {
     KKT_TRY(plan, reaction_debug_array(S, which, out, cap));
+}
+int kkt_anderson_set(kkt_handle h, int depth, double beta, double cond_max) {
+    KKT_TRY(h, anderson_set(S, depth, beta, cond_max));
+}
+int kkt_anderson_step(kkt_handle h, double *d_u, kkt_anderson_info *info) {
+    KKT_TRY(h, anderson_step(S, d_u, info));
+}
+int kkt_anderson_reset(kkt_handle h) { KKT_TRY(h, anderson_reset(S)); }
+int kkt_debug_anderson_op(kkt_handle h, kkt_anderson_op *op) {
+    KKT_TRY(h, debug_anderson_op(S, op));
 }
 int kkt_debug_block_values(kkt_handle h, int quadrant, int i, int j, double *out, int64_t cap,
                            int64_t *nnz, int *padding_zero) {

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "anderson.hpp"
 #include "comm.hpp"
 #include "pc.hpp"
 #include "reaction.hpp"

@@ -132,6 +132,7 @@ class PcBase;
 class Comm;
 struct RelinPlan;
 struct ReactionPlan;
+struct AndersonMixer;
 
 struct KrylovCfg {
     int type = KKT_KSP_FGMRES;
@@ -249,6 +250,7 @@ struct System {
 
     std::unique_ptr<RelinPlan> relin;   // kkt_set_relinearisation (relin.hpp)
     std::unique_ptr<ReactionPlan> reaction;   // kkt_set_reaction_relinearisation (reaction.hpp)
+    std::unique_ptr<AndersonMixer> anderson;  // kkt_anderson_set (anderson.hpp)
 
     KrylovCfg ksp;
     kkt_steplock steplock{};   // test hook (kkt_debug_set_steplock); n_steps == 0: off

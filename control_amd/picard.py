@@ -426,36 +426,47 @@ class GpuLinearSolver:
 
 
 def _device_non_linear_solve(pb, ls, v, zeta, p, mu, max_non_linear_iter, rtol, atol,
-                             print_error_non_linear):
+                             print_error_non_linear, anderson=0, anderson_beta=1.0):
     """``incompressible_non_linear_solve`` with the iterate in HBM: per iteration one assembly
     of the convection blocks, one residual (the host reads its norm), one linearised solve and
     one update, all on the device -- on a time-sharded solver every rank on its own levels, the
-    norm the same on all of them."""
+    norm the same on all of them.  ``anderson > 0``: the updates go through the device mixer on
+    the outer system, which is removed again afterwards (the solver outlives the call)."""
+    from .anderson import DeviceAnderson
     from .relinearise import device_picard_loop, device_vectors
     fresh = ls.outer is None
     if fresh:                # the first call builds the systems (host blocks or patterns)
         ls.setup(v, zeta, p, mu)
     dev = ls.device_plan()
     dev.set_state(v, zeta, p, mu)
-    with device_vectors(ls.outer) as (d_b, d_u):
-        dev.assemble()
-        norm_0 = dev.residual(d_b, rhs=True)
-        if print_error_non_linear:
-            print(f"Initial non-linear residual: {norm_0:.16e}")
-        norms, lin_its = device_picard_loop(dev, d_b, d_u, norm_0, ls.device_solve,
-                                            ls.device_relinearise, fresh, rtol, atol,
-                                            max_non_linear_iter, print_error_non_linear)
-        v, zeta, p, mu = dev.get_state()
+    mixer = DeviceAnderson(ls.outer, anderson, anderson_beta) if anderson else None
+    try:
+        with device_vectors(ls.outer) as (d_b, d_u):
+            dev.assemble()
+            norm_0 = dev.residual(d_b, rhs=True)
+            if print_error_non_linear:
+                print(f"Initial non-linear residual: {norm_0:.16e}")
+            norms, lin_its = device_picard_loop(dev, d_b, d_u, norm_0, ls.device_solve,
+                                                ls.device_relinearise, fresh, rtol, atol,
+                                                max_non_linear_iter, print_error_non_linear,
+                                                mixer=mixer)
+            v, zeta, p, mu = dev.get_state()
+    finally:
+        if mixer is not None:
+            mixer.close()
     norm_k = norms[-1]
-    return dict(v=v, zeta=zeta, p=p, mu=mu, norms=norms, linear_iterations=lin_its,
-                converged=bool(norm_k <= rtol * norm_0 or norm_k <= atol))
+    out = dict(v=v, zeta=zeta, p=p, mu=mu, norms=norms, linear_iterations=lin_its,
+               converged=bool(norm_k <= rtol * norm_0 or norm_k <= atol))
+    if mixer is not None:
+        out["anderson"] = mixer.history
+    return out
 
 
 def incompressible_non_linear_solve(pb: NavierStokesControl, linear_solver=None, *,
                                     max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                                     absolute_non_linear_tol=1.0e-8, v=None, zeta=None, p=None,
                                     mu=None, print_error_non_linear=True, Multigrid=False,
-                                    device=False):
+                                    device=False, anderson=0, anderson_beta=1.0):
     """``control.py:4886-5232`` (BE).  ``linear_solver.linear_solve(D, Dp, b_0, b_1)`` returns
     the update ``(u_0, u_1, iterations)`` of the linearised system whose forward operator at
     time level ``i`` is ``D[i]`` (velocity space) / ``Dp[i]`` (pressure space).  ``None``: a
@@ -466,8 +477,16 @@ def incompressible_non_linear_solve(pb: NavierStokesControl, linear_solver=None,
     update on the GPU; the host reads one norm per iteration and the fields once at the end).
     Needs a ``GpuLinearSolver(..., relinearise="device")`` (``None``: one is built).
 
+    ``anderson`` (depth 1..8; 0, the default: off), ``anderson_beta``: Anderson acceleration of
+    the loop in update space (``control_amd.anderson``): the flat update ``(u_0, u_1)`` is mixed
+    with the last ``anderson`` secant pairs before it is added, on the GPU with ``device=True``,
+    by the NumPy mirror otherwise.  ``ValueError`` on a time-sharded solver and outside 0..8.
+
     Returns a dict with the converged fields, the non-linear residual norms (``norm_0``
-    first) and the linear iteration counts."""
+    first) and the linear iteration counts (with ``anderson > 0`` also ``anderson``: per
+    iteration the pairs used and dropped)."""
+    from .anderson import HostAnderson, check_anderson
+    check_anderson(anderson, anderson_beta, getattr(linear_solver, "dist", None))
     if device and getattr(pb.disc, "elem", None) is None:
         raise ValueError("device=True needs a discretisation with element data "
                          "(fem.rectangle_p2p1 or fem.rectangle_q2q1)")
@@ -490,7 +509,8 @@ def incompressible_non_linear_solve(pb: NavierStokesControl, linear_solver=None,
     if device:
         return _device_non_linear_solve(pb, linear_solver, v, zeta, p, mu, max_non_linear_iter,
                                         relative_non_linear_tol, absolute_non_linear_tol,
-                                        print_error_non_linear)
+                                        print_error_non_linear, anderson, anderson_beta)
+    mixer = HostAnderson(anderson, anderson_beta) if anderson else None
 
     def evaluate():
         D = [pb.D_v(v[i]) for i in range(n_t)]
@@ -513,6 +533,8 @@ def incompressible_non_linear_solve(pb: NavierStokesControl, linear_solver=None,
         b_1 = np.concatenate([s10, s11])
         u_0, u_1, its = linear_solver.linear_solve(D, Dp, b_0, b_1)
         lin_its.append(its)
+        if mixer is not None:
+            u_0, u_1 = mixer.step(u_0, u_1)
         if pb.CN:                # unknown block i: v at level i + 1, zeta at level i
             v[1:] += u_0[:m]
             zeta[:m] += u_0[m:]
@@ -529,6 +551,9 @@ def incompressible_non_linear_solve(pb: NavierStokesControl, linear_solver=None,
             print(f"Non-linear solver: iteration {k:d}, non-linear residual norm {norm_k:.16e}")
         if k + 1 > max_non_linear_iter:                          # :5186-5187
             break
-    return dict(v=v, zeta=zeta, p=p, mu=mu, norms=norms, linear_iterations=lin_its,
-                converged=bool(norm_k <= relative_non_linear_tol * norm_0
-                               or norm_k <= absolute_non_linear_tol))
+    out = dict(v=v, zeta=zeta, p=p, mu=mu, norms=norms, linear_iterations=lin_its,
+               converged=bool(norm_k <= relative_non_linear_tol * norm_0
+                              or norm_k <= absolute_non_linear_tol))
+    if mixer is not None:
+        out["anderson"] = mixer.history
+    return out

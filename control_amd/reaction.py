@@ -19,6 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .anderson import DeviceAnderson
 from .fem import ReactionTerm
 from .relinearise import (DevicePlanBinding, _marshal, _recipe_array, contribution_lists,
                           device_picard_loop, device_vectors, transpose_permutation)
@@ -224,7 +225,8 @@ def build_system(ctl, backend, plan, comm=None):
 def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bounds=None,
                             max_non_linear_iter=10, relative_non_linear_tol=1.0e-5,
                             absolute_non_linear_tol=1.0e-8, print_error_non_linear=False,
-                            backend=None, Multigrid=False, comm=None, host_allreduce=None):
+                            backend=None, Multigrid=False, comm=None, host_allreduce=None,
+                            anderson=0, anderson_beta=1.0):
     """``Instationary.non_linear_solve`` with the iterate in HBM.  One ``MultiBlockSystem`` is
     built from patterns and composed on the device, one ``SchurPC`` is attached to it; every
     iteration then assembles, evaluates the residual (the host reads its norm), re-composes the
@@ -239,8 +241,15 @@ def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bou
     is still by pattern, composed on the device from the rank's rows of the build recipes, so no
     block values ever cross from the host.  The boundary lift and the final download go through
     the collective ``get_state`` (``host_allreduce``): ``ctl._v`` and ``ctl._zeta`` end whole on
-    every rank."""
+    every rank.
+
+    ``anderson`` (depth 1..8; 0: off) and ``anderson_beta``: Anderson acceleration of the loop in
+    update space by the device mixer (``control_amd.anderson``); not on
+    time shards, not under ``set_Gauss_Newton()``.  ``non_linear_info["anderson"]``: per
+    iteration the pairs used and dropped."""
+    from .anderson import check_anderson
     from .control import GpuBackend, _multigrid_kw
+    check_anderson(anderson, anderson_beta, comm, ctl._Gauss_Newton)
     _check(ctl, P, comm, host_allreduce)
     backend = backend or GpuBackend()
     if not isinstance(backend, GpuBackend):
@@ -268,19 +277,23 @@ def device_non_linear_solve(ctl, *, P=None, solver_parameters=None, lambda_v_bou
     pc_fn = backend.construct_pc("CN" if CN else "BE", plan.term.M, quads[1], quads[2], n_t,
                                  plan.tau, plan.beta, nodes, lambda_v_bounds or (0.5, 2.0),
                                  1.0e-3, **_multigrid_kw(disc, Multigrid))
-    norms, lin_its, v_new, zeta_new = _run_loop(
+    norms, lin_its, v_new, zeta_new, mixed = _run_loop(
         dev, pc_fn, solver_parameters, v_fixed if lift else None, relative_non_linear_tol,
-        absolute_non_linear_tol, max_non_linear_iter, print_error_non_linear)
+        absolute_non_linear_tol, max_non_linear_iter, print_error_non_linear,
+        anderson, anderson_beta)
     ctl._v, ctl._zeta = v_new, zeta_new
-    ctl.non_linear_info = {"linear_iterations": lin_its, "window": dev.window}
+    ctl.non_linear_info = {"linear_iterations": lin_its, "window": dev.window, **mixed}
     return norms
 
 
-def _run_loop(dev, pc_fn, solver_parameters, v_fixed, rtol, atol, max_iter, verbose):
+def _run_loop(dev, pc_fn, solver_parameters, v_fixed, rtol, atol, max_iter, verbose,
+              anderson=0, anderson_beta=1.0):
     """What both drivers do with a composed system: the first residual, ``device_picard_loop``
     and the download; the system is closed afterwards.  ``v_fixed`` (``(levels, n)``, or ``None``):
     the starting iterate did not carry these boundary values -- they are put in once, after the
-    first update.  Returns ``(norms, linear iterations, v, zeta)``."""
+    first update.  ``anderson > 0``: the loop's updates go through a ``DeviceAnderson`` on the
+    system.  Returns ``(norms, linear iterations, v, zeta, info)``; ``info``: ``{"anderson": the
+    mixer's (columns, dropped) per iteration}``, or empty without a mixer."""
     system, nodes = dev.system, dev.ctl._disc.boundary
     if solver_parameters is None:              # linear_solve's, control.py:3260-3266 and 556-562
         solver_parameters = {"linear_solver": "gmres", "gmres_restart": 10,
@@ -296,15 +309,17 @@ def _run_loop(dev, pc_fn, solver_parameters, v_fixed, rtol, atol, max_iter, verb
         v_new[:, nodes] = v_fixed[:, nodes]
         dev.set_state(v_new, zeta_new)
     try:
+        mixer = DeviceAnderson(system, anderson, anderson_beta) if anderson else None
         with device_vectors(system) as (d_b, d_u):
             norm_0 = dev.residual(d_b, rhs=True)
             norms, lin_its = device_picard_loop(
                 dev, d_b, d_u, norm_0, solve, dev.relinearise, True, rtol, atol, max_iter,
-                verbose, after_first_update=lift_boundary if v_fixed is not None else None)
+                verbose, after_first_update=lift_boundary if v_fixed is not None else None,
+                mixer=mixer)
             v_new, zeta_new = dev.get_state()
     finally:
         system.close()
-    return norms, lin_its, v_new, zeta_new
+    return norms, lin_its, v_new, zeta_new, ({"anderson": mixer.history} if mixer else {})
 
 
 def device_stationary_non_linear_solve(ctl, *, P=None, solver_parameters=None,
@@ -312,7 +327,7 @@ def device_stationary_non_linear_solve(ctl, *, P=None, solver_parameters=None,
                                        relative_non_linear_tol=1.0e-5,
                                        absolute_non_linear_tol=1.0e-8,
                                        print_error_non_linear=False, backend=None,
-                                       Multigrid=False):
+                                       Multigrid=False, anderson=0, anderson_beta=1.0):
     """``Stationary.non_linear_solve`` with the iterate in HBM: the loop of
     ``device_non_linear_solve`` on the one-level plan.  One ``MultiBlockSystem`` of four
     ``PatternOnly`` blocks is composed on the device, one ``SchurPC(kind="stationary")`` is
@@ -320,8 +335,11 @@ def device_stationary_non_linear_solve(ctl, *, P=None, solver_parameters=None,
     ``Stationary.non_linear_res_eval`` (they are the right-hand side), re-composes ``D^T`` and
     ``D`` (the preconditioner is marked stale and rebuilt by the next solve), solves and updates
     on the GPU.  P1 or P2 triangles, P1 tetrahedra, Q2 quadrilaterals; ``lambda_v_bounds`` is the
-    caller's (P2 triangles: ``(0.3924, 2.0598)``, Q2: ``(0.25, 1.5625)``)."""
+    caller's (P2 triangles: ``(0.3924, 2.0598)``, Q2: ``(0.25, 1.5625)``).  ``anderson``,
+    ``anderson_beta``: as in ``device_non_linear_solve``."""
+    from .anderson import check_anderson
     from .control import GpuBackend, _multigrid_kw
+    check_anderson(anderson, anderson_beta, None, ctl._Gauss_Newton)
     _check(ctl, P)
     backend = backend or GpuBackend()
     if not isinstance(backend, GpuBackend):
@@ -344,11 +362,12 @@ def device_stationary_non_linear_solve(ctl, *, P=None, solver_parameters=None,
     pc_fn = backend.construct_pc("stationary", plan.term.M, quads[1], quads[2], 1, 0.0,
                                  plan.beta, nodes, lambda_v_bounds or (0.5, 2.0), 0.0,
                                  **_multigrid_kw(disc, Multigrid))
-    norms, lin_its, v_new, zeta_new = _run_loop(
+    norms, lin_its, v_new, zeta_new, mixed = _run_loop(
         dev, pc_fn, solver_parameters, v_fixed[None] if lift else None, relative_non_linear_tol,
-        absolute_non_linear_tol, max_non_linear_iter, print_error_non_linear)
+        absolute_non_linear_tol, max_non_linear_iter, print_error_non_linear,
+        anderson, anderson_beta)
     if lin_its:              # the host loop ends every iteration in set_v / set_zeta
         ctl.set_v(v_new[0])
         ctl.set_zeta(zeta_new[0])
-    ctl.non_linear_info = {"linear_iterations": lin_its, "window": dev.window}
+    ctl.non_linear_info = {"linear_iterations": lin_its, "window": dev.window, **mixed}
     return norms

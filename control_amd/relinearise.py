@@ -302,12 +302,15 @@ def device_vectors(system):
 
 
 def device_picard_loop(dev, d_b, d_u, norm_0, solve, relinearise, fresh, rtol, atol, max_iter,
-                       verbose, after_first_update=None):
+                       verbose, after_first_update=None, mixer=None):
     """The device Picard iterations from the assembled iterate of ``dev`` with right-hand side
     ``d_b`` and residual norm ``norm_0``: re-linearise (unless the blocks are ``fresh`` from the
     build), ``solve(d_b, d_u)`` (it returns the linear iterations), update, assemble, residual,
     until the host loops' stopping rule holds.  ``after_first_update()`` runs once, before the
-    first re-assembly.  Returns the norms (``norm_0`` first) and the linear iteration counts."""
+    first re-assembly.  ``mixer`` (``anderson.DeviceAnderson``): ``mixer.step(d_u)`` turns the
+    solver's update into the accelerated step before it is added; after ``after_first_update``,
+    which moves the iterate outside any step, ``mixer.reset()``: no secant pair spans the lift.
+    Returns the norms (``norm_0`` first) and the linear iteration counts."""
     norm_k, k = norm_0, 0
     norms, lin_its = [norm_0], []
     while norm_k > rtol * norm_0 and norm_k > atol:
@@ -315,9 +318,13 @@ def device_picard_loop(dev, d_b, d_u, norm_0, solve, relinearise, fresh, rtol, a
             relinearise()
         fresh = False
         lin_its.append(solve(d_b, d_u))
+        if mixer is not None:
+            mixer.step(d_u)
         dev.update(d_u)
         if k == 0 and after_first_update is not None:
             after_first_update()
+            if mixer is not None:
+                mixer.reset()
         dev.assemble()
         norm_k = dev.residual(d_b, rhs=True)
         norms.append(norm_k)

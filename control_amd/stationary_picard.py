@@ -111,10 +111,14 @@ def device_stationary_incompressible_non_linear_solve(
         ctl, nullspace_p=None, *, forward_operator_p=None, P=None, solver_parameters=None,
         lambda_v_bounds=None, lambda_p_bounds=None, max_non_linear_iter=10,
         relative_non_linear_tol=1.0e-5, absolute_non_linear_tol=1.0e-8,
-        print_error_non_linear=False, backend=None, Multigrid=False):
+        print_error_non_linear=False, backend=None, Multigrid=False, anderson=0,
+        anderson_beta=1.0):
     """``Stationary.incompressible_non_linear_solve`` with the iterate in HBM; returns the
     residual norms (initial one first) and leaves ``_v``, ``_zeta``, ``_p``, ``_mu`` and
-    ``non_linear_info`` on ``ctl``."""
+    ``non_linear_info`` on ``ctl``.  ``anderson > 0``: the updates go through the device mixer
+    on the outer system (``control_amd.anderson``)."""
+    from .anderson import DeviceAnderson, check_anderson
+    check_anderson(anderson, anderson_beta, None, getattr(ctl, "_Gauss_Newton", False))
     from .blocks import (stationary_incompressible_build_recipes,
                          stationary_incompressible_relinearisation_recipes)
     from .control import GpuBackend
@@ -162,12 +166,13 @@ def device_stationary_incompressible_non_linear_solve(
             v, zeta, p, mu = dev.get_state()
             v[:, nodes] = v_fixed[nodes]
             dev.set_state(v, zeta, p, mu)
+        mixer = DeviceAnderson(outer, anderson, anderson_beta) if anderson else None
         with device_vectors(outer) as (d_b, d_u):
             norm_0 = dev.residual(d_b, rhs=True)
             norms, lin_its = device_picard_loop(
                 dev, d_b, d_u, norm_0, solve, relinearise, True, relative_non_linear_tol,
                 absolute_non_linear_tol, max_non_linear_iter, print_error_non_linear,
-                after_first_update=lift_boundary if lift else None)
+                after_first_update=lift_boundary if lift else None, mixer=mixer)
             v_new, zeta_new, p_new, mu_new = dev.get_state()
     finally:
         for system in systems:
@@ -177,4 +182,6 @@ def device_stationary_incompressible_non_linear_solve(
         ctl.set_zeta(zeta_new[0])
         ctl._p, ctl._mu = p_new[0].copy(), mu_new[0].copy()
     ctl.non_linear_info = {"linear_iterations": lin_its, "window": dev.window}
+    if mixer is not None:
+        ctl.non_linear_info["anderson"] = mixer.history
     return norms

@@ -652,6 +652,72 @@ int kkt_debug_reaction_array(kkt_handle plan, int which, double *out, int64_t ca
 int kkt_debug_block_values(kkt_handle h, int quadrant, int i, int j, double *out, int64_t cap,
                            int64_t *nnz, int *padding_zero);
 
+/* ---- Anderson acceleration of a device Picard loop, in update space.
+ * Call k = 0, 1, ... of kkt_anderson_step receives in d_u (a local vector of the handle,
+ * kkt_vec_alloc) the update f_k of the linearised solve and leaves there the step s_k the loop
+ * adds to its iterate:
+ *   history   k >= 1: the pair dF = f_k - f_{k-1}, dX = s_{k-1} enters a ring of at most `depth`
+ *             pairs; the oldest falls out
+ *   Gram      with c pairs kept, G = dF^T dF (c x c) and r = dF^T f_k, every entry recomputed at
+ *             every call by one deterministic two-stage reduction (no atomics: equal input gives
+ *             equal bits on every run and device)
+ *   condition G = L L^T by unpivoted Cholesky on the host in double, columns oldest first;
+ *             accepted when every pivot is positive and max L_ii / min L_ii <= cond_max; otherwise
+ *             the oldest pair leaves the ring and the rest is factored again
+ *   solve     gamma from the two triangular solves
+ *   step      s = beta f[i]; for j = oldest .. newest kept: t = dX_j[i] + beta dF_j[i],
+ *             s = s - gamma_j t; every product and sum rounded on its own.  c = 0: s = beta f,
+ *             which for beta = 1 leaves the bits of f alone.
+ * s_k is also kept as the next dX, f_k as f_prev: the caller may zero d_u afterwards.
+ * kkt_anderson_set: depth 1 .. KKT_ANDERSON_MAX_DEPTH allocates the history (2 depth + 1 vectors
+ * in one pool of the handle, released by kkt_destroy or by depth 0, which removes the mixer) and
+ * starts at k = 0; KKT_ERR_ARG naming the argument for another depth, a beta that is not finite
+ * or is zero, or cond_max <= 1; KKT_ERR_STATE before kkt_finalize and on a time-sharded handle
+ * (the Gram sums would have to ride the ranks' all-reduce).  kkt_anderson_reset: the next call is
+ * k = 0 again.  kkt_anderson_step / _reset without a mixer: KKT_ERR_STATE.
+ * info (may be NULL): the pairs used by the call and dropped by the condition rule, and the
+ * system gamma solves: G (columns x columns, row-major, both triangles, oldest first) and r of
+ * the pairs used; with option "stage_timers" the three kernels' times by HIP events (else 0). */
+#define KKT_ANDERSON_MAX_DEPTH 8
+typedef struct kkt_anderson_info {
+    int32_t columns, dropped;
+    double gamma[KKT_ANDERSON_MAX_DEPTH];
+    double G[KKT_ANDERSON_MAX_DEPTH * KKT_ANDERSON_MAX_DEPTH];
+    double r[KKT_ANDERSON_MAX_DEPTH];
+    double push_ms, gram_ms, mix_ms;
+} kkt_anderson_info;
+int kkt_anderson_set(kkt_handle h, int depth, double beta, double cond_max);
+int kkt_anderson_step(kkt_handle h, double *d_u, kkt_anderson_info *info);
+int kkt_anderson_reset(kkt_handle h);
+/* Test hook: one kernel of the mixer on host data, once, on the handle's stream (works on a
+ * created handle; every pointer is host memory), or a read-out of the handle's ring.
+ *   PUSH  f (n); f_prev (n + slack, read and written); out = dF_new (n + slack)
+ *   GRAM  c in 0 .. 8 columns dF (c x n, oldest first), f (n); G (c x c, both triangles filled),
+ *         r (c); c = 0 launches nothing
+ *   MIX   c, dF, dX (c x n), f (n), gamma (c), beta; out = s (n + slack), out2 = the new dX slot
+ *         (n + slack).  alias != 0 (c >= 1): the slot IS column 0 of dX, as in a full ring
+ *   READ  which (0 dF, 1 dX: ring slot `slot`; 2: f_prev) of the handle's mixer, n = the
+ *         handle's local size, into out (n); ring[0] = head (the slot the next pair enters),
+ *         ring[1] = pairs kept (the slots before the head, oldest first), ring[2] = 1 when a
+ *         previous call is held, ring[3] = depth.  dX of the head slot holds the last step; in a
+ *         full ring that slot is also the oldest pair's, whose dX the step replaced after
+ *         reading it (the pair leaves with the next call)
+ * The `slack` doubles behind a written array go up as the caller filled them and come back, so
+ * that a write past n can be recognised.  inputs_changed: how many read-only arrays came back
+ * different.  KKT_ERR_ARG for an unknown op, n < 1, c outside 0 .. 8, slack < 0 or a null array
+ * the operation needs. */
+enum { KKT_ANDERSON_PUSH = 0, KKT_ANDERSON_GRAM = 1, KKT_ANDERSON_MIX = 2, KKT_ANDERSON_READ = 3 };
+typedef struct kkt_anderson_op {
+    int32_t op, c, alias, which, slot, inputs_changed;
+    int64_t n, slack;
+    double beta;
+    double gamma[KKT_ANDERSON_MAX_DEPTH];
+    const double *f, *dF, *dX;
+    double *f_prev, *out, *out2, *G, *r;
+    int32_t ring[4];
+} kkt_anderson_op;
+int kkt_debug_anderson_op(kkt_handle h, kkt_anderson_op *op);
+
 /* `reps` back-to-back kkt_apply_device / kkt_pc_apply_device launches timed with HIP
  * events on the library's own stream; *ms = total elapsed milliseconds. */
 int kkt_time_apply(kkt_handle h, const double *d_x, double *d_y, int reps, float *ms);
